@@ -16,6 +16,10 @@ repack) on a synthetic batch of 256x256x1 tiles that is already resident in HBM.
       as a child (before anything touches the GPU - no exec of a GPU process), relays its output and exits with its code.
   --dry-run   plumbing rehearsal without a GPU: a 6-parameter per-pixel stand-in model on the CPU driven through the SAME
               step.TrainStepDriver / MainParallel.MirroredTrainer code over gloo; its `value` measures nothing ("dry_run": true).
+  --dump-outputs DIR  after the timed steps, rank 0 writes what the last one computed - loss.npy, probs.npy and the updated weights
+              params.npy, float32 - so that two builds can be compared output for output (the inputs are seeded: identical
+              from run to run).  An array larger than its share of 60 MB is written as a fixed, seeded sample of its elements.
+              With N > 1: the global loss, rank 0's own slice of the probabilities (what MirroredTrainer.train_step returns there).
 
 Prints ONE JSON line on rank 0 (see the keys below).  Extra objects:
   roofline     - the dominant kernel family (the conv kernels that run every plain conv / tconv forward and
@@ -306,6 +310,36 @@ def cpu_baseline(arch, seconds_budget: float = 25.0):
                       f"{torch.get_num_threads()} threads; TensorFlow (the reference) is not installable here"}
 
 
+DUMP_MAX_BYTES = 60_000_000     # --dump-outputs: all files together stay under 64 MB
+
+
+def collect_outputs(loss, probs, net):
+    """What the caller of the timed step holds after its last step: the loss, the probabilities and the updated fp32 master
+    weights (with the BatchNorm statistics that live in the same flat buffer), as host float32 arrays.  Taken right after the
+    timed region: the profiling steps that follow change the weights."""
+    return {"loss": loss.detach().float().reshape(-1).cpu().numpy(),
+            "probs": probs.detach().float().contiguous().cpu().numpy(),
+            "params": net.flat.flat.detach().float().cpu().numpy()}
+
+
+def dump_outputs(outs, out_dir):
+    """Write ``outs`` as <out_dir>/<name>.npy.  An array over its share of DUMP_MAX_BYTES is replaced by a fixed, seeded sample of
+    its flattened elements (sorted indices, the same on every run), so that two builds can be compared file by file."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_MAX_BYTES // len(outs)
+    info = {}
+    for name, a in outs.items():
+        shape = list(a.shape)
+        if a.nbytes > share:
+            k = share // a.itemsize
+            idx = torch.randperm(a.size, generator=torch.Generator().manual_seed(0))[:k].sort().values.numpy()
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+        info[name] = {"shape": shape, "dtype": str(a.dtype), "sampled": int(a.size) if list(a.shape) != shape else None}
+    return {"dir": out_dir, "arrays": info}
+
+
 def launch_ranks(n: int) -> int:
     """`bench.py --gpus N` started by hand (no torchrun environment): start the N ranks as a child torch.distributed.run and
     relay its stdout / stderr / exit code.  Called before any torch.cuda / library call, so no GPU process is ever exec'd."""
@@ -401,7 +435,13 @@ def main():
     ap.add_argument("--dp-chunks", type=int, default=0, help="pieces the gradient exchange is pipelined in (0 = automatic)")
     ap.add_argument("--profile-steps", type=int, default=3, help="extra eager steps with per-launch HIP events (roofline leg)")
     ap.add_argument("--dry-run", action="store_true", help="CPU / gloo rehearsal of the launch + exchange + reporting plumbing with a stand-in model")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them returned (loss, probabilities) and the updated weights as DIR/<name>.npy "
+                         "(float32; a fixed, seeded sample of an array over its share of 60 MB).  With N > 1 rank 0 writes them: the global loss, the "
+                         "probabilities of its own slice of the batch and the weights, which every replica holds alike")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:     # started by hand: become the launcher (nothing has touched the GPU yet)
         sys.exit(launch_ranks(args.gpus))
@@ -491,9 +531,10 @@ def main():
     sync()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss, _ = trainer.train_step(x, y)
+        loss, probs = trainer.train_step(x, y)
     sync()
     el = time.perf_counter() - t0
+    outs = collect_outputs(loss, probs, net) if args.dump_outputs and rank == 0 else None
     if world > 1:
         t = torch.tensor([el], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -571,6 +612,8 @@ def main():
                "roofline": roofline}
         if dry:
             out.update({"dry_run": True, "data": "synthetic (dry run: CPU stand-in model over gloo, the value measures nothing)", "dtype": "f32"})
+        if outs is not None:
+            out["dump_outputs"] = dump_outputs(outs, args.dump_outputs)
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(arch)
         print(json.dumps(out), flush=True)

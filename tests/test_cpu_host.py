@@ -283,3 +283,53 @@ def test_bench_launches_its_own_ranks(tmp_path):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--dry-run", "--scaling", "strong",
                         "--arch", "T"], capture_output=True, text=True, timeout=600, env=dict(env, USSEG_BENCH_FAIL_RANK="1"))
     assert r.returncode != 0
+
+
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs DIR` writes what the last timed step returned (loss, probabilities) and the updated weights as float32
+    .npy files, the same on every run of the same arguments; an array over its share of the size cap becomes a fixed, seeded sample.
+    In the dry run a warm-up step is the same train step as a timed one, so the dump after 1 + 3 steps equals the dump after 2 + 2
+    and differs from the one after 1 + 2: it holds the LAST step, not an earlier one."""
+    import json
+    import subprocess
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    got = {}
+    for run, warmup, steps in (("a", 1, 3), ("b", 1, 3), ("c", 2, 2), ("d", 1, 2)):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+                            "--dry-run", "--dump-outputs", str(tmp_path / run)], capture_output=True, text=True, timeout=600, env=env)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert d["steps"] == steps and d["ms_per_step"] > 0
+        assert set(d["dump_outputs"]["arrays"]) == {"loss", "probs", "params"}
+        got[run] = {n: np.load(tmp_path / run / f"{n}.npy") for n in ("loss", "probs", "params")}
+        assert round(float(got[run]["loss"][0]), 4) == d["config"]["final_loss"]
+    for n, a in got["a"].items():
+        assert a.dtype == np.float32 and np.isfinite(a).all(), n
+        assert np.array_equal(a, got["b"][n]), n           # same arguments, same files
+        assert np.array_equal(a, got["c"][n]), n           # the fourth step either way
+    assert not np.array_equal(got["a"]["loss"], got["d"]["loss"]) and not np.array_equal(got["a"]["params"], got["d"]["params"])
+    assert got["a"]["probs"].shape == (16, 256, 256, 3) and got["a"]["params"].shape == (6,)
+    assert sum(a.nbytes for a in got["a"].values()) <= 64 << 20
+
+    monkeypatch.setenv("HIP_FORCE_DEV_KERNARG", os.environ.get("HIP_FORCE_DEV_KERNARG", "1"))     # importing bench sets it: undone after the test
+    import bench
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 8000)
+    big = {"x": np.arange(3000, dtype=np.float32), "y": np.ones(3, dtype=np.float32)}
+    info = bench.dump_outputs(big, str(tmp_path / "c"))
+    bench.dump_outputs(big, str(tmp_path / "d"))
+    x1, x2 = np.load(tmp_path / "c" / "x.npy"), np.load(tmp_path / "d" / "x.npy")
+    assert info["arrays"]["x"]["sampled"] == x1.size == 1000
+    assert np.array_equal(x1, x2) and (np.diff(x1) > 0).all()           # the same sorted sample every time
+    assert info["arrays"]["y"]["sampled"] is None
+
+
+def test_side_stream_needs_three_hardware_queues():
+    """The weight-gradient side stream forks only where the HIP runtime gives it a hardware queue of its own (GPU_MAX_HW_QUEUES >= 3,
+    default 4): on fewer, the replay of a captured two-stream step crashes or hangs, so its launches run in line instead.  The rule is
+    checked on the setting's strings, in this process: no environment is changed."""
+    from ultrasound_modeling_amd import ops
+    for value, want in ((None, True), ("", True), ("4", True), ("3", True), ("8", True), ("2", False), ("1", False), ("0", False),
+                        ("x", True)):
+        assert ops._fork_allowed(value) is want, value
+    assert ops._Side.fork is ops._fork_allowed(os.environ.get("GPU_MAX_HW_QUEUES"))

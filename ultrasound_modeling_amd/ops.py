@@ -48,7 +48,22 @@ WGRAD_WS_FLOATS = 64 << 20   # 256 MB of the 288 GB: split-K partial slabs of th
 # caching allocator cannot hand their memory to a later main-stream tensor.
 # Off by default since the conv / wgrad kernels got ~1.5x faster: the fork/join edges of the captured graph now cost more
 # than the overlap returns (Arch B 4.17 vs 4.23 ms, Arch A 9.47 vs 9.87 ms per step; USSEG_SIDE_STREAM=1 turns it back on).
+# The fork needs a hardware queue of its own for the side stream: with GPU_MAX_HW_QUEUES below 3 (the runtime's default is 4) the
+# replay of a captured two-stream step crashes or never finishes, so there nothing forks and the side-stream launches run in line on
+# the current stream, in the order they were queued (the same bits: tests/test_gpu_concurrency.py).
+def _fork_allowed(max_hw_queues: Optional[str]) -> bool:
+    """Whether the side stream may fork, given the value of GPU_MAX_HW_QUEUES (None: unset, the runtime's default of 4).  Any value
+    below 3 - 0 included - means no fork; a value that is not a number is taken as the default."""
+    try:
+        n = int(max_hw_queues) if max_hw_queues else 4
+    except ValueError:
+        n = 4
+    return n >= 3
+
+
 class _Side:
+    # read once, like the HIP runtime itself, which takes the setting when it loads (with torch, before this module)
+    fork = _fork_allowed(os.environ.get("GPU_MAX_HW_QUEUES"))
     enabled = os.environ.get("USSEG_SIDE_STREAM", "0") != "0"
     defer = os.environ.get("USSEG_DEFER", "1") != "0"
     depth = 0
@@ -125,7 +140,7 @@ def overlap_region():
 @contextlib.contextmanager
 def side_stream(*keep):
     """Enqueue the enclosed launches on the side stream, ordered after everything already on the current stream."""
-    if not (_Side.enabled and _Side.depth > 0):
+    if not (_Side.enabled and _Side.fork and _Side.depth > 0):
         yield
         return
     if _Side.stream is None:
