@@ -390,17 +390,45 @@ static inline int wg_map_fill(WgMap& m, const UssegWgradDst* d) {
   return 1;
 }
 
-// per-output-channel multiplier applied before the bias in the conv epilogues (folded inference BatchNorm): set by the
-// *_affine / multi entry points for the duration of one call, read by the launchers (slot = job index)
-extern thread_local const float* usseg_epi_scale[4];
-
-// per-channel-class tap masks of the quad-form transposed conv (set by the usseg_tconv_quad_* entry points for one call):
-// output channels (fwd, wgrad) or input channels (dgrad) [cls*group_ch, (cls+1)*group_ch) only use the stencil taps in mask[cls]
+// per-channel-class stencil masks of the quad-form transposed conv (usseg_tconv_quad_*): output channels (fwd, wgrad) or input
+// channels (dgrad) [cls*group_ch, (cls+1)*group_ch) only use the stencil taps in mask[cls]
 struct UssegTapMask {
   int32_t group_ch;      // 0 = no masking
   uint16_t mask[4];
 };
-extern thread_local UssegTapMask usseg_tap_mask;
+
+static inline int roundup(int a, int b) { return (a + b - 1) / b * b; }
+
+// One conv pass as the planners see it (host only): a forward pass, or a backward-data pass (flip = 1: x = dy, y = dx, operand
+// packed with in/out swapped, weight tap 8 - t at tap t).  Cin / ldx describe the pass's input, Nout / ldy its output.
+struct ConvPass {
+  const bf16_t* x; const bf16_t* w; void* y; const float* bias; const bf16_t* res;
+  const float* scale;   // per-output-channel multiplier applied before the bias (folded inference BatchNorm), or NULL
+  int B, H, W, d, Cin, ldx, Nout, ldy, ldr, Nw, Kw, ksize, act;
+  float alpha;
+  int out_f32, accumulate, flip;
+  int one_tap;          // forward 1x1 (dilation 1): may ride in a launch of 3x3 convs as a centre-tap job, operand [N][Cin] (conv_big.hip)
+  UssegTapMask mask;
+};
+// The one translation from an entry point's job (flip = 0: usseg_conv2d_fwd*, 1: usseg_conv2d_dgrad*) to a pass.
+static inline ConvPass conv_pass(const UssegConvJob& q, int flip) {
+  const UssegConvDesc& d = q.desc;
+  ConvPass p = {};
+  p.x = (const bf16_t*)q.x; p.w = (const bf16_t*)q.wp; p.y = q.y; p.res = (const bf16_t*)q.residual; p.ldr = q.ldr;
+  p.B = d.B; p.H = d.H; p.W = d.W; p.d = d.dilation; p.ksize = d.ksize;
+  p.Cin = flip ? d.Cout : d.Cin; p.ldx = flip ? d.ldy : d.ldx;
+  p.Nout = flip ? d.Cin : d.Cout; p.ldy = flip ? d.ldx : d.ldy;
+  p.Nw = roundup(p.Nout, 16); p.Kw = d.ksize * d.ksize * p.Cin;
+  p.accumulate = (d.flags & USSEG_ACCUMULATE) ? 1 : 0;
+  p.flip = flip;
+  if (!flip) {   // backward-data: no bias, no scale, no activation, bf16 output
+    p.bias = q.bias; p.scale = q.scale;
+    p.act = d.act; p.alpha = d.alpha;
+    p.out_f32 = (d.flags & USSEG_OUT_F32) ? 1 : 0;
+    p.one_tap = d.ksize == 1 && d.dilation == 1;
+  }
+  return p;
+}
 
 void usseg_set_error(const char* fmt, ...);
 #define USSEG_CHECK_ARG(cond, ...)                 \
@@ -436,22 +464,33 @@ void usseg_prof_stop(int kind, int slot, hipStream_t s);
 void usseg_launch_reduce_finish(const float* ws, int groups, int nb, int K, int Cp, int C, float scale, float* d0, float* d1, float* d2,
                                 hipStream_t s, int overwrite = 0);
 
-// 3x3 conv with an LDS halo tile (conv_halo.hip): returns 1 if it took the launch, 0 if the geometry does not fit
-int usseg_try_launch_conv_halo(const bf16_t* x, const bf16_t* w, void* y, const float* bias, const bf16_t* res, int B, int H, int W, int d,
-                               int Cin, int ldx, int Nout, int ldy, int ldr, int Nw, int Kw, int act, float alpha, int out_f32,
-                               int accumulate, int flip, hipStream_t s);
+// Planners of the 3x3 conv kernels for 1..4 independent passes in one launch (blockIdx.z = pass): 1 if they took the launch, 0 if
+// the geometry does not fit and the caller must use another kernel.  Each honours the passes' scale; the tap mask is honoured
+// by conv_big and ignored by conv_halo (masked taps carry zero weights).
+// 256-pixel tiles with double-buffered LDS-DMA stages, or the streaming kernel (conv_big.hip); 1x1 passes ride as centre-tap jobs
+int usseg_try_launch_conv_big(const ConvPass* p, int njobs, hipStream_t s);
+// 128-pixel LDS halo tiles (conv_halo.hip); 3x3 passes only
+int usseg_try_launch_conv_halo(const ConvPass* p, int njobs, hipStream_t s);
 
-// 3x3 conv, 256-pixel tiles with double-buffered LDS-DMA stages (conv_big.hip): 1 if it took the launch, 0 otherwise
-int usseg_try_launch_conv_big(const bf16_t* x, const bf16_t* w, void* y, const float* bias, const bf16_t* res, int B, int H, int W, int d,
-                              int Cin, int ldx, int Nout, int ldy, int ldr, int Nw, int Kw, int act, float alpha, int out_f32,
-                              int accumulate, int flip, hipStream_t s);
-
-int usseg_try_launch_conv_halo_multi(int njobs, const UssegConvJob* jobs, int flip, hipStream_t s);
-int usseg_try_launch_conv_big_multi(int njobs, const UssegConvJob* jobs, int flip, hipStream_t s);
-
-// 3x3 weight gradient with an LDS halo tile (wgrad_halo.hip): 1 if it took the launch, 0 otherwise
-int usseg_try_launch_wgrad_halo(const bf16_t* x, const bf16_t* dy, float* out, const WgMap& map, int B, int H, int W, int d, int Ma, int Nb,
-                                int ldx, int lddy, float* ws, int64_t ws_floats, hipStream_t s);
+// one 3x3 weight gradient on the LDS halo-tile kernel (wgrad_halo.hip)
+struct WgHaloGeom {
+  const bf16_t* x; const bf16_t* dy; float* out; WgMap map;
+  int B, H, W, d, Ma, Nb, ldx, lddy;
+  int tconv_cls = -1;      // >= 0: parity class 2a+b of a stride-2 transposed conv (x = dy tensor at 2H x 2W, dy = x tensor; see the views)
+  uint32_t tapmask = 0x1ff;
+  UssegTapMask mask = {};  // quad-form transposed conv: per-class taps of the output channels
+};
+static inline WgHaloGeom wgrad_halo_geom(const UssegConvDesc& d, const void* x, const void* dy, float* out, const WgMap& map,
+                                         const UssegTapMask& mask = {}) {
+  WgHaloGeom g = {(const bf16_t*)x, (const bf16_t*)dy, out, map, d.B, d.H, d.W, d.dilation, d.Cin, d.Cout, d.ldx, d.ldy};
+  g.mask = mask;
+  return g;
+}
+// 1..4 weight gradients of identical (B, H, W) in one launch: 1 if it took the launch, 0 if the caller must use the per-tap kernel
+int usseg_try_launch_wgrad_halo(const WgHaloGeom* g, int njobs, float* ws, int64_t ws_floats, hipStream_t s);
+// 3x3 / 1x1 weight gradient, halo-tile kernel first, then the per-tap kernel (wgrad.hip); `mask` as in WgHaloGeom
+int conv2d_wgrad_impl(const UssegConvDesc* d, const void* x, const void* dy, float* dw, const UssegWgradDst* dst, float* ws, int64_t ws_floats,
+                      const UssegTapMask& mask, usseg_stream_t stream);
 
 // deferral of the finishing reductions (defer.hip): workspace regions for producers between usseg_defer_begin and _flush
 float* usseg_defer_reduce_ws(hipStream_t s, float* caller_ws, int64_t need);
@@ -459,10 +498,8 @@ float* usseg_defer_wgrad_ws(hipStream_t s, float* caller_ws, int64_t caller_floa
 // out (identity or mapped) += sum over the split slabs ws[split][slab_floats] (wgrad_halo.hip)
 void usseg_launch_wgrad_finish(const float* ws, int splits, int64_t slab_floats, float* out, const WgMap& map, int Ma, int Nb, hipStream_t s);
 
-int usseg_try_launch_wgrad_halo_multi(int njobs, const UssegWgradJob* jobs, float* ws, int64_t ws_floats, hipStream_t s);
 // stride-2 transposed-conv weight gradient as four tap-masked parity-class jobs of the halo-tile kernel (wgrad_halo.hip): 1 if taken
 int usseg_try_launch_tconv_wgrad_halo(const bf16_t* x, const bf16_t* dy, const WgMap& map, int B, int H, int W, int Cin, int Cout, int ldx,
                                       int lddy, int k, float* ws, int64_t ws_floats, hipStream_t s);
 
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
-static inline int roundup(int a, int b) { return (a + b - 1) / b * b; }

@@ -416,12 +416,11 @@ __global__ __launch_bounds__(256, 2) void conv_stream_kernel(const BigParams P, 
 #endif
 }
 
-// Fills a job from a conv geometry; returns 0 if the geometry does not fit the 256-pixel tiling.
-static int big_fill_job(BigJob& p, const bf16_t* x, const bf16_t* w, void* y, const float* bias, const bf16_t* res, int B, int H, int W,
-                        int d, int Cin, int ldx, int Nout, int ldy, int ldr, int Nw, int Kw, int act, float alpha, int out_f32,
-                        int accumulate, int flip, int PX, int any_cin = 0) {
+// Fills a job from a pass for a PX-pixel tile; returns 0 if the pass does not fit that tiling.
+static int big_fill_job(BigJob& p, const ConvPass& g, int PX, int any_cin = 0) {
   static const int min_cin = getenv("USSEG_BIG_MIN_CIN") ? atoi(getenv("USSEG_BIG_MIN_CIN")) : 33;
-  if (d < 1 || H % d || W % d || (Cin < min_cin && !any_cin)) return 0;
+  const int B = g.B, H = g.H, W = g.W, d = g.d, ldx = g.ldx;
+  if (d < 1 || H % d || W % d || (g.Cin < min_cin && !any_cin)) return 0;
   const int Hl = H / d, Wl = W / d;
   int PW;
   if (Wl % 16 == 0) PW = 16;
@@ -433,20 +432,23 @@ static int big_fill_job(BigJob& p, const bf16_t* x, const bf16_t* w, void* y, co
   const int NV = PX / (PH * PW);
   const int NHP = NV * (PH + 2) * (PW + 2);
   if (NHP > (PX == 256 ? 576 : 288)) return 0;
-  if ((int64_t)B * H * W * ldx >= (1ll << 30) || (int64_t)Nw * Kw >= (1ll << 30)) return 0;   // byte offsets < 2^31
+  if ((int64_t)B * H * W * ldx >= (1ll << 30) || (int64_t)g.Nw * g.Kw >= (1ll << 30)) return 0;   // byte offsets < 2^31
   if ((int64_t)B * H * W >= (1ll << 23) || (int64_t)B * d * d * (Hl / PH) * (Wl / PW) >= (1ll << 20)) return 0;   // signed 24-bit multiplies / fdiv() in the kernels' tile decodes
   p = {};
-  p.x = x; p.w = w; p.y = y; p.bias = bias; p.res = res;
+  p.x = g.x; p.w = g.w; p.y = g.y; p.bias = g.bias; p.scale = g.scale; p.res = g.res;
   p.H = H; p.W = W; p.d = d; p.Hl = Hl; p.Wl = Wl; p.PH = PH; p.PW = PW; p.NV = NV;
   p.tiles_x = Wl / PW;
   p.tiles_per_v = (Hl / PH) * p.tiles_x;
   p.npatches = B * d * d * p.tiles_per_v;
-  p.ldx = ldx; p.ldy = ldy; p.ldr = ldr; p.Cin = Cin; p.nchunks = (Cin + 31) / 32;
-  p.Nw = Nw; p.Kw = Kw; p.Nout = Nout; p.act = act; p.alpha = alpha; p.out_f32 = out_f32; p.accumulate = accumulate; p.flip = flip;
+  p.ldx = ldx; p.ldy = g.ldy; p.ldr = g.ldr; p.Cin = g.Cin; p.nchunks = (g.Cin + 31) / 32;
+  p.Nw = g.Nw; p.Kw = g.Kw; p.Nout = g.Nout; p.act = g.act; p.alpha = g.alpha; p.out_f32 = g.out_f32; p.accumulate = g.accumulate; p.flip = g.flip;
   p.gx = (p.npatches + NV - 1) / NV;
   p.x_bytes = (uint32_t)((int64_t)B * H * W * ldx * 2);
-  p.w_bytes = (uint32_t)((int64_t)Nw * Kw * 2);
+  p.w_bytes = (uint32_t)((int64_t)g.Nw * g.Kw * 2);
   p.npa = (NHP + 15) / 16;
+  p.mask_ch = g.mask.group_ch;
+  for (int c = 0; c < 4; ++c) p.tapmask[c] = g.mask.mask[c];
+  p.one_tap = g.one_tap;
   return 1;
 }
 
@@ -500,12 +502,6 @@ static void big_launch(BigParams& P, int njobs, int nt, int PX, hipStream_t s, i
   usseg_prof_stop(1, slot, s);
 }
 
-struct BigGeom {   // what big_fill_job needs, so that a job can be re-filled for another pixel tile
-  const bf16_t* x; const bf16_t* w; void* y; const float* bias; const bf16_t* res;
-  int B, H, W, d, Cin, ldx, Nout, ldy, ldr, Nw, Kw, act; float alpha; int out_f32, accumulate, flip;
-  int one_tap = 0;
-};
-
 template <int NT, int NS, bool RES = false>
 static void stream_launch_t(const BigParams& P, dim3 grid, size_t dyn, int fast_wait, hipStream_t s) {
   static bool attr_done = false;
@@ -523,7 +519,7 @@ struct StreamPlan {
   size_t dyn;
   unsigned wgx, gy;
 };
-static int stream_plan(const BigGeom& g, const float* epi_scale, StreamPlan& sp) {
+static int stream_plan(const ConvPass& g, StreamPlan& sp) {
   static const int mode = getenv("USSEG_STREAM") ? atoi(getenv("USSEG_STREAM")) : 1;
   static const int px_env = getenv("USSEG_STREAM_PX") ? atoi(getenv("USSEG_STREAM_PX")) : 0;
   // read per call (not cached): the parity tests use these two to drive small shapes through many steps per workgroup
@@ -531,10 +527,10 @@ static int stream_plan(const BigGeom& g, const float* epi_scale, StreamPlan& sp)
   const char* wgx_env = getenv("USSEG_STREAM_WGX");
   const int min_steps = ms_env ? atoi(ms_env) : 1;
   static const int occ_env = getenv("USSEG_STREAM_OCC") ? atoi(getenv("USSEG_STREAM_OCC")) : 0;
-  if (!mode || usseg_tap_mask.group_ch) return 0;
+  if (!mode || g.mask.group_ch) return 0;
   // its epilogue is bias + activation + bf16 store (no loads inside the streaming loop), or the RES variant with a preloaded residual
   static const int res_env = getenv("USSEG_STREAM_RES") ? atoi(getenv("USSEG_STREAM_RES")) : 1;
-  if (g.out_f32 || g.accumulate || (!g.flip && epi_scale)) return 0;
+  if (g.out_f32 || g.accumulate || g.scale) return 0;
   if (g.res && (!res_env || (g.ldr & 3))) return 0;
   const int nt = nt_for(g.Nout);
   const int nchunks = (g.Cin + 31) / 32;
@@ -544,12 +540,9 @@ static int stream_plan(const BigGeom& g, const float* epi_scale, StreamPlan& sp)
   BigJob& p = sp.job;
   for (int PX = 256; PX >= 128; PX >>= 1) {
     if (px_env && PX != px_env) continue;
-    if (!big_fill_job(p, g.x, g.w, g.y, g.bias, g.res, g.B, g.H, g.W, g.d, g.Cin, g.ldx, g.Nout, g.ldy, g.ldr, g.Nw, g.Kw, g.act, g.alpha,
-                      g.out_f32, g.accumulate, g.flip, PX, 1))
-      continue;
+    if (!big_fill_job(p, g, PX, 1)) continue;
     if (p.NV != 1 || p.PW != 16) continue;
     if (g.one_tap && (nt == 4 || g.res)) return 0;      // (those instantiations carry no centre-tap path: conv_big takes the launch)
-    p.one_tap = g.one_tap;
     const size_t dyn = wbytes + 2 * (size_t)p.npa * 1024;
     int occ = (int)((160 * 1024 - 2048) / (dyn + 1024));
     if (occ > 4) occ = 4;
@@ -603,21 +596,21 @@ static bool stream_same_plan(const StreamPlan& a, const StreamPlan& b) {
   return a.nt == b.nt && a.PX == b.PX && a.res == b.res && a.fast_wait == b.fast_wait && a.dyn == b.dyn && a.wgx == b.wgx && a.gy == b.gy;
 }
 
-// Chooses the tile (pixels per workgroup, channel tile) and launches; 0 if no tiling fits or the launch would be too small.
-static int big_plan_and_launch(const BigGeom* g, int njobs, hipStream_t s) {
+// Chooses the kernel and the tile (pixels per workgroup, channel tile) and launches; 0 if no tiling fits or the launch would be too small.
+int usseg_try_launch_conv_big(const ConvPass* g, int njobs, hipStream_t s) {
   static const int mode = getenv("USSEG_BIG") ? atoi(getenv("USSEG_BIG")) : 1;
   static const int px_env = getenv("USSEG_BIG_PX") ? atoi(getenv("USSEG_BIG_PX")) : 0;
   static const int nt_env = getenv("USSEG_BIG_NT") ? atoi(getenv("USSEG_BIG_NT")) : 0;
   static const int min_wg = getenv("USSEG_BIG_MIN_WG") ? atoi(getenv("USSEG_BIG_MIN_WG")) : 128;
   static const int wg_min = getenv("USSEG_BIG_WG_TILE") ? atoi(getenv("USSEG_BIG_WG_TILE")) : 512;
-  if (!mode) return 0;
+  if (!mode || njobs < 1 || njobs > 4) return 0;
   {   // HBM-bound jobs whose weights fit in LDS: the streaming kernel, one full-chip launch per job
     static const int multi = getenv("USSEG_STREAM_MULTI") ? atoi(getenv("USSEG_STREAM_MULTI")) : 1;
     const char* merge_env = getenv("USSEG_STREAM_MERGE");      // read per call: the parity test flips it inside one process
     const int merge = merge_env ? atoi(merge_env) : 1;         // jobs of one plan in ONE launch (0: a launch per job)
     bool all = (njobs == 1 || multi) && njobs <= 4;
     StreamPlan sp[4];
-    for (int j = 0; j < njobs && all; ++j) all = stream_plan(g[j], usseg_epi_scale[j], sp[j]) != 0;
+    for (int j = 0; j < njobs && all; ++j) all = stream_plan(g[j], sp[j]) != 0;
     if (all) {
       for (int j = 0; j < njobs;) {
         int n = 1;
@@ -638,9 +631,7 @@ static int big_plan_and_launch(const BigGeom* g, int njobs, hipStream_t s) {
   for (int PX = 256; PX >= 128 && !best_px; PX >>= 1) {
     if (px_env && PX != px_env) continue;
     bool ok = true;
-    for (int j = 0; j < njobs && ok; ++j)
-      ok = big_fill_job(P.job[j], g[j].x, g[j].w, g[j].y, g[j].bias, g[j].res, g[j].B, g[j].H, g[j].W, g[j].d, g[j].Cin, g[j].ldx, g[j].Nout,
-                        g[j].ldy, g[j].ldr, g[j].Nw, g[j].Kw, g[j].act, g[j].alpha, g[j].out_f32, g[j].accumulate, g[j].flip, PX);
+    for (int j = 0; j < njobs && ok; ++j) ok = big_fill_job(P.job[j], g[j], PX);
     if (!ok) continue;
     for (int nt = nt_max; nt >= 1; nt >>= 1) {
       if (nt_env && nt != nt_env) continue;
@@ -666,8 +657,7 @@ static int big_plan_and_launch(const BigGeom* g, int njobs, hipStream_t s) {
       bool ok = true;
       int64_t wg = 0;
       for (int j = 0; j < njobs && ok; ++j) {
-        ok = big_fill_job(P.job[j], g[j].x, g[j].w, g[j].y, g[j].bias, g[j].res, g[j].B, g[j].H, g[j].W, g[j].d, g[j].Cin, g[j].ldx, g[j].Nout,
-                          g[j].ldy, g[j].ldr, g[j].Nw, g[j].Kw, g[j].act, g[j].alpha, g[j].out_f32, g[j].accumulate, g[j].flip, 256);
+        ok = big_fill_job(P.job[j], g[j], 256);
         if (ok) wg += (int64_t)P.job[j].gx * ((P.job[j].Nout + 16 * best_nt - 1) / (16 * best_nt));
       }
       // measured: it pays with the 64-channel tile (36 KB weight stage); with the narrower tiles the planner falls back to
@@ -676,46 +666,9 @@ static int big_plan_and_launch(const BigGeom* g, int njobs, hipStream_t s) {
     }
   }
   for (int j = 0; j < njobs; ++j)
-    if (!big_fill_job(P.job[j], g[j].x, g[j].w, g[j].y, g[j].bias, g[j].res, g[j].B, g[j].H, g[j].W, g[j].d, g[j].Cin, g[j].ldx, g[j].Nout,
-                      g[j].ldy, g[j].ldr, g[j].Nw, g[j].Kw, g[j].act, g[j].alpha, g[j].out_f32, g[j].accumulate, g[j].flip, best_px))
-      return 0;
-  for (int j = 0; j < njobs; ++j) { P.job[j].scale = g[j].flip ? nullptr : usseg_epi_scale[j]; P.job[j].one_tap = g[j].one_tap; }
-  if (usseg_tap_mask.group_ch) {
-    // the tile (fwd: 16*nt output channels; dgrad: one 32-channel K chunk) must lie inside one class
-    const int unit = g[0].flip ? 32 : 16 * best_nt;
-    if (njobs != 1 || usseg_tap_mask.group_ch % unit) return 0;
-    P.job[0].mask_ch = usseg_tap_mask.group_ch;
-    for (int c = 0; c < 4; ++c) P.job[0].tapmask[c] = usseg_tap_mask.mask[c];
-  }
+    if (!big_fill_job(P.job[j], g[j], best_px)) return 0;
+  // a masked pass: the tile (fwd: 16*nt output channels; dgrad: one 32-channel K chunk) must lie inside one class
+  if (g[0].mask.group_ch && (njobs != 1 || g[0].mask.group_ch % (g[0].flip ? 32 : 16 * best_nt))) return 0;
   big_launch(P, njobs, best_nt, best_px, s, w8);
   return 1;
-}
-
-// Returns 1 and launches if the geometry fits, 0 if the caller must use another kernel.
-int usseg_try_launch_conv_big(const bf16_t* x, const bf16_t* w, void* y, const float* bias, const bf16_t* res, int B, int H, int W, int d,
-                              int Cin, int ldx, int Nout, int ldy, int ldr, int Nw, int Kw, int act, float alpha, int out_f32,
-                              int accumulate, int flip, hipStream_t s) {
-  BigGeom g = {x, w, y, bias, res, B, H, W, d, Cin, ldx, Nout, ldy, ldr, Nw, Kw, act, alpha, out_f32, accumulate, flip};
-  return big_plan_and_launch(&g, 1, s);
-}
-
-int usseg_try_launch_conv_big_multi(int njobs, const UssegConvJob* jobs, int flip, hipStream_t s) {
-  if (njobs < 1 || njobs > 4) return 0;
-  BigGeom g[4];
-  for (int j = 0; j < njobs; ++j) {
-    const UssegConvJob& q = jobs[j];
-    const UssegConvDesc& d = q.desc;
-    const int out_f32 = (d.flags & USSEG_OUT_F32) ? 1 : 0, acc = (d.flags & USSEG_ACCUMULATE) ? 1 : 0;
-    if (flip)
-      g[j] = {(const bf16_t*)q.x, (const bf16_t*)q.wp, q.y, nullptr, (const bf16_t*)q.residual, d.B, d.H, d.W, d.dilation, d.Cout, d.ldy,
-              d.Cin, d.ldx, q.ldr, roundup(d.Cin, 16), 9 * d.Cout, USSEG_ACT_NONE, 0.f, 0, acc, 1};
-    else if (d.ksize == 1) {     // rides along as a centre-tap-only job of the 3x3 geometry (dilation 1); its operand is the 1x1 conv's own [N][Cin]
-      g[j] = {(const bf16_t*)q.x, (const bf16_t*)q.wp, q.y, q.bias, (const bf16_t*)q.residual, d.B, d.H, d.W, 1, d.Cin, d.ldx,
-              d.Cout, d.ldy, q.ldr, roundup(d.Cout, 16), d.Cin, d.act, d.alpha, out_f32, acc, 0};
-      g[j].one_tap = 1;
-    } else
-      g[j] = {(const bf16_t*)q.x, (const bf16_t*)q.wp, q.y, q.bias, (const bf16_t*)q.residual, d.B, d.H, d.W, d.dilation, d.Cin, d.ldx,
-              d.Cout, d.ldy, q.ldr, roundup(d.Cout, 16), 9 * d.Cin, d.act, d.alpha, out_f32, acc, 0};
-  }
-  return big_plan_and_launch(g, njobs, s);
 }

@@ -331,10 +331,9 @@ __global__ __launch_bounds__(256, NT <= 1 ? 4 : (NT == 2 ? 3 : 2)) void conv_hal
   }
 }
 
-// Fills p from a conv geometry; returns 0 if the geometry does not fit the halo tiling.
-static int halo_fill(HaloParams& p, const bf16_t* x, const bf16_t* w, void* y, const float* bias, const bf16_t* res, int B, int H, int W, int d,
-                     int Cin, int ldx, int Nout, int ldy, int ldr, int Nw, int Kw, int act, float alpha, int out_f32, int accumulate,
-                     int flip) {
+// Fills p from a pass; returns 0 if the pass does not fit the halo tiling.
+static int halo_fill(HaloParams& p, const ConvPass& g) {
+  const int B = g.B, H = g.H, W = g.W, d = g.d;
   if (d < 1 || H % d || W % d) return 0;
   const int Hl = H / d, Wl = W / d;
   int PW;
@@ -346,15 +345,15 @@ static int halo_fill(HaloParams& p, const bf16_t* x, const bf16_t* w, void* y, c
   if (Hl % PH || (PH * PW) % 16) return 0;
   const int NV = 128 / (PH * PW);
   if (NV * (PH + 2) * (PW + 2) > 288) return 0;
-  if ((int64_t)B * H * W * ldx >= (1ll << 31)) return 0;
+  if ((int64_t)B * H * W * g.ldx >= (1ll << 31)) return 0;
   p = {};
-  p.x = x; p.w = w; p.y = y; p.bias = bias; p.res = res;
+  p.x = g.x; p.w = g.w; p.y = g.y; p.bias = g.bias; p.scale = g.scale; p.res = g.res;
   p.B = B; p.H = H; p.W = W; p.d = d; p.Hl = Hl; p.Wl = Wl; p.PH = PH; p.PW = PW; p.NV = NV;
   p.tiles_x = Wl / PW;
   p.tiles_per_v = (Hl / PH) * p.tiles_x;
   p.npatches = B * d * d * p.tiles_per_v;
-  p.ldx = ldx; p.ldy = ldy; p.ldr = ldr; p.Cin = Cin; p.nchunks = (Cin + 31) / 32;
-  p.Nw = Nw; p.Kw = Kw; p.Nout = Nout; p.act = act; p.alpha = alpha; p.out_f32 = out_f32; p.accumulate = accumulate; p.flip = flip;
+  p.ldx = g.ldx; p.ldy = g.ldy; p.ldr = g.ldr; p.Cin = g.Cin; p.nchunks = (g.Cin + 31) / 32;
+  p.Nw = g.Nw; p.Kw = g.Kw; p.Nout = g.Nout; p.act = g.act; p.alpha = g.alpha; p.out_f32 = g.out_f32; p.accumulate = g.accumulate; p.flip = g.flip;
   return 1;
 }
 
@@ -416,33 +415,13 @@ static int halo_launch(HaloMulti& P, int njobs, hipStream_t s) {
   return 1;
 }
 
-// Returns 1 and launches if the geometry fits the halo kernel, 0 if the caller must use the gather kernel.
-int usseg_try_launch_conv_halo(const bf16_t* x, const bf16_t* w, void* y, const float* bias, const bf16_t* res, int B, int H, int W, int d,
-                               int Cin, int ldx, int Nout, int ldy, int ldr, int Nw, int Kw, int act, float alpha, int out_f32,
-                               int accumulate, int flip, hipStream_t s) {
-  static const int disabled = getenv("USSEG_NO_HALO") != nullptr;
-  if (disabled) return 0;
-  HaloMulti P;
-  if (!halo_fill(P.job[0], x, w, y, bias, res, B, H, W, d, Cin, ldx, Nout, ldy, ldr, Nw, Kw, act, alpha, out_f32, accumulate, flip)) return 0;
-  P.job[0].scale = flip ? nullptr : usseg_epi_scale[0];
-  return halo_launch(P, 1, s);
-}
-
-// Multi-job form (usseg_conv2d_fwd_multi / _dgrad_multi): every job must fit and share the grid shape.
-int usseg_try_launch_conv_halo_multi(int njobs, const UssegConvJob* jobs, int flip, hipStream_t s) {
+// Returns 1 and launches if every pass fits the halo kernel and they share the grid shape, 0 if the caller must use another kernel.
+// (The passes' tap masks are ignored: masked taps carry zero weights.)
+int usseg_try_launch_conv_halo(const ConvPass* g, int njobs, hipStream_t s) {
   static const int disabled = getenv("USSEG_NO_HALO") != nullptr;
   if (disabled || njobs < 1 || njobs > 4) return 0;
   HaloMulti P;
-  for (int j = 0; j < njobs; ++j) {
-    const UssegConvJob& q = jobs[j];
-    const UssegConvDesc& d = q.desc;
-    const int out_f32 = (d.flags & USSEG_OUT_F32) ? 1 : 0, acc = (d.flags & USSEG_ACCUMULATE) ? 1 : 0;
-    int ok = flip ? halo_fill(P.job[j], (const bf16_t*)q.x, (const bf16_t*)q.wp, q.y, nullptr, (const bf16_t*)q.residual, d.B, d.H, d.W,
-                              d.dilation, d.Cout, d.ldy, d.Cin, d.ldx, q.ldr, roundup(d.Cin, 16), 9 * d.Cout, USSEG_ACT_NONE, 0.f, 0, acc, 1)
-                  : halo_fill(P.job[j], (const bf16_t*)q.x, (const bf16_t*)q.wp, q.y, q.bias, (const bf16_t*)q.residual, d.B, d.H, d.W,
-                              d.dilation, d.Cin, d.ldx, d.Cout, d.ldy, q.ldr, roundup(d.Cout, 16), 9 * d.Cin, d.act, d.alpha, out_f32, acc, 0);
-    if (!ok) return 0;
-    P.job[j].scale = flip ? nullptr : usseg_epi_scale[j];
-  }
+  for (int j = 0; j < njobs; ++j)
+    if (!halo_fill(P.job[j], g[j])) return 0;
   return halo_launch(P, njobs, s);
 }

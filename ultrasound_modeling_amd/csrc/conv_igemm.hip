@@ -710,125 +710,147 @@ static int check_desc(const UssegConvDesc* d, bool tconv) {
   return USSEG_OK;
 }
 
-extern "C" int usseg_conv2d_fwd(const UssegConvDesc* d, const void* x, const void* wp, const float* bias,
-                                const void* residual, int32_t ldr, void* y, usseg_stream_t stream) {
+// The entry points' own checks of one conv job (flip = 1: backward-data).
+static int check_conv(const UssegConvDesc* d, int flip, bool ptrs_ok, const char* null_msg) {
   int rc = check_desc(d, false);
   if (rc) return rc;
-  USSEG_CHECK_ARG(x && wp && y, "null pointer");
-  if (d->ksize == 3 &&
-      usseg_try_launch_conv_big((const bf16_t*)x, (const bf16_t*)wp, y, bias, (const bf16_t*)residual, d->B, d->H, d->W, d->dilation, d->Cin,
-                                d->ldx, d->Cout, d->ldy, ldr, roundup(d->Cout, 16), 9 * d->Cin, d->act, d->alpha,
-                                (d->flags & USSEG_OUT_F32) ? 1 : 0, (d->flags & USSEG_ACCUMULATE) ? 1 : 0, 0, (hipStream_t)stream))
-    return usseg_check_launch("conv_big");
-  if (d->ksize == 3 &&
-      usseg_try_launch_conv_halo((const bf16_t*)x, (const bf16_t*)wp, y, bias, (const bf16_t*)residual, d->B, d->H, d->W, d->dilation, d->Cin,
-                                 d->ldx, d->Cout, d->ldy, ldr, roundup(d->Cout, 16), 9 * d->Cin, d->act, d->alpha,
-                                 (d->flags & USSEG_OUT_F32) ? 1 : 0, (d->flags & USSEG_ACCUMULATE) ? 1 : 0, 0, (hipStream_t)stream))
-    return usseg_check_launch("conv_halo");
+  USSEG_CHECK_ARG(ptrs_ok, "%s", null_msg);
+  if (flip) USSEG_CHECK_ARG(!(d->flags & USSEG_OUT_F32) && d->Cout % 8 == 0, "dgrad needs bf16 dy with Cout % 8 == 0");
+  return USSEG_OK;
+}
+
+// The gather GEMM of a pass: y[p] uses x[p + off_t], so backward-data gathers dy[q - off_t] with the same W[t].
+static IgemmParams igemm_conv(const ConvPass& c) {
   IgemmParams p = {};
-  p.x = (const bf16_t*)x; p.w = (const bf16_t*)wp; p.y = y; p.bias = bias; p.res = (const bf16_t*)residual; p.ldr = ldr;
-  p.scale = usseg_epi_scale[0];
-  p.B = d->B; p.Hg = d->H; p.Wg = d->W; p.M = (int64_t)d->B * d->H * d->W;
-  p.Hi = d->H; p.Wi = d->W; p.ldx = d->ldx; p.isy = p.isx = 1;
-  p.Ho = d->H; p.Wo = d->W; p.ldy = d->ldy; p.osy = p.osx = 1; p.oay = p.oax = 0;
-  p.cpt = d->Cin / 8;
-  const int k = d->ksize, half = k / 2;
+  p.x = c.x; p.w = c.w; p.y = c.y; p.bias = c.bias; p.scale = c.scale; p.res = c.res; p.ldr = c.ldr;
+  p.B = c.B; p.Hg = c.H; p.Wg = c.W; p.M = (int64_t)c.B * c.H * c.W;
+  p.Hi = c.H; p.Wi = c.W; p.ldx = c.ldx; p.isy = p.isx = 1;
+  p.Ho = c.H; p.Wo = c.W; p.ldy = c.ldy; p.osy = p.osx = 1; p.oay = p.oax = 0;
+  p.cpt = c.Cin / 8;
+  const int k = c.ksize, half = k / 2, step = c.flip ? -c.d : c.d;
   p.ntaps = k * k;
   for (int kh = 0; kh < k; ++kh)
     for (int kw = 0; kw < k; ++kw) {
       int t = kh * k + kw;
-      p.tap_dy[t] = (int16_t)((kh - half) * d->dilation);
-      p.tap_dx[t] = (int16_t)((kw - half) * d->dilation);
+      p.tap_dy[t] = (int16_t)((kh - half) * step);
+      p.tap_dx[t] = (int16_t)((kw - half) * step);
       p.tap_w[t] = (int16_t)t;
     }
   p.nchunks = p.ntaps * p.cpt;
-  p.Nw = roundup(d->Cout, 16); p.Kw = p.ntaps * d->Cin; p.Nout = d->Cout;
-  p.act = d->act; p.alpha = d->alpha; p.out_f32 = (d->flags & USSEG_OUT_F32) ? 1 : 0;
-  p.accumulate = (d->flags & USSEG_ACCUMULATE) ? 1 : 0;
-  return launch_igemm(p, (hipStream_t)stream);
+  p.Nw = c.Nw; p.Kw = c.Kw; p.Nout = c.Nout;
+  p.act = c.act; p.alpha = c.alpha; p.out_f32 = c.out_f32; p.accumulate = c.accumulate;
+  return p;
 }
 
-extern "C" int usseg_conv2d_dgrad(const UssegConvDesc* d, const void* dy, const void* wp, const void* residual,
-                                  int32_t ldr, void* dx, usseg_stream_t stream) {
-  int rc = check_desc(d, false);
-  if (rc) return rc;
-  USSEG_CHECK_ARG(dy && wp && dx, "null pointer");
-  USSEG_CHECK_ARG(!(d->flags & USSEG_OUT_F32) && d->Cout % 8 == 0, "dgrad needs bf16 dy with Cout % 8 == 0");
-  if (d->ksize == 3 &&
-      usseg_try_launch_conv_big((const bf16_t*)dy, (const bf16_t*)wp, dx, nullptr, (const bf16_t*)residual, d->B, d->H, d->W, d->dilation,
-                                d->Cout, d->ldy, d->Cin, d->ldx, ldr, roundup(d->Cin, 16), 9 * d->Cout, USSEG_ACT_NONE, 0.f, 0,
-                                (d->flags & USSEG_ACCUMULATE) ? 1 : 0, 1, (hipStream_t)stream))
-    return usseg_check_launch("conv_big_dgrad");
-  if (d->ksize == 3 &&
-      usseg_try_launch_conv_halo((const bf16_t*)dy, (const bf16_t*)wp, dx, nullptr, (const bf16_t*)residual, d->B, d->H, d->W, d->dilation,
-                                 d->Cout, d->ldy, d->Cin, d->ldx, ldr, roundup(d->Cin, 16), 9 * d->Cout, USSEG_ACT_NONE, 0.f, 0,
-                                 (d->flags & USSEG_ACCUMULATE) ? 1 : 0, 1, (hipStream_t)stream))
-    return usseg_check_launch("conv_halo_dgrad");
-  IgemmParams p = {};
-  p.x = (const bf16_t*)dy; p.w = (const bf16_t*)wp; p.y = dx; p.bias = nullptr; p.res = (const bf16_t*)residual; p.ldr = ldr;
-  p.B = d->B; p.Hg = d->H; p.Wg = d->W; p.M = (int64_t)d->B * d->H * d->W;
-  p.Hi = d->H; p.Wi = d->W; p.ldx = d->ldy; p.isy = p.isx = 1;
-  p.Ho = d->H; p.Wo = d->W; p.ldy = d->ldx; p.osy = p.osx = 1; p.oay = p.oax = 0;
-  p.cpt = d->Cout / 8;
-  const int k = d->ksize, half = k / 2;
-  p.ntaps = k * k;
-  for (int kh = 0; kh < k; ++kh)
-    for (int kw = 0; kw < k; ++kw) {
-      int t = kh * k + kw;  // y[p] uses x[p + off_t]  =>  dx[q] gathers dy[q - off_t] with the same W[t]
-      p.tap_dy[t] = (int16_t)(-(kh - half) * d->dilation);
-      p.tap_dx[t] = (int16_t)(-(kw - half) * d->dilation);
-      p.tap_w[t] = (int16_t)t;
-    }
-  p.nchunks = p.ntaps * p.cpt;
-  p.Nw = roundup(d->Cin, 16); p.Kw = p.ntaps * d->Cout; p.Nout = d->Cin;
-  p.act = USSEG_ACT_NONE; p.alpha = 0.f; p.out_f32 = 0; p.accumulate = (d->flags & USSEG_ACCUMULATE) ? 1 : 0;
-  return launch_igemm(p, (hipStream_t)stream);
-}
-
-static int conv_multi(int32_t njobs, const UssegConvJob* jobs, int flip, usseg_stream_t stream) {
-  USSEG_CHECK_ARG(jobs && njobs >= 1 && njobs <= 4, "conv multi: 1 <= njobs <= 4");
-  bool all3 = true;     // every job a 3x3 - or, forward only, a 1x1 beside at least one 3x3 (it rides along as a centre-tap job: conv_big.hip)
+// Runs 1..4 independent passes.  Several of them share one launch of conv_big or conv_halo when every pass is a 3x3 or a forward
+// 1x1 riding along as a centre-tap job (conv_big only), at least one a 3x3; otherwise each pass takes the first of conv_big,
+// conv_halo (3x3 only) and the gather GEMM that fits.
+static int run_convs(const ConvPass* p, int n, hipStream_t s) {
+  bool all3 = true;
   int n3 = 0, n1 = 0;
-  for (int j = 0; j < njobs; ++j) {
-    int rc = check_desc(&jobs[j].desc, false);
-    if (rc) return rc;
-    USSEG_CHECK_ARG(jobs[j].x && jobs[j].wp && jobs[j].y, "conv multi: null pointer");
-    if (flip) USSEG_CHECK_ARG(!(jobs[j].desc.flags & USSEG_OUT_F32) && jobs[j].desc.Cout % 8 == 0, "dgrad needs bf16 dy with Cout % 8 == 0");
-    all3 = all3 && (jobs[j].desc.ksize == 3 || (jobs[j].desc.ksize == 1 && !flip && jobs[j].desc.dilation == 1));
-    n3 += jobs[j].desc.ksize == 3; n1 += jobs[j].desc.ksize == 1;
+  for (int j = 0; j < n; ++j) {
+    all3 = all3 && (p[j].ksize == 3 || p[j].one_tap);
+    n3 += p[j].ksize == 3; n1 += p[j].ksize == 1;
   }
-  all3 = all3 && n3 >= 1;
-  struct ScaleGuard {   // the per-job epilogue multipliers are visible to the launchers only during this call
-    ~ScaleGuard() { for (int j = 0; j < 4; ++j) usseg_epi_scale[j] = nullptr; }
-  } guard;
-  if (njobs > 1 && all3) {
-    for (int j = 0; j < njobs; ++j) usseg_epi_scale[j] = flip ? nullptr : jobs[j].scale;
-    if (usseg_try_launch_conv_big_multi(njobs, jobs, flip, (hipStream_t)stream)) return usseg_check_launch("conv_big_multi");
-    if (n1 == 0 && usseg_try_launch_conv_halo_multi(njobs, jobs, flip, (hipStream_t)stream)) return usseg_check_launch("conv_halo_multi");
+  if (n > 1 && all3 && n3 >= 1) {
+    if (usseg_try_launch_conv_big(p, n, s)) return usseg_check_launch("conv_big_multi");
+    if (n1 == 0 && usseg_try_launch_conv_halo(p, n, s)) return usseg_check_launch("conv_halo_multi");
   }
-  for (int j = 0; j < njobs; ++j) {
-    const UssegConvJob& q = jobs[j];
-    for (int k = 0; k < 4; ++k) usseg_epi_scale[k] = nullptr;
-    usseg_epi_scale[0] = flip ? nullptr : q.scale;
-    int rc = flip ? usseg_conv2d_dgrad(&q.desc, q.x, q.wp, q.residual, q.ldr, q.y, stream)
-                  : usseg_conv2d_fwd(&q.desc, q.x, q.wp, q.bias, q.residual, q.ldr, q.y, stream);
+  for (int j = 0; j < n; ++j) {
+    int rc;
+    if (p[j].ksize == 3 && usseg_try_launch_conv_big(p + j, 1, s)) rc = usseg_check_launch(p[j].flip ? "conv_big_dgrad" : "conv_big");
+    else if (p[j].ksize == 3 && usseg_try_launch_conv_halo(p + j, 1, s)) rc = usseg_check_launch(p[j].flip ? "conv_halo_dgrad" : "conv_halo");
+    else rc = launch_igemm(igemm_conv(p[j]), s);
     if (rc) return rc;
   }
   return USSEG_OK;
 }
+
+extern "C" int usseg_conv2d_fwd(const UssegConvDesc* d, const void* x, const void* wp, const float* bias,
+                                const void* residual, int32_t ldr, void* y, usseg_stream_t stream) {
+  int rc = check_conv(d, 0, x && wp && y, "null pointer");
+  if (rc) return rc;
+  const ConvPass p = conv_pass({*d, x, wp, bias, residual, ldr, 0, y, nullptr}, 0);
+  return run_convs(&p, 1, (hipStream_t)stream);
+}
+
+extern "C" int usseg_conv2d_dgrad(const UssegConvDesc* d, const void* dy, const void* wp, const void* residual,
+                                  int32_t ldr, void* dx, usseg_stream_t stream) {
+  int rc = check_conv(d, 1, dy && wp && dx, "null pointer");
+  if (rc) return rc;
+  const ConvPass p = conv_pass({*d, dy, wp, nullptr, residual, ldr, 0, dx, nullptr}, 1);
+  return run_convs(&p, 1, (hipStream_t)stream);
+}
+
 extern "C" int usseg_conv2d_fwd_affine(const UssegConvDesc* d, const void* x, const void* wp, const float* scale, const float* shift,
                                        const void* residual, int32_t ldr, void* y, usseg_stream_t stream) {
   USSEG_CHECK_ARG(scale && shift && ((((uintptr_t)scale) | ((uintptr_t)shift)) & 15) == 0, "conv2d_fwd_affine: scale/shift must be non-null, 16-byte aligned");
-  usseg_epi_scale[0] = scale;
-  int rc = usseg_conv2d_fwd(d, x, wp, shift, residual, ldr, y, stream);
-  usseg_epi_scale[0] = nullptr;
-  return rc;
+  int rc = check_conv(d, 0, x && wp && y, "null pointer");
+  if (rc) return rc;
+  const ConvPass p = conv_pass({*d, x, wp, shift, residual, ldr, 0, y, scale}, 0);
+  return run_convs(&p, 1, (hipStream_t)stream);
+}
+
+static int conv_multi(int32_t njobs, const UssegConvJob* jobs, int flip, usseg_stream_t stream) {
+  USSEG_CHECK_ARG(jobs && njobs >= 1 && njobs <= 4, "conv multi: 1 <= njobs <= 4");
+  ConvPass p[4];
+  for (int j = 0; j < njobs; ++j) {
+    const UssegConvJob& q = jobs[j];
+    int rc = check_conv(&q.desc, flip, q.x && q.wp && q.y, "conv multi: null pointer");
+    if (rc) return rc;
+    p[j] = conv_pass(q, flip);
+  }
+  return run_convs(p, njobs, (hipStream_t)stream);
 }
 extern "C" int usseg_conv2d_fwd_multi(int32_t njobs, const UssegConvJob* jobs, usseg_stream_t stream) {
   return conv_multi(njobs, jobs, 0, stream);
 }
 extern "C" int usseg_conv2d_dgrad_multi(int32_t njobs, const UssegConvJob* jobs, usseg_stream_t stream) {
   return conv_multi(njobs, jobs, 1, stream);
+}
+
+// Quad-form transposed conv (stride 2, 'same', k = 3 or 4) as tap-masked 3x3 convs on space-to-depth tensors: class c of the
+// Np-channel groups uses the stencil taps of mask[c] (kernels that do not honour the mask still compute the right result: the
+// masked taps carry zero weights / unused gradient entries).  reversed: the backward-data loop uses weight tap 8 - t at loop tap t.
+static UssegTapMask quad_masks(int k, int Np, bool reversed) {
+  UssegTapMask tm = {Np, {}};
+  const int pad = k == 4 ? 1 : 0;
+  for (int a = 0; a < 2; ++a)
+    for (int b = 0; b < 2; ++b) {
+      unsigned m = 0;
+      for (int kh = 0; kh < k; ++kh)
+        for (int kw = 0; kw < k; ++kw)
+          if (((kh + pad) & 1) == a && ((kw + pad) & 1) == b) {
+            int t = ((a + pad - kh) / 2 + 1) * 3 + ((b + pad - kw) / 2 + 1);
+            m |= 1u << (reversed ? 8 - t : t);
+          }
+      tm.mask[a * 2 + b] = (uint16_t)m;
+    }
+  return tm;
+}
+extern "C" int usseg_tconv_quad_fwd(const UssegConvDesc* d, int32_t ksize, int32_t Np, const void* x, const void* wq_f, const float* bias_q,
+                                    void* y4, usseg_stream_t stream) {
+  USSEG_CHECK_ARG(d && (ksize == 3 || ksize == 4) && Np > 0 && d->Cout == 4 * Np && d->ksize == 3 && d->dilation == 1, "tconv_quad_fwd: bad args");
+  int rc = check_conv(d, 0, x && wq_f && y4, "null pointer");
+  if (rc) return rc;
+  ConvPass p = conv_pass({*d, x, wq_f, bias_q, nullptr, 0, 0, y4, nullptr}, 0);
+  p.mask = quad_masks(ksize, Np, false);
+  return run_convs(&p, 1, (hipStream_t)stream);
+}
+extern "C" int usseg_tconv_quad_dgrad(const UssegConvDesc* d, int32_t ksize, int32_t Np, const void* dy4, const void* wq_d, void* dx,
+                                      usseg_stream_t stream) {
+  USSEG_CHECK_ARG(d && (ksize == 3 || ksize == 4) && Np > 0 && d->Cout == 4 * Np && d->ksize == 3 && d->dilation == 1, "tconv_quad_dgrad: bad args");
+  int rc = check_conv(d, 1, dy4 && wq_d && dx, "null pointer");
+  if (rc) return rc;
+  ConvPass p = conv_pass({*d, dy4, wq_d, nullptr, nullptr, 0, 0, dx, nullptr}, 1);
+  p.mask = quad_masks(ksize, Np, true);
+  return run_convs(&p, 1, (hipStream_t)stream);
+}
+extern "C" int usseg_tconv_quad_wgrad(const UssegConvDesc* d, int32_t ksize, int32_t Np, const void* x, const void* dy4, float* dq, float* ws,
+                                      int64_t ws_floats, usseg_stream_t stream) {
+  USSEG_CHECK_ARG(d && (ksize == 3 || ksize == 4) && Np > 0 && d->Cout == 4 * Np && d->ksize == 3 && d->dilation == 1, "tconv_quad_wgrad: bad args");
+  USSEG_CHECK_ARG(dq, "null pointer");
+  return conv2d_wgrad_impl(d, x, dy4, dq, nullptr, ws, ws_floats, quad_masks(ksize, Np, false), stream);
 }
 
 // dx = sum over parallel conv branches of their backward-data passes, as ONE implicit GEMM whose K axis walks every

@@ -1391,51 +1391,6 @@ extern "C" int usseg_space_to_depth2(const void* full, int32_t B, int32_t H, int
   return usseg_check_launch("space_to_depth2");
 }
 
-// Quad-form transposed conv (stride 2, 'same', k = 3 or 4) as tap-masked 3x3 convs on space-to-depth tensors: sets the per-class
-// stencil masks for one call of the conv entry point (kernels that do not honour the mask still compute the right result: the
-// masked taps carry zero weights / unused gradient entries).
-static void quad_masks(int k, bool reversed) {
-  const int pad = k == 4 ? 1 : 0;
-  for (int a = 0; a < 2; ++a)
-    for (int b = 0; b < 2; ++b) {
-      unsigned m = 0;
-      for (int kh = 0; kh < k; ++kh)
-        for (int kw = 0; kw < k; ++kw)
-          if (((kh + pad) & 1) == a && ((kw + pad) & 1) == b) {
-            int t = ((a + pad - kh) / 2 + 1) * 3 + ((b + pad - kw) / 2 + 1);
-            m |= 1u << (reversed ? 8 - t : t);
-          }
-      usseg_tap_mask.mask[a * 2 + b] = (uint16_t)m;
-    }
-}
-struct TapMaskGuard {
-  ~TapMaskGuard() { usseg_tap_mask.group_ch = 0; }
-};
-extern "C" int usseg_tconv_quad_fwd(const UssegConvDesc* d, int32_t ksize, int32_t Np, const void* x, const void* wq_f, const float* bias_q,
-                                    void* y4, usseg_stream_t stream) {
-  USSEG_CHECK_ARG(d && (ksize == 3 || ksize == 4) && Np > 0 && d->Cout == 4 * Np && d->ksize == 3 && d->dilation == 1, "tconv_quad_fwd: bad args");
-  TapMaskGuard guard;
-  quad_masks(ksize, false);
-  usseg_tap_mask.group_ch = Np;
-  return usseg_conv2d_fwd(d, x, wq_f, bias_q, nullptr, 0, y4, stream);
-}
-extern "C" int usseg_tconv_quad_dgrad(const UssegConvDesc* d, int32_t ksize, int32_t Np, const void* dy4, const void* wq_d, void* dx,
-                                      usseg_stream_t stream) {
-  USSEG_CHECK_ARG(d && (ksize == 3 || ksize == 4) && Np > 0 && d->Cout == 4 * Np && d->ksize == 3 && d->dilation == 1, "tconv_quad_dgrad: bad args");
-  TapMaskGuard guard;
-  quad_masks(ksize, true);      // the backward-data loop uses weight tap 8 - t at loop tap t
-  usseg_tap_mask.group_ch = Np;
-  return usseg_conv2d_dgrad(d, dy4, wq_d, nullptr, 0, dx, stream);
-}
-extern "C" int usseg_tconv_quad_wgrad(const UssegConvDesc* d, int32_t ksize, int32_t Np, const void* x, const void* dy4, float* dq, float* ws,
-                                      int64_t ws_floats, usseg_stream_t stream) {
-  USSEG_CHECK_ARG(d && (ksize == 3 || ksize == 4) && Np > 0 && d->Cout == 4 * Np && d->ksize == 3 && d->dilation == 1, "tconv_quad_wgrad: bad args");
-  TapMaskGuard guard;
-  quad_masks(ksize, false);
-  usseg_tap_mask.group_ch = Np;
-  return usseg_conv2d_wgrad(d, x, dy4, dq, ws, ws_floats, stream);
-}
-
 // ---- dropout mask (tf.nn.dropout(x, rate), TBI_ResNest.py:216): mask[m][c] = keep ? 1/(1-rate) : 0, counter-based hash RNG
 __device__ __forceinline__ uint32_t hash32(uint64_t v) {
   v ^= v >> 33; v *= 0xff51afd7ed558ccdULL; v ^= v >> 33; v *= 0xc4ceb9fe1a85ec53ULL; v ^= v >> 33;

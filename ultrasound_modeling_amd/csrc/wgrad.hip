@@ -470,16 +470,17 @@ static int launch_wgrad(WgradParams& p, int ntaps, float* ws, int64_t ws_floats,
   return usseg_check_launch("wgrad");
 }
 
-static int conv2d_wgrad_impl(const UssegConvDesc* d, const void* x, const void* dy, float* dw, const UssegWgradDst* dst, float* ws,
-                             int64_t ws_floats, usseg_stream_t stream) {
+int conv2d_wgrad_impl(const UssegConvDesc* d, const void* x, const void* dy, float* dw, const UssegWgradDst* dst, float* ws, int64_t ws_floats,
+                      const UssegTapMask& mask, usseg_stream_t stream) {
   USSEG_CHECK_ARG(d && x && dy && (dw || dst), "null pointer");
   WgMap map;
   USSEG_CHECK_ARG(wg_map_fill(map, dst), "wgrad: bad destination map (1..4 blocks, non-null dst)");
   USSEG_CHECK_ARG(d->Cin % 8 == 0 && d->Cout % 8 == 0 && d->ldx % 8 == 0 && d->ldy % 8 == 0, "channels must be multiples of 8");
   USSEG_CHECK_ARG(d->ksize == 1 || d->ksize == 3, "conv ksize must be 1 or 3");
-  if (d->ksize == 3 && usseg_try_launch_wgrad_halo((const bf16_t*)x, (const bf16_t*)dy, dw, map, d->B, d->H, d->W, d->dilation, d->Cin,
-                                                   d->Cout, d->ldx, d->ldy, ws, ws_floats, (hipStream_t)stream))
-    return usseg_check_launch("wgrad_halo");
+  if (d->ksize == 3) {
+    const WgHaloGeom g = wgrad_halo_geom(*d, x, dy, dw, map, mask);
+    if (usseg_try_launch_wgrad_halo(&g, 1, ws, ws_floats, (hipStream_t)stream)) return usseg_check_launch("wgrad_halo");
+  }
   WgradParams p = {};
   p.map = map;
   p.a = (const bf16_t*)x; p.b = (const bf16_t*)dy; p.out = dw;
@@ -500,20 +501,27 @@ static int conv2d_wgrad_impl(const UssegConvDesc* d, const void* x, const void* 
 extern "C" int usseg_conv2d_wgrad(const UssegConvDesc* d, const void* x, const void* dy, float* dw, float* ws, int64_t ws_floats,
                                   usseg_stream_t stream) {
   USSEG_CHECK_ARG(dw, "null pointer");
-  return conv2d_wgrad_impl(d, x, dy, dw, nullptr, ws, ws_floats, stream);
+  return conv2d_wgrad_impl(d, x, dy, dw, nullptr, ws, ws_floats, {}, stream);
 }
 extern "C" int usseg_conv2d_wgrad_mapped(const UssegConvDesc* d, const void* x, const void* dy, const UssegWgradDst* dst, float* ws,
                                          int64_t ws_floats, usseg_stream_t stream) {
   USSEG_CHECK_ARG(dst, "null destination map");
-  return conv2d_wgrad_impl(d, x, dy, nullptr, dst, ws, ws_floats, stream);
+  return conv2d_wgrad_impl(d, x, dy, nullptr, dst, ws, ws_floats, {}, stream);
 }
 
 extern "C" int usseg_conv2d_wgrad_multi(int32_t njobs, const UssegWgradJob* jobs, float* ws, int64_t ws_floats, usseg_stream_t stream) {
   USSEG_CHECK_ARG(jobs && njobs >= 1 && njobs <= 4, "wgrad multi: 1 <= njobs <= 4");
   for (int j = 0; j < njobs; ++j) USSEG_CHECK_ARG(jobs[j].x && jobs[j].dy && (jobs[j].dw || jobs[j].dst), "wgrad multi: null pointer");
-  if (njobs > 1 && usseg_try_launch_wgrad_halo_multi(njobs, jobs, ws, ws_floats, (hipStream_t)stream)) return usseg_check_launch("wgrad_halo_multi");
+  WgHaloGeom g[4];
+  bool halo = njobs > 1;
+  for (int j = 0; j < njobs && halo; ++j) {
+    WgMap map;
+    halo = jobs[j].desc.ksize == 3 && wg_map_fill(map, jobs[j].dst);
+    if (halo) g[j] = wgrad_halo_geom(jobs[j].desc, jobs[j].x, jobs[j].dy, jobs[j].dw, map);
+  }
+  if (halo && usseg_try_launch_wgrad_halo(g, njobs, ws, ws_floats, (hipStream_t)stream)) return usseg_check_launch("wgrad_halo_multi");
   for (int j = 0; j < njobs; ++j) {
-    int rc = conv2d_wgrad_impl(&jobs[j].desc, jobs[j].x, jobs[j].dy, jobs[j].dst ? nullptr : jobs[j].dw, jobs[j].dst, ws, ws_floats, stream);
+    int rc = conv2d_wgrad_impl(&jobs[j].desc, jobs[j].x, jobs[j].dy, jobs[j].dst ? nullptr : jobs[j].dw, jobs[j].dst, ws, ws_floats, {}, stream);
     if (rc) return rc;
   }
   return USSEG_OK;

@@ -369,18 +369,10 @@ __global__ __launch_bounds__(256 * NTG, NTG == 1 ? 2 : 1) void wgrad_halo_kernel
       }
 }
 
-// Returns 1 and launches if the geometry fits, 0 if the caller must use the per-tap kernel.
-struct WgHaloGeom {
-  const bf16_t* x; const bf16_t* dy; float* out; WgMap map;
-  int B, H, W, d, Ma, Nb, ldx, lddy;
-  int tconv_cls = -1;      // >= 0: parity class 2a+b of a stride-2 transposed conv (x = dy tensor at 2H x 2W, dy = x tensor; see the views)
-  uint32_t tapmask = 0x1ff;
-};
-
 // Launches njobs (1..4) weight gradients of identical (B,H,W) - dilations may differ as long as the group counts match, channel counts may
 // differ as long as the jobs take the same tile shape and the same number of tiles (the stem's three convs: 32x32, 16x32 and 8x16 channels are
 // one 32x32 tile each) - as one grid; returns 0 if the geometry does not fit (the caller then launches the jobs one at a time).
-static int wgrad_halo_launch(const WgHaloGeom* gm, int njobs, float* ws, int64_t ws_floats, hipStream_t s) {
+int usseg_try_launch_wgrad_halo(const WgHaloGeom* gm, int njobs, float* ws, int64_t ws_floats, hipStream_t s) {
   static const int disabled = getenv("USSEG_NO_HALO") != nullptr;
   if (disabled || njobs < 1 || njobs > 4) return 0;
   WgHaloMulti P;
@@ -395,7 +387,7 @@ static int wgrad_halo_launch(const WgHaloGeom* gm, int njobs, float* ws, int64_t
     const WgHaloGeom& q = gm[j];
     if (q.B != gm[0].B || q.H != gm[0].H || q.W != gm[0].W) return 0;
     if (shape_of(q.Ma, q.Nb) != shape_of(Ma, Nb) || tiles_of(q.Ma, q.Nb) != tiles_of(Ma, Nb)) return 0;
-    if ((q.Ma != Ma || q.Nb != Nb) && (usseg_tap_mask.group_ch || q.tconv_cls >= 0)) return 0;
+    if ((q.Ma != Ma || q.Nb != Nb) && (q.mask.group_ch || q.tconv_cls >= 0)) return 0;
     slab_sum += (int64_t)9 * q.Ma * q.Nb;
     if ((int64_t)9 * q.Ma * q.Nb > slab_max) slab_max = (int64_t)9 * q.Ma * q.Nb;
     const int d = q.d;
@@ -501,11 +493,12 @@ static int wgrad_halo_launch(const WgHaloGeom* gm, int njobs, float* ws, int64_t
       off += (int64_t)splits * 9 * gm[j].Ma * gm[j].Nb;
     }
   }
-  const bool masked = usseg_tap_mask.group_ch != 0 || gm[0].tconv_cls >= 0;
-  if (usseg_tap_mask.group_ch) {
-    if (njobs != 1 || usseg_tap_mask.group_ch % bn) return 0;      // an output-channel tile must lie inside one class
-    P.job[0].mask_ch = usseg_tap_mask.group_ch;
-    for (int c = 0; c < 4; ++c) P.job[0].tapmask[c] = usseg_tap_mask.mask[c];
+  const UssegTapMask& qm = gm[0].mask;
+  const bool masked = qm.group_ch != 0 || gm[0].tconv_cls >= 0;
+  if (qm.group_ch) {
+    if (njobs != 1 || qm.group_ch % bn) return 0;      // an output-channel tile must lie inside one class
+    P.job[0].mask_ch = qm.group_ch;
+    for (int c = 0; c < 4; ++c) P.job[0].tapmask[c] = qm.mask[c];
   }
   const dim3 grid(splits, tiles, njobs);
   static const int xcd_env = getenv("USSEG_WGHALO_XCD") ? atoi(getenv("USSEG_WGHALO_XCD")) : 1;
@@ -533,26 +526,6 @@ static int wgrad_halo_launch(const WgHaloGeom* gm, int njobs, float* ws, int64_t
     for (int j = 0; j < njobs; ++j) usseg_launch_wgrad_finish(P.job[j].ws, splits, (int64_t)9 * gm[j].Ma * gm[j].Nb, gm[j].out, gm[j].map, gm[j].Ma, gm[j].Nb, s);
   usseg_prof_stop(2, slot, s);
   return 1;
-}
-
-// Returns 1 and launches if the geometry fits, 0 if the caller must use the per-tap kernel.
-int usseg_try_launch_wgrad_halo(const bf16_t* x, const bf16_t* dy, float* out, const WgMap& map, int B, int H, int W, int d, int Ma, int Nb,
-                                int ldx, int lddy, float* ws, int64_t ws_floats, hipStream_t s) {
-  WgHaloGeom g = {x, dy, out, map, B, H, W, d, Ma, Nb, ldx, lddy};
-  return wgrad_halo_launch(&g, 1, ws, ws_floats, s);
-}
-
-int usseg_try_launch_wgrad_halo_multi(int njobs, const UssegWgradJob* jobs, float* ws, int64_t ws_floats, hipStream_t s) {
-  if (njobs < 1 || njobs > 4) return 0;
-  WgHaloGeom g[4];
-  for (int j = 0; j < njobs; ++j) {
-    const UssegWgradJob& q = jobs[j];
-    const UssegConvDesc& d = q.desc;
-    if (d.ksize != 3) return 0;
-    g[j] = {(const bf16_t*)q.x, (const bf16_t*)q.dy, q.dw, WgMap(), d.B, d.H, d.W, d.dilation, d.Cin, d.Cout, d.ldx, d.ldy};
-    if (!wg_map_fill(g[j].map, q.dst)) return 0;
-  }
-  return wgrad_halo_launch(g, njobs, ws, ws_floats, s);
 }
 
 // Weight gradient of a stride-2 'same' Conv2DTranspose (k = 3 or 4) on the halo-tile kernel: its four output-parity classes are
@@ -591,5 +564,5 @@ int usseg_try_launch_tconv_wgrad_halo(const bf16_t* x, const bf16_t* dy, const W
       u.sT = 2 * sk;
     }
   }
-  return wgrad_halo_launch(g, 4, ws, ws_floats, s);
+  return usseg_try_launch_wgrad_halo(g, 4, ws, ws_floats, s);
 }
