@@ -501,6 +501,29 @@ int usseg_head_quad_softmax_loss(const void* x, int32_t B, int32_t h, int32_t w,
  * argmax(probs) equals argmax(y_true) (first maximum, as tf.argmax); probs, y_true fp32 [M][C].  acc is a USSEG_ACC_FLOATS
  * accumulator (zeroed once by the caller), [0] OVERWRITTEN.  One pass instead of the reference's four framework reductions. */
 int usseg_accuracy(const float* probs, const float* y_true, int64_t M, int32_t C, float* acc, usseg_stream_t stream);
+/* ---- validation metrics (metrics.hip) ---------------------------------------------------------
+ * The counters behind the drivers' Keras Precision / Recall / MeanIoU objects and their `c2` pair (MainNumpy.py:20-27,49-53,
+ * 100-106; TBI_ResNest.py:9-12,421-426; TBI_TransUNet.py:749-756,947-956; MainParallel.py:86-114,148-176), as exact integers:
+ * one streaming pass over y_true and y_pred, contiguous fp32 [B][H][W][C] (the layout of probs and label2vec).  Per element:
+ *  - round = 1: both values first go through tf.math.round, half to even (rintf): a label of exactly 0.5 - label2vec of a raw
+ *    label 1.5 - counts as 0 (MainNumpy.py:49-50,100-101).  round = 0: the values as they are (TBI_ResNest.py:423-426);
+ *  - a true value is positive when it is non-zero (Precision / Recall cast y_true to bool), a prediction when it is > 0.5 (their
+ *    default threshold);
+ *  - the confusion-matrix class of a value is the value truncated to an integer (tf.math.confusion_matrix casts to int64; MeanIoU
+ *    flattens its inputs and takes no argmax: MainNumpy.py:53,106);
+ *  - the element is INVALID when either class lies outside [0, num_classes) or the prediction outside [0, 1] (TF raises for both).
+ * counts: USSEG_SEG_COUNTS uint64, ADDED INTO (never cleared: the caller zeroes the buffer once, e.g. per epoch):
+ *   [0..2] TP, FP, FN over every element;  [3..5] TP, FP, FN over the elements with w == W-1 only - the reference's
+ *   `c2` metrics index y[:, :, -1] of a 4-D tensor, the last image COLUMN, not class 2 (MainNumpy.py:104-105);
+ *   [6 .. 6+nc*nc) the confusion matrix cm[true][pred];  [6+nc*nc] the count of invalid elements.
+ * 1 <= num_classes <= 4; B, H >= 0; W, C >= 1.  Integer adds: bitwise reproducible; no allocation, no synchronisation. */
+typedef struct UssegSegCountDesc {
+  int32_t B, H, W, C;
+  int32_t num_classes; /* of the confusion matrix, 1..4 */
+  int32_t round;       /* 0 or 1 */
+} UssegSegCountDesc;
+#define USSEG_SEG_COUNTS 23 /* 6 + 4*4 + 1 */
+int usseg_seg_counts(const UssegSegCountDesc* d, const float* y_true, const float* y_pred, uint64_t* counts, usseg_stream_t stream);
 int usseg_loss_from_probs(const UssegLossDesc* d, const float* probs, const float* y_true, const float* scale, float* loss,
                           usseg_stream_t stream);
 /* The <= 4-class head Conv2DTranspose(k x k, stride 2, 'same') (Decoder.py:120 k=3; TBI_ResNest.py:124 k=4) in "quad" form: a

@@ -1,0 +1,93 @@
+"""The reference's single-GPU training / test driver (``MainNumpy.py:14-147``) with its validation metrics counted on the device.
+
+``Process(batch_size, num_classes).training(neuralnet, dataset, epochs)`` and ``.test(neuralnet, dataset, epoch)`` drive any
+model with ``train_step(x, y) -> (loss, probs)`` and ``step(x, y) -> (loss, probs)`` (VisionTransformer, TBI_TransUNet) over a
+``Dataset_2.Dataset``.  Differences, all deliberate:
+  * the eight Keras metric objects (:20-27) are two ``metrics.SegMetrics`` counter buffers: one launch per batch, stream-ordered
+    behind the step that produced the probabilities (also behind a replayed HIP graph, whose ``probs`` is the static buffer), and
+    ONE read-back per epoch instead of a host read of five metric objects;
+  * every metric is reset after the epoch that reported it, and each epoch's numbers (loss included) are appended to
+    ``self.history`` as well as printed;
+  * no TensorBoard summaries or image dumps (:16-17,54-60,108-113,124-133);
+  * no learning-rate "schedule" (:83-88): the reference assigns ``neuralnet.learning_rate`` / ``weight_decay``, plain attributes its
+    optimiser never reads again, and ``flat.AdamClip`` captures ``lr`` at construction the same way,
+    so applying it would change what the reference computes.
+"""
+from __future__ import annotations
+
+import torch
+
+from .metrics import SegMetrics
+
+input_size = (256, 80)      # :12
+
+
+class Process(object):
+    def __init__(self, batch_size=16, num_classes=3, device=None):
+        self.batch_size = batch_size
+        self.num_classes = num_classes
+        self.input_shape = [input_size[0], input_size[1], 10]                                    # :19
+        dev = device if device is not None else "cuda"
+        self.metrics = SegMetrics(num_classes, round=True, device=dev)        # precision / recall / pre_c2 / re_c2 / mio (:20-24)
+        self.tr_metrics = SegMetrics(num_classes, round=True, device=dev)     # tr_recall / tr_precision / tr_mio (:25-27)
+        self.test_iter = 0
+        self.history = []
+
+    def training(self, neuralnet, dataset, epochs):
+        """MainNumpy.py:31-88 -> None; one dict per epoch in ``self.history`` (``phase`` "train")."""
+        print("\nTraining to %d epochs (%d of minibatch size)" % (epochs, self.batch_size))
+        iteration = 0
+        prev_loss = 0
+        for epoch in range(1, epochs + 1):
+            while True:
+                x_tr, y_tr, terminator = dataset.next_train(self.batch_size)                     # :43
+                loss, class_score = neuralnet.train_step(x=x_tr, y=y_tr)                         # :45
+                iteration += 1
+                self.tr_metrics.update_state(_labels(y_tr, class_score), class_score)            # :49-53, read back once per epoch
+                print('.', end='')
+                if (iteration + 1) % 100 == 0:
+                    print()
+                if terminator:
+                    break
+            print()
+            loss = float(loss)      # the epoch's last step (:47,70: reduce_sum of a scalar); after a graph replay the static buffer
+            m = self.tr_metrics.result()
+            print("Epoch [%d / %d] (%d iteration)  Loss:%.5f, Recall:%.5f, Precision:%.5f, IoU:%.5f"
+                  % (epoch, epochs, iteration, loss, m["recall"], m["precision"], m["mean_iou"]))
+            self.history.append(dict(m, phase="train", epoch=epoch, iteration=iteration, loss=loss))
+            self.tr_metrics.reset_states()                                                       # :73-75
+            if prev_loss == loss:
+                print("Model is throwing a fit")
+                print(class_score)
+            prev_loss = loss
+            if epoch % 5 == 0:
+                self.test(neuralnet, dataset, epoch)
+            # :83-88 (the learning-rate "schedule") is not applied: see the module docstring
+
+    def test(self, neuralnet, dataset, epoch):
+        """MainNumpy.py:90-147 -> F1 of the epoch's test set; its dict (``phase`` "test") is appended to ``self.history``."""
+        print("\nTest...")
+        total_loss = None
+        while True:
+            x_te, y_te, terminator = dataset.next_test(16)                                       # :97
+            loss, class_score = neuralnet.step(x=x_te, y=y_te)                                   # :98
+            total_loss = loss.detach().reshape(()).clone() if total_loss is None else total_loss.add_(loss.reshape(()))   # :107, on the device
+            self.metrics.update_state(_labels(y_te, class_score), class_score)                   # :100-106
+            if terminator:
+                break
+            self.test_iter += 1
+        total_loss = float(total_loss)
+        m = self.metrics.result()
+        print("loss = {}".format(total_loss))
+        print("IoU = {}".format(m["mean_iou"]))
+        print("f1 = {}".format(m["f1"]))
+        print("precision = {}".format(m["precision"]))
+        print("recall = {}".format(m["recall"]))
+        self.history.append(dict(m, phase="test", epoch=epoch, loss=total_loss))
+        self.metrics.reset_states()                                                              # :142-146
+        return m["f1"]
+
+
+def _labels(y, probs):
+    """The labels the step consumed, as the fp32 contiguous device tensor the counting kernel reads (the model's own _prep_y)."""
+    return torch.as_tensor(y).to(device=probs.device, dtype=torch.float32).contiguous()

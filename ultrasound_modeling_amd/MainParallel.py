@@ -10,6 +10,9 @@ Reference behaviour being mirrored (MainParallel.py:16,117-146,209-210; SURVEY.m
 MI355X design: one process per GPU (torchrun), ONE RCCL all-reduce over the flat fp32 gradient buffer per step
 (25 MB for the conv-only Arch B): on the fully connected xGMI node a single large collective uses all 7 links.
 BatchNorm statistics are NOT synchronised (the reference uses plain BatchNormalization, ResNest.py:19).
+Validation metrics (:86-114,148-176): instead of gathering every replica's probabilities and labels (``test_step`` still does,
+as the reference), a replica counts its own slice with ``metrics.SegMetrics.update_state`` and calls ``SegMetrics.reduce()`` (a SUM
+all-reduce of 23 int64 counters, exact) before ``result()``: the numbers of one process on the concatenated batch.
 """
 from __future__ import annotations
 

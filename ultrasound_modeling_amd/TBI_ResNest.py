@@ -643,3 +643,33 @@ class ResNest(TrainStepDriver):
         if getattr(self, "_lsum", None) is None or self._lsum.device != loss_map.device:
             self._lsum = torch.zeros(ops.ACC_FLOATS, dtype=torch.float32, device=loss_map.device)
         return ops.sum_f32(loss_map.contiguous().reshape(-1), self._lsum)
+
+
+history = []     # one dict per test() call: precision, recall, f1, c2_*, loss (what the reference logs to TensorBoard)
+
+
+def test(neuralnet, dataset, epoch):
+    """TBI_ResNest.py:413-449 -> F1 of the test set, batch size 1.  This loop passes y_te and class_score to Precision / Recall
+    UNROUNDED (:423-426), so a soft label of 0.3 counts as positive: the counters run with ``round=False``.  It has no MeanIoU,
+    and the loss is divided by num_te (:429).  Unlike the reference (:439-449 reset ``precision`` four times and never
+    ``recall`` / ``pre_c2`` / ``re_c2``), every metric starts from zero on each call: the numbers describe this epoch only."""
+    from .metrics import SegMetrics
+    print("\nTest...")
+    m = SegMetrics(neuralnet.num_class, round=False, device=neuralnet.device)
+    total_loss = None
+    while True:
+        x_te, y_te, terminator = dataset.next_test(1)                                          # :419
+        loss_map, _, class_score = neuralnet.step(x=x_te, y=y_te, train=False)                 # :420
+        loss = neuralnet._loss_total(loss_map)                                                 # :421 reduce_sum (the library's ordered sum)
+        total_loss = loss.reshape(()).clone() if total_loss is None else total_loss.add_(loss.reshape(()))   # :427, on the device
+        m.update_state(neuralnet._prep_y(y_te), class_score)                                   # :422-426
+        if terminator:
+            break
+    total_loss = float(total_loss) / dataset.num_te                                            # :429
+    r = m.result()
+    print("loss = {}".format(total_loss))
+    print("f1 = {}".format(r["f1"]))
+    print("precision = {}".format(r["precision"]))
+    print("recall = {}".format(r["recall"]))
+    history.append({k: r[k] for k in ("precision", "recall", "f1", "c2_precision", "c2_recall", "c2_f1")} | {"epoch": epoch, "loss": total_loss})
+    return r["f1"]

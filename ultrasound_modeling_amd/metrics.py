@@ -1,0 +1,88 @@
+"""The drivers' validation metrics (MainNumpy.py:17-27,49-53,97-147; TBI_ResNest.py:9-12,413-449; TBI_TransUNet.py:749-756,
+893-898,947-990; MainParallel.py:86-114,148-176) from exact device-side counters.
+
+The reference updates five Keras metric objects per batch - Precision, Recall, MeanIoU(num_classes) and a second
+Precision / Recall pair named ``c2`` - and reads them back on the host; under MirroredStrategy it also gathers every replica's
+probabilities and labels.  Here one launch per batch (``ops.seg_counts`` -> ``usseg_seg_counts``) adds into a small int64
+counter buffer that stays in HBM until the epoch ends; ``SegMetrics.result()`` copies it back once and ``counts_to_metrics``
+turns it into the numbers the drivers print.  Replicas exchange the counters (a SUM all-reduce of 23 int64) instead of the
+tensors: the sum is exact, so N replicas give the numbers of one process on the concatenated batch.
+
+Two behaviours of the reference, reproduced on purpose:
+  * ``c2`` is the last image COLUMN, not class 2: ``y[:, :, -1]`` indexes the width axis of the 4-D tensor (MainNumpy.py:104-105).
+  * The counts are exact 64-bit integers; Keras keeps its counters in fp32 variables, inexact past 2^24.
+"""
+from __future__ import annotations
+
+from typing import Dict
+
+import torch
+
+from ._lib import SEG_COUNTS
+from .ops import seg_counts  # noqa: F401  (the kernel wrapper; re-exported here)
+
+__all__ = ["SEG_COUNTS", "SegMetrics", "counts_to_metrics", "seg_counts"]
+
+
+def _div_no_nan(a: float, b: float) -> float:
+    return a / b if b != 0 else 0.0
+
+
+def _f1(p: float, r: float) -> float:
+    """2PR/(P+R) as the drivers compute it (MainNumpy.py:121-122): NaN, not an exception, when P + R = 0."""
+    return 2.0 * p * r / (p + r) if p + r != 0 else float("nan")
+
+
+def counts_to_metrics(counts, num_classes: int = 3) -> Dict[str, float]:
+    """Counter buffer (``USSEG_SEG_COUNTS`` int64, CPU or device) -> ``precision, recall, f1, c2_precision, c2_recall, c2_f1,
+    mean_iou`` with Keras semantics: Precision / Recall = div_no_nan; MeanIoU = the mean of IoU over the classes whose
+    row + column - diagonal is non-zero (0 when there is none).  Raises ``ValueError`` when the kernel counted invalid elements
+    (a class outside [0, num_classes) or a prediction outside [0, 1]: TF raises for both)."""
+    nc = int(num_classes)
+    if not 1 <= nc <= 4:
+        raise ValueError(f"num_classes must be 1..4, got {nc}")
+    c = [int(v) for v in torch.as_tensor(counts).reshape(-1)[:SEG_COUNTS].cpu().tolist()]
+    invalid = c[6 + nc * nc]
+    if invalid:
+        raise ValueError(f"{invalid} invalid elements: a class outside [0, {nc}) or a prediction outside [0, 1] (TF raises for both)")
+    tp, fp, fn, tp2, fp2, fn2 = c[:6]
+    cm = [c[6 + i * nc:6 + (i + 1) * nc] for i in range(nc)]          # cm[true][pred]
+    p, r = _div_no_nan(tp, tp + fp), _div_no_nan(tp, tp + fn)
+    p2, r2 = _div_no_nan(tp2, tp2 + fp2), _div_no_nan(tp2, tp2 + fn2)
+    iou, valid = 0.0, 0
+    for k in range(nc):
+        denom = sum(cm[k]) + sum(row[k] for row in cm) - cm[k][k]
+        if denom != 0:
+            iou += cm[k][k] / denom
+            valid += 1
+    return {"precision": p, "recall": r, "f1": _f1(p, r), "c2_precision": p2, "c2_recall": r2, "c2_f1": _f1(p2, r2),
+            "mean_iou": _div_no_nan(iou, valid)}
+
+
+class SegMetrics:
+    """The drivers' five Keras metric objects as ONE counter buffer: ``update_state`` is one launch, ``result`` one copy to the
+    host, ``reset_states`` one fill.  ``round=True`` is the MainNumpy / TBI_TransUNet / MainParallel scoring (tf.math.round of
+    labels and probabilities first); ``round=False`` is TBI_ResNest.test's, which passes them unrounded (TBI_ResNest.py:423-426).
+    Update tensors must live on the device: there is no CPU fallback."""
+
+    def __init__(self, num_classes: int = 3, round: bool = True, device=None):
+        if not 1 <= int(num_classes) <= 4:
+            raise ValueError(f"num_classes must be 1..4, got {num_classes}")
+        self.num_classes, self.round = int(num_classes), bool(round)
+        self.counts = torch.zeros(SEG_COUNTS, dtype=torch.int64, device=device if device is not None else "cuda")
+
+    def update_state(self, y_true: torch.Tensor, probs: torch.Tensor) -> None:
+        """Add one batch, fp32 [B,H,W,C] on the counters' device; enqueued on the current stream (no host synchronisation)."""
+        seg_counts(y_true, probs, self.counts, self.round, self.num_classes)
+
+    def reduce(self, group=None) -> None:
+        """SUM all-reduce of the counters over the replicas of ``group`` (replaces MirroredStrategy.reduce / gather of the
+        probabilities and labels, MainParallel.py:148-176).  Exact; call once before ``result()``."""
+        import torch.distributed as dist
+        dist.all_reduce(self.counts, op=dist.ReduceOp.SUM, group=group)
+
+    def result(self) -> Dict[str, float]:
+        return counts_to_metrics(self.counts.cpu(), self.num_classes)
+
+    def reset_states(self) -> None:
+        self.counts.zero_()

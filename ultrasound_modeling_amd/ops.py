@@ -586,6 +586,21 @@ def accuracy(probs, y_true, acc):
     return acc[0]
 
 
+def seg_counts(y_true, probs, counts, round=True, num_classes=3):
+    """counts += the metric counters of one batch (usseg_seg_counts: TP / FP / FN, the same over the last image column, the
+    confusion matrix, invalid elements; include/usseg.h).  y_true, probs: contiguous fp32 [B,H,W,C] on the device; ``counts``:
+    int64 [SEG_COUNTS] on the same device, zeroed by the caller.  One launch, no host synchronisation."""
+    assert y_true.shape == probs.shape and y_true.dim() == 4, (tuple(y_true.shape), tuple(probs.shape))
+    assert y_true.dtype == probs.dtype == torch.float32 and y_true.is_contiguous() and probs.is_contiguous()
+    assert counts.dtype == torch.int64 and counts.is_contiguous() and counts.numel() >= L.SEG_COUNTS
+    if not (y_true.is_cuda and probs.is_cuda and counts.is_cuda):
+        raise RuntimeError("seg_counts: device tensors only (there is no CPU fallback)")
+    B, H, W, C_ = y_true.shape
+    d = L.SegCountDesc(B, H, W, C_, int(num_classes), int(bool(round)))
+    L.check(L.load().usseg_seg_counts(C.byref(d), y_true.data_ptr(), probs.data_ptr(), counts.data_ptr(), _stream()), "seg_counts")
+    return counts
+
+
 def norm_act_bwd_res(x, dy, C_logical, gamma, beta, dres, dx, dgamma, dbeta, eps, dbias=None):
     """Plain LayerNormalization backward + the residual branch of a pre-norm block: dx = bf16(bf16(LN'(dy)) + dres) in one pass;
     ``dbias`` += the column sums of the stored dx."""
