@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import usseg_oracle as O
+from route_probe import U_BF16, U_F32, assert_elementwise, kernels, short
 
 pytestmark = pytest.mark.gpu
 
@@ -47,6 +48,16 @@ def finalize(layer):
     return FlatParams(layer, DEV)
 
 
+def on_route(want, fn):
+    """fn() after asserting the device kernels it launched include `want` (a short kernel name, or a tuple of them): the route a
+    case's label names is checked before any of its numbers."""
+    out, got = kernels(fn)
+    got = [short(n) for n in got]
+    for w in (want,) if isinstance(want, str) else want:
+        assert w in got, f"expected kernel {w!r}, launched {got}"
+    return out
+
+
 @pytest.fixture(scope="module")
 def gen():
     return torch.Generator().manual_seed(1234)
@@ -66,14 +77,19 @@ CONV_CASES = [
     (1, 24, 24, 128, 16, 3, 4),
     (1, 20, 20, 72, 136, 3, 8),   # dilation larger than half the image, Cout spans two N tiles
     (1, 1, 1, 10, 5, 1, 1),       # dense on a [B,1,1,C] tensor
-    # 256-pixel LDS-DMA kernel (conv_big.hip): Cin > 32, lattice width 16 / 8 / 4, ragged channel tails, partial groups
+    # lattice classes of the LDS-DMA kernel (conv_big.hip): Cin > 32, lattice width 16 / 8 / 4, ragged channel tails, partial groups.
+    # At these sizes (< 128 workgroups) the planner sends the forward passes to conv_halo (8x16 lattice: conv_stream) and only the
+    # 256-channel backward-data pass to conv_big; the last case reaches conv_big on the forward pass (CONV_ROUTES)
     (2, 16, 16, 72, 136, 3, 2),   # 8x8 lattices (4 per workgroup), Cin tail 72 = 2*32 + 8, three N tiles (last partial)
     (3, 16, 16, 96, 40, 3, 4),    # 4x4 lattices (16 per workgroup)
     (1, 32, 16, 40, 64, 3, 1),    # two 16x16 patches, second channel chunk partial
     (5, 8, 8, 64, 24, 3, 1),      # 5 patches -> last workgroup has one valid patch of four
     (1, 8, 16, 64, 32, 3, 1),     # one 8x16 patch in a two-patch workgroup
     (2, 32, 32, 256, 64, 3, 1),   # eight channel chunks through the double buffer
-    # halo-tile kernel variants (conv_halo.hip): lattice patches 8x16, 8x8 (2 per workgroup), 4x4 (8 per workgroup), 4x8
+    (1, 128, 128, 64, 64, 3, 1),  # 128 workgroups of 128 pixels, 73 KB of weights (too many for conv_stream): conv_big forward
+    # halo-tile kernel variants (conv_halo.hip): lattice patches 8x16, 8x8 (2 per workgroup), 4x4 (8 per workgroup), 4x8.
+    # The out_f32 pass of every case runs conv_halo; the bf16 passes of the cases with 16-wide lattices and <= 40 KB of weights
+    # run conv_stream (stream_plan) - CONV_ROUTES lists each pass
     (2, 32, 32, 64, 64, 3, 8),    # d=8 on 32x32: 4x4 virtual images
     (1, 32, 32, 48, 24, 3, 4),    # d=4 on 32x32: 8x8 virtual images, Cin not a multiple of 32
     (1, 64, 32, 88, 16, 3, 2),    # d=2: 32x16 lattice, Cin = 88 (cardinal conv2 input width at stage 4)
@@ -81,27 +97,71 @@ CONV_CASES = [
     (1, 64, 64, 8, 16, 3, 1),     # stem conv1 class
     (2, 16, 32, 32, 8, 3, 4),     # 4x8 lattice patches (4 per workgroup)
     (5, 8, 8, 16, 32, 3, 1),      # 8x8 images, odd batch: last workgroup half empty
-    # persistent-weights variant (>= 1024 pixel groups, whole weight operand resident in LDS)
+    # persistent-weights variant (>= 1024 pixel groups, whole weight operand resident in LDS).  conv_stream takes the bf16 passes
+    # of the first three (16-wide lattices); they reach conv_halo_persist on the out_f32 pass only, and the decoder b2 class not at
+    # all (its out_f32 pass is a conv_big launch).  The last case (8-wide lattice) reaches it on every pass
     (2, 256, 256, 16, 32, 3, 1),  # stem convtmp_1 class, 1024 groups
     (2, 256, 256, 64, 16, 3, 4),  # decoder b2 class: 2 channel chunks resident, dilation 4
     (5, 256, 128, 24, 8, 3, 2),   # 1280 groups, 2 per workgroup, Cin not a multiple of 32
+    (8, 256, 64, 16, 32, 3, 8),   # d=8: 32x8 lattices (conv_stream needs 16-wide ones), 1024 groups
     # LDS-DMA gather GEMM (igemm_dma_kernel): K tail inside the last stage, ragged pixel tile, partial channel tiles, long K ring
     (3, 9, 7, 136, 200, 1, 1),    # 17 K chunks (last step 1/8 full), 189 pixels (second tile partial), N = 128 + 72
     (2, 12, 12, 1024, 40, 1, 1),  # 128 K chunks through the 3-stage ring, 64-wide channel tile with 40 valid
     (1, 6, 10, 40, 8, 1, 1),      # 5 K chunks: shorter than one K step
 ]
 
+# The kernel each pass of a route-labelled CONV_CASES case lands on (measured on the MI355X with the default thresholds):
+# (out_f32 forward, bf16 forward, backward data).  A planner change that moves a case to another kernel fails here first: update
+# the label of the case, or add a case that still reaches the named kernel.
+_HALO, _PERSIST1, _PERSIST2 = "conv_halo_kernel<1>", "conv_halo_persist_kernel<1>", "conv_halo_persist_kernel<2>"
+_BIG, _S14, _S44 = "conv_big_kernel<1, 2, 4>", "conv_stream_kernel<1, 4, false>", "conv_stream_kernel<4, 4, false>"
+CONV_ROUTES = {
+    (2, 16, 16, 72, 136, 3, 2): (_HALO, _HALO, _HALO),
+    (3, 16, 16, 96, 40, 3, 4): (_HALO, _HALO, _HALO),
+    (1, 32, 16, 40, 64, 3, 1): (_HALO, _HALO, _HALO),
+    (5, 8, 8, 64, 24, 3, 1): (_HALO, _HALO, _HALO),
+    (1, 8, 16, 64, 32, 3, 1): (_HALO, "conv_stream_kernel<2, 2, false>", "conv_stream_kernel<4, 2, false>"),
+    (2, 32, 32, 256, 64, 3, 1): (_HALO, _HALO, _BIG),
+    (1, 128, 128, 64, 64, 3, 1): (_BIG, _BIG, _BIG),
+    (2, 32, 32, 64, 64, 3, 8): (_HALO, _HALO, _HALO),
+    (1, 32, 32, 48, 24, 3, 4): (_HALO, _HALO, _HALO),
+    (1, 64, 32, 88, 16, 3, 2): (_HALO, _S14, _S44),
+    (3, 16, 16, 24, 136, 3, 1): (_HALO, _S44, _HALO),
+    (1, 64, 64, 8, 16, 3, 1): (_HALO, _S14, _S14),
+    (2, 16, 32, 32, 8, 3, 4): (_HALO, _HALO, _HALO),
+    (5, 8, 8, 16, 32, 3, 1): (_HALO, _HALO, _HALO),
+    (2, 256, 256, 16, 32, 3, 1): (_PERSIST2, "conv_stream_kernel<2, 4, false>", _S14),
+    (2, 256, 256, 64, 16, 3, 4): (_BIG, _S14, _S44),
+    (5, 256, 128, 24, 8, 3, 2): (_PERSIST1, _S14, "conv_stream_kernel<2, 4, false>"),
+    (8, 256, 64, 16, 32, 3, 8): (_PERSIST2, _PERSIST2, _PERSIST1),
+    (3, 9, 7, 136, 200, 1, 1): ("igemm_dma_kernel<2, 3>", "igemm_dma_kernel<2, 3>", "igemm_dma_kernel<2, 3>"),
+    (2, 12, 12, 1024, 40, 1, 1): ("igemm_dma_kernel<2, 3>", "igemm_dma_kernel<2, 3>", "igemm_dma_kernel<2, 3>"),
+    (1, 6, 10, 40, 8, 1, 1): ("igemm_dma_kernel<1, 3>", "igemm_dma_kernel<1, 3>", "igemm_kernel<2, 4>"),
+}
+
 
 # streaming kernel (conv_big.hip conv_stream_kernel): persistent workgroups, weights resident, double-buffered halo DMA.
 # (B, H, W, Cin, Cout, dil, forced workgroups or 0): the forced grid drives small shapes through many steps per workgroup.
 STREAM_CASES = [
     (8, 256, 256, 32, 32, 1, 0),   # natural plan at 2048 groups: 256-pixel tiles, 4 steps per workgroup, counted wait
-    (4, 256, 256, 8, 64, 1, 0),    # fwd: 128-pixel tiles x 64 channels; dgrad 64 -> 8: two resident chunks, 16-channel tile
+    (4, 256, 256, 8, 64, 1, 0),    # fwd: 256-pixel tiles x 64 channels; dgrad 64 -> 8: two resident chunks, 16-channel tile
     (3, 48, 32, 24, 16, 1, 8),     # 18 groups on 8 workgroups: ragged per-XCD split, Cin tail, one workgroup per XCD
     (2, 64, 64, 40, 24, 2, 8),     # dilation 2 (32x32 lattices), two chunks (second partial), Cout 24: partial channel tile
     (5, 32, 64, 16, 40, 1, 16),    # Cout 40 of a 64-wide tile (no counted wait), 40 groups on 16 workgroups
     (1, 128, 128, 32, 32, 4, 8),   # dilation 4 on 128x128: 32x32 lattices, 64 groups: 8 steps per workgroup
 ]
+
+
+# (streaming forward, the same forward with the streaming kernel refused, backward data) per STREAM_CASES case
+_S = "conv_stream_kernel<{}, {}, {}>".format
+STREAM_ROUTES = {
+    (8, 256, 256, 32, 32, 1, 0): (_S(2, 4, "false"), "conv_halo_persist_kernel<2>", _S(2, 4, "false")),
+    (4, 256, 256, 8, 64, 1, 0): (_S(4, 4, "false"), "conv_halo_persist_kernel<4>", _S(1, 4, "false")),
+    (3, 48, 32, 24, 16, 1, 8): (_S(1, 4, "false"), "conv_halo_kernel<1>", _S(2, 4, "false")),
+    (2, 64, 64, 40, 24, 2, 8): (_S(2, 4, "false"), "conv_big_kernel<1, 2, 4>", _S(4, 4, "false")),
+    (5, 32, 64, 16, 40, 1, 16): (_S(4, 4, "false"), "conv_halo_kernel<1>", _S(1, 4, "false")),
+    (1, 128, 128, 32, 32, 4, 8): (_S(2, 4, "false"), "conv_halo_kernel<1>", _S(2, 4, "false")),
+}
 
 
 @pytest.mark.parametrize("B,H,W,Cin,Cout,dil,wgx", STREAM_CASES)
@@ -120,13 +180,14 @@ def test_conv_stream(gen, monkeypatch, B, H, W, Cin, Cout, dil, wgx):
     x = rnd(gen, B, H, W, Cin)
     xd = to_dev_padded(x)
     ref = O.conv2d_same(x, w, b, dil)
-    y = layer.forward(xd, act=ops.ACT_LRELU, alpha=0.3)
+    routes = STREAM_ROUTES[(B, H, W, Cin, Cout, dil, wgx)]
+    y = on_route(routes[0], lambda: layer.forward(xd, act=ops.ACT_LRELU, alpha=0.3))
     torch.cuda.synchronize()
     assert rel(y[..., :Cout], bf(O.leaky_relu(ref))) < REL_BF16
     assert y[..., Cout:].abs().max().item() == 0 if layer.cout_p > Cout else True
     # the other kernels on the same input must agree to the bf16 bit (same products, fp32 accumulation order aside)
     monkeypatch.setenv("USSEG_STREAM_MIN_STEPS", "1000000")
-    y2 = layer.forward(xd, act=ops.ACT_LRELU, alpha=0.3)
+    y2 = on_route(routes[1], lambda: layer.forward(xd, act=ops.ACT_LRELU, alpha=0.3))
     assert rel(y, y2) < 2e-3
     monkeypatch.setenv("USSEG_STREAM_MIN_STEPS", "1" if wgx else "4")
     # backward data through the same kernel (flipped taps, no bias)
@@ -134,12 +195,25 @@ def test_conv_stream(gen, monkeypatch, B, H, W, Cin, Cout, dil, wgx):
     dy = rnd(gen, B, H, W, Cout)
     xr = x.clone().requires_grad_(True)
     (O.conv2d_same(xr, w, b, dil) * dy).sum().backward()
-    dx = layer.backward(to_dev_padded(dy), skip_wgrad=True)
+    dxd = to_dev_padded(dy)
+    dx = on_route(routes[2], lambda: layer.backward(dxd, skip_wgrad=True))
     torch.cuda.synchronize()
     assert rel(dx[..., :Cin], bf(xr.grad)) < 2 * REL_BF16
 
 
-@pytest.mark.parametrize("B,H,W,Cin,Cout,dil,wgx", [(2, 128, 128, 30, 64, 1, 0), (2, 64, 64, 32, 30, 1, 8), (1, 32, 48, 16, 16, 2, 8), (3, 32, 32, 24, 40, 1, 16)])
+# (residual forward, the same with the streaming kernel refused).  (1, 32, 48, 16, 16, 2, 8) has 16x24 lattices, which the streaming
+# kernel cannot tile: both of its passes are gather GEMMs; (1, 32, 64, 16, 16, 2, 8) is its dilation-2 case that does stream.
+STREAM_RES_ROUTES = {
+    (2, 128, 128, 30, 64, 1, 0): (_S(4, 4, "true"), "conv_halo_kernel<4>"),
+    (2, 64, 64, 32, 30, 1, 8): (_S(2, 4, "true"), "conv_halo_kernel<1>"),
+    (1, 32, 48, 16, 16, 2, 8): ("igemm_dma_kernel<1, 3>", "igemm_dma_kernel<1, 3>"),
+    (1, 32, 64, 16, 16, 2, 8): (_S(1, 4, "true"), "conv_halo_kernel<1>"),
+    (3, 32, 32, 24, 40, 1, 16): (_S(4, 4, "true"), "conv_halo_kernel<1>"),
+}
+
+
+@pytest.mark.parametrize("B,H,W,Cin,Cout,dil,wgx", [(2, 128, 128, 30, 64, 1, 0), (2, 64, 64, 32, 30, 1, 8), (1, 32, 48, 16, 16, 2, 8), (3, 32, 32, 24, 40, 1, 16),
+                                                    (1, 32, 64, 16, 16, 2, 8)])
 def test_conv_stream_with_residual(gen, monkeypatch, B, H, W, Cin, Cout, dil, wgx):
     """The streaming conv's residual variant (y = act(conv + bias) + residual: concats_2 + shortcut of residual_S, ResNest.py:96-100)
     against the oracle and, to the bf16 bit, against the tiled kernels with the same epilogue."""
@@ -157,21 +231,37 @@ def test_conv_stream_with_residual(gen, monkeypatch, B, H, W, Cin, Cout, dil, wg
     x, r = rnd(gen, B, H, W, Cin), rnd(gen, B, H, W, Cout)
     xd, rd = to_dev_padded(x), to_dev_padded(r)
     ref = O.leaky_relu(O.conv2d_same(x, w, b, dil)) + r
-    y = layer.forward(xd, act=ops.ACT_LRELU, alpha=0.3, residual=rd)
+    routes = STREAM_RES_ROUTES[(B, H, W, Cin, Cout, dil, wgx)]
+    y = on_route(routes[0], lambda: layer.forward(xd, act=ops.ACT_LRELU, alpha=0.3, residual=rd))
     torch.cuda.synchronize()
     assert rel(y[..., :Cout], bf(ref)) < REL_BF16
     assert y[..., Cout:].abs().max().item() == 0 if layer.cout_p > Cout else True
     monkeypatch.setenv("USSEG_STREAM_RES", "0")       # read once per process: compare with the non-streaming kernels through the step planner instead
     monkeypatch.setenv("USSEG_STREAM_MIN_STEPS", "1000000")
-    y2 = layer.forward(xd, act=ops.ACT_LRELU, alpha=0.3, residual=rd)
+    y2 = on_route(routes[1], lambda: layer.forward(xd, act=ops.ACT_LRELU, alpha=0.3, residual=rd))
     assert rel(y, y2) < 2e-3
 
 
+# USSEG_BIG_W8 mode -> (forward, backward data).  conv_big only takes launches of >= 128 workgroups: the small cases run conv_halo
+# (or conv_stream) whatever the mode; (2, 32, 32, 256, 64, 1) reaches the eight-wave tile on backward data only and
+# (1, 128, 128, 64, 64, 1) on both passes.
+_B8, _B4, _H1 = "conv_big_kernel<1, 2, 8>", "conv_big_kernel<1, 2, 4>", "conv_halo_kernel<1>"
+EIGHT_WAVE_ROUTES = {
+    (2, 32, 32, 256, 64, 1): {"2": (_H1, _B8), "0": (_H1, _B4)},
+    (1, 32, 16, 40, 64, 1): {"2": (_H1, _H1), "0": (_H1, _H1)},
+    (2, 16, 16, 72, 136, 2): {"2": (_H1, _H1), "0": (_H1, _H1)},
+    (3, 16, 16, 96, 40, 4): {"2": (_H1, _H1), "0": (_H1, _H1)},
+    (5, 8, 8, 64, 24, 1): {"2": (_H1, _H1), "0": (_H1, _H1)},
+    (2, 64, 64, 128, 16, 2): {m: (_S(1, 4, "false"), _S(4, 4, "false")) for m in "20"},
+    (1, 128, 128, 64, 64, 1): {"2": (_B8, _B8), "0": (_B4, _B4)},
+}
+
+
 @pytest.mark.parametrize("B,H,W,Cin,Cout,dil", [(2, 32, 32, 256, 64, 1), (1, 32, 16, 40, 64, 1), (2, 16, 16, 72, 136, 2), (3, 16, 16, 96, 40, 4),
-                                                (5, 8, 8, 64, 24, 1), (2, 64, 64, 128, 16, 2)])
+                                                (5, 8, 8, 64, 24, 1), (2, 64, 64, 128, 16, 2), (1, 128, 128, 64, 64, 1)])
 def test_conv_big_eight_wave_tile(gen, monkeypatch, B, H, W, Cin, Cout, dil):
     """conv_big's 256-pixel tile on eight waves (forced: the planner only picks it for large launches) against the oracle and
-    against the four-wave tiles, forward and backward-data."""
+    against the four-wave tiles, forward and backward-data (EIGHT_WAVE_ROUTES: which cases reach it)."""
     from ultrasound_modeling_amd import ops
     from ultrasound_modeling_amd.layers import Conv2D
     layer = Conv2D(Cin, Cout, 3, dil)
@@ -189,8 +279,10 @@ def test_conv_big_eight_wave_tile(gen, monkeypatch, B, H, W, Cin, Cout, dil):
     outs = []
     for mode in ("2", "0"):
         monkeypatch.setenv("USSEG_BIG_W8", mode)
-        y = layer.forward(xd, act=ops.ACT_LRELU, alpha=0.3)
-        dx = layer.backward(to_dev_padded(dy), skip_wgrad=True)
+        want = EIGHT_WAVE_ROUTES[(B, H, W, Cin, Cout, dil)][mode]
+        y = on_route(want[0], lambda: layer.forward(xd, act=ops.ACT_LRELU, alpha=0.3))
+        dyd = to_dev_padded(dy)
+        dx = on_route(want[1], lambda: layer.backward(dyd, skip_wgrad=True))
         torch.cuda.synchronize()
         assert rel(y[..., :Cout], bf(O.leaky_relu(ref))) < REL_BF16
         assert rel(dx[..., :Cin], bf(xr.grad)) < 2 * REL_BF16
@@ -211,31 +303,44 @@ def test_conv2d_fwd_dgrad_wgrad(gen, B, H, W, Cin, Cout, k, dil):
     x = rnd(gen, B, H, W, Cin)
     xd = to_dev_padded(x)
     ref = O.conv2d_same(x, w, b, dil)
+    mag = O.conv2d_same(x.abs(), w.abs(), b.abs(), dil)         # |x| (*) |w| + |b|: the per-element error scale
+    routes = CONV_ROUTES.get((B, H, W, Cin, Cout, k, dil))
+
+    def run(i, fn):     # the kernel a labelled case's pass lands on, asserted before its numbers
+        return fn() if routes is None else on_route(routes[i], fn)
     # fp32 output
-    y32 = layer.forward(xd, out_f32=True)
+    y32 = run(0, lambda: layer.forward(xd, out_f32=True))
     torch.cuda.synchronize()
     assert rel(y32[..., :Cout], ref) < REL_F32
+    assert_elementwise(y32[..., :Cout], ref, mag, U_F32, 4.0 + math.sqrt(k * k * Cin) / 8, what="fp32 forward")
     # bf16 output: pad channels must be exactly zero
-    y16 = layer.forward(xd)
+    y16 = run(1, lambda: layer.forward(xd))
     assert rel(y16[..., :Cout], bf(ref)) < REL_BF16
+    assert_elementwise(y16[..., :Cout], ref, mag, U_BF16, 4.0, what="bf16 forward")
     assert y16[..., Cout:].abs().max().item() == 0 if layer.cout_p > Cout else True
     # fused LeakyReLU + residual epilogue
     r = rnd(gen, B, H, W, Cout)
     yr = layer.forward(xd, act=ops.ACT_LRELU, alpha=0.3, residual=to_dev_padded(r))
     assert rel(yr[..., :Cout], bf(O.leaky_relu(ref) + r)) < REL_BF16
+    assert_elementwise(yr[..., :Cout], O.leaky_relu(ref) + r, mag + r.abs(), U_BF16, 4.0, what="residual forward")
     # backward: dgrad, wgrad, bias grad
     layer.forward(xd)
     dy = rnd(gen, B, H, W, Cout)
     xr = x.clone().requires_grad_(True)
     wr, br = w.clone().requires_grad_(True), b.clone().requires_grad_(True)
     (O.conv2d_same(xr, wr, br, dil) * dy).sum().backward()
-    dx = layer.backward(to_dev_padded(dy))
+    xm, wm = x.abs().requires_grad_(True), w.abs().requires_grad_(True)
+    (O.conv2d_same(xm, wm, None, dil) * dy.abs()).sum().backward()
+    dyd = to_dev_padded(dy)
+    dx = run(2, lambda: layer.backward(dyd))
     torch.cuda.synchronize()
     assert rel(dx[..., :Cin], bf(xr.grad)) < REL_BF16
+    assert_elementwise(dx[..., :Cin], xr.grad, xm.grad, U_BF16, 4.0, what="backward data")
     if layer.cin_p > Cin:
         assert dx[..., Cin:].abs().max().item() == 0
     assert rel(layer.kernel.grad, wr.grad) < REL_F32
     assert rel(layer.bias.grad, br.grad) < REL_F32
+    assert_elementwise(layer.kernel.grad, wr.grad, wm.grad, U_F32, 4.0 + math.sqrt(B * H * W) / 8, what="weight gradient")
     # gradients ACCUMULATE (second backward doubles them)
     layer.backward(to_dev_padded(dy))
     assert rel(layer.kernel.grad, 2 * wr.grad) < REL_F32
@@ -278,6 +383,21 @@ TCONV_CASES = [
 ]
 
 
+# (forward, backward data, weight gradient) of each TCONV_CASES case: the parity-class gather GEMM both ways, the per-tap weight gradient
+_G1, _G2, _WD1, _WD2 = "igemm_dma_kernel<1, 3>", "igemm_dma_kernel<2, 3>", "wgrad_dma_kernel<1, 3>", "wgrad_dma_kernel<2, 2>"
+TCONV_ROUTES = {
+    (1, 4, 4, 8, 8, 3): (_G1, _G1, _WD1), (2, 5, 3, 16, 24, 3): (_G2, _G1, _WD1), (1, 8, 8, 72, 3, 3): (_G1, _G2, _WD1),
+    (1, 16, 16, 160, 64, 3): (_G2, _G2, _WD1), (1, 4, 4, 8, 8, 4): (_G1, _G1, _WD1), (2, 3, 5, 24, 16, 4): (_G1, _G2, _WD1),
+    (1, 8, 8, 160, 3, 4): (_G1, _G2, _WD1), (1, 1, 1, 16, 8, 4): (_G1, _G1, _WD1), (3, 9, 7, 136, 72, 4): (_G2, _G2, _WD2),
+    (1, 16, 16, 264, 136, 3): (_G2, _G2, _WD2),
+}
+# USSEG_TCONV_HALO -> the weight-gradient kernel: four tap-masked parity-class jobs of wgrad_halo, or the per-tap LDS-DMA kernel
+TCONV_WGRAD_HALO_ROUTES = {
+    (1, 8, 8, 72, 40, 3): "wgrad_halo_kernel<2, 2, 2, true, 2, true>", (2, 16, 16, 160, 64, 4): "wgrad_halo_kernel<2, 2, 2, true, 2, true>",
+    (1, 4, 4, 8, 8, 4): "wgrad_halo_kernel<2, 1, 1, true, 1, true>", (3, 32, 16, 24, 136, 3): "wgrad_halo_kernel<4, 1, 2, true, 1, true>",
+}
+
+
 @pytest.mark.parametrize("B,H,W,Cin,Cout,k", [(1, 8, 8, 72, 40, 3), (2, 16, 16, 160, 64, 4), (1, 4, 4, 8, 8, 4), (3, 32, 16, 24, 136, 3)])
 def test_tconv_wgrad_parity_class_halo_form(gen, monkeypatch, B, H, W, Cin, Cout, k):
     """The transposed-conv weight gradient as four tap-masked parity-class jobs of the halo-tile kernel (built, off by default:
@@ -297,7 +417,9 @@ def test_tconv_wgrad_parity_class_halo_form(gen, monkeypatch, B, H, W, Cin, Cout
         layer.bias.data.copy_(b)
         finalize(layer)
         layer.forward(to_dev_padded(x))
-        layer.backward(to_dev_padded(dy))
+        dyd = to_dev_padded(dy)
+        want = TCONV_WGRAD_HALO_ROUTES[(B, H, W, Cin, Cout, k)] if flag == "1" else "wgrad_dma_kernel<1, 3>"
+        on_route(want, lambda: layer.backward(dyd))
         torch.cuda.synchronize()
         assert rel(layer.kernel.grad, wr.grad) < REL_F32
         grads.append(layer.kernel.grad.detach().clone())
@@ -316,16 +438,26 @@ def test_tconv2d_fwd_dgrad_wgrad(gen, B, H, W, Cin, Cout, k):
     x = rnd(gen, B, H, W, Cin)
     xd = to_dev_padded(x)
     ref = O.conv2d_transpose_s2_same(x, w, b)
-    y32 = layer.forward(xd, out_f32=True)
+    mag = O.conv2d_transpose_s2_same(x.abs(), w.abs(), b.abs())
+    routes = TCONV_ROUTES[(B, H, W, Cin, Cout, k)]
+    y32 = on_route(routes[0], lambda: layer.forward(xd, out_f32=True))
     assert rel(y32[..., :Cout], ref) < REL_F32
-    y16 = layer.forward(xd)
+    assert_elementwise(y32[..., :Cout], ref, mag, U_F32, 4.0 + math.sqrt(k * k * Cin) / 8, what="fp32 forward")
+    y16 = on_route(routes[0], lambda: layer.forward(xd))
     assert rel(y16[..., :Cout], bf(ref)) < REL_BF16
+    assert_elementwise(y16[..., :Cout], ref, mag, U_BF16, 4.0, what="bf16 forward")
     dy = rnd(gen, B, 2 * H, 2 * W, Cout)
     xr, wr, br = x.clone().requires_grad_(True), w.clone().requires_grad_(True), b.clone().requires_grad_(True)
     (O.conv2d_transpose_s2_same(xr, wr, br) * dy).sum().backward()
-    dx = layer.backward(to_dev_padded(dy))
+    xm, wm = x.abs().requires_grad_(True), w.abs().requires_grad_(True)
+    (O.conv2d_transpose_s2_same(xm, wm, None) * dy.abs()).sum().backward()
+    dyd = to_dev_padded(dy)
+    dx = on_route(routes[1:], lambda: layer.backward(dyd))
+    torch.cuda.synchronize()
     assert rel(dx[..., :Cin], bf(xr.grad)) < REL_BF16
+    assert_elementwise(dx[..., :Cin], xr.grad, xm.grad, U_BF16, 4.0, what="backward data")
     assert rel(layer.kernel.grad, wr.grad) < REL_F32
+    assert_elementwise(layer.kernel.grad, wr.grad, wm.grad, U_F32, 4.0 + math.sqrt(4 * B * H * W) / 8, what="weight gradient")
     assert rel(layer.bias.grad, br.grad) < REL_F32
 
 
@@ -835,10 +967,18 @@ def test_deferred_finishing_matches_immediate(gen):
         a = ln.forward(r, ops.ACT_LRELU, 0.3)
         conv2.forward(a)
         ctx = ops.overlap_region() if deferred else __import__("contextlib").nullcontext()
-        with ctx:
-            d = conv2.backward(dy)
-            d = ln.backward(d, dbias=conv.bias.grad)
-            conv.backward(d, need_dx=False, skip_bias=True)
+
+        def backward():
+            with ctx:
+                d = conv2.backward(dy)
+                d = ln.backward(d, dbias=conv.bias.grad)
+                conv.backward(d, need_dx=False, skip_bias=True)
+        # deferred: the queued finishing reductions run as one batched launch; immediate: one finishing launch per weight gradient
+        _, got = kernels(backward)
+        got = [short(n) for n in got]
+        finish = "wgrad_finish_batched_kernel" if deferred else "wgrad_finish_kernel"
+        other = "wgrad_finish_kernel" if deferred else "wgrad_finish_batched_kernel"
+        assert finish in got and other not in got, got
         torch.cuda.synchronize()
         return [p.grad.clone() for p in holder.parameters()]
 
@@ -889,13 +1029,17 @@ def test_quad_form_transposed_conv(gen, B, H, W, Cin, Cout, k):
     x = rnd(gen, B, H, W, Cin)
     xd = to_dev_padded(x)
     ref = O.conv2d_transpose_s2_same(x, w, b)
-    y = q.forward(xd)
+    # forward: one stride-1 3x3 conv on the space-to-depth tensors; backward: the same kernel for backward data, the weight
+    # gradient as tap-masked parity-class jobs of wgrad_halo (k=4) or the per-tap kernel (k=3), then the quad unpack
+    wg = "wgrad_halo_kernel<2, 2, 2, true, 2, true>" if k == 4 else "wgrad_dma_kernel<1, 3>"
+    y = on_route("conv_halo_kernel<1>", lambda: q.forward(xd))
     torch.cuda.synchronize()
     assert rel(y[..., :Cout], bf(ref)) < REL_BF16
     dy = rnd(gen, B, 2 * H, 2 * W, Cout)
     xr, wr = x.clone().requires_grad_(True), w.clone().requires_grad_(True)
     (O.conv2d_transpose_s2_same(xr, wr, b) * dy).sum().backward()
-    dx = q.backward(to_dev_padded(dy))
+    dyd = to_dev_padded(dy)
+    dx = on_route(("conv_halo_kernel<1>", wg, "tconv_quad_unpack_kernel"), lambda: q.backward(dyd))
     torch.cuda.synchronize()
     assert rel(dx[..., :Cin], bf(xr.grad)) < 2 * REL_BF16
     assert rel(layer.kernel.grad, wr.grad) < REL_F32
