@@ -246,6 +246,8 @@ int usseg_dropout_mask(void* mask, int64_t M, int32_t C, int32_t ld, uint64_t se
  * training step then draws a fresh mask at every replay. */
 int usseg_dropout_mask_step(void* mask, int64_t M, int32_t C, int32_t ld, uint64_t seed, const int32_t* step_dev, float rate,
                             usseg_stream_t stream);
+/* *counter += inc on the device (one thread): advances a counter that usseg_dropout_mask_step reads, eagerly or inside a captured HIP graph. */
+int usseg_counter_add(int32_t* counter, int32_t inc, usseg_stream_t stream);
 /* dx, and dgamma/dbeta accumulated.  x is the SAME pre-normalisation input as in fwd. */
 int usseg_norm_act_bwd(const UssegNormDesc* d, const void* x, const void* dy, const float* gamma, const float* beta,
                        const float* mean, const float* var, const void* mask, int32_t ldm, void* dx, float* dgamma,
@@ -287,6 +289,11 @@ int usseg_norm_act_bwd_pair(const UssegNormDesc* da, const void* xa, const void*
 int usseg_stem_fwd(int32_t B, int32_t H, int32_t W, const void* x, int32_t ldx, const void* w1, const float* b1, const void* w2, const float* b2,
                    const void* w3, const float* b3, const float* gamma, const float* beta, const float* mean, const float* var, float eps,
                    float alpha, void* y1, void* t1, void* c2, void* pooled, usseg_stream_t stream);
+/* The same launch for inference: same inputs and checks, ONE output, pooled [B,H/2,W/2,32], bit-identical to what usseg_stem_fwd writes.
+ * y1, t1 and c2 (the tensors only the backward pass reads, 80 of the 112 bf16 channels written per pixel) are not stored. */
+int usseg_stem_fwd_infer(int32_t B, int32_t H, int32_t W, const void* x, int32_t ldx, const void* w1, const float* b1, const void* w2,
+                         const float* b2, const void* w3, const float* b3, const float* gamma, const float* beta, const float* mean,
+                         const float* var, float eps, float alpha, void* pooled, usseg_stream_t stream);
 /* A stem conv's 3x3 backward-data pass + the backward of the layer in front of it, in ONE launch (GradientTape through ResNest.py:41-44 /
  * :39-41): dy [B,H,W,32] -> dx_in = conv3x3_backward_data(dy, wd) (wd = the packed operand of usseg_conv2d_dgrad, [Co][9*32]) -> then
  *   mode 2 (Co = 32): the folded inference BatchNormalization + LeakyReLU backward from the ACTIVATED tensor yact the forward stored
@@ -320,6 +327,12 @@ int usseg_cardinal_fwd(const UssegCardinalDesc* d, const void* x, const void* w1
                        const void* w2, const float* b2, const float* g2, const float* be2, const void* wsc, const float* bsc,
                        const float* gsc, const float* besc, void* u_raw, void* u, void* v_raw, void* y, float* gap_rows, void* sc_raw,
                        void* sc, usseg_stream_t stream);
+/* The same launch for inference: the same descriptor (ldu is not read), weights and checks, and three outputs - y [B,H,W,Vp], gap_rows and
+ * sc [B,H,W,Oc] - bit-identical to what usseg_cardinal_fwd writes.  u_raw, u, v_raw and sc_raw (read only by the backward pass) are not
+ * stored.  usseg_cardinal_supported decides support for both entry points. */
+int usseg_cardinal_fwd_infer(const UssegCardinalDesc* d, const void* x, const void* w1, const float* b1, const float* g1, const float* be1,
+                             const void* w2, const float* b2, const float* g2, const float* be2, const void* wsc, const float* bsc,
+                             const float* gsc, const float* besc, void* y, float* gap_rows, void* sc, usseg_stream_t stream);
 /* The backward pass of the same stage half as ONE launch (K3 backward; GradientTape through ResNest.py:136-147 and :100-101): replaces the
  * split-attention re-weighting's backward + LayerNormalization/LeakyReLU backward of conv2_bn, the grouped 3x3's backward-data pass, the
  * LayerNormalization/LeakyReLU backward of conv1_bn, and the shortcut norm's backward.

@@ -1,0 +1,85 @@
+"""Timing of label-free predict (eager and HIP-graph replay) next to the eval step, for Arch B and Arch A (diagnostic).
+
+    python tools/time_predict.py                 # the table: ms per call, median of --repeats runs of --calls back-to-back calls
+    python tools/time_predict.py --trace         # one Arch B predict and one eval step at [16,256,256,1] (after one warm-up of each),
+                                                 # for a kernel trace: rocprofv3 --kernel-trace --stats -- python tools/time_predict.py --trace
+
+Shapes: B=1 at 256x80x10 (the MainNumpy shape) and B=16 at 256x256x1 (the bench shape).  Arch A needs H and W divisible by 64, so its
+B=1 row runs at 256x256x1 as well.  One JSON line per row.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import torch  # noqa: E402
+
+
+def build(arch, B, H, W, C):
+    if arch == "B":
+        from ultrasound_modeling_amd.VisionTransformer import VisionTransformer
+        return VisionTransformer(batch_size=B, img_size=(H, W), in_channels=C)
+    from ultrasound_modeling_amd.TBI_ResNest import ResNest
+    return ResNest(H, W, C, 3, ksize=3, radix=3, kpaths=4)
+
+
+def batch(B, H, W, C):
+    x = torch.randn(B, H, W, C, device="cuda").clamp_(-1, 1)
+    y = torch.nn.functional.one_hot(torch.randint(0, 3, (B, H, W), device="cuda"), 3).float()
+    return x, y
+
+
+def per_call_ms(fn, calls, repeats):
+    for _ in range(3):
+        fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(repeats):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(calls):
+            fn()
+        e1.record()
+        e1.synchronize()
+        out.append(e0.elapsed_time(e1) / calls)
+    return statistics.median(out), min(out), max(out)
+
+
+def table(args):
+    rows = [("B", 1, 256, 80, 10), ("B", 16, 256, 256, 1), ("A", 1, 256, 256, 1), ("A", 16, 256, 256, 1)]
+    for arch, B, H, W, C in rows:
+        net = build(arch, B, H, W, C)
+        x, y = batch(B, H, W, C)
+        step = (lambda: net.step(x, y)) if arch == "B" else (lambda: net.step(x, y, train=False))
+        r = {"arch": arch, "shape": [B, H, W, C], "calls": args.calls, "repeats": args.repeats}
+        r["eval_step_ms"] = per_call_ms(step, args.calls, args.repeats)
+        r["predict_eager_ms"] = per_call_ms(lambda: net.predict(x), args.calls, args.repeats)
+        net.capture_predict_graph(x)
+        r["predict_graph_ms"] = per_call_ms(lambda: net.predict(x), args.calls, args.repeats)
+        print(f"arch {arch} {B}x{H}x{W}x{C}: eval step {r['eval_step_ms'][0]:.3f} ms, predict eager {r['predict_eager_ms'][0]:.3f} ms, "
+              f"predict graph {r['predict_graph_ms'][0]:.3f} ms (median of {args.repeats} x {args.calls} calls)", flush=True)
+        print(json.dumps(r), flush=True)
+        del net
+        torch.cuda.empty_cache()
+
+
+def trace():
+    net = build("B", 16, 256, 256, 1)
+    x, y = batch(16, 256, 256, 1)
+    for _ in range(2):            # the first of each is the warm-up
+        net.predict(x)
+        net.step(x, y)
+    torch.cuda.synchronize()
+    print("trace: 2 predict + 2 eval step calls at [16,256,256,1]", flush=True)
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--calls", type=int, default=20)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--trace", action="store_true")
+    a = ap.parse_args()
+    trace() if a.trace else table(a)

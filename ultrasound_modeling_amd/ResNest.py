@@ -251,12 +251,22 @@ class _CardinalGroup:
                                    ops.cardinal_supported(self.cin_p, self.P, self.cv11, self.cvkk, self.Up, self.Vp, sc_conv.cout))
         return ok and _FUSED_CARDINAL
 
-    def forward_fused(self, x, sc_conv, sc_norm, out=None):
+    def forward_fused(self, x, sc_conv, sc_norm, out=None, stash=True):
         """ResNest.py:136-147 for all paths + the shortcut :99-101 in one launch, then the split-attention MLP and re-weighting
         (:171-199).  Leaves exactly the state the unfused forward leaves (``_saved``, the shortcut layers' saved inputs), so the
-        backward pass is the same code. -> (concats_1, sc)"""
+        backward pass is the same code.  ``stash=False`` (predict): the launch writes only y, the pool rows and sc (bit-identical), and
+        the saved state is cleared - no backward pass may follow. -> (concats_1, sc)"""
         B, H, W, _, _ = ops.geom(x)
         a = KERAS_LRELU_ALPHA
+        if not stash:
+            y, gap, sc = ops.cardinal_fwd_infer(x, self.w1_f, self.b1, self.g1, self.be1, self.w2_f, self.b2, self.g2, self.be2, sc_conv.wp_f,
+                                                sc_conv.bias.data, sc_norm.gamma.data, sc_norm.beta.data, self.P, self.cv11, self.cvkk,
+                                                self.Up, self.Vp, sc_conv.cout, KERAS_LN_EPS, a)
+            out = out if out is not None else ops.new_act(B, H, W, self.Vp, x.device)
+            ops.splitattn_fwd(self._sa_desc(B, H * W), y, self._mlp_params(), out, gap=gap)
+            self._saved = None
+            sc_conv._x = sc_norm._x = None
+            return out, sc
         u_raw, u, v_raw, y, gap, sc_raw, sc = ops.cardinal_fwd(x, self.w1_f, self.b1, self.g1, self.be1, self.w2_f, self.b2, self.g2, self.be2,
                                                                sc_conv.wp_f, sc_conv.bias.data, sc_norm.gamma.data, sc_norm.beta.data,
                                                                self.P, self.cv11, self.cvkk, self.Up, self.Vp, sc_conv.cout, KERAS_LN_EPS, a)
@@ -379,9 +389,10 @@ class residual_S(nn.Module):
             jobs.append(ops.pack_job(sc.kernel.data, sT, sI, sO, 1, sc.cin, sc.cout, self.wcat_d, Kc, Kc, 0, g.Up))
         return jobs
 
-    def forward(self, x, out=None):
+    def forward(self, x, out=None, stash=True):
+        """``stash=False``: the fused cardinal launch writes no tensor of the backward pass (predict); every other layer runs as in training."""
         if self._group.fused_ok(self.convtmp_sc):
-            concats_1, sc = self._group.forward_fused(x, self.convtmp_sc, self.convtmp_scbn)        # :91-96 and :99-101, one launch + the attention
+            concats_1, sc = self._group.forward_fused(x, self.convtmp_sc, self.convtmp_scbn, stash=stash)   # :91-96 and :99-101, one launch + the attention
             return self.concats_2.forward(concats_1, out=out, residual=sc)                           # :98,:102
         concats_1 = self._group.forward(x)                                                          # :91-96
         sc_raw = self.convtmp_sc.forward(x)                                                          # :99
@@ -450,9 +461,11 @@ class ResNest(nn.Module):
         self.conv_3 = residual_S(ksize, w[2], radix, kpaths, wDecay=wDecay, in_channels=w[1], norm=norm)
         self.conv_4 = residual_S(ksize, w[3], radix, kpaths, wDecay=wDecay, in_channels=w[2], norm=norm)
 
-    def forward(self, x, outs=None):
+    def forward(self, x, outs=None, stash=True):
         """x: NHWC float32/float64 [B,H,W,channel] (cast to bf16 here, ResNest.py:39) or an already-cast bf16 tensor.
-        ``outs``: optional destinations [x_3, x_2, x_1] (channel-slice views allowed) the stage outputs are written into."""
+        ``outs``: optional destinations [x_3, x_2, x_1] (channel-slice views allowed) the stage outputs are written into.
+        ``stash=False`` (predict): the fused stem and cardinal launches go to their inference entry points, which write none of the tensors
+        the backward pass reads, and the saved state that would point at them is cleared; no backward pass may follow."""
         o3, o2, o1 = outs if outs is not None else (None, None, None)
         if x.dtype != BF16:
             x = ops.cast_input(x.contiguous(), roundup(self.channel, 8))
@@ -462,6 +475,12 @@ class ResNest(nn.Module):
         if (_FUSED_STEM and self._fold and not bn2.training_mode and self.conv1.cin_p == 8 and x.shape[1] % 2 == 0 and x.shape[2] % 2 == 0
                 and (self.conv1.cout, self.convtmp_1.cout, self.convtmp_2.cout) == (16, 32, 32)):
             # :39-47 as ONE launch (csrc/stem.hip); leaves the state the four launches below leave, so the backward pass is the same code
+            if not stash:
+                t = ops.stem_fwd_infer(x, self.conv1.wp_f, self.conv1.bias.data, self.convtmp_1.wp_f, bn1.fold_shift, self.convtmp_2.wp_f,
+                                       self.convtmp_2.bias.data, bn2.gamma.data, bn2.beta.data, bn2.moving_mean_p, bn2.moving_variance_p, bn2.eps, a)
+                self._y1 = self._t1 = self.conv1._x = self.convtmp_1._x = self.convtmp_2._x = bn2._x = None
+                self._pool_fused = self._stem_fused = True
+                return self._stages_forward(t, o1, o2, o3, stash=False)
             self._y1, self._t1, c2, t = ops.stem_fwd(x, self.conv1.wp_f, self.conv1.bias.data, self.convtmp_1.wp_f, bn1.fold_shift,
                                                      self.convtmp_2.wp_f, self.convtmp_2.bias.data, bn2.gamma.data, bn2.beta.data,
                                                      bn2.moving_mean_p, bn2.moving_variance_p, bn2.eps, a)
@@ -483,13 +502,13 @@ class ResNest(nn.Module):
             t = self.convtmp_2bn.forward_pool(t, ACT_LRELU, a)
         else:
             t = self.conv1_pool.forward(self.convtmp_2bn.forward(t, ACT_LRELU, a))               # :45-47
-        return self._stages_forward(t, o1, o2, o3)
+        return self._stages_forward(t, o1, o2, o3, stash=stash)
 
-    def _stages_forward(self, t, o1, o2, o3):
-        x_1 = self.conv_1.forward(t, out=o1)                                                     # :48
-        x_2 = self.conv_2.forward(self.conv2_pool.forward(x_1), out=o2)                          # :49-50
-        x_3 = self.conv_3.forward(self.conv3_pool.forward(x_2), out=o3)                          # :51-52
-        x_4 = self.conv_4.forward(self.conv4_pool.forward(x_3))                                  # :53-54
+    def _stages_forward(self, t, o1, o2, o3, stash=True):
+        x_1 = self.conv_1.forward(t, out=o1, stash=stash)                                        # :48
+        x_2 = self.conv_2.forward(self.conv2_pool.forward(x_1), out=o2, stash=stash)             # :49-50
+        x_3 = self.conv_3.forward(self.conv3_pool.forward(x_2), out=o3, stash=stash)             # :51-52
+        x_4 = self.conv_4.forward(self.conv4_pool.forward(x_3), stash=stash)                     # :53-54
         return x_4, [x_3, x_2, x_1]                                                              # :55
 
     def backward(self, d_x4, d_feats):

@@ -27,9 +27,10 @@ from .flat import AdamClip, FlatParams
 from .layers import (KERAS_BN_EPS, KERAS_ELU_ALPHA, AveragePooling2D, BatchNormalization, Conv2D, Conv2DTranspose, QuadHead, QuadTConv,
                      _Workspace)
 from .ops import ACT_ELU, ACT_NONE, ACT_RELU, BF16, roundup
-from .step import TrainStepDriver
+from .step import PredictDriver, TrainStepDriver, inference_norms
 
 _STEM_WGRAD_MERGE = os.environ.get("USSEG_STEM_WGRAD_MERGE", "1") != "0"   # the stem's three weight gradients in one multi-job launch (as ResNest.py's)
+_PREDICT_SALT = 1 << 31     # the dropout seeds of predict calls: apart from training (salt 0) and the numbered evaluation calls
 _STAGE_LAZY = os.environ.get("USSEG_STAGE_LAZY", "1") != "0"    # per-stage lazy weight gradients (ops.lazy_wgrads) in the backward pass: -1.5 %
 
 
@@ -290,6 +291,7 @@ class _ResModel(nn.Module):
         self.dropout_seed = 0           # model-level seed of the always-on dropout masks
         self._eval_salt = 0             # 0 inside training steps; the wrapper numbers evaluation calls
         self.injected_masks = None      # tests inject {0,1} keep masks to make the always-on dropout deterministic
+        self._predict_counter = None    # set during predict: the masks then follow the wrapper's device-resident predict counter
 
     # grouped-kernel plumbing -----------------------------------------------------------------------------------
     def _build(self):
@@ -342,6 +344,8 @@ class _ResModel(nn.Module):
         # evaluation-call number): the eager step t and the HIP-graph replay of step t draw the same mask, successive steps and
         # successive evaluation calls draw fresh ones
         mask = torch.empty_like(like)
+        if self._predict_counter is not None:
+            return ops.dropout_mask(mask, (self.dropout_seed * 1000003 + _PREDICT_SALT) * 7919 + i, 0.5, self._predict_counter)
         return ops.dropout_mask(mask, (self.dropout_seed * 1000003 + self._eval_salt) * 7919 + i, 0.5, getattr(self, "step_dev", None))
 
     def forward(self, x, return_logits=False):
@@ -482,7 +486,7 @@ class _ResModel(nn.Module):
         return ops.tconv2d_dgrad(dy, layer.wp_d, layer.k, ops.new_act(B, H, W, layer.cin_p, dy.device))
 
 
-class ResNest(TrainStepDriver):
+class ResNest(TrainStepDriver, PredictDriver):
     """TBI_ResNest.py:15-55.  ``step(x, y, train)`` -> (loss map [H,W], accuracy, probabilities)."""
 
     def __init__(self, height, width, channel, num_class, ksize, radix=4, kpaths=4, learning_rate=1e-3, ckpt_dir="./Checkpoint", *,
@@ -505,6 +509,7 @@ class ResNest(TrainStepDriver):
         self._scale = torch.zeros(height * width * num_class, dtype=torch.float32, device=self.device)
         self.grad_sync = None
         self._graph = None
+        self._predict_dev = torch.zeros(1, dtype=torch.int32, device=self.device)     # predict calls so far (dropout masks of predict)
         self.resModel.step_dev = self.optimizer.step_dev      # dropout masks follow the device step counter (graph replays)
         object.__setattr__(self.resModel, "save", self.save_params)     # the driver calls neuralnet.resModel.save(path) (TBI_ResNest.py:472)
 
@@ -621,6 +626,23 @@ class ResNest(TrainStepDriver):
         if train and self._graph is not None:   # replayed step: loss map / accuracy / probabilities are static buffers, valid until the next call
             return self._loss_map.reshape(self.height, self.width), accuracy, probs     # (two clones = two more dispatches behind every replay)
         return self._loss_map.clone().reshape(self.height, self.width), accuracy.clone(), probs
+
+    def _predict_body(self, x):
+        """The forward of ``step(train=False)`` without labels or loss.  The reference's dropout in upsample_0..2 is always on, in
+        ``SegNet(testX)`` too, so predict draws masks: a function of (model seed, layer, predict counter).  The counter lives on the device
+        and each call advances it by one launch, eagerly and inside a captured graph alike, so successive calls draw fresh masks and an
+        eager sequence draws the masks its replayed twin draws.  ``injected_masks`` override them as in training."""
+        net = self.resModel
+        ops.counter_add(self._predict_dev)
+        net._predict_counter = self._predict_dev
+        try:
+            with inference_norms(self._norm_layers()):
+                return net.forward(x)                                                          # :40, :125
+        finally:
+            net._predict_counter = None
+
+    def _predict_state(self):
+        return [self._predict_dev]
 
     def modules(self):
         return self.resModel.modules()

@@ -30,7 +30,7 @@ from .ResNest import ResNest, cardinal, residual_S
 
 _FUSED_HEAD = os.environ.get("USSEG_FUSED_HEAD", "1") != "0"      # quad-form head conv + softmax + loss as one launch (csrc/attn_loss_optim.hip)
 from .ops import BF16, roundup
-from .step import TrainStepDriver
+from .step import PredictDriver, TrainStepDriver, inference_norms
 
 input_size = (256, 80)   # VisionTransformer.py:7
 _VIT_LAZY = os.environ.get("USSEG_VIT_LAZY", "enc")              # ops.lazy_wgrads over the whole encoder ("enc"), per block, or "0"
@@ -80,10 +80,11 @@ class Embeddings(nn.Module):
         self.hybrid_model.stage_lazy = _ENC._STAGE_LAZY           # (Transformer.__init__ clears it when a ViT follows the embedding)
         self.patch_embeddings = Conv2D(widths[3], hidden_size, 1, init="glorot")                          # :106
 
-    def forward(self, x, feature_slots=None):
+    def forward(self, x, feature_slots=None, stash=True):
         """``feature_slots``: optional [x_3, x_2, x_1] destinations (the skip slices of the decoder's concat buffers): the
-        encoder stages write their outputs there, so ``tf.concat([x, skip])`` (Decoder.py:66) costs no copy."""
-        x4, features = self.hybrid_model.forward(x, outs=feature_slots)               # :113
+        encoder stages write their outputs there, so ``tf.concat([x, skip])`` (Decoder.py:66) costs no copy.
+        ``stash=False``: the encoder's forward for predict (``ResNest.forward``)."""
+        x4, features = self.hybrid_model.forward(x, outs=feature_slots, stash=stash)  # :113
         e = self.patch_embeddings.forward(x4)                                         # :114
         B = e.shape[0]
         return e.reshape(B, self.seq_len, self.hidden_size), features                 # :116 (+ zeros, :118; dropout 0)
@@ -287,8 +288,8 @@ class Transformer(nn.Module):
         if self.encoder is not None and _ENC._STAGE_LAZY_ENV is None:
             self.embeddings.hybrid_model.stage_lazy = 0       # the side stream carries the ViT's weight gradients (ResNest.py of this repo, _STAGE_LAZY)
 
-    def forward(self, input_ids, feature_slots=None, need_weights=True):
-        embedding_output, features = self.embeddings.forward(input_ids, feature_slots)
+    def forward(self, input_ids, feature_slots=None, need_weights=True, stash=True):
+        embedding_output, features = self.embeddings.forward(input_ids, feature_slots, stash=stash)
         if self.encoder is None:
             return embedding_output, [], features
         B, N, hs = embedding_output.shape
@@ -304,7 +305,7 @@ class Transformer(nn.Module):
         self.embeddings.backward(d_hidden, d_feats)
 
 
-class VisionTransformer(TrainStepDriver, nn.Module):
+class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
     def __init__(self, batch_size, img_size=(256, 80), num_classes=3, learning_rate=1e-3, weight_decay=1e-4, *,
                  in_channels: int = 10, use_vit: bool = False, device: Optional[str] = None, seed: Optional[int] = 0,
                  transunet: bool = False):
@@ -432,6 +433,25 @@ class VisionTransformer(TrainStepDriver, nn.Module):
         ops.softmax_loss(logits, y, probs, self._loss, dlogits, HW=H * W, C_classes=self.num_classes, loss_kind=0,
                          label_smoothing=0.1, clip_eps=1e-7, inv_global_batch=scale, quad_w=qw)
         return probs, dlogits
+
+    def _predict_body(self, x):
+        """The forward of ``_forward_loss`` without labels: the encoder with ``stash=False``, the fused attention, the decoder, and the head
+        softmax with no loss.  No loss buffer, gradient, optimiser state or BatchNorm statistic is read or written."""
+        with inference_norms(self._norm_layers()):
+            hidden, _, features = self.transformer.forward(x, feature_slots=self.decoder.prepare(x.shape[0], self.device), need_weights=False,
+                                                           stash=False)
+            fused = _FUSED_HEAD and self.decoder.quad_head
+            xh = self.decoder.forward(hidden, features, return_head_input=True) if fused else None
+            logits = None if fused else self.decoder.forward(hidden, features, return_logits=True)
+            B = (xh if fused else logits).shape[0]
+            H, W = self.decoder.out_hw
+            probs = torch.empty((B, H, W, self.num_classes), dtype=torch.float32, device=self.device)
+            if fused:       # head conv + softmax in one launch (head_quad_loss_kernel with no labels); the head conv + softmax where it has no kernel
+                if self.decoder._quad.forward_loss(xh, None, probs, None, None):
+                    return probs
+                logits = self.decoder._head_forward(xh)
+            ops.softmax_loss(logits, None, probs, None, None, HW=H * W, C_classes=self.num_classes, quad_w=self.decoder.quad_w)
+            return probs
 
     def compute_loss(self, y_true, y_pred):
         """VisionTransformer.py:225-227: CategoricalCrossentropy(label_smoothing=0.1, reduction NONE) on PROBABILITIES, summed

@@ -130,6 +130,7 @@ _PROTOS = {
     "usseg_norm_act_fwd": (C.c_int, [P(NormDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
     "usseg_dropout_mask": (C.c_int, [c_vp, c_i64, c_i32, c_i32, C.c_uint64, c_f32, c_vp]),
     "usseg_dropout_mask_step": (C.c_int, [c_vp, c_i64, c_i32, c_i32, C.c_uint64, c_vp, c_f32, c_vp]),
+    "usseg_counter_add": (C.c_int, [c_vp, c_i32, c_vp]),
     "usseg_norm_act_bwd": (C.c_int, [P(NormDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "usseg_bn_act_pool_fwd": (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_f32, c_i32, c_f32, c_vp, c_i32, c_vp]),
     "usseg_bn_act_pool_bwd": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_f32, c_i32, c_f32,
@@ -155,10 +156,13 @@ _PROTOS = {
     # fused encoder stem (ResNest.py:39-47): three convs, two BatchNorms, the activations and the pool
     "usseg_stem_fwd": (C.c_int, [c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_f32,
                                  c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "usseg_stem_fwd_infer": (C.c_int, [c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_f32,
+                                       c_vp, c_vp]),
     "usseg_conv3_dgrad_actbwd": (C.c_int, [c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_f32, c_f32, c_vp, c_i32,
                                            c_vp, c_vp, c_vp, c_vp, c_vp]),
     "usseg_cardinal_supported": (c_i32, [P(CardinalDesc)]),
     "usseg_cardinal_fwd": (C.c_int, [P(CardinalDesc)] + [c_vp] * 21),
+    "usseg_cardinal_fwd_infer": (C.c_int, [P(CardinalDesc)] + [c_vp] * 17),
     # ... and its backward pass: (re-weighting + conv2_bn) backward -> grouped 3x3 backward-data -> conv1_bn backward | shortcut norm backward
     "usseg_cardinal_bwd": (C.c_int, [P(CardinalDesc), c_vp, c_i32, c_vp, c_i32] + [c_vp] * 12 + [c_f32, c_vp, c_vp, c_i32] + [c_vp] * 11),
     "usseg_accuracy": (C.c_int, [c_vp, c_vp, c_i64, c_i32, c_vp, c_vp]),

@@ -1428,6 +1428,15 @@ extern "C" int usseg_dropout_mask_step(void* mask, int64_t M, int32_t C, int32_t
                      C / 8, ld, seed, rate, step_dev);
   return usseg_check_launch("dropout_mask_step");
 }
+// one thread: *counter += inc (the predict counter of Arch A's always-on dropout; replayable from a HIP graph)
+__global__ __launch_bounds__(64) void counter_add_kernel(int32_t* counter, int32_t inc) {
+  if (threadIdx.x == 0) *counter += inc;
+}
+extern "C" int usseg_counter_add(int32_t* counter, int32_t inc, usseg_stream_t stream) {
+  USSEG_CHECK_ARG(counter, "counter_add: null pointer");
+  hipLaunchKernelGGL(counter_add_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, counter, inc);
+  return usseg_check_launch("counter_add");
+}
 
 // ---- BatchNormalization TRAINING mode (Keras: batch mean / biased variance, moving statistics updated with momentum) -------
 // forward : usseg_channel_stats -> usseg_bn_finalize_stats -> usseg_norm_act_fwd(mode 1, batch statistics)

@@ -639,6 +639,12 @@ def dropout_mask(mask, seed: int, rate: float, step_dev=None):
     return mask
 
 
+def counter_add(counter, inc: int = 1):
+    """counter (int32 device tensor) += inc, one launch (capturable)."""
+    assert counter.dtype == torch.int32
+    L.check(L.load().usseg_counter_add(counter.data_ptr(), inc, _stream()), "counter_add")
+
+
 def channel_stats(x, C_logical, s, s2):
     B, H, W, _, ldx = geom(x)
     L.check(L.load().usseg_channel_stats(x.data_ptr(), B * H * W, C_logical, ldx, s.data_ptr(), s2.data_ptr(),
@@ -794,6 +800,17 @@ def stem_fwd(x, w1, b1, w2, b2, w3, b3, gamma, beta, mean, var, eps, alpha):
     return y1, t1, c2, pooled
 
 
+def stem_fwd_infer(x, w1, b1, w2, b2, w3, b3, gamma, beta, mean, var, eps, alpha):
+    """``stem_fwd`` without the tensors of the backward pass -> pooled [B,H/2,W/2,32], bit-identical to ``stem_fwd``'s."""
+    B, H, W, Cin, ldx = geom(x)
+    assert Cin == 8 and x.dtype == BF16
+    pooled = new_act(B, H // 2, W // 2, 32, x.device)
+    L.check(L.load().usseg_stem_fwd_infer(B, H, W, x.data_ptr(), ldx, w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), w3.data_ptr(),
+                                          b3.data_ptr(), gamma.data_ptr(), beta.data_ptr(), mean.data_ptr(), var.data_ptr(), eps, alpha,
+                                          pooled.data_ptr(), _stream()), "stem_fwd_infer")
+    return pooled
+
+
 def conv3_dgrad_actbwd(dy, wd, yact, dx, mode, alpha, dbias, gamma=None, beta=None, var=None, eps=1e-3, dgamma=None, dbeta=None) -> bool:
     """3x3 backward-data of a 32-output-channel stem conv + the backward of the layer in front of it in one launch: mode 2 = folded inference
     BatchNorm + LeakyReLU from the activated tensor ``yact`` (32 channels), mode 0 = LeakyReLU + column sums (16 channels).  False - nothing
@@ -839,6 +856,21 @@ def cardinal_fwd(x, w1, b1, g1, be1, w2, b2, g2, be2, wsc, bsc, gsc, besc, P, cv
                                         u_raw.data_ptr(), u.data_ptr(), v_raw.data_ptr(), y.data_ptr(), rows.data_ptr(), sc_raw.data_ptr(),
                                         sc.data_ptr(), _stream()), "cardinal_fwd")
     return u_raw, u, v_raw, y, (rows, tiles, Vp), sc_raw, sc
+
+
+def cardinal_fwd_infer(x, w1, b1, g1, be1, w2, b2, g2, be2, wsc, bsc, gsc, besc, P, cv11, cvkk, Up, Vp, Oc, eps, alpha):
+    """``cardinal_fwd`` without the tensors of the backward pass -> (y, gap, sc), bit-identical to ``cardinal_fwd``'s."""
+    B, H, W, Cin, ldx = geom(x)
+    dev = x.device
+    y, sc = new_act(B, H, W, Vp, dev), new_act(B, H, W, Oc, dev)
+    tiles = ((H + 7) // 8) * ((W + 7) // 8)
+    rows = torch.empty((B, tiles, Vp), dtype=torch.float32, device=dev)
+    d = cardinal_desc(B, H, W, Cin, P, cv11, cvkk, Up, Vp, Oc, ldx, Up, Vp, Oc, eps, alpha)
+    g1, be1, g2, be2, gsc, besc = (_readable(t, n) for t, n in ((g1, P * cv11), (be1, P * cv11), (g2, P * cvkk), (be2, P * cvkk), (gsc, Oc), (besc, Oc)))
+    L.check(L.load().usseg_cardinal_fwd_infer(C.byref(d), x.data_ptr(), w1.data_ptr(), b1.data_ptr(), g1.data_ptr(), be1.data_ptr(), w2.data_ptr(),
+                                              b2.data_ptr(), g2.data_ptr(), be2.data_ptr(), wsc.data_ptr(), bsc.data_ptr(), gsc.data_ptr(),
+                                              besc.data_ptr(), y.data_ptr(), rows.data_ptr(), sc.data_ptr(), _stream()), "cardinal_fwd_infer")
+    return y, (rows, tiles, Vp), sc
 
 
 def cardinal_bwd(dout, dsc, v_raw, u_raw, sc_raw, w2d, g2, be2, g1, be1, gsc, besc, sa_s, sa_dg, sa_mult, dv, dcat, grads, Cin, P, cv11, cvkk, Up,

@@ -17,6 +17,7 @@ step is one graph up to the per-replica clip, the collective, then the update).
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Callable, Iterable, List, Optional, Tuple
 
 import torch
@@ -136,6 +137,79 @@ class TrainStepDriver:
             else:
                 self._sync_and_update()
         return self._gprobs
+
+
+class PredictDriver:
+    """Label-free inference, eager or replayed from a captured forward-only HIP graph.  A wrapper supplies ``_prep_x``,
+    ``_predict_body(x) -> probabilities`` (no loss, no gradient, no optimiser or BatchNorm-statistics write) and optionally
+    ``_predict_state()``: device tensors a predict call advances (a dropout counter) that the capture warm-up must put back."""
+    _pgraph = None
+
+    def _predict_body(self, x):
+        raise NotImplementedError
+
+    def _predict_state(self) -> List[torch.Tensor]:
+        return []
+
+    def predict(self, x):
+        """x [B,H,W,C] (numpy or tensor) -> fp32 probabilities [B,H,W,classes].  After ``capture_predict_graph`` an input with the captured
+        shape, dtype and strides is copied into ``predict_inputs()`` (no copy if it already is that buffer) and the graph is replayed: the
+        result is then the graph's STATIC probability buffer, valid until the next call (clone it to keep it).  Any other input runs eagerly."""
+        x = self._prep_x(x)
+        px = getattr(self, "_px", None)
+        if self._pgraph is not None and x.dtype == px.dtype and x.shape == px.shape and x.stride() == px.stride() and x.device == px.device:
+            if x.data_ptr() != px.data_ptr():
+                px.copy_(x)
+            self._pgraph.replay()
+            return self._pprobs
+        return self._predict_body(x)
+
+    def capture_predict_graph(self, x, warmup: int = 2):
+        """Capture one forward-only HIP graph of ``predict`` for inputs of this shape, dtype and strides.  The eager warm-up calls run
+        on a side stream and the predict state they advance is restored, so capturing consumes no dropout draws; training state is
+        never touched.  Coexists with a captured training step (``capture_graph``) in either order."""
+        x = self._prep_x(x)
+        self._px = x.clone()
+        state = self._predict_state()
+        saved = [t.clone() for t in state]
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            for _ in range(warmup):
+                self._predict_body(self._px)
+        torch.cuda.current_stream().wait_stream(s)
+        torch.cuda.synchronize()
+        for t, v in zip(state, saved):
+            t.copy_(v)
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            self._pprobs = self._predict_body(self._px)
+        self._pgraph = g
+
+    def _norm_layers(self) -> list:
+        """The layers with a ``training_mode`` switch (BatchNormalization), listed once: ``inference_norms`` takes them."""
+        if getattr(self, "_pnorms", None) is None:
+            self._pnorms = [m for m in self.modules() if hasattr(m, "training_mode")]
+        return self._pnorms
+
+    def predict_inputs(self):
+        """The input buffer the captured predict graph reads: write the next batch THERE and pass it to ``predict`` - no copy."""
+        return self._px
+
+
+@contextlib.contextmanager
+def inference_norms(modules: Iterable):
+    """BatchNormalization layers in batch-statistics mode run on their moving statistics (Keras ``training=False``) inside the block,
+    so a predict call neither reads the batch's statistics nor moves the running ones."""
+    bns = [m for m in modules if getattr(m, "training_mode", False)]
+    for m in bns:
+        m.training_mode = False
+    try:
+        yield
+    finally:
+        for m in bns:
+            m.training_mode = True
 
 
 class _LocalSync:
