@@ -374,11 +374,16 @@ int usseg_channel_stats(const void* x, int64_t M, int32_t C, int32_t ldx, float*
                         usseg_stream_t stream);
 
 /* BatchNormalization TRAINING mode (Keras semantics: batch mean, biased variance, moving statistics *= momentum).
- * forward : usseg_channel_stats -> usseg_bn_finalize_stats -> usseg_norm_act_fwd(mode 1, mean/var = batch statistics);
+ * forward : usseg_bn_batch_stats (or usseg_channel_stats -> usseg_bn_finalize_stats) -> usseg_norm_act_fwd(mode 1, mean/var = batch statistics);
  * backward: usseg_norm_act_bwd(mode 1) with ZEROED scratch tg/tb as dgamma/dbeta, then usseg_bn_train_bwd_fix
  *           (dx -= gamma*rstd*(tb + xhat*tg)/M), then add tg/tb to the real gradients. */
 int usseg_bn_finalize_stats(const float* sum, const float* sumsq, int64_t M, int32_t C, float momentum, float* mean, float* var,
                             float* moving_mean, float* moving_var, usseg_stream_t stream);
+/* The forward's statistics in one call: mean / var (C floats each) are OVERWRITTEN with the batch mean and biased variance, taken as sums
+ * of x - x[pixel 0] (no cancellation when |mean| >> std, which the one-pass sum x^2 / M - mean^2 of usseg_bn_finalize_stats has);
+ * moving statistics (both or neither) *= momentum as above; ws: usseg_reduce_ws_floats() floats. */
+int usseg_bn_batch_stats(const void* x, int64_t M, int32_t C, int32_t ldx, float momentum, float* mean, float* var, float* moving_mean,
+                         float* moving_var, float* ws, usseg_stream_t stream);
 int usseg_bn_train_bwd_fix(const void* x, void* dx, int64_t M, int32_t C, int32_t Cphys, int32_t ldx, int32_t lddx, const float* gamma,
                            const float* mean, const float* var, float eps, const float* tg, const float* tb, usseg_stream_t stream);
 

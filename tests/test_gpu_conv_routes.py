@@ -28,46 +28,11 @@ import pytest
 import torch
 
 import usseg_oracle as O
-from route_probe import U_BF16, U_F32, assert_elementwise, routed
+from route_probe import U_BF16, U_F32, assert_elementwise, bf, c_f32, routed, seam_data, to_dev
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 ALPHA = 0.3
-
-
-def bf(t):
-    return t.to(torch.bfloat16).to(torch.float64)
-
-
-def c_f32(k):
-    """Bound constant for fp32 outputs of a K-term fp32 sum (rounding grows like sqrt(K) for these sums)."""
-    return 4.0 + math.sqrt(k) / 8.0
-
-
-def seam_data(gen, B, H, W, C, scale=1.0):
-    """bf16-exact fp64 NHWC data with one large element and a last image that is zero except near the 16-row seams."""
-    x = bf(torch.randn(B, H, W, C, generator=gen, dtype=torch.float64) * scale)
-    if B > 1 and H > 4:
-        keep = torch.zeros(H, dtype=torch.bool)
-        for r in range(H):
-            keep[r] = r % 16 in (0, 15) or r >= H - 2
-        x[B - 1, ~keep] = 0
-    x[B - 1, H - 1, W - 1, C - 1] = 64 * scale      # the last element of the tensor: the ragged tail of every walk
-    x[0, H // 2, 0, 0] = -48 * scale
-    return x
-
-
-def to_dev(x64, ld=None, off=0, fill=0.0):
-    """fp64 NHWC -> device bf16 view [..., off:off+roundup(C,8)] of a buffer with `ld` channels (default: no slack)."""
-    B, H, W, C = x64.shape
-    cp = (C + 7) // 8 * 8
-    ld = ld or cp
-    buf = torch.full((B, H, W, ld), fill, dtype=torch.bfloat16)
-    buf[..., off:off + C] = x64.to(torch.bfloat16)
-    if cp > C:
-        buf[..., off + C:off + cp] = 0
-    buf = buf.to(DEV)
-    return buf, buf[..., off:off + cp]
 
 
 def rows_checked(B, H, force=False):

@@ -12,7 +12,7 @@ import pytest
 import torch
 
 import usseg_oracle as O
-from route_probe import U_BF16, U_F32, assert_elementwise, kernels, short
+from route_probe import U_BF16, U_F32, assert_elementwise, c_f32, check, check_norm_bwd, kernels, kname, ng_of, norm_ref, sa_reference, short
 
 pytestmark = pytest.mark.gpu
 
@@ -478,7 +478,7 @@ def test_layernorm_grouped_fwd_bwd(gen, B, H, W, C, G):
         parts = [O.layer_norm(xx[..., i * Cg:(i + 1) * Cg], g_[i * Cg:(i + 1) * Cg], b_[i * Cg:(i + 1) * Cg]) for i in range(G)]
         return O.leaky_relu(torch.cat(parts, dim=-1))
     ref = ref_fn(x, gamma, beta)
-    y = ops.norm_act_fwd(xd, C, pad(gamma), pad(beta), torch.empty_like(xd), 0, G, 1e-3, ops.ACT_LRELU, 0.3)
+    y = on_route(kname(False, 0, ng_of(G)), lambda: ops.norm_act_fwd(xd, C, pad(gamma), pad(beta), torch.empty_like(xd), 0, G, 1e-3, ops.ACT_LRELU, 0.3))
     assert rel(y[..., :C], bf(ref)) < REL_BF16
     if cp > C:
         assert y[..., C:].abs().max().item() == 0
@@ -486,10 +486,15 @@ def test_layernorm_grouped_fwd_bwd(gen, B, H, W, C, G):
     xr, gr, br = x.clone().requires_grad_(True), gamma.clone().requires_grad_(True), beta.clone().requires_grad_(True)
     (ref_fn(xr, gr, br) * dy).sum().backward()
     dgam, dbet = torch.zeros(cp, device=DEV), torch.zeros(cp, device=DEV)
-    dx = ops.norm_act_bwd(xd, to_dev_padded(dy), C, pad(gamma), pad(beta), torch.empty_like(xd), dgam, dbet, 0, G, 1e-3, ops.ACT_LRELU, 0.3)
+    dx = on_route(kname(True, 0, ng_of(G)), lambda: ops.norm_act_bwd(xd, to_dev_padded(dy), C, pad(gamma), pad(beta), torch.empty_like(xd), dgam, dbet,
+                                                                     0, G, 1e-3, ops.ACT_LRELU, 0.3))
     assert rel(dx[..., :C], bf(xr.grad)) < 2 * REL_BF16
     assert rel(dgam[:C], gr.grad) < REL_F32
     assert rel(dbet[:C], br.grad) < REL_F32
+    M = B * H * W          # every element (test_gpu_norm_routes.py states the bounds)
+    r = norm_ref(x.reshape(M, C).to(DEV), gamma.to(DEV), beta.to(DEV), "lrelu", G, dy=dy.reshape(M, C).to(DEV))
+    check("LN y", y[..., :C].reshape(M, C), r["y"], r["ymag"], U_BF16, 4.0)
+    check_norm_bwd("LN", M, C, r, dx[..., :C].reshape(M, C), dgam, dbet)
 
 
 @pytest.mark.parametrize("B,H,W,C", [(2, 6, 5, 96), (1, 32, 32, 512), (3, 7, 9, 40), (1, 2, 2, 8)])
@@ -529,16 +534,21 @@ def test_batchnorm_inference_fwd_bwd(gen, C, act):
     d = lambda v: v.float().to(DEV)
     xd = to_dev_padded(x)
     ref = actf(O.batch_norm(x, gamma, beta, mm, mv, training=False))
-    y = ops.norm_act_fwd(xd, C, d(gamma), d(beta), torch.empty_like(xd), 1, 1, 1e-3, act, alpha, d(mm), d(mv))
+    y = on_route(kname(False, 1, 1), lambda: ops.norm_act_fwd(xd, C, d(gamma), d(beta), torch.empty_like(xd), 1, 1, 1e-3, act, alpha, d(mm), d(mv)))
     assert rel(y, bf(ref)) < REL_BF16
     dy = rnd(gen, B, H, W, C)
     xr, gr, br = x.clone().requires_grad_(True), gamma.clone().requires_grad_(True), beta.clone().requires_grad_(True)
     (actf(O.batch_norm(xr, gr, br, mm, mv, training=False)) * dy).sum().backward()
     dgam, dbet = torch.zeros(C, device=DEV), torch.zeros(C, device=DEV)
-    dx = ops.norm_act_bwd(xd, to_dev_padded(dy), C, d(gamma), d(beta), torch.empty_like(xd), dgam, dbet, 1, 1, 1e-3, act, alpha, d(mm), d(mv))
+    dx = on_route(kname(True, 1, 1), lambda: ops.norm_act_bwd(xd, to_dev_padded(dy), C, d(gamma), d(beta), torch.empty_like(xd), dgam, dbet, 1, 1, 1e-3,
+                                                              act, alpha, d(mm), d(mv)))
     assert rel(dx, bf(xr.grad)) < REL_BF16
     assert rel(dgam, gr.grad) < REL_F32
     assert rel(dbet, br.grad) < REL_F32
+    M, dv = B * H * W, lambda t: t.to(DEV)
+    r = norm_ref(x.reshape(M, C).to(DEV), dv(gamma), dv(beta), {1: "lrelu", 2: "relu", 3: "elu"}[act], 1, 1, dv(mm), dv(mv), dy=dy.reshape(M, C).to(DEV))
+    check("BN y", y.reshape(M, C), r["y"], r["ymag"], U_BF16, 4.0)
+    check_norm_bwd("BN", M, C, r, dx.reshape(M, C), dgam, dbet)
 
 
 # ------------------------------------------------------------------------------------------------ pooling / copies / cast
@@ -605,13 +615,21 @@ def test_split_attention_shared_branches(gen, B, H, W, P, Cg, radix):
     params = (dev(w1), dev(b1), dev(ga), dev(be), None, None, dev(w2), dev(b2))
     yd = to_dev_padded(y)
     d = ops.splitattn_desc(B, H * W, P, 1, Cg, Hd, Vp, Vp, Vp, Vp, float(radix), 0, 1e-3, ops.ACT_LRELU, 0.3, radix == 1)
-    out, g, s, ws = ops.splitattn_fwd(d, yd, params, ops.new_act(B, H, W, Vp, DEV))
+    out, g, s, ws = on_route(("sa_reduce_kernel", "sa_mlp_kernel<false>", "sa_apply_kernel<false>"), lambda: ops.splitattn_fwd(d, yd, params, ops.new_act(B, H, W, Vp, DEV)))
     assert rel(out[..., :V], bf(ref)) < REL_BF16
     grads = tuple(torch.zeros_like(t) for t in (params[0], params[1], params[2], params[3], params[6], params[7]))
-    dy = ops.splitattn_bwd(d, yd, to_dev_padded(dout), params, grads, g, s, ws, torch.empty_like(yd))
+    dy = on_route(("sa_reduce_kernel", "sa_mlp_kernel<true>", "sa_apply_kernel<true>"), lambda: ops.splitattn_bwd(d, yd, to_dev_padded(dout), params, grads, g, s, ws, torch.empty_like(yd)))
     assert rel(dy[..., :V], bf(leaves[0].grad)) < 2 * REL_BF16
     for got, want in zip(grads, (leaves[1].grad, leaves[2].grad, leaves[3].grad, leaves[4].grad, leaves[5].grad, leaves[6].grad)):
         assert rel(got, want) < 2e-3, (got.shape,)
+    torch.cuda.synchronize()
+    prm = [t.to(DEV) for t in (w1, b1, ga, be, torch.zeros(P, Hd, dtype=torch.float64), torch.ones(P, Hd, dtype=torch.float64), w2.unsqueeze(1), b2.unsqueeze(1))]
+    r = sa_reference(y.reshape(B, H * W, V).to(DEV), dout.reshape(B, H * W, V).to(DEV), prm, P, 1, Cg, Hd, float(radix), 0, "lrelu", radix == 1)
+    check("sa out", out[..., :V].reshape(B, H * W, V), r["out"], r["outm"], U_BF16, 4.0)
+    check("sa dy", dy[..., :V].reshape(B, H * W, V), r["dy"], r["dym"], U_BF16, 4.0)
+    for got, want, mag in zip(grads, (r["grads"][0], r["grads"][1], r["grads"][2], r["grads"][3], r["grads"][4][:, 0], r["grads"][5][:, 0]),
+                              (r["gmags"][0], r["gmags"][1], r["gmags"][2], r["gmags"][3], r["gmags"][4][:, 0], r["gmags"][5][:, 0])):
+        check("sa gradient", got, want, mag, U_F32, c_f32(B * H * W))
 
 
 @pytest.mark.parametrize("B,H,W,P,Cg,R", [(2, 6, 6, 4, 8, 3), (1, 4, 8, 2, 64, 3), (2, 4, 4, 4, 16, 3), (2, 3, 5, 3, 10, 3), (2, 8, 8, 2, 32, 2),
@@ -652,18 +670,24 @@ def test_split_attention_distinct_branches(gen, B, H, W, P, Cg, R):
     cat = ops.new_act(B, H, W, Cop + 16, DEV, zero=True)          # the stage's concats_1 buffer: this slab owns channels [8, 8 + Co)
     out = cat[..., 8:8 + Cop]
     d = ops.splitattn_desc(B, H * W, P, R, Cg, Hd, Vp, Cop + 16, Vp, Cop, 1.0, 1, 1e-3, ops.ACT_ELU, 1.0, R == 1)
-    _, g, s, ws = ops.splitattn_fwd(d, yd, params, out)
+    _, g, s, ws = on_route(("sa_reduce_kernel", "sa_mlp_kernel<false>", "sa_apply_kernel<false>"), lambda: ops.splitattn_fwd(d, yd, params, out))
     assert rel(out[..., :Co], bf(ref)) < REL_BF16
     assert cat[..., :8].abs().max().item() == 0 and cat[..., 8 + Cop:].abs().max().item() == 0
     grads = tuple(torch.zeros_like(t) for t in (params[0], params[1], params[2], params[3], params[6], params[7]))
     dcat = ops.new_act(B, H, W, Cop + 16, DEV, zero=True)
     dcat[..., 8:8 + Co] = dout.to(torch.bfloat16).to(DEV)
-    dy = ops.splitattn_bwd(d, yd, dcat[..., 8:8 + Cop], params, grads, g, s, ws, torch.empty_like(yd))
+    dy = on_route(("sa_reduce_kernel", "sa_mlp_kernel<true>", "sa_apply_kernel<true>"), lambda: ops.splitattn_bwd(d, yd, dcat[..., 8:8 + Cop], params, grads, g, s, ws, torch.empty_like(yd)))
     torch.cuda.synchronize()
     assert rel(dy[..., :V], bf(leaves[0].grad)) < 2 * REL_BF16
     assert Vp == V or dy[..., V:].abs().max().item() == 0
     for got, want in zip(grads, (leaves[1].grad, leaves[2].grad, leaves[3].grad, leaves[4].grad, leaves[5].grad, leaves[6].grad)):
         assert rel(got, want) < 2e-3, (got.shape,)
+    r = sa_reference(y.reshape(B, H * W, V).to(DEV), dout.reshape(B, H * W, Co).to(DEV), [t.to(DEV) for t in (w1, b1, ga, be, mm, mv, w2, b2)],
+                     P, R, Cg, Hd, 1.0, 1, "elu", R == 1)
+    check("sa out", out[..., :Co].reshape(B, H * W, Co), r["out"], r["outm"], U_BF16, 4.0)
+    check("sa dy", dy[..., :V].reshape(B, H * W, V), r["dy"], r["dym"], U_BF16, 4.0)
+    for got, want, mag in zip(grads, r["grads"], r["gmags"]):
+        check("sa gradient", got, want, mag, U_F32, c_f32(B * H * W))
 
 
 @pytest.mark.parametrize("B,H,W,P,Cg,radix", [(2, 8, 8, 3, 10, 3), (3, 16, 8, 3, 21, 3), (2, 4, 4, 3, 85, 3), (2, 32, 32, 3, 42, 3)])
@@ -699,22 +723,22 @@ def test_split_attention_folded_into_its_norms(gen, B, H, W, P, Cg, radix):
     params = (dev(w1), dev(b1), dev(ga), dev(be), None, None, dev(w2), dev(b2))
     xd = to_dev_padded(v_raw)
     gam, bet = pad(g2), pad(be2)
-    y, gap = ops.norm_act_fwd_gap(xd, V, gam, bet, torch.empty_like(xd), 0, P, 1e-3, ops.ACT_LRELU, 0.3)
+    y, gap = on_route(kname(False, 0, 3, fuse=True), lambda: ops.norm_act_fwd_gap(xd, V, gam, bet, torch.empty_like(xd), 0, P, 1e-3, ops.ACT_LRELU, 0.3))
     y_plain = ops.norm_act_fwd(xd, V, gam, bet, torch.empty_like(xd), 0, P, 1e-3, ops.ACT_LRELU, 0.3)
     assert torch.equal(y, y_plain)                                   # same values as the plain launch, bit for bit
     pooled = gap[0].sum(dim=1)[:, :V] / (H * W)
     assert rel(pooled, y[..., :V].float().mean(dim=(1, 2))) < 1e-5
     d = ops.splitattn_desc(B, H * W, P, 1, Cg, Hd, Vp, Vp, Vp, Vp, float(radix), 0, 1e-3, ops.ACT_LRELU, 0.3, radix == 1)
-    out, g, s, ws = ops.splitattn_fwd(d, y, params, ops.new_act(B, H, W, Vp, DEV), gap=gap)
+    out, g, s, ws = on_route(("sa_mlp_kernel<false>", "sa_apply_kernel<false>"), lambda: ops.splitattn_fwd(d, y, params, ops.new_act(B, H, W, Vp, DEV), gap=gap))
     assert rel(out[..., :V], bf(ref)) < REL_BF16
     out2, *_ = ops.splitattn_fwd(d, y, params, ops.new_act(B, H, W, Vp, DEV))       # the pooling-pass form agrees
     assert rel(out, out2) < 1e-3
     grads = tuple(torch.zeros_like(t) for t in (params[0], params[1], params[2], params[3], params[6], params[7]))
     doutd = to_dev_padded(dout)
-    sa_s, sa_dg = ops.splitattn_bwd(d, y, doutd, params, grads, g, s, ws, None)
+    sa_s, sa_dg = on_route(("sa_reduce_kernel", "sa_mlp_kernel<true>"), lambda: ops.splitattn_bwd(d, y, doutd, params, grads, g, s, ws, None))
     dgam, dbet, dbias = torch.zeros(Vp, device=DEV), torch.zeros(Vp, device=DEV), torch.zeros(Vp, device=DEV)
-    dv = ops.norm_act_bwd_sa(xd, doutd, V, gam, bet, torch.empty_like(xd), dgam, dbet, 0, P, 1e-3, ops.ACT_LRELU, 0.3, sa_s, sa_dg, float(radix),
-                             dbias=dbias)
+    dv = on_route(kname(True, 0, 3, fuse=True), lambda: ops.norm_act_bwd_sa(xd, doutd, V, gam, bet, torch.empty_like(xd), dgam, dbet, 0, P, 1e-3,
+                                                                           ops.ACT_LRELU, 0.3, sa_s, sa_dg, float(radix), dbias=dbias))
     torch.cuda.synchronize()
     assert rel(dv[..., :V], bf(vr.grad)) < 2 * REL_BF16
     assert Vp == V or dv[..., V:].abs().max().item() == 0
@@ -722,6 +746,19 @@ def test_split_attention_folded_into_its_norms(gen, B, H, W, P, Cg, radix):
     assert rel(dbias[:V], vr.grad.sum(dim=(0, 1, 2))) < 2e-3
     for got, want in zip(grads, (w1_.grad, b1_.grad, ga_.grad, be_.grad, w2_.grad, b2_.grad)):
         assert rel(got, want) < 2e-3, (got.shape,)
+    # every element: y against the LayerNorm, the split attention on the kernel's own y, and dv from the kernel's own (s, dg)
+    M, HW = B * H * W, H * W
+    x64, do64 = v_raw.reshape(M, V).to(DEV), dout.reshape(M, V).to(DEV)
+    ry = norm_ref(x64, g2.to(DEV), be2.to(DEV), "lrelu", P)
+    check("folded y", y[..., :V].reshape(M, V), ry["y"], ry["ymag"], U_BF16, 4.0)
+    prm = [t.to(DEV) for t in (w1, b1, ga, be, torch.zeros(P, Hd, dtype=torch.float64), torch.ones(P, Hd, dtype=torch.float64), w2.unsqueeze(1), b2.unsqueeze(1))]
+    r = sa_reference(y[..., :V].double().reshape(B, HW, V), do64.view(B, HW, V), prm, P, 1, Cg, Hd, float(radix), 0, "lrelu", radix == 1)
+    check("folded sa out", out[..., :V].reshape(B, HW, V), r["out"], r["outm"], U_BF16, 4.0)
+    se, ge = (t.double().repeat_interleave(HW, 0) for t in (sa_s, sa_dg))
+    rd = norm_ref(x64, g2.to(DEV), be2.to(DEV), "lrelu", P, dy=radix * se * do64 + ge)
+    rm = norm_ref(x64, g2.to(DEV), be2.to(DEV), "lrelu", P, dy=radix * se * do64.abs() + ge.abs())
+    rd.update({k: rm[k] for k in ("dxmag", "dxext", "dgmag", "dbmag", "dgext", "dbext")}, kink=rd["kink"] | rm["kink"])
+    check_norm_bwd("folded", M, V, rd, dv[..., :V].reshape(M, V), dgam, dbet, dbias)
 
 
 @pytest.mark.parametrize("B,H,W,C,act", [(2, 16, 16, 32, "lrelu"), (3, 8, 12, 24, "elu"), (1, 64, 32, 32, "lrelu")])
@@ -743,7 +780,7 @@ def test_bn_act_pool_one_pass(gen, B, H, W, C, act):
     ref = O.avg_pool2(fa(O.batch_norm(xl, gl, bl, mean, var)))
     gx, gg, gb = torch.autograd.grad(ref, [xl, gl, bl], dy)
     xd, dyd = to_dev_padded(x), to_dev_padded(dy)
-    pooled = bn.forward_pool(xd, A, alpha)
+    pooled = on_route("bn_act_pool_kernel<false>", lambda: bn.forward_pool(xd, A, alpha))
     two = AveragePooling2D()
     want = two.forward(bn.forward(xd, A, alpha))
     assert torch.equal(pooled, want)
@@ -752,8 +789,14 @@ def test_bn_act_pool_one_pass(gen, B, H, W, C, act):
     assert rel(pooled[..., :C], bf(ref)) < 4e-3
     bn.gamma.grad.zero_(); bn.beta.grad.zero_()
     db = torch.zeros((C + 7) // 8 * 8, device=DEV)
-    dx = bn.backward_pool(dyd, dbias=db)
+    dx = on_route(kname(True, 1, 1, pool=True), lambda: bn.backward_pool(dyd, dbias=db))
     torch.cuda.synchronize()
+    M, dv = B * H * W, lambda t: t.to(DEV)
+    dyu = (dy.repeat_interleave(2, 1).repeat_interleave(2, 2) * 0.25).reshape(M, C).to(DEV)
+    r = norm_ref(x.reshape(M, C).to(DEV), dv(gam), dv(bet), act, 1, 1, dv(mean), dv(var), dy=dyu)
+    pool = lambda t: t.reshape(B, H // 2, 2, W // 2, 2, C).mean((2, 4))
+    check("pool y", pooled[..., :C], pool(r["y"]), pool(r["ymag"]), U_BF16, 4.0)
+    check_norm_bwd("pool", M, C, r, dx[..., :C].reshape(M, C), bn.gamma.grad, bn.beta.grad, db)
     g1, b1 = bn.gamma.grad.clone(), bn.beta.grad.clone()
     bn.gamma.grad.zero_(); bn.beta.grad.zero_()
     db2 = torch.zeros_like(db)
@@ -851,14 +894,24 @@ def test_batchnorm_training_mode(gen):
     xr, gr, br = x.clone().requires_grad_(True), ga.clone().requires_grad_(True), be.clone().requires_grad_(True)
     y_ref, (mm, mv) = O.batch_norm(xr, gr, br, torch.zeros(C, dtype=torch.float64), torch.ones(C, dtype=torch.float64), training=True)
     y_ref = O.leaky_relu(y_ref)
-    y = bn.forward(xd, ops.ACT_LRELU, 0.3)
+    y = on_route(("colsum_kernel<2>", "bn_batch_finalize_kernel", kname(False, 1, 1)), lambda: bn.forward(xd, ops.ACT_LRELU, 0.3))
     assert rel(y, bf(y_ref)) < 2e-3
     assert rel(bn.moving_mean, mm) < 1e-4 and rel(bn.moving_variance, mv) < 1e-4
     dy = rnd(gen, B, H, W, C)
     (y_ref * dy).sum().backward()
-    dx = bn.backward(to_dev_padded(dy))
+    dx = on_route((kname(True, 1, 1), "bn_train_bwd_fix_kernel"), lambda: bn.backward(to_dev_padded(dy)))
     assert rel(dx, bf(xr.grad)) < 5e-3
     assert rel(bn.gamma.grad, gr.grad) < 2e-3 and rel(bn.beta.grad, br.grad) < 2e-3
+    M = B * H * W
+    x64 = x.reshape(M, C).to(DEV)
+    r = norm_ref(x64, ga.to(DEV), be.to(DEV), "lrelu", mode="batch", dy=dy.reshape(M, C).to(DEV))
+    var = ((x64 - x64.mean(0)) ** 2).mean(0)
+    check("batch mean", bn._bmean[:C], x64.mean(0), x64.abs().mean(0), U_F32, c_f32(M))
+    check("batch variance", bn._bvar[:C], var, var, U_F32, c_f32(M))
+    check("moving mean", bn.moving_mean, r["stats"][0], 0.01 * x64.abs().mean(0), U_F32, c_f32(M))
+    check("moving variance", bn.moving_variance, r["stats"][1], 0.99 + 0.01 * var, U_F32, c_f32(M))
+    check("batch y", y.reshape(M, C), r["y"], r["ymag"], U_BF16, 4.0)
+    check_norm_bwd("batch", M, C, r, dx.reshape(M, C), bn.gamma.grad, bn.beta.grad)
 
 
 # ------------------------------------------------------------------------------------------------ decoder-stage entry points

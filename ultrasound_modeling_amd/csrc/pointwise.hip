@@ -749,21 +749,24 @@ extern "C" int usseg_bn_act_pool_bwd(const void* x, const void* dy, int32_t B, i
 }
 
 // ------------------------------------------------------------------------------------------ column sums
-// MODE 0: out[c] += sum_m a[m][c]; MODE 1: out[c] += sum a, out2[c] += sum a^2
+// MODE 0: out[c] += sum_m a[m][c]; MODE 1: out[c] += sum a, out2[c] += sum a^2; MODE 2: the sums of MODE 1 taken of a[m][c] - a[0][c]
+// (BatchNorm batch statistics about a per-channel pivot: sum a^2 / M - mean^2 cancels in fp32 once |mean| is many standard deviations)
 // Rows wider than 512 channels: grid.y walks 512-channel slabs (partial rows of slab y at ws + y * gridDim.x * rows-per-block * 512).
 template <int MODE>
 __global__ __launch_bounds__(256) void colsum_kernel(const bf16_t* a, int64_t M, int Ctot, int ld, int LPP, float* ws) {
   __shared__ float s_red[4 * 512];
   const int c0 = blockIdx.y * 512, C = Ctot - c0 < 512 ? Ctot - c0 : 512;
   a += c0;
-  ws += (int64_t)blockIdx.y * gridDim.x * (MODE + 1) * 512;
+  constexpr int NS = MODE ? 2 : 1;
+  ws += (int64_t)blockIdx.y * gridDim.x * NS * 512;
   const int Cp = gridDim.y > 1 ? 512 : (C + 7) & ~7;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int ppw = 64 / LPP, chunk = lane & (LPP - 1), slot = lane / LPP;
   const bool chunk_ok = chunk * 8 < C;
-  float s[8], s2[8];
+  float s[8], s2[8], pv[8];
 #pragma unroll
-  for (int j = 0; j < 8; ++j) { s[j] = 0.f; s2[j] = 0.f; }
+  for (int j = 0; j < 8; ++j) { s[j] = 0.f; s2[j] = 0.f; pv[j] = 0.f; }
+  if (MODE == 2) unpack8(*reinterpret_cast<const uint4*>(a + (chunk_ok ? chunk * 8 : 0)), pv);    // pixel 0's values
   const int64_t ppb = 4 * ppw, stride = (int64_t)gridDim.x * ppb;
   // four rows per lane and trip, loaded at clamped addresses before the first use (one load per trip was a chain of 8 dependent HBM latencies)
   for (int64_t base = (int64_t)blockIdx.x * ppb; base < M; base += 4 * stride) {
@@ -781,12 +784,16 @@ __global__ __launch_bounds__(256) void colsum_kernel(const bf16_t* a, int64_t M,
       float v[8];
       unpack8(raw[u], v);
 #pragma unroll
-      for (int j = 0; j < 8; ++j) { s[j] += okf[u] * v[j]; if (MODE == 1) s2[j] += okf[u] * v[j] * v[j]; }
+      for (int j = 0; j < 8; ++j) {
+        const float d = v[j] - pv[j];     // exact: two bf16 values
+        s[j] += okf[u] * d;
+        if (MODE) s2[j] += okf[u] * d * d;
+      }
     }
   }
-  float* row = ws + (int64_t)blockIdx.x * (MODE + 1) * Cp;
+  float* row = ws + (int64_t)blockIdx.x * NS * Cp;
   block_chunk_partial(s, LPP, chunk, chunk_ok, row, Cp, s_red);
-  if (MODE == 1) block_chunk_partial(s2, LPP, chunk, chunk_ok, row + Cp, Cp, s_red);
+  if (MODE) block_chunk_partial(s2, LPP, chunk, chunk_ok, row + Cp, Cp, s_red);
 }
 
 extern "C" int usseg_colsum(const void* dy, int64_t M, int32_t C, int32_t ld, float* db, float* ws, usseg_stream_t stream) {
@@ -1439,7 +1446,8 @@ extern "C" int usseg_counter_add(int32_t* counter, int32_t inc, usseg_stream_t s
 }
 
 // ---- BatchNormalization TRAINING mode (Keras: batch mean / biased variance, moving statistics updated with momentum) -------
-// forward : usseg_channel_stats -> usseg_bn_finalize_stats -> usseg_norm_act_fwd(mode 1, batch statistics)
+// forward : usseg_bn_batch_stats -> usseg_norm_act_fwd(mode 1, batch statistics)   (usseg_channel_stats -> usseg_bn_finalize_stats is the
+//           one-pass form kept for the ABI: it cancels once |mean| >> std)
 // backward: usseg_norm_act_bwd(mode 1) gives dx0 = dyh*gamma*rstd and this launch's sums tg = sum dyh*xhat, tb = sum dyh;
 //           usseg_bn_train_bwd_fix subtracts the batch-statistics terms: dx = dx0 - gamma*rstd*(tb + xhat*tg)/M.
 __global__ void bn_finalize_stats_kernel(const float* sum, const float* sumsq, float inv_m, int C, float momentum, float* mean, float* var,
@@ -1461,6 +1469,37 @@ extern "C" int usseg_bn_finalize_stats(const float* sum, const float* sumsq, int
   hipLaunchKernelGGL(bn_finalize_stats_kernel, dim3((C + 255) / 256), dim3(256), 0, (hipStream_t)stream, sum, sumsq, 1.f / (float)M, C, momentum,
                      mean, var, moving_mean, moving_var);
   return usseg_check_launch("bn_finalize_stats");
+}
+
+// The batch statistics in one call, without the cancellation of sum x^2 / M - mean^2: colsum_kernel<2> sums d = x - x[0][c] and d^2
+// (fp32 over |d| ~ a few standard deviations instead of |x|), the finishing kernel overwrites mean / var with those sums, and
+// bn_batch_finalize_kernel forms mean = x[0][c] + S1/M, var = S2/M - (S1/M)^2.
+__global__ void bn_batch_finalize_kernel(const bf16_t* x, float inv_m, int C, float momentum, float* mean, float* var, float* moving_mean,
+                                         float* moving_var) {
+  int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  const float d = mean[c] * inv_m;
+  const float mu = bf2f(x[c]) + d;
+  const float v = fmaxf(var[c] * inv_m - d * d, 0.f);
+  mean[c] = mu;
+  var[c] = v;
+  if (moving_mean) {
+    moving_mean[c] = moving_mean[c] * momentum + mu * (1.f - momentum);
+    moving_var[c] = moving_var[c] * momentum + v * (1.f - momentum);
+  }
+}
+extern "C" int usseg_bn_batch_stats(const void* x, int64_t M, int32_t C, int32_t ldx, float momentum, float* mean, float* var, float* moving_mean,
+                                    float* moving_var, float* ws, usseg_stream_t stream) {
+  USSEG_CHECK_ARG(x && mean && var && ws && M > 0 && C > 0 && C <= 512 && ldx % 8 == 0 && (!moving_mean == !moving_var), "bn_batch_stats: bad args");
+  const int Cp = roundup(C, 8);
+  const int LPP = lanes_per_pixel(Cp / 8);
+  const int ppb = 4 * (64 / LPP);
+  unsigned grid = grid_for(M, ppb * 8, USSEG_REDUCE_MAX_BLOCKS);
+  hipLaunchKernelGGL(colsum_kernel<2>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, M, C, ldx, LPP, ws);
+  usseg_launch_reduce_finish(ws, 1, (int)grid, 2, Cp, C, 1.f, mean, var, nullptr, (hipStream_t)stream, 1);    // mean / var OVERWRITTEN by S1 / S2
+  hipLaunchKernelGGL(bn_batch_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, 1.f / (float)M, C, momentum,
+                     mean, var, moving_mean, moving_var);
+  return usseg_check_launch("bn_batch_stats");
 }
 
 __global__ __launch_bounds__(256) void bn_train_bwd_fix_kernel(const bf16_t* x, bf16_t* dx, int64_t M, int C, int CH, int ldx, int lddx, const float* gamma,

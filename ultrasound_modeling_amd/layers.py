@@ -474,12 +474,9 @@ class BatchNormalization(LayerNormalization):
     def forward(self, x, act=ACT_NONE, alpha=0.0, out=None):
         if self.training_mode:
             # Keras training=True: normalise with the batch mean / biased variance and move the running statistics
-            B, H, W, _, _ = ops.geom(x)
             cp, dev = self.moving_mean_p.numel(), x.device
-            s, s2 = torch.zeros(cp, device=dev), torch.zeros(cp, device=dev)
-            ops.channel_stats(x, self.C, s, s2)
             self._bmean, self._bvar = torch.zeros(cp, device=dev), torch.ones(cp, device=dev)
-            ops.bn_finalize_stats(s, s2, B * H * W, self.C, self.momentum, self._bmean, self._bvar, self.moving_mean_p, self.moving_variance_p)
+            ops.bn_batch_stats(x, self.C, self.momentum, self._bmean, self._bvar, self.moving_mean_p, self.moving_variance_p)
         return super().forward(x, act, alpha, out)
 
     def forward_pool(self, x, act=ACT_NONE, alpha=0.0, out=None):

@@ -656,6 +656,13 @@ def bn_finalize_stats(s, s2, M, C_logical, momentum, mean, var, moving_mean=None
                                              _ptr(moving_mean), _ptr(moving_var), _stream()), "bn_finalize_stats")
 
 
+def bn_batch_stats(x, C_logical, momentum, mean, var, moving_mean=None, moving_var=None):
+    """mean / var (overwritten) = the batch mean and biased variance of x's channels; the moving statistics move with momentum."""
+    B, H, W, _, ldx = geom(x)
+    L.check(L.load().usseg_bn_batch_stats(x.data_ptr(), B * H * W, C_logical, ldx, momentum, mean.data_ptr(), var.data_ptr(), _ptr(moving_mean),
+                                          _ptr(moving_var), reduce_ws(x.device).data_ptr(), _stream()), "bn_batch_stats")
+
+
 def bn_train_bwd_fix(x, dx, C_logical, gamma, mean, var, eps, tg, tb):
     B, H, W, Cphys, ldx = geom(x)
     L.check(L.load().usseg_bn_train_bwd_fix(x.data_ptr(), dx.data_ptr(), B * H * W, C_logical, Cphys, ldx, geom(dx)[4], gamma.data_ptr(),
