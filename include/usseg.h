@@ -542,6 +542,18 @@ typedef struct UssegSegCountDesc {
 } UssegSegCountDesc;
 #define USSEG_SEG_COUNTS 23 /* 6 + 4*4 + 1 */
 int usseg_seg_counts(const UssegSegCountDesc* d, const float* y_true, const float* y_pred, uint64_t* counts, usseg_stream_t stream);
+/* ---- brain-mask cascade (cascade.hip; TBIEvaluator.py:221-252, use_brainMask=True) --------------------------------------------
+ * The step between the brain-mask model and the bleed model, on the device.  probs: the mask model's fp32 [M][C_mask] (2 <= C_mask <= 4);
+ * x: the bf16 input [M][ldx] as usseg_cast_input wrote it (ldx a positive multiple of 8; x and x_gated 16-byte aligned).  Pixel m is
+ * gated iff probs[m*C_mask] > 0.5f, which is the reference's np.round(mask)[..., 0] == 1 (:224-225): round-half-to-even sends exactly
+ * 0.5 to 0, and NaN is not gated.  A gated row of x_gated is ldx zeros, any other row a copy of x's (:226-227 zero all ten input
+ * channels; 0.0 is exact in bf16, so zeroing after the cast gives the bits of the reference's zero-then-cast).  x_gated == x (in place)
+ * is allowed and then rewrites only the gated rows.  mask (may be NULL): the gate as u8 [M]. */
+int usseg_cascade_gate(const float* probs, int32_t C_mask, int64_t M, const void* x, int32_t ldx, void* x_gated, uint8_t* mask,
+                       usseg_stream_t stream);
+/* The evaluator's two maps of the bleed model's probabilities, fp32 [M][C] with C == 3: prob_map[m] = ((1 - p0) - 0.5f*p1) + p2 in fp32,
+ * rounded in that order (:249-252; the reference evaluates it in float64), bleed_prob[m] = p2 (:239). */
+int usseg_cascade_maps(const float* probs, int32_t C, int64_t M, float* prob_map, float* bleed_prob, usseg_stream_t stream);
 int usseg_loss_from_probs(const UssegLossDesc* d, const float* probs, const float* y_true, const float* scale, float* loss,
                           usseg_stream_t stream);
 /* The <= 4-class head Conv2DTranspose(k x k, stride 2, 'same') (Decoder.py:120 k=3; TBI_ResNest.py:124 k=4) in "quad" form: a

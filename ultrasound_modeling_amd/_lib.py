@@ -168,6 +168,8 @@ _PROTOS = {
     "usseg_cardinal_bwd": (C.c_int, [P(CardinalDesc), c_vp, c_i32, c_vp, c_i32] + [c_vp] * 12 + [c_f32, c_vp, c_vp, c_i32] + [c_vp] * 11),
     "usseg_accuracy": (C.c_int, [c_vp, c_vp, c_i64, c_i32, c_vp, c_vp]),
     "usseg_seg_counts": (C.c_int, [P(SegCountDesc), c_vp, c_vp, c_vp, c_vp]),
+    "usseg_cascade_gate": (C.c_int, [c_vp, c_i32, c_i64, c_vp, c_i32, c_vp, c_vp, c_vp]),
+    "usseg_cascade_maps": (C.c_int, [c_vp, c_i32, c_i64, c_vp, c_vp, c_vp]),
     "usseg_norm_act_bwd_res": (C.c_int, [P(NormDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "usseg_norm_act_bwd_sa": (C.c_int, [P(NormDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "usseg_norm_act_bwd_pair": (C.c_int, [P(NormDesc)] + [c_vp] * 8 + [P(NormDesc)] + [c_vp] * 4 + [c_i32, c_vp, c_vp, c_f32] + [c_vp] * 6),

@@ -601,6 +601,37 @@ def seg_counts(y_true, probs, counts, round=True, num_classes=3):
     return counts
 
 
+# ------------------------------------------------------------------------------------------------ brain-mask cascade (cascade.hip)
+def cascade_gate(probs, x, out=None, mask=None):
+    """The brain-mask gate (TBIEvaluator.py:221-231): rows of the bf16 input ``x`` [B,H,W,ldx] (``cast_input``'s output) whose mask-model
+    probability p0 = ``probs[..., 0]`` rounds to 1 (p0 > 0.5) become zeros in ``out``, the others are copied.  ``out`` defaults to a new
+    tensor; ``out is x`` gates in place.  ``mask``: optional uint8 [B,H,W] that receives the gate.  -> ``out``."""
+    B, H, W, Cm = probs.shape
+    assert probs.dtype == torch.float32 and probs.is_contiguous() and probs.is_cuda
+    assert x.dtype == BF16 and x.is_contiguous() and tuple(x.shape[:3]) == (B, H, W), (tuple(x.shape), tuple(probs.shape))
+    out = torch.empty_like(x) if out is None else out
+    assert out.dtype == BF16 and out.is_contiguous() and out.shape == x.shape
+    if mask is not None:
+        assert mask.dtype == torch.uint8 and mask.is_contiguous() and tuple(mask.shape) == (B, H, W)
+    L.check(L.load().usseg_cascade_gate(probs.data_ptr(), Cm, B * H * W, x.data_ptr(), x.shape[3], out.data_ptr(), _ptr(mask), _stream()),
+            "cascade_gate")
+    return out
+
+
+def cascade_maps(probs, prob_map=None, bleed_prob=None):
+    """The evaluator's maps of the bleed model's fp32 probabilities [B,H,W,3]: prob_map = ((1 - p0) - 0.5*p1) + p2 (TBIEvaluator.py:249-252)
+    and bleed_prob = p2 (:239), each fp32 [B,H,W].  -> (prob_map, bleed_prob)."""
+    B, H, W, Cc = probs.shape
+    assert probs.dtype == torch.float32 and probs.is_contiguous() and probs.is_cuda
+    prob_map = torch.empty((B, H, W), dtype=torch.float32, device=probs.device) if prob_map is None else prob_map
+    bleed_prob = torch.empty((B, H, W), dtype=torch.float32, device=probs.device) if bleed_prob is None else bleed_prob
+    for t in (prob_map, bleed_prob):
+        assert t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (B, H, W)
+    L.check(L.load().usseg_cascade_maps(probs.data_ptr(), Cc, B * H * W, prob_map.data_ptr(), bleed_prob.data_ptr(), _stream()),
+            "cascade_maps")
+    return prob_map, bleed_prob
+
+
 def norm_act_bwd_res(x, dy, C_logical, gamma, beta, dres, dx, dgamma, dbeta, eps, dbias=None):
     """Plain LayerNormalization backward + the residual branch of a pre-norm block: dx = bf16(bf16(LN'(dy)) + dres) in one pass;
     ``dbias`` += the column sums of the stored dx."""
