@@ -671,6 +671,29 @@ int usseg_adam_advance(int32_t* step, float* lr_t_dev, float lr, float beta1, fl
 int usseg_fill_f32(float* p, int64_t n, float value, usseg_stream_t stream);
 int usseg_scale_f32(float* p, int64_t n, const float* sumsq, float clip_norm, usseg_stream_t stream);
 
+/* ---- learning-rate / weight-decay schedule on the device + decoupled weight decay (AdamW)
+ * The table lives in DEVICE memory and is never a kernel argument, so a captured graph reads whatever the table holds when it
+ * replays.  PiecewiseConstantDecay(boundary[0..n-2], lr/wd[0..n-1]), 1 <= n <= USSEG_SCHED_MAX_PIECES, boundaries strictly increasing:
+ * at step x (= *step BEFORE the increment, as Keras evaluates a schedule at optimizer.iterations) the piece is #{i : x > boundary[i]}. */
+#define USSEG_SCHED_MAX_PIECES 16
+typedef struct UssegLrSchedule {
+  int32_t n;                                   /* number of pieces */
+  int32_t boundary[USSEG_SCHED_MAX_PIECES - 1];
+  float lr[USSEG_SCHED_MAX_PIECES];            /* learning rate of each piece */
+  float wd[USSEG_SCHED_MAX_PIECES];            /* decoupled weight decay of each piece (0 = none) */
+} UssegLrSchedule;
+/* x = *step; *step = t = x + 1; *lr_t = lr[piece]*sqrt(1-b2^t)/(1-b1^t) (usseg_adam_advance's expression); *wd_t = wd[piece] */
+int usseg_sched_advance(int32_t* step, const UssegLrSchedule* sched_dev, float* lr_t_dev, float* wd_t_dev, float beta1, float beta2,
+                        usseg_stream_t stream);
+/* usseg_sumsq (same grid, same bits of out[0]) with usseg_sched_advance done by the workgroup that performs the final addition */
+int usseg_sumsq_sched_advance(const float* g, int64_t n, float* out, int32_t* step, const UssegLrSchedule* sched_dev, float* lr_t_dev,
+                              float* wd_t_dev, float beta1, float beta2, usseg_stream_t stream);
+/* tfa AdamW: if *wd_t != 0 and (decay_mask == NULL or decay_mask[i] != 0): p[i] = p[i] - wd_t*p[i] (fp32, two roundings); then
+ * usseg_adam_clip_step's arithmetic on the decayed p.  wd_t is NOT multiplied by the learning rate.  p, g, m, v 16-byte aligned,
+ * decay_mask (u8 per element, nullable) 4-byte aligned, any n >= 0. */
+int usseg_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, const float* sumsq, float clip_norm, const float* lr_t_dev,
+                     const float* wd_t_dev, const uint8_t* decay_mask, float beta1, float beta2, float eps, usseg_stream_t stream);
+
 /* ---- ViT bottleneck helpers (VisionTransformer.py:9-79,127-174) ------------------------
  * Batched GEMMs on the conv kernels (bf16 operands, fp32 accumulate), 2-level batch (image, head) with element strides:
  *   nt: Y[b1,b2][m][n]  = sum_k X[b1,b2][m][k] * W[b1,b2][n][k]   (M rows, K contiguous in both operands)

@@ -9,22 +9,28 @@ model with ``train_step(x, y) -> (loss, probs)`` and ``step(x, y) -> (loss, prob
   * every metric is reset after the epoch that reported it, and each epoch's numbers (loss included) are appended to
     ``self.history`` as well as printed;
   * no TensorBoard summaries or image dumps (:16-17,54-60,108-113,124-133);
-  * no learning-rate "schedule" (:83-88): the reference assigns ``neuralnet.learning_rate`` / ``weight_decay``, plain attributes its
-    optimiser never reads again, and ``flat.AdamClip`` captures ``lr`` at construction the same way,
-    so applying it would change what the reference computes.
+  * the learning-rate "schedule" (:83-88) is off by default: the reference reassigns ``neuralnet.learning_rate`` / ``weight_decay``
+    at every epoch's end, plain attributes its optimiser never reads again, so it trains at the fixed
+    rate the model was built with, and so does this driver.  ``Process(..., schedule=True)`` applies what :83-88 meant instead: the
+    schedule ``PiecewiseConstantDecay([2000, 4000, 8000, 10000, 15000], [1, .3, .1, .03, .01, .003])`` is installed ONCE, before the
+    first step, as ``1e-2 * schedule`` on the learning rate and - if the model runs AdamW (``adamw=True``) - ``1e-4 * schedule`` on
+    the weight decay.  The optimiser evaluates it at its device step counter on every step (graph replays included), where the
+    reference would have evaluated it at epoch ends only.
 """
 from __future__ import annotations
 
 import torch
 
 from .metrics import SegMetrics
+from .schedules import PiecewiseConstantDecay
 
 input_size = (256, 80)      # :12
 
 
 class Process(object):
-    def __init__(self, batch_size=16, num_classes=3, device=None):
+    def __init__(self, batch_size=16, num_classes=3, device=None, schedule=False):
         self.batch_size = batch_size
+        self.schedule = schedule            # apply the :83-88 learning-rate / weight-decay schedule (module docstring)
         self.num_classes = num_classes
         self.input_shape = [input_size[0], input_size[1], 10]                                    # :19
         dev = device if device is not None else "cuda"
@@ -38,6 +44,8 @@ class Process(object):
         print("\nTraining to %d epochs (%d of minibatch size)" % (epochs, self.batch_size))
         iteration = 0
         prev_loss = 0
+        if self.schedule:
+            install_schedule(neuralnet)
         for epoch in range(1, epochs + 1):
             while True:
                 x_tr, y_tr, terminator = dataset.next_train(self.batch_size)                     # :43
@@ -62,7 +70,7 @@ class Process(object):
             prev_loss = loss
             if epoch % 5 == 0:
                 self.test(neuralnet, dataset, epoch)
-            # :83-88 (the learning-rate "schedule") is not applied: see the module docstring
+            # :83-88 (the learning-rate "schedule"): installed before the first step with schedule=True, see the module docstring
 
     def test(self, neuralnet, dataset, epoch):
         """MainNumpy.py:90-147 -> F1 of the epoch's test set; its dict (``phase`` "test") is appended to ``self.history``."""
@@ -86,6 +94,22 @@ class Process(object):
         self.history.append(dict(m, phase="test", epoch=epoch, loss=total_loss))
         self.metrics.reset_states()                                                              # :142-146
         return m["f1"]
+
+
+def reference_schedule() -> PiecewiseConstantDecay:
+    """MainNumpy.py:83-84."""
+    return PiecewiseConstantDecay([2000, 4000, 8000, 10000, 15000], [1e-0, 3e-1, 1e-1, 3e-2, 1e-2, 3e-3])
+
+
+def install_schedule(neuralnet):
+    """MainNumpy.py:86-87 on the model's optimiser: lr = 1e-2 * schedule, and wd = 1e-4 * schedule if the model runs AdamW."""
+    schedule = reference_schedule()
+    opt = neuralnet.optimizer
+    neuralnet.learning_rate = 1e-2 * schedule
+    opt.set_learning_rate(neuralnet.learning_rate)
+    if opt.weight_decay is not None:
+        neuralnet.weight_decay = 1e-4 * schedule
+        opt.set_weight_decay(neuralnet.weight_decay)
 
 
 def _labels(y, probs):

@@ -490,7 +490,9 @@ class ResNest(TrainStepDriver, PredictDriver):
     """TBI_ResNest.py:15-55.  ``step(x, y, train)`` -> (loss map [H,W], accuracy, probabilities)."""
 
     def __init__(self, height, width, channel, num_class, ksize, radix=4, kpaths=4, learning_rate=1e-3, ckpt_dir="./Checkpoint", *,
-                 device: Optional[str] = None, seed: Optional[int] = 0):
+                 device: Optional[str] = None, seed: Optional[int] = 0, weight_decay=None):
+        """``learning_rate`` may be a ``schedules.PiecewiseConstantDecay``; ``weight_decay`` (a float or a schedule) turns on the
+        decoupled weight decay of tfa AdamW (None: plain Adam, as the reference)."""
         if seed is not None:
             torch.manual_seed(seed)
         assert height % 64 == 0 and width % 64 == 0, "six 2x2 poolings: H and W must be multiples of 64"
@@ -503,7 +505,7 @@ class ResNest(TrainStepDriver, PredictDriver):
         self.resModel = _ResModel(height, width, channel, num_class, ksize, radix, kpaths)       # :26
         self.flat = FlatParams(self.resModel, self.device)
         self.resModel.repack()
-        self.optimizer = AdamClip(self.flat, lr=learning_rate, clip_norm=None)                  # :28 (no clipping, :46)
+        self.optimizer = AdamClip(self.flat, lr=learning_rate, clip_norm=None, weight_decay=weight_decay)   # :28 (no clipping, :46)
         self.class_factor = [0.06329, 0.027567, 0.90914]                                        # :30 (unused by my_loss_cat)
         self._loss_map = torch.zeros(height * width, dtype=torch.float32, device=self.device)
         self._scale = torch.zeros(height * width * num_class, dtype=torch.float32, device=self.device)
@@ -665,6 +667,43 @@ class ResNest(TrainStepDriver, PredictDriver):
         if getattr(self, "_lsum", None) is None or self._lsum.device != loss_map.device:
             self._lsum = torch.zeros(ops.ACC_FLOATS, dtype=torch.float32, device=loss_map.device)
         return ops.sum_f32(loss_map.contiguous().reshape(-1), self._lsum)
+
+
+def training(neuralnet, dataset, epochs, batch_size, *, live_lr=False):
+    """TBI_ResNest.py:382-411: train ``epochs`` epochs; test every 3rd epoch (0, 3, 6 ...); when the F1 drops below the previous
+    epoch's, divide ``neuralnet.learning_rate`` by 5; stop before an epoch once it is below 1e-5.  As in the reference the division
+    changes only the attribute - the optimiser keeps its rate - unless ``live_lr=True``, which also hands the new rate to
+    ``neuralnet.optimizer.set_learning_rate``.  That moves a fixed-rate optimiser to the rate-table kernels, which a step graph captured
+    before it does not hold (``set_learning_rate`` then raises): with a captured graph, build the model with ``weight_decay`` or a
+    schedule.  ``learning_rate`` must be a float here, as in the reference.  -> the number of steps taken."""
+    print("\nTraining to %d epochs (%d of minibatch size)" % (epochs, batch_size))
+    iteration = 0
+    f1cur = 0
+    f1prev = 0
+    for epoch in range(epochs):
+        if neuralnet.learning_rate < 1e-5:                                                     # :391-392
+            break
+        while True:
+            x_tr, y_tr, terminator = dataset.next_train(batch_size)                           # :394
+            loss_map, accuracy, class_score = neuralnet.step(x=x_tr, y=y_tr, train=True)       # :395
+            iteration += 1
+            print('.', end='')
+            if (iteration + 1) % 100 == 0:
+                print()
+            if terminator:
+                break
+        print()
+        loss = float(neuralnet._loss_total(loss_map))        # :396 reduce_sum, of the epoch's last step only (the one printed)
+        print("Epoch [%d / %d] (%d iteration)  Loss:%.5f, Acc:%.5f" % (epoch, epochs, iteration, loss, float(accuracy)))
+        if epoch % 3 == 0:                                                                     # :407-408
+            f1cur = test(neuralnet, dataset, epoch)
+        if f1cur < f1prev:                                                                     # :409-411
+            neuralnet.learning_rate /= 5
+            print("New Learning Rate = {}".format(neuralnet.learning_rate))
+            if live_lr:
+                neuralnet.optimizer.set_learning_rate(neuralnet.learning_rate)
+        f1prev = f1cur
+    return iteration
 
 
 history = []     # one dict per test() call: precision, recall, f1, c2_*, loss (what the reference logs to TensorBoard)

@@ -21,9 +21,9 @@ class VisionTransformer(_VisionTransformer):
     """TBI_TransUNet.py:532-592.  Note the reference's argument order here: batch_size comes LAST (:533)."""
 
     def __init__(self, img_size=(256, 80), num_classes=3, learning_rate=1e-3, weight_decay=1e-4, batch_size=16, *,
-                 in_channels: int = 10, device: Optional[str] = None, seed: Optional[int] = 0):
+                 in_channels: int = 10, device: Optional[str] = None, seed: Optional[int] = 0, adamw: bool = False):
         super().__init__(batch_size, img_size, num_classes, learning_rate, weight_decay, in_channels=in_channels, use_vit=True,
-                         device=device, seed=seed, transunet=True)
+                         device=device, seed=seed, transunet=True, adamw=adamw)
 
     def step(self, x, y, train=False):
         """TBI_TransUNet.py:571-588 -> (loss, probabilities); ``train=True`` also clips and applies the gradients."""

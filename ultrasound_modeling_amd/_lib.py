@@ -213,6 +213,9 @@ _PROTOS = {
     "usseg_adam_advance": (C.c_int, [c_vp, c_vp, c_f32, c_f32, c_f32, c_vp]),
     "usseg_fill_f32": (C.c_int, [c_vp, c_i64, c_f32, c_vp]),
     "usseg_scale_f32": (C.c_int, [c_vp, c_i64, c_vp, c_f32, c_vp]),
+    "usseg_sched_advance": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_f32, c_f32, c_vp]),
+    "usseg_sumsq_sched_advance": (C.c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_f32, c_vp]),
+    "usseg_adamw_step": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_f32, c_vp, c_vp, c_vp, c_f32, c_f32, c_f32, c_vp]),
     "usseg_gemm_nt_batched": (C.c_int, [P(GemmDesc), c_vp, c_vp, c_vp, c_vp]),
     "usseg_gemm_tn_batched": (C.c_int, [P(GemmDesc), c_vp, c_vp, c_vp, c_vp]),
     "usseg_flash_attn_fwd": (C.c_int, [P(FlashDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),

@@ -1088,7 +1088,8 @@ extern "C" int usseg_sum_f32(const float* x, int64_t n, float* out, usseg_stream
 }
 
 // ------------------------------------------------------------------------------------------ optimiser
-__global__ __launch_bounds__(256) void sumsq_kernel(const float* g, int64_t n, float* out, int32_t* step, float* lr_t, float lr, float b1, float b2) {
+// out[0] = sum g^2 by grid_ordered_sum; true in the workgroup that performed the final addition (shared by the two sumsq kernels)
+__device__ __forceinline__ bool sumsq_ordered(const float* g, int64_t n, float* out) {
   __shared__ float red[4];
   float s = 0.f;
   int64_t n4 = n >> 2;
@@ -1112,7 +1113,10 @@ __global__ __launch_bounds__(256) void sumsq_kernel(const float* g, int64_t n, f
   for (int msk = 32; msk >= 1; msk >>= 1) s += __shfl_xor(s, msk, 64);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
   __syncthreads();
-  const bool last = grid_ordered_sum((red[0] + red[1]) + (red[2] + red[3]), out, gridDim.x);   // reproducible: the clip factor scales every update
+  return grid_ordered_sum((red[0] + red[1]) + (red[2] + red[3]), out, gridDim.x);   // reproducible: the clip factor scales every update
+}
+__global__ __launch_bounds__(256) void sumsq_kernel(const float* g, int64_t n, float* out, int32_t* step, float* lr_t, float lr, float b1, float b2) {
+  const bool last = sumsq_ordered(g, n, out);
   if (last && step && threadIdx.x == 0) {   // usseg_sumsq_advance: the optimiser's step counter moves on in the same launch
     const int t = *step + 1;
     *step = t;
@@ -1169,6 +1173,113 @@ extern "C" int usseg_adam_advance(int32_t* step, float* lr_t_dev, float lr, floa
   USSEG_CHECK_ARG(step && lr_t_dev, "adam_advance: null pointer");
   hipLaunchKernelGGL(adam_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, step, lr_t_dev, lr, beta1, beta2);
   return usseg_check_launch("adam_advance");
+}
+
+// ---- device-resident learning-rate / weight-decay schedule and decoupled weight decay
+// The table is read from device memory, never passed by value, so a captured graph follows every stream-ordered rewrite of it.
+// Keras evaluates a LearningRateSchedule at optimizer.iterations BEFORE the increment: x = *step, t = x + 1 for the bias correction.
+// PiecewiseConstantDecay: piece = #{i : x > boundary[i]} (x <= b[0] -> 0; b[i-1] < x <= b[i] -> i; x > b[n-2] -> n-1).
+__device__ __forceinline__ void sched_advance_one(int32_t* step, const UssegLrSchedule* sched, float* lr_t, float* wd_t, float b1, float b2) {
+  const int x = *step;
+  const int n = min(max(sched->n, 1), USSEG_SCHED_MAX_PIECES);
+  int piece = 0;
+  for (int i = 0; i < n - 1; ++i) piece += x > sched->boundary[i] ? 1 : 0;
+  const int t = x + 1;
+  *step = t;
+  const float lr = sched->lr[piece];
+  *lr_t = lr * sqrtf(1.f - powf(b2, (float)t)) / (1.f - powf(b1, (float)t));   // usseg_adam_advance's expression, lr from the table
+  *wd_t = sched->wd[piece];
+}
+__global__ void sched_advance_kernel(int32_t* step, const UssegLrSchedule* sched, float* lr_t, float* wd_t, float b1, float b2) {
+  sched_advance_one(step, sched, lr_t, wd_t, b1, b2);
+}
+extern "C" int usseg_sched_advance(int32_t* step, const UssegLrSchedule* sched_dev, float* lr_t_dev, float* wd_t_dev, float beta1, float beta2,
+                                   usseg_stream_t stream) {
+  USSEG_CHECK_ARG(step && sched_dev && lr_t_dev && wd_t_dev, "sched_advance: null pointer");
+  hipLaunchKernelGGL(sched_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, step, sched_dev, lr_t_dev, wd_t_dev, beta1, beta2);
+  return usseg_check_launch("sched_advance");
+}
+
+__global__ __launch_bounds__(256) void sumsq_sched_kernel(const float* g, int64_t n, float* out, int32_t* step, const UssegLrSchedule* sched,
+                                                           float* lr_t, float* wd_t, float b1, float b2) {
+  const bool last = sumsq_ordered(g, n, out);
+  if (last && threadIdx.x == 0) sched_advance_one(step, sched, lr_t, wd_t, b1, b2);
+}
+extern "C" int usseg_sumsq_sched_advance(const float* g, int64_t n, float* out, int32_t* step, const UssegLrSchedule* sched_dev, float* lr_t_dev,
+                                         float* wd_t_dev, float beta1, float beta2, usseg_stream_t stream) {
+  USSEG_CHECK_ARG(step && sched_dev && lr_t_dev && wd_t_dev, "sumsq_sched_advance: null pointer");
+  USSEG_CHECK_ARG(g && out && n > 0 && ((uintptr_t)g % 16) == 0, "sumsq_sched_advance: bad args (g must be 16-byte aligned, n > 0)");
+  int64_t grid = cdiv64(n, 256 * 16);     // sumsq_launch's grid: the same partials, so the same bits of out[0]
+  if (grid > 256) grid = 256;
+  hipLaunchKernelGGL(sumsq_sched_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, g, n, out, step, sched_dev, lr_t_dev, wd_t_dev,
+                     beta1, beta2);
+  return usseg_check_launch("sumsq_sched_advance");
+}
+
+// tfa DecoupledWeightDecayExtension: p - wd_t*p, two roundings (a fused multiply-add would round once)
+__device__ __forceinline__ float decoupled_decay(float p, float wd_t) {
+#pragma clang fp contract(off)
+  return p - wd_t * p;
+}
+// one element of the update: the decay (if on), then adam_kernel's arithmetic on the decayed p.  adam_kernel's two moment statements
+// compile to fma(b1, m, (1-b1)*g') and fma(b2, v, ((1-b2)*g')*g'); left to contraction, the scalar tail here fused the OTHER product
+// (fma((1-b1), g', b1*m)), which differs in the last bit now and then, so the contraction is written out
+__device__ __forceinline__ void adamw_elem(float& p, float g, float& m, float& v, bool decay, float scale, float lr_t, float wd_t, float b1, float b2,
+                                           float eps) {
+  float pi = decay ? decoupled_decay(p, wd_t) : p;
+  float gi = g * scale;
+  float mi = fmaf(b1, m, (1.f - b1) * gi);
+  float vi = fmaf(b2, v, (1.f - b2) * gi * gi);
+  m = mi;
+  v = vi;
+  pi -= lr_t * mi / (sqrtf(vi) + eps);
+  p = pi;
+}
+__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                                     int64_t n, const float* sumsq, float clip_norm, const float* lr_t_dev, const float* wd_t_dev,
+                                                     const uint8_t* __restrict__ mask, float b1, float b2, float eps) {
+  float scale = 1.f;
+  if (clip_norm > 0.f) scale = clip_norm / fmaxf(sqrtf(*sumsq), clip_norm);  // tf.clip_by_global_norm
+  const float lr_t = *lr_t_dev, wd_t = *wd_t_dev;
+  const bool wd_on = wd_t != 0.f;        // p - 0*p would turn -0 into +0: no decay at all
+  const int64_t n4 = n >> 2;
+  float4* p4 = reinterpret_cast<float4*>(p);
+  float4* m4 = reinterpret_cast<float4*>(m);
+  float4* v4 = reinterpret_cast<float4*>(v);
+  const float4* g4 = reinterpret_cast<const float4*>(g);
+  const uchar4* k4 = reinterpret_cast<const uchar4*>(mask);
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+    float4 pi = p4[i], mi = m4[i], vi = v4[i];
+    const float4 gi = g4[i];
+    uchar4 k = make_uchar4(1, 1, 1, 1);
+    if (mask && wd_on) k = k4[i];
+    adamw_elem(pi.x, gi.x, mi.x, vi.x, wd_on && k.x, scale, lr_t, wd_t, b1, b2, eps);
+    adamw_elem(pi.y, gi.y, mi.y, vi.y, wd_on && k.y, scale, lr_t, wd_t, b1, b2, eps);
+    adamw_elem(pi.z, gi.z, mi.z, vi.z, wd_on && k.z, scale, lr_t, wd_t, b1, b2, eps);
+    adamw_elem(pi.w, gi.w, mi.w, vi.w, wd_on && k.w, scale, lr_t, wd_t, b1, b2, eps);
+    p4[i] = pi;
+    m4[i] = mi;
+    v4[i] = vi;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {       // scalar tail: n need not be a multiple of 4
+    const int64_t i = n4 * 4 + threadIdx.x;
+    const bool decay = wd_on && (mask == nullptr || mask[i] != 0);
+    adamw_elem(p[i], g[i], m[i], v[i], decay, scale, lr_t, wd_t, b1, b2, eps);
+  }
+}
+extern "C" int usseg_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, const float* sumsq, float clip_norm, const float* lr_t_dev,
+                                const float* wd_t_dev, const uint8_t* decay_mask, float beta1, float beta2, float eps, usseg_stream_t stream) {
+  USSEG_CHECK_ARG(p && g && m && v && lr_t_dev && wd_t_dev, "adamw_step: null pointer");
+  USSEG_CHECK_ARG(clip_norm <= 0.f || sumsq, "adamw_step: clip_norm > 0 needs sumsq");
+  USSEG_CHECK_ARG(n >= 0, "adamw_step: n < 0");
+  USSEG_CHECK_ARG(((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) % 16 == 0, "adamw_step: p, g, m and v must be 16-byte aligned");
+  USSEG_CHECK_ARG((uintptr_t)decay_mask % 4 == 0, "adamw_step: decay_mask must be 4-byte aligned");
+  if (n == 0) return USSEG_OK;
+  int64_t grid = cdiv64(n >> 2 > 0 ? n >> 2 : 1, 256);
+  if (grid > 4096) grid = 4096;
+  hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, sumsq, clip_norm, lr_t_dev, wd_t_dev,
+                     decay_mask, beta1, beta2, eps);
+  return usseg_check_launch("adamw_step");
 }
 
 __global__ __launch_bounds__(256) void fill_kernel(float* p, int64_t n, float v) {

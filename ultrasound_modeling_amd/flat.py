@@ -14,12 +14,15 @@ variables to be laid out back to back ("adjacent groups", used by the grouped sp
 from __future__ import annotations
 
 import math
-from typing import Dict, List, Optional
+import re
+from typing import Dict, List, Optional, Sequence
 
+import numpy as np
 import torch
 import torch.nn as nn
 
 from . import ops
+from .schedules import MAX_PIECES, PiecewiseConstantDecay
 
 
 def _pad8(n: int) -> int:
@@ -86,10 +89,20 @@ class AdamClip:
     ``clip_norm=None`` disables clipping (TBI_ResNest.py:46 applies raw gradients).
     The step counter and the bias-corrected learning rate live on the device so that a captured HIP graph of the
     whole training step can be replayed.
+
+    ``lr`` and ``weight_decay`` may each be a float or a ``schedules.PiecewiseConstantDecay``.  ``weight_decay`` (None: off) is tfa's
+    DecoupledWeightDecayExtension (AdamW): ``p -= wd_t * p`` before the Adam update, not scaled by the learning rate.
+    ``decay_exclude`` (regexes searched in ``FlatParams.names``) keeps matching variables out of the decay.  With a schedule or a
+    decay the rates come from a device table (``UssegLrSchedule``) read at the device step counter by the step kernels, so
+    ``set_learning_rate`` / ``set_weight_decay`` reach a captured graph's next replay without a recapture.  A float ``lr`` with no
+    decay launches exactly the fixed-rate kernels it always did.  
     """
 
-    def __init__(self, flat: FlatParams, lr: float = 1e-3, clip_norm: Optional[float] = 1.0, beta1=0.9, beta2=0.999, eps=1e-7):
-        self.flat, self.lr, self.clip_norm = flat, float(lr), clip_norm
+    def __init__(self, flat: FlatParams, lr=1e-3, clip_norm: Optional[float] = 1.0, beta1=0.9, beta2=0.999, eps=1e-7, weight_decay=None,
+                 decay_exclude: Optional[Sequence[str]] = None):
+        self.flat, self.clip_norm = flat, clip_norm
+        self.lr = _rate(lr, "lr")
+        self.weight_decay = None if weight_decay is None else _rate(weight_decay, "weight_decay")
         self.b1, self.b2, self.eps = beta1, beta2, eps
         dev = flat.device
         self.m = torch.zeros_like(flat.flat)
@@ -97,7 +110,58 @@ class AdamClip:
         self.step_dev = torch.zeros(1, dtype=torch.int32, device=dev)
         self.lr_t_dev = torch.zeros(1, dtype=torch.float32, device=dev)
         self.sumsq = torch.zeros(ops.ACC_FLOATS, dtype=torch.float32, device=dev)   # [0] = squared global norm (reproducible accumulator)
+        self.sched_dev = None            # UssegLrSchedule as int32[48] (n, boundary[15], lr bits[16], wd bits[16]); None = fixed-rate kernels
+        self.wd_t_dev = None
+        self.decay_mask = _decay_mask(flat, decay_exclude)
+        self._captured = False
+        if isinstance(self.lr, PiecewiseConstantDecay) or self.weight_decay is not None:
+            self._enable_table()
 
+    # ---- the device table -------------------------------------------------------------------------------------------
+    @property
+    def scheduled(self) -> bool:
+        """True when the step reads its rates from the device table (a schedule or a weight decay was given)."""
+        return self.sched_dev is not None
+
+    def _enable_table(self):
+        if self.sched_dev is None:
+            if self._captured:
+                raise RuntimeError("AdamClip: a step graph captured with the fixed-rate kernels cannot follow a schedule or weight decay; "
+                                   "give the schedule / weight_decay at construction, or capture the graph again after setting it")
+            dev = self.flat.device
+            self.sched_dev = torch.zeros(_TABLE_WORDS, dtype=torch.int32, device=dev)
+            self.wd_t_dev = torch.zeros(1, dtype=torch.float32, device=dev)
+        self._write_table()
+
+    def _write_table(self):
+        """Stream-ordered copy of the host table: a step (or graph replay) enqueued after it reads the new rates."""
+        self.sched_dev.copy_(torch.from_numpy(_table(self.lr, self.weight_decay)))
+
+    def mark_captured(self):
+        """Called by ``TrainStepDriver.capture_graph``: from now on the kernel path of the step may not change."""
+        self._captured = True
+
+    def set_learning_rate(self, lr):
+        """A float or a schedule, from the next step on (eager or replayed)."""
+        self.lr = _rate(lr, "lr")
+        self._enable_table()
+
+    def set_weight_decay(self, weight_decay):
+        """A float or a schedule (read at the same step as the learning rate), from the next step on; 0 turns the decay off."""
+        self.weight_decay = _rate(weight_decay, "weight_decay")
+        self._enable_table()
+
+    def current_learning_rate(self) -> float:
+        """The (not bias-corrected) learning rate the next step uses, from the device step counter and table.  Synchronises: for logging."""
+        if self.sched_dev is None:
+            return float(self.lr)
+        table = self.sched_dev.cpu().numpy()
+        x = int(self.step_dev.item())
+        n = int(table[0])
+        piece = sum(1 for b in table[1:n] if x > b)
+        return float(table[16:32].view(np.float32)[piece])
+
+    # ---- the step ---------------------------------------------------------------------------------------------------
     def global_norm_sq(self):
         ops.sumsq(self.flat.grad, self.sumsq)        # sumsq[0] is overwritten: no zero-fill launch
         return self.sumsq
@@ -110,11 +174,19 @@ class AdamClip:
 
     def advance(self):
         """step += 1 and the bias-corrected learning rate of that step (device side: replayable from a HIP graph)."""
-        ops.adam_advance(self.step_dev, self.lr_t_dev, self.lr, self.b1, self.b2)
+        if self.sched_dev is not None:
+            ops.sched_advance(self.step_dev, self.sched_dev, self.lr_t_dev, self.wd_t_dev, self.b1, self.b2)
+        else:
+            ops.adam_advance(self.step_dev, self.lr_t_dev, self.lr, self.b1, self.b2)
 
     def apply_range(self, lo: int, hi: int, clip: float = 0.0):
         """Adam update of flat[lo:hi] (elementwise, so any partition of the buffer gives the same result as one launch)."""
         f = self.flat
+        if self.sched_dev is not None:
+            mask = None if self.decay_mask is None else self.decay_mask[lo:hi]
+            ops.adamw_step(f.flat[lo:hi], f.grad[lo:hi], self.m[lo:hi], self.v[lo:hi], self.sumsq, clip, self.lr_t_dev, self.wd_t_dev, mask,
+                           self.b1, self.b2, self.eps)
+            return
         ops.adam_clip_step(f.flat[lo:hi], f.grad[lo:hi], self.m[lo:hi], self.v[lo:hi], self.sumsq, clip, self.lr_t_dev, self.b1, self.b2,
                            self.eps)
 
@@ -122,18 +194,25 @@ class AdamClip:
         clip = 0.0
         if self.clip_norm is not None and not already_clipped:
             # squared global norm and the step counter in one launch
-            ops.sumsq_advance(self.flat.grad, self.sumsq, self.step_dev, self.lr_t_dev, self.lr, self.b1, self.b2)
+            if self.sched_dev is not None:
+                ops.sumsq_sched_advance(self.flat.grad, self.sumsq, self.step_dev, self.sched_dev, self.lr_t_dev, self.wd_t_dev, self.b1, self.b2)
+            else:
+                ops.sumsq_advance(self.flat.grad, self.sumsq, self.step_dev, self.lr_t_dev, self.lr, self.b1, self.b2)
             clip = float(self.clip_norm)
         else:
             self.advance()
         self.apply_range(0, self.flat.total, clip)
 
     def state_tensors(self):
-        return [self.m, self.v, self.step_dev, self.lr_t_dev]
+        t = [self.m, self.v, self.step_dev, self.lr_t_dev]
+        return t if self.sched_dev is None else t + [self.sched_dev, self.wd_t_dev]
 
     def state_dict(self):
-        """Adam moments in the flat layout + the step counter (what Keras saves with a compiled model)."""
-        return {"__adam_m__": self.m.detach().clone(), "__adam_v__": self.v.detach().clone(), "__adam_step__": self.step_dev.detach().clone()}
+        """Adam moments in the flat layout + the step counter (what Keras saves with a compiled model); + the rate table if one is used."""
+        d = {"__adam_m__": self.m.detach().clone(), "__adam_v__": self.v.detach().clone(), "__adam_step__": self.step_dev.detach().clone()}
+        if self.sched_dev is not None:
+            d["__adam_sched__"] = self.sched_dev.detach().clone()
+        return d
 
     def load_state_dict(self, d):
         if not d:
@@ -141,3 +220,65 @@ class AdamClip:
         self.m.copy_(d["__adam_m__"].to(self.m.device))
         self.v.copy_(d["__adam_v__"].to(self.v.device))
         self.step_dev.copy_(d["__adam_step__"].to(self.step_dev.device))
+        if "__adam_sched__" in d:           # the saved schedule / decay replace the constructor's; the step counter selects the piece
+            self.lr, self.weight_decay = _from_table(d["__adam_sched__"].cpu().numpy().astype(np.int32))
+            self._enable_table()
+
+
+# ---------------------------------------------------------------------------------------------------- table helpers
+_TABLE_WORDS = 1 + (MAX_PIECES - 1) + 2 * MAX_PIECES          # sizeof(UssegLrSchedule) / 4
+
+
+def _rate(x, what):
+    if isinstance(x, PiecewiseConstantDecay):
+        return x
+    x = float(x)
+    if not math.isfinite(x):
+        raise ValueError(f"AdamClip: {what} must be finite, got {x}")
+    return x
+
+
+def _pieces(s):
+    return s.boundaries if isinstance(s, PiecewiseConstantDecay) else ()
+
+
+def _at(s, x) -> np.float32:
+    return s(x) if isinstance(s, PiecewiseConstantDecay) else np.float32(s)
+
+
+def _table(lr, wd) -> np.ndarray:
+    """UssegLrSchedule of lr and wd (None: 0) over the union of their boundaries: every merged piece takes both values at a step inside it."""
+    b = sorted(set(_pieces(lr)) | set(_pieces(wd)))
+    if len(b) + 1 > MAX_PIECES:
+        raise ValueError(f"AdamClip: learning rate and weight decay need {len(b) + 1} pieces together, at most {MAX_PIECES} are supported")
+    xs = b + [b[-1] + 1] if b else [0]          # a step inside each piece: x = b[0] for x <= b[0], b[i] for b[i-1] < x <= b[i], b[-1] + 1
+    t = np.zeros(_TABLE_WORDS, dtype=np.int32)
+    t[0] = len(xs)
+    t[1:1 + len(b)] = b
+    t[16:16 + len(xs)] = np.array([_at(lr, x) for x in xs], dtype=np.float32).view(np.int32)
+    t[32:32 + len(xs)] = np.array([0.0 if wd is None else _at(wd, x) for x in xs], dtype=np.float32).view(np.int32)
+    return t
+
+
+def _from_table(t: np.ndarray):
+    n = int(t[0])
+    if not 1 <= n <= MAX_PIECES:
+        raise ValueError(f"AdamClip: a saved rate table with {n} pieces")
+    b = [int(x) for x in t[1:n]]
+    lr, wd = t[16:16 + n].view(np.float32), t[32:32 + n].view(np.float32)
+    mk = (lambda v: PiecewiseConstantDecay(b, v)) if n > 1 else (lambda v: float(v[0]))
+    return mk(lr), mk(wd)
+
+
+def _decay_mask(flat: FlatParams, exclude) -> Optional[torch.Tensor]:
+    """u8 per flat element, 1 = decayed, 0 = excluded (a variable whose name matches one of the regexes); None when nothing is excluded."""
+    if not exclude:
+        return None
+    pats = [re.compile(p) for p in ([exclude] if isinstance(exclude, str) else exclude)]
+    hit = [(o, p.numel()) for n, p, o in zip(flat.names, flat.params, flat.offsets) if any(r.search(n) for r in pats)]
+    if not hit:
+        return None
+    mask = torch.ones(flat.total, dtype=torch.uint8)
+    for o, n in hit:
+        mask[o:o + n] = 0
+    return mask.to(flat.device)

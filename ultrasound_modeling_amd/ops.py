@@ -824,6 +824,25 @@ def adam_advance(step_dev, lr_t_dev, lr, b1, b2):
     L.check(L.load().usseg_adam_advance(step_dev.data_ptr(), lr_t_dev.data_ptr(), lr, b1, b2, _stream()), "adam_advance")
 
 
+def sched_advance(step_dev, sched_dev, lr_t_dev, wd_t_dev, b1, b2):
+    """step += 1 with lr_t / wd_t of the schedule piece of the step BEFORE the increment, read from the device table ``sched_dev``."""
+    L.check(L.load().usseg_sched_advance(step_dev.data_ptr(), sched_dev.data_ptr(), lr_t_dev.data_ptr(), wd_t_dev.data_ptr(), b1, b2, _stream()),
+            "sched_advance")
+
+
+def sumsq_sched_advance(g: torch.Tensor, out: torch.Tensor, step_dev, sched_dev, lr_t_dev, wd_t_dev, b1, b2):
+    """sumsq + sched_advance in ONE launch (the last workgroup of the ordered sum reads the table)."""
+    assert out.numel() >= ACC_FLOATS
+    L.check(L.load().usseg_sumsq_sched_advance(g.data_ptr(), g.numel(), out.data_ptr(), step_dev.data_ptr(), sched_dev.data_ptr(), lr_t_dev.data_ptr(),
+                                               wd_t_dev.data_ptr(), b1, b2, _stream()), "sumsq_sched_advance")
+
+
+def adamw_step(p, g, m, v, sumsq_t, clip_norm, lr_t_dev, wd_t_dev, decay_mask, b1, b2, eps):
+    """Decoupled weight decay (p -= wd_t*p where ``decay_mask`` is nonzero, or everywhere if it is None) then the Adam update."""
+    L.check(L.load().usseg_adamw_step(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), _ptr(sumsq_t), clip_norm,
+                                      lr_t_dev.data_ptr(), wd_t_dev.data_ptr(), _ptr(decay_mask), b1, b2, eps, _stream()), "adamw_step")
+
+
 # ------------------------------------------------------------------------------------------------ fused stem
 def stem_fwd(x, w1, b1, w2, b2, w3, b3, gamma, beta, mean, var, eps, alpha):
     """ResNest.py:39-47 in one launch -> (y1 [B,H,W,16], t1 [B,H,W,32], c2 [B,H,W,32] pre-norm, pooled [B,H/2,W/2,32])."""

@@ -101,6 +101,9 @@ class TrainStepDriver:
             t.copy_(v)
         self._repack()
         torch.cuda.synchronize()
+        mark = getattr(self.optimizer, "mark_captured", None)
+        if mark is not None:
+            mark()                    # the optimiser's kernel path is now part of the graph (flat.AdamClip)
         g1 = torch.cuda.CUDAGraph()
         if self.grad_sync is None:
             with torch.cuda.graph(g1):
