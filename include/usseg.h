@@ -592,12 +592,14 @@ int usseg_label2vec(const float* label, int64_t M, int32_t num_classes, float* o
 /* dataAug (DataAugs.py:82-102) AS EXECUTED for a batch, one fused pass: imageReduc (zeroes the image where the label is 0,
  * DataAugs.py:76-78), up to 2 clip boxes (:27-38), shift (:6-24, last row/column stay zero) and noisy (:41-51, unit Gaussian
  * / 5000: from `noise` [B,H,W,C] if given, else a counter-based generator seeded per sample), then label2vec and the cast
- * to the model's input.  The draws are made on the host in the reference's order and passed per sample. */
+ * to the model's input.  The draws are made on the host in the reference's order and passed per sample.
+ * do_flip (TBI_TransUNet.py:840-842; 0 in DataAugs' draws) mirrors image and label left-right FIRST: every later step (reduc,
+ * clip boxes, shift) works in the frame of the flipped image, and the noise field stays in output coordinates. */
 typedef struct UssegAugSample {
   int32_t do_reduc, nclip;
   int32_t clip[2][4];        /* r, c, ra, ca per box */
   int32_t do_shift, shift_r, shift_c, shift_dir;
-  int32_t do_noise, reserved;
+  int32_t do_noise, do_flip;
   uint64_t seed;
 } UssegAugSample;
 typedef struct UssegAugDesc {

@@ -43,6 +43,7 @@ def _sample_table(params: List[dict], device) -> torch.Tensor:
         if p["shift"] is not None:
             s.do_shift, (s.shift_r, s.shift_c, s.shift_dir) = 1, p["shift"]
         s.do_noise, s.seed = int(p["noise"]), int(p.get("seed", 0)) & ((1 << 63) - 1)
+        s.do_flip = int(p.get("flip", False))          # TBI_TransUNet.draw only; DataAugs' draws never flip
     raw = bytes(arr)
     return torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(device)
 

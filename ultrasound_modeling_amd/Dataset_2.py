@@ -19,7 +19,7 @@ import torch
 
 from . import _lib as L
 from . import ops
-from .DataAugs import dataAug_batch
+from .DataAugs import dataAug_batch, draw
 
 
 def label2vec(label: torch.Tensor, num_classes: int) -> torch.Tensor:
@@ -32,6 +32,8 @@ def label2vec(label: torch.Tensor, num_classes: int) -> torch.Tensor:
 
 
 class Dataset(object):
+    draw = staticmethod(draw)       # one sample's augmentation draws (DataAugs.draw); TBI_TransUNet.Dataset draws its script's
+
     def __init__(self, train_path=None, val_path=None, num_classes=3, device="cuda", train_data=None, val_data=None):
         """``train_data`` / ``val_data``: arrays of the on-disk layout [N,1,H,W,12] (label, 10 displacement channels, bMode;
         Dataset_2.py:33-43) may be passed instead of paths."""
@@ -67,6 +69,8 @@ class Dataset(object):
             self.idx_tr = start
         if x_tr.shape[0] != batch_size:
             x_tr, y_tr = self.x_tr[-1 - batch_size:-1], self.y_tr[-1 - batch_size:-1]
+        if params is None:
+            params = [self.draw() for _ in range(x_tr.shape[0])]
         x, y = dataAug_batch(x_tr, y_tr, params=params, num_classes=self.num_classes)      # :106-112
         return x, y, terminator
 

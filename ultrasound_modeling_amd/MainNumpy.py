@@ -101,14 +101,15 @@ def reference_schedule() -> PiecewiseConstantDecay:
     return PiecewiseConstantDecay([2000, 4000, 8000, 10000, 15000], [1e-0, 3e-1, 1e-1, 3e-2, 1e-2, 3e-3])
 
 
-def install_schedule(neuralnet):
-    """MainNumpy.py:86-87 on the model's optimiser: lr = 1e-2 * schedule, and wd = 1e-4 * schedule if the model runs AdamW."""
-    schedule = reference_schedule()
+def install_schedule(neuralnet, schedule=None, lr_scale=1e-2, wd_scale=1e-4):
+    """MainNumpy.py:86-87 on the model's optimiser: lr = 1e-2 * schedule, and wd = 1e-4 * schedule if the model runs AdamW.
+    ``schedule`` (default ``reference_schedule()``) and the two scales let the other drivers install their own (TBI_TransUNet.py:927-932)."""
+    schedule = reference_schedule() if schedule is None else schedule
     opt = neuralnet.optimizer
-    neuralnet.learning_rate = 1e-2 * schedule
+    neuralnet.learning_rate = lr_scale * schedule
     opt.set_learning_rate(neuralnet.learning_rate)
     if opt.weight_decay is not None:
-        neuralnet.weight_decay = 1e-4 * schedule
+        neuralnet.weight_decay = wd_scale * schedule
         opt.set_weight_decay(neuralnet.weight_decay)
 
 

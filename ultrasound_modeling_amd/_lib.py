@@ -48,7 +48,7 @@ class WgradJob(C.Structure):
 
 class AugSample(C.Structure):
     _fields_ = [("do_reduc", c_i32), ("nclip", c_i32), ("clip", (c_i32 * 4) * 2), ("do_shift", c_i32), ("shift_r", c_i32),
-                ("shift_c", c_i32), ("shift_dir", c_i32), ("do_noise", c_i32), ("reserved", c_i32), ("seed", C.c_uint64)]
+                ("shift_c", c_i32), ("shift_dir", c_i32), ("do_noise", c_i32), ("do_flip", c_i32), ("seed", C.c_uint64)]
 
 
 class AugDesc(C.Structure):

@@ -41,7 +41,10 @@ __device__ __forceinline__ uint32_t aug_hash(uint64_t v) {
   return (uint32_t)v;
 }
 
-// dataAug (DataAugs.py:82-102) for a whole batch + label2vec + the cast to the model's bf16 NHWC input.
+// dataAug (DataAugs.py:82-102) for a whole batch + label2vec + the cast to the model's bf16 NHWC input.  TBI_TransUNet.py:835-875 is the
+// same chain behind a left-right flip (do_flip): (si, sj) are computed in the frame of the flipped image, as the reference's later steps
+// see it, and only the column that is finally read is mirrored.  Its imageReduc(., r % 5) needs no iteration count: the dilation never
+// fires for any count >= 1 (TBI_TransUNet.py:815, the quirk of DataAugs.py:63), so every count zeroes the image where the label is 0.
 template <typename T>
 __global__ __launch_bounds__(256) void augment_kernel(const UssegAugDesc d, const UssegAugSample* samples, const T* x, const float* y,
                                                       const float* noise, bf16_t* x_out, float* x_out_f32, float* y_out, float* y_vec) {
@@ -63,10 +66,10 @@ __global__ __launch_bounds__(256) void augment_kernel(const UssegAugDesc d, cons
     bool zero_img = !valid;
     int64_t src = 0;
     if (valid) {
-      src = ((int64_t)b * d.H + si) * d.W + sj;
+      src = ((int64_t)b * d.H + si) * d.W + (s.do_flip ? d.W - 1 - sj : sj);   // flip (TBI_TransUNet.py:840-842): the source column
       lab = y[src];
       if (s.do_reduc && lab == 0.f) zero_img = true;      // imageReduc as executed (DataAugs.py:76-78)
-      for (int k = 0; k < s.nclip; ++k) {                  // clip (DataAugs.py:27-38), in source coordinates
+      for (int k = 0; k < s.nclip; ++k) {                  // clip (DataAugs.py:27-38), in source coordinates of the (flipped) image
         const int r = s.clip[k][0], c = s.clip[k][1], ra = s.clip[k][2], ca = s.clip[k][3];
         if (r + ra > si && si > r - ra && c + ca > sj && sj > c - ca && si < d.H - 1 && sj < d.W - 1) {
           zero_img = true;
