@@ -13,10 +13,37 @@ BatchNorm statistics are NOT synchronised (the reference uses plain BatchNormali
 Validation metrics (:86-114,148-176): instead of gathering every replica's probabilities and labels (``test_step`` still does,
 as the reference), a replica counts its own slice with ``metrics.SegMetrics.update_state`` and calls ``SegMetrics.reduce()`` (a SUM
 all-reduce of 23 int64 counters, exact) before ``result()``: the numbers of one process on the concatenated batch.
+
+The epoch driver (``Process.training`` / ``test`` / ``mirrored_train_step`` / ``mirrored_test_step``, ``main`` and the command line,
+MainParallel.py:24-176,201-220) runs any model with ``train_step`` / ``step`` / ``empty_step`` (``VisionTransformer``) over a
+``Dataset.Dataset``, one process per replica:
+    python -m torch.distributed.run --nproc_per_node N -m ultrasound_modeling_amd.MainParallel TRAIN VAL [--save P] [--epochs N]
+        [--batch-size B] [--no-vit]
+(world size 1 runs without the launcher).  As the reference executes: epochs count from 0; ``test`` runs after EVERY epoch (:72); the
+test loss is the plain sum over the test batches (:89 is commented out); test batches are ``batch_size`` images (:155) split like the
+training batches; each replica's loss is divided by the GLOBAL batch (``VisionTransformer.batch_size``, a short last batch included,
+``compute_average_loss(global_batch_size=...)``); the printed training loss is the last step's SUM-reduced loss (:131,146); "Model is
+throwing a fit" on an equal loss (:69-70); BatchNorm statistics stay per replica; only rank 0 saves.  The loss and the counters stay on
+the device: ONE loss all-reduce and ONE ``SegMetrics.reduce()`` per epoch and per ``test`` call, no gather and no per-step host read.
+A replica whose share of a short last batch is empty still joins the step (``TrainStepDriver.empty_step``: zero gradient, the same
+exchange and update) and adds 0 to the loss and nothing to the counters.  Full local batches replay the captured two-graph step
+(``capture_graph`` on the first one; ``Process(capture_graph=False)`` keeps every step eager); any other local batch runs eagerly.
+Deliberate deviations:
+  * the reference driver cannot run as committed: it unpacks five values from a ``train_step`` that returns two (:130, SURVEY.md:143)
+    and its metric attributes are the int 0 (:30-37).  The training Recall / Precision / IoU are counted from each step's
+    probabilities, as ``MainNumpy`` does (``SegMetrics(3, round=True)``, reset after every epoch);
+  * the rate reassignment after every epoch (:74-79) sets attributes the plain Adam never reads again,
+    so the driver trains at the fixed rate by default.  ``Process(schedule=True)`` installs ``1e-3 * PiecewiseConstantDecay([10000,
+    20000, 40000, 60000, 80000], [1, .3, .1, .03, .01, .003])`` ONCE, before the first step (``MainNumpy.install_schedule``; ``1e-4 *``
+    the same on the weight decay under AdamW), evaluated by the optimiser at its device step counter; the ``learning_rate < 1e-5`` stop
+    (:49) reads ``optimizer.current_learning_rate()`` once per epoch;
+  * no TensorBoard scalars or image summaries (:26-27,93-102,136-139,171-174).
 """
 from __future__ import annotations
 
+import argparse
 import os
+import random
 from typing import Optional, Tuple
 
 import torch
@@ -124,3 +151,174 @@ class MirroredTrainer:
         parts = [torch.empty_like(t) for _ in range(self.world)]
         dist.all_gather(parts, t.contiguous(), group=self.group)
         return torch.cat(parts, dim=0)
+
+
+# ---------------------------------------------------------------------------------------------------- the epoch driver (:24-220)
+def reference_schedule():
+    """MainParallel.py:74-75."""
+    from .schedules import PiecewiseConstantDecay
+    return PiecewiseConstantDecay([10000, 20000, 40000, 60000, 80000], [1e-0, 3e-1, 1e-1, 3e-2, 1e-2, 3e-3])
+
+
+class Process(object):
+    """MainParallel.py:24-176 (module docstring).  ``history``: one dict per training epoch (``phase`` "train") and per ``test`` call
+    (``phase`` "test"), the same on every rank."""
+
+    def __init__(self, batch_size=16, *, schedule=False, capture_graph=True, group=None):
+        self.batch_size = batch_size
+        self.input_shape = [256, 80, 10]                                                           # :29
+        self.schedule, self.capture_graph, self.group = schedule, capture_graph, group
+        self.train_iter = 0
+        self.test_iter = 0
+        self.history = []
+        self.trainer = None
+
+    def _mirror(self, neuralnet) -> MirroredTrainer:
+        """Wrap the model once (rank-0 broadcast, gradient exchange) and make its counters: precision / recall / pre_c2 / re_c2 / mio
+        (:30-34) and tr_recall / tr_precision / tr_mio (:35-37)."""
+        if self.trainer is None or self.trainer.net is not neuralnet:
+            from .metrics import SegMetrics
+            self.trainer = MirroredTrainer(neuralnet, self.group)
+            self.metrics = SegMetrics(3, round=True, device=neuralnet.device)
+            self.tr_metrics = SegMetrics(3, round=True, device=neuralnet.device)
+            self._zero = torch.zeros((), dtype=torch.float32, device=neuralnet.device)
+        return self.trainer
+
+    def _print(self, *args, **kwargs):
+        if self.trainer is None or self.trainer.rank == 0:
+            print(*args, **kwargs)
+
+    def training(self, neuralnet, dataset, epochs, batch_size):
+        """MainParallel.py:41-79 -> None."""
+        assert batch_size == self.batch_size == dataset.BATCH_SIZE, "one global batch size for the driver, the dataset and the model"
+        self._mirror(neuralnet)
+        self._print("\nTraining to %d epochs (%d of minibatch size)" % (epochs, batch_size))
+        if self.schedule:
+            from .MainNumpy import install_schedule
+            install_schedule(neuralnet, reference_schedule(), lr_scale=1e-3, wd_scale=1e-4)      # :74-79, once (module docstring)
+        prev_loss = 0
+        for epoch in range(epochs):
+            if neuralnet.optimizer.current_learning_rate() < 1e-5:                                # :49
+                break
+            loss = self.mirrored_train_step(neuralnet, dataset)                                  # :52-60
+            self._print()
+            m = self.tr_metrics.result()
+            self._print("Epoch [%d / %d] (%d iteration)  Loss:%.5f, Recall:%.5f, Precision:%.5f, IoU:%.5f"
+                        % (epoch, epochs, self.train_iter, loss, m["recall"], m["precision"], m["mean_iou"]))
+            self.history.append(dict(m, phase="train", epoch=epoch, iteration=self.train_iter, loss=loss))
+            self.tr_metrics.reset_states()                                                       # :66-68
+            if prev_loss == loss:
+                self._print("Model is throwing a fit")
+            prev_loss = loss
+            self.test(neuralnet, dataset, epoch)                                                 # :72
+
+    def test(self, neuralnet, dataset, epoch):
+        """MainParallel.py:81-115 -> F1 of the test set; its dict (``phase`` "test") is appended to ``history``."""
+        self._mirror(neuralnet)
+        self._print("\nTest...")
+        total_loss = self.mirrored_test_step(neuralnet, dataset)                                 # :86, not divided (:89)
+        m = self.metrics.result()
+        self._print("loss = {}".format(total_loss))
+        self._print("IoU = {}".format(m["mean_iou"]))
+        self._print("f1 = {}".format(m["f1"]))
+        self._print("precision = {}".format(m["precision"]))
+        self._print("recall = {}".format(m["recall"]))
+        self.history.append(dict(m, phase="test", epoch=epoch, loss=total_loss))
+        self.metrics.reset_states()                                                              # :110-114
+        return m["f1"]
+
+    def save(self, neuralnet, path) -> bool:
+        """``visionModel.save(path)`` on rank 0 only (MainParallel.py:216; every rank holds the same weights) -> whether this rank saved."""
+        rank = dist.get_rank(self.group) if dist.is_initialized() else 0
+        if rank == 0:
+            neuralnet.visionModel.save(path)
+        return rank == 0
+
+    def mirrored_train_step(self, neuralnet, dataset) -> float:
+        """MainParallel.py:117-146: one epoch of this replica's slices -> the last step's SUM-reduced loss.  The training counters are
+        SUM-reduced once at the end."""
+        tr = self._mirror(neuralnet)
+        local = self.batch_size // tr.world                                                      # images of a full local batch
+        last = self._zero
+        for x, y, _ in dataset.train_batches(tr.rank, tr.world):
+            if x is None:
+                neuralnet.empty_step()                                                           # joins the exchange: no deadlock
+                last = self._zero
+            else:
+                if self.capture_graph and getattr(neuralnet, "_graph", None) is None and x.shape[0] == local:
+                    neuralnet.capture_graph(x, y)
+                last, class_score = neuralnet.train_step(x, y)                                   # :130
+                self.tr_metrics.update_state(y, class_score)
+            self.train_iter += 1
+            self._print('.', end='')
+            if (self.train_iter + 1) % 100 == 0:
+                self._print()
+        loss = last.detach().reshape(()).clone()         # after a replay ``last`` is the step's static buffer, still this last step's
+        if tr.world > 1:
+            dist.all_reduce(loss, op=dist.ReduceOp.SUM, group=self.group)                        # :131
+            self.tr_metrics.reduce(self.group)
+        return float(loss)
+
+    def mirrored_test_step(self, neuralnet, dataset) -> float:
+        """MainParallel.py:148-176: the test set in batches of ``batch_size`` (:155) -> the sum of the batch losses (:170).  The loss
+        and the counters are summed on the device and SUM-reduced once (the reference gathers probabilities and labels, :160,163)."""
+        tr = self._mirror(neuralnet)
+        total = self._zero.clone()
+        for x, y, _ in dataset.test_batches(tr.rank, tr.world):
+            if x is not None:
+                loss, class_score = neuralnet.step(x, y)                                         # :158
+                total.add_(loss.reshape(()))
+                self.metrics.update_state(y, class_score)                                        # :162-169
+            self.test_iter += 1
+        if tr.world > 1:
+            dist.all_reduce(total, op=dist.ReduceOp.SUM, group=self.group)                       # :159
+            self.metrics.reduce(self.group)
+        return float(total)
+
+
+def main(train_path, val_path, save_path=None, epochs=51, batch_size=64, use_vit=True, *, seed=0, schedule=False, capture_graph=True):
+    """MainParallel.py:201-216 with the paths as arguments: ``VisionTransformer(batch_size=64)`` with the ViT bottleneck, 51 epochs,
+    then rank 0 saves if ``save_path`` is given.  Every rank seeds ``random`` with ``seed``, so all draw the same augmentations.
+    Under ``nccl`` the model lives on ``cuda:LOCAL_RANK``; the ``USSEG_DIST_BACKEND=gloo`` rehearsal keeps every rank on device 0."""
+    from .Dataset import Dataset
+    from .VisionTransformer import VisionTransformer
+    rank, world, local = init_distributed()
+    nccl = world > 1 and dist.get_backend() == "nccl"
+    device = torch.device("cuda", local if nccl else 0)
+    torch.cuda.set_device(device)
+    random.seed(seed)
+    dataset = Dataset(train_path, val_path, batch_size, device=device)
+    neuralnet = VisionTransformer(batch_size, img_size=(dataset.height, dataset.width), in_channels=dataset.channel, use_vit=use_vit,
+                                  device=str(device))
+    if rank == 0:
+        print(len(neuralnet.visionModel.layers))
+    process = Process(batch_size, schedule=schedule, capture_graph=capture_graph)
+    process.training(neuralnet=neuralnet, dataset=dataset, epochs=epochs, batch_size=batch_size)
+    if save_path is not None:
+        process.save(neuralnet, save_path)                                                       # :216
+    return neuralnet, process
+
+
+def _cli(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m ultrasound_modeling_amd.MainParallel",
+                                 description="Data-parallel training of the VisionTransformer (MainParallel.py); launch N ranks with "
+                                             "torch.distributed.run, or run world size 1 directly.")
+    ap.add_argument("train", help="training .npy [N,1,H,W,12]")
+    ap.add_argument("val", help="validation .npy [N,1,H,W,12]")
+    ap.add_argument("--save", default=None, help="rank 0 saves the model here after training")
+    ap.add_argument("--epochs", type=int, default=51)
+    ap.add_argument("--batch-size", type=int, default=64, help="GLOBAL batch, divided evenly over the ranks")
+    ap.add_argument("--no-vit", action="store_true", help="the conv-only model (no ViT bottleneck)")
+    ap.add_argument("--seed", type=int, default=0, help="augmentation draws (the same on every rank)")
+    ap.add_argument("--schedule", action="store_true", help="install the MainParallel.py:74-79 rate schedule once")
+    ap.add_argument("--no-graph", action="store_true", help="run every step eagerly")
+    a = ap.parse_args(argv)
+    main(a.train, a.val, a.save, epochs=a.epochs, batch_size=a.batch_size, use_vit=not a.no_vit, seed=a.seed, schedule=a.schedule,
+         capture_graph=not a.no_graph)
+    if dist.is_initialized():
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+if __name__ == "__main__":
+    _cli()

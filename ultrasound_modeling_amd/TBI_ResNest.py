@@ -616,16 +616,17 @@ class ResNest(TrainStepDriver, PredictDriver):
     def step(self, x, y, train=False):
         """TBI_ResNest.py:35-55 -> (loss map [H,W], accuracy, probabilities)."""
         x, y = self._prep_x(x), self._prep_y(y)
+        replayed = train and self._graph_takes(x, y)          # any other input than the captured one's runs eagerly
         if not train:
             probs, _ = self._forward_loss(x, y, with_grad=False)
-        elif self._graph is not None:
+        elif replayed:
             probs = self._graph_replay(x, y)
         else:
             probs = self._train_body(x, y)                                                     # :43-46 (no clipping: clip_norm None)
         if getattr(self, "_acc", None) is None or self._acc.device != probs.device:
             self._acc = torch.zeros(ops.ACC_FLOATS, dtype=torch.float32, device=probs.device)
         accuracy = ops.accuracy(probs, y, self._acc)                                           # :48-51 (metric only): one pass, one count
-        if train and self._graph is not None:   # replayed step: loss map / accuracy / probabilities are static buffers, valid until the next call
+        if replayed:                            # replayed step: loss map / accuracy / probabilities are static buffers, valid until the next call
             return self._loss_map.reshape(self.height, self.width), accuracy, probs     # (two clones = two more dispatches behind every replay)
         return self._loss_map.clone().reshape(self.height, self.width), accuracy.clone(), probs
 

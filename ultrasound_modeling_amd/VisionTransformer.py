@@ -496,9 +496,10 @@ class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
     def train_step(self, x, y):
         """One optimisation step (:235-246): -> (loss, probs).  Loss = sum of per-pixel CCE / GLOBAL batch size.
         After ``capture_graph`` the returned loss and probabilities are the captured step's static buffers: valid until the next call
-        (a clone of the scalar would be one more dispatch - 4.6 us - behind every replay)."""
+        (a clone of the scalar would be one more dispatch - 4.6 us - behind every replay).  An input whose shape, dtype, strides or device
+        differ from the captured ones runs eagerly."""
         x, y = self._prep_x(x), self._prep_y(y)
-        if self._graph is not None:
+        if self._graph_takes(x, y):
             return self._loss[0], self._graph_replay(x, y)
         probs = self._train_body(x, y)
         return self._loss[0].clone(), probs

@@ -78,6 +78,24 @@ class TrainStepDriver:
             self._update_body()
         return probs
 
+    def empty_step(self):
+        """This replica's part of a step in which it holds no image (a short last batch split over the replicas): no forward pass and
+        so no BatchNorm-statistics update, a zero gradient, and the same exchange and update as every other replica - the collective is
+        joined, so no rank waits on it, and the weights stay identical.  The per-replica clip of a zero gradient is a no-op
+        (scale = clip / max(0, clip) = 1), so the replica adds exactly nothing to the sum.  With a captured step the update replays
+        the captured update graph; a single replica (no ``grad_sync``) takes one Adam step on the zero gradient."""
+        self._zero_grad()
+        if self.grad_sync is None:
+            self._update_body()
+            return
+        self.optimizer.clip_local()
+        g2 = None if self._graph is None else self._graph[1]
+        if g2 is not None:
+            self.grad_sync(self.flat.grad)
+            g2.replay()
+        else:
+            self._sync_and_update()
+
     # ------------------------------------------------------------------ HIP-graph replay of the whole step
     def capture_graph(self, x, y, warmup: int = 2):
         """Capture the training step for inputs of this shape.  The ``warmup`` eager steps it needs (workspaces grow, lazy
@@ -122,6 +140,14 @@ class TrainStepDriver:
     def graph_inputs(self):
         """The (x, y) buffers the captured step reads: write the next batch THERE and pass these tensors to ``train_step`` - no copy."""
         return self._gx, self._gy
+
+    def _graph_takes(self, x, y) -> bool:
+        """True when the captured step can run on (x, y): the shape, dtype, strides and device of the buffers it was captured with.
+        Any other input (a short last batch) runs eagerly - a copy into the captured buffers would broadcast or fail."""
+        if self._graph is None:
+            return False
+        return all(a.dtype == b.dtype and a.shape == b.shape and a.stride() == b.stride() and a.device == b.device
+                   for a, b in ((x, self._gx), (y, self._gy)))
 
     def _graph_replay(self, x, y):
         """-> the STATIC probability buffer of the captured step (overwritten by the next replay)."""
