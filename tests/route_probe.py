@@ -10,6 +10,9 @@ of test_gpu_ops.py average an error over the whole tensor; this one fails on a s
 
 norm_ref / check_norm_bwd restate the LayerNorm / BatchNorm + activation forward and backward in fp64 with the magnitudes and the
 kink rule that test_gpu_norm_routes.py states once in its docstring.
+
+attn_ref / window_ref / ln_wide_ref restate the attention kernels and the wide LayerNorm in fp64 with the magnitudes and the
+score-error terms that test_gpu_attn_routes.py states once in its docstring; acheck bounds an output on the device.
 """
 import math
 
@@ -105,7 +108,7 @@ def assert_elementwise(y, ref, mag, u, c=C_BOUND, tiny=TINY, what=""):
     assert y.shape == ref.shape == mag.shape, (y.shape, ref.shape, mag.shape)
     err = (y - ref).abs()
     lim = c * u * mag + tiny
-    bad = err > lim
+    bad = ~(err <= lim)          # a NaN output is out of bounds, not silently inside them
     if bad.any():
         idx = bad.nonzero()
         first = tuple(idx[0].tolist())
@@ -312,3 +315,142 @@ def sa_reference(y, dout, prm, P, R, Cg, Hd, mult, norm_mode, act, sigmoid):
     fwd = tuple(t.detach() for t in fw)
     outm, dym, gm = sa_mags(y, dout, prm, fwd, B, HW, P, R, Cg, Hd, mult, norm_mode, act, sigmoid)
     return dict(out=out.detach(), outm=outm, dy=yl.grad, dym=dym, grads=(w1.grad, b1.grad, ga.grad, be.grad, w2.grad, b2.grad), gmags=gm)
+
+
+# ------------------------------------------------------------------------------------------------ attention restatement (fp64)
+def acheck(what, y, ref, mag, u, c, extra=None):
+    """|y - ref| <= c*u*mag + extra + tiny for every element, evaluated on y's device (NaN fails); prints and returns the worst
+    ratio err / bound.  mag may be None (the bound is extra alone)."""
+    y = y.detach().double()
+    ref = ref.detach().double().to(y.device)
+    lim = torch.full_like(ref, TINY)
+    if mag is not None:
+        lim = lim + c * u * mag.detach().double().to(y.device)
+    if extra is not None:
+        lim = lim + extra.detach().double().to(y.device)
+    assert y.shape == ref.shape == lim.shape, (what, y.shape, ref.shape, lim.shape)
+    err = (y - ref).abs()
+    bad = ~(err <= lim)
+    ratio = (err / lim).nan_to_num(nan=float("inf")).max().item() if y.numel() else 0.0
+    print(f"\n  bound {what}: worst ratio {ratio:.3f}", end="")
+    if bad.any():
+        first = tuple(bad.nonzero()[0].tolist())
+        pytest.fail(f"{what}: {int(bad.sum())} of {y.numel()} elements out of bounds (worst ratio {ratio:.2f}); first at {first}: "
+                    f"got {y[first].item():.6g}, ref {ref[first].item():.6g}, bound {lim[first].item():.3g}")
+    return ratio
+
+
+def attn_ref(q, k, v, do, scale, bias=None, bias_abs=None, chunk=1 << 26):
+    """Attention restated in fp64 for G independent problems: q, k, v, do [G, N, d] on the device, bias [G, N, N] (or None) added to
+    the scaled score s = scale*q.k.  Returns the exact results (o, lse in log2 units, delta = sum_j P*dP, dS = dL/ds = P*(dP - delta),
+    dq = scale*dS.k, dk = scale*dS^T.q, dv = P^T.do) and their magnitudes:
+      a      = scale*|q|.|k| + |bias|                 (what the fp32 score is summed from)
+      ds     = c_f32(d)*2^-20*(a + max_row a + ln N)  (score error: the fp32 dot product and the rounding of s - running max)
+      r      = ds + sum_j P*ds + c_f32(N)*2^-20      (relative error of a probability: its score, the row's softmax, the normaliser)
+      om     = P.|v|                                  (oext = (P*r).|v|)
+      dsm    = P*(|do|.|v|^T + |do|.om)                (dsext = dsm*r)
+      dqm    = scale*dsm.|k|,  dkm = scale*dsm^T.|q|,  dvm = P^T.|do|   (and the ext terms the same way from dsext, P*r)
+      lse_b  = (sum_j P*ds + c_f32(N)*2^-20)/ln 2 + 2^-20*|lse|   (an absolute bound)"""
+    G, N, d = q.shape
+    per = max(1, chunk // (N * N))
+    outs = []
+    for g0 in range(0, G, per):
+        sl = slice(g0, min(G, g0 + per))
+        outs.append(_attn_ref_chunk(q[sl], k[sl], v[sl], do[sl], scale, None if bias is None else bias[sl],
+                                    None if bias_abs is None else bias_abs[sl]))
+    return {key: torch.cat([o[key] for o in outs]) for key in outs[0]}
+
+
+def _attn_ref_chunk(q, k, v, do, scale, bias, bias_abs):
+    N, d = q.shape[1:]
+    tr = lambda t: t.transpose(-1, -2)
+    s = scale * (q @ tr(k))
+    a = scale * (q.abs() @ tr(k.abs()))
+    if bias is not None:
+        s = s + bias
+        a = a + (bias.abs() if bias_abs is None else bias_abs)
+    P = torch.softmax(s, -1)
+    lse = torch.logsumexp(s, -1) / math.log(2.0)
+    o = P @ v
+    dP = do @ tr(v)
+    delta = (P * dP).sum(-1, keepdim=True)
+    dS = P * (dP - delta)
+    r = dict(o=o, lse=lse, delta=delta.squeeze(-1), dS=dS, dq=scale * (dS @ k), dk=scale * (tr(dS) @ q), dv=tr(P) @ do)
+    ds = c_f32(d) * U_F32 * (a + a.amax(-1, keepdim=True) + math.log(N))
+    pds = (P * ds).sum(-1, keepdim=True)
+    rel = ds + pds + c_f32(N) * U_F32
+    av, ak, aq, ado = v.abs(), k.abs(), q.abs(), do.abs()
+    om = P @ av
+    dsm = P * (ado @ tr(av) + (ado * om).sum(-1, keepdim=True))
+    dse = dsm * rel
+    r.update(om=om, oext=(P * rel) @ av, lse_b=(pds.squeeze(-1) + c_f32(N) * U_F32) / math.log(2.0) + U_F32 * lse.abs(),
+             deltam=(ado * om).sum(-1), deltaext=(ado * ((P * rel) @ av)).sum(-1),
+             dsm=dsm, dsext=dse, dqm=scale * (dsm @ ak), dqext=scale * (dse @ ak), dkm=scale * (tr(dsm) @ aq), dkext=scale * (tr(dse) @ aq),
+             dvm=tr(P) @ ado, dvext=tr(P * rel) @ ado)
+    return r
+
+
+def window_ref(qkv, dout, table, heads, ws, shift, keep):
+    """The windowed attention of SwinTransformer.py (oracle/swin_oracle.py: roll, window_partition, relative_position_index,
+    shift_mask) in fp64 through attn_ref.  qkv [B,H,W,3C], dout [B,H,W,C] fp64 on the device (processed an image at a time),
+    table [(2ws-1)^2, heads].  Returns, for the images in `keep`, o / dqkv and their mags and ext terms as [len(keep),H,W,*] tensors,
+    and dtable, its mag and ext summed over ALL images."""
+    import swin_oracle as S
+    B, H, W, C3 = qkv.shape
+    C, N, dev = C3 // 3, ws * ws, qkv.device
+    d, nW = C // heads, (H // ws) * (W // ws)
+    rpi = S.relative_position_index(ws).reshape(-1).to(dev)
+    bias = table[rpi].reshape(N, N, heads).permute(2, 0, 1)                           # [heads, N, N]
+    mask = S.shift_mask(H, W, ws, shift).to(dev) if shift else torch.zeros(nW, N, N, dtype=torch.float64, device=dev)
+    full = (bias[None] + mask[:, None]).reshape(nW * heads, N, N)
+    fabs = (bias.abs()[None] + mask.abs()[:, None]).reshape(nW * heads, N, N)
+    T2 = (2 * ws - 1) ** 2
+    dtab = {k: torch.zeros(T2, heads, dtype=torch.float64, device=dev) for k in ("dS", "dsm", "dsext")}
+    kept = {}
+
+    def part(x):       # [1,H,W,c] -> [nW*heads, N, c/heads] for c = n*C: (n, heads) split
+        if shift:
+            x = torch.roll(x, shifts=(-shift, -shift), dims=(1, 2))
+        n = x.shape[-1] // C
+        xw = S.window_partition(x, ws).reshape(nW, N, n, heads, d).permute(2, 0, 3, 1, 4)
+        return xw.reshape(n, nW * heads, N, d)
+
+    def unpart(t):     # [n][nW*heads, N, d] -> [1,H,W,n*C]
+        n = len(t)
+        x = torch.stack(t).reshape(n, nW, heads, N, d).permute(1, 3, 0, 2, 4).reshape(nW, ws, ws, n * C)
+        x = S.window_reverse(x, ws, H, W)
+        return torch.roll(x, shifts=(shift, shift), dims=(1, 2)) if shift else x
+
+    for b in range(B):
+        q, k, v = part(qkv[b:b + 1].double())
+        (do,) = part(dout[b:b + 1].double())
+        r = attn_ref(q, k, v, do, d ** -0.5, full, fabs)
+        for key in dtab:
+            dtab[key].index_add_(0, rpi, r[key].reshape(nW, heads, N * N).sum(0).T)
+        if b in keep:
+            kept[b] = dict(o=unpart([r["o"]]), om=unpart([r["om"]]), oext=unpart([r["oext"]]),
+                           dqkv=unpart([r["dq"], r["dk"], r["dv"]]), dqkvm=unpart([r["dqm"], r["dkm"], r["dvm"]]),
+                           dqkvext=unpart([r["dqext"], r["dkext"], r["dvext"]]))
+    out = {key: torch.cat([kept[b][key] for b in keep]) for key in kept[keep[0]]}
+    out.update(dtable=dtab["dS"], dtablem=dtab["dsm"], dtableext=dtab["dsext"])
+    return out
+
+
+def ln_wide_ref(x, dy, gamma, beta, eps=1e-5):
+    """LayerNorm over the last axis (oracle/swin_oracle.py layer_norm, eps 1e-5) of x [M, C] fp64 on the device, its backward for dy,
+    and the mags of test_gpu_norm_routes.py (no activation).  ext terms: the fp32 mean's rounding (2^-20*|mean|, amplified by rstd)
+    enters xhat - it is what a row of zero variance shows."""
+    import swin_oracle as S
+    assert S.LN_EPS == eps
+    xr, gr, br = (t.clone().requires_grad_(True) for t in (x, gamma, beta))
+    y = S.layer_norm(xr, gr, br)
+    (y * dy).sum().backward()
+    mu = x.mean(-1, keepdim=True)
+    rstd = (((x - mu) ** 2).mean(-1, keepdim=True) + eps).rsqrt()
+    xh = (x - mu) * rstd
+    xe = U_F32 * rstd * mu.abs()                              # error of the kernel's xhat from its fp32 mean
+    gg = (gamma * dy).abs()
+    mean = lambda t: t.mean(-1, keepdim=True)
+    return dict(y=y.detach(), ymag=(gamma * xh).abs() + beta.abs(), yext=xe * gamma.abs(),
+                dx=xr.grad, dxmag=rstd * (gg + mean(gg) + xh.abs() * mean(gg * xh.abs())),
+                dgamma=gr.grad, dgmag=(dy * xh).abs().sum(0), dgext=(dy.abs() * xe).sum(0), dbeta=br.grad, dbmag=dy.abs().sum(0))

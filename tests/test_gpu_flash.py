@@ -8,6 +8,8 @@ import math
 import pytest
 import torch
 
+from route_probe import U_BF16, acheck, attn_ref, routed
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 
@@ -73,7 +75,8 @@ def test_flash_attention_matches_fp64(B, N, nh, with_o32):
     out = torch.full((B, N, 1, hs), float("nan"), dtype=torch.bfloat16, device=DEV)
     lse = torch.empty((B * nh, N), dtype=torch.float32, device=DEV)
     o32 = torch.full((B, N, hs), float("nan"), dtype=torch.float32, device=DEV) if with_o32 else None
-    ops.flash_attn_fwd(qkv, nh, scale, out, lse, o32)
+    tile = "<1, 8>" if B * nh * ((N + 127) // 128) >= 256 else "<1, 4>"
+    routed(lambda: ops.flash_attn_fwd(qkv, nh, scale, out, lse, o32), f"flash_fwd_kernel{tile}")
     o_ref, g_ref, p_ref = reference(qkv.cpu(), d_out.cpu(), nh, scale)
     e_o = rel(out, o_ref)
     # base-2 log-sum-exp of the scaled scores
@@ -83,8 +86,17 @@ def test_flash_attention_matches_fp64(B, N, nh, with_o32):
     e_l = (lse.double().cpu() - lse_ref).abs().max().item()
     dqkv = torch.full((B, N, 1, 3 * hs), float("nan"), dtype=torch.bfloat16, device=DEV)
     delta = torch.empty((B * nh, N), dtype=torch.float32, device=DEV)
-    ops.flash_attn_bwd(qkv, nh, scale, out, d_out, lse, delta, dqkv, o32)
+    routed(lambda: ops.flash_attn_bwd(qkv, nh, scale, out, d_out, lse, delta, dqkv, o32), f"flash_bwd_dq_kernel{tile}", f"flash_bwd_dkv_kernel{tile}")
     torch.cuda.synchronize()
+    # every element within the bounds of test_gpu_attn_routes.py
+    xr = qkv.double().reshape(B, N, 3, nh, 128)
+    heads = lambda t: t.permute(0, 2, 1, 3).reshape(B * nh, N, 128)
+    back = lambda t: t.reshape(B, nh, N, 128).permute(0, 2, 1, 3).reshape(B, N, hs)
+    r = attn_ref(heads(xr[:, :, 0]), heads(xr[:, :, 1]), heads(xr[:, :, 2]), heads(d_out.double().reshape(B, N, nh, 128)), scale)
+    acheck("O", out.reshape(B, N, hs), back(r["o"]), back(r["om"]), U_BF16, 4.0, back(r["oext"]))
+    acheck("lse", lse, r["lse"], None, 0, 0, r["lse_b"])
+    for i, nm in enumerate(("dq", "dk", "dv")):
+        acheck(nm, dqkv.reshape(B, N, 3 * hs)[..., i * hs:(i + 1) * hs], back(r[nm]), back(r[nm + "m"]), U_BF16, 8.0, back(r[nm + "ext"]))
     if with_o32:
         assert rel(o32.reshape(B, N, 1, hs), o_ref) < 5e-5 and torch.equal(o32.reshape(B, N, 1, hs).to(torch.bfloat16), out)
         # rows of dS sum to zero: the key gradient summed over keys (= the key bias gradient) vanishes

@@ -9,6 +9,7 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle"))
 import swin_oracle as S
+from route_probe import U_BF16, U_F32, acheck, c_f32, ln_wide_ref, routed, window_ref
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -57,13 +58,24 @@ def test_window_attention_kernel(B, H, W, C, heads, ws, shift):
     want = ref(ql, tl)
     gq, gt = torch.autograd.grad(want, [ql, tl], dout)
     qd, td = dev(qkv), table.float().to(DEV)
-    out = ops.window_attn_fwd(qd, td, heads, ws, shift, torch.empty(B, H, W, C, dtype=torch.bfloat16, device=DEV))
+    if ws == 8 and d == 32:
+        nW = (H // 8) * (W // 8)
+        one = [nW % w != 0 or nW // w * heads * B < floor for w, floor in ((2, 8192), (2, 1024))]      # wa_launch's wpb > 1 test
+        kf, kb = (f"window_attn_mfma_kernel<{b}, {'true' if o else 'false'}>" for b, o in zip(("false", "true"), one))
+    else:
+        kf, kb = f"window_attn_kernel<false, {ws}>", f"window_attn_kernel<true, {ws}>"
+    out, _ = routed(lambda: ops.window_attn_fwd(qd, td, heads, ws, shift, torch.empty(B, H, W, C, dtype=torch.bfloat16, device=DEV)), kf)
     assert rel(out, bf(want)) < 1e-3
     dtab = torch.zeros_like(td)
-    dqkv = ops.window_attn_bwd(qd, dev(dout), td, heads, ws, shift, torch.empty_like(qd), dtab)
+    dqkv, _ = routed(lambda: ops.window_attn_bwd(qd, dev(dout), td, heads, ws, shift, torch.empty_like(qd), dtab), kb, "reduce_finish_kernel")
     torch.cuda.synchronize()
     assert rel(dqkv, bf(gq)) < 1e-3
     assert rel(dtab, gt) < 1e-3
+    # every element within the bounds of test_gpu_attn_routes.py
+    r = window_ref(qkv.to(DEV), dout.to(DEV), table.to(DEV), heads, ws, shift, list(range(B)))
+    acheck("O", out, r["o"], r["om"], U_BF16, 4.0, r["oext"])
+    acheck("dqkv", dqkv, r["dqkv"], r["dqkvm"], U_BF16, 4.0, r["dqkvext"])
+    acheck("dtable", dtab, r["dtable"], r["dtablem"], U_F32, c_f32(B * H * W), r["dtableext"])
 
 
 @pytest.mark.parametrize("M,C", [(37, 96), (64, 512), (50, 768), (33, 1536), (17, 3072), (9, 4096)])
@@ -77,12 +89,21 @@ def test_wide_layer_norm(M, C):
     want = S.layer_norm(xl, gl, bl)
     gx, gg, gb = torch.autograd.grad(want, [xl, gl, bl], dy)
     xd = dev(x)
-    out = ops.ln_wide_fwd(xd, gam.float().to(DEV), bet.float().to(DEV), 1e-5, torch.empty_like(xd))
+    ch = (C // 8 + 63) // 64
+    nk = 1 if ch <= 1 else (2 if ch <= 2 else (4 if ch <= 4 else 8))
+    out, _ = routed(lambda: ops.ln_wide_fwd(xd, gam.float().to(DEV), bet.float().to(DEV), 1e-5, torch.empty_like(xd)), f"ln_wide_kernel<{nk}, false>")
     assert rel(out, bf(want)) < 1e-3
     dga, dbe = torch.zeros(C, device=DEV), torch.zeros(C, device=DEV)
-    dx = ops.ln_wide_bwd(xd, dev(dy), gam.float().to(DEV), 1e-5, torch.empty_like(xd), dga, dbe)
+    dx, _ = routed(lambda: ops.ln_wide_bwd(xd, dev(dy), gam.float().to(DEV), 1e-5, torch.empty_like(xd), dga, dbe), f"ln_wide_kernel<{nk}, true>",
+                   "reduce_finish_kernel")
     torch.cuda.synchronize()
     assert rel(dx, bf(gx)) < 1e-3 and rel(dga, gg) < 1e-3 and rel(dbe, gb) < 1e-3
+    # every element within the bounds of test_gpu_attn_routes.py
+    r = ln_wide_ref(x.reshape(M, C).to(DEV), dy.reshape(M, C).to(DEV), gam.to(DEV), bet.to(DEV))
+    acheck("y", out.reshape(M, C), r["y"], r["ymag"], U_BF16, 4.0, r["yext"])
+    acheck("dx", dx.reshape(M, C), r["dx"], r["dxmag"], U_BF16, 4.0)
+    acheck("dgamma", dga, r["dgamma"], r["dgmag"], U_F32, c_f32(M), r["dgext"])
+    acheck("dbeta", dbe, r["dbeta"], r["dbmag"], U_F32, c_f32(M))
 
 
 def test_patchify_merge_and_token_mean():

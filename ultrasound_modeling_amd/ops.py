@@ -1115,11 +1115,20 @@ def softmax_rows_bwd(p32, dp, n, scale, ds):
     L.check(L.load().usseg_softmax_rows_bwd(p32.data_ptr(), dp.data_ptr(), p32.numel() // n, n, scale, ds.data_ptr(), _stream()), "softmax_rows_bwd")
 
 
+def _dense_f32(t, n, what):
+    """The attention kernels index lse / delta as dense [B*heads][N] and out32 as dense [B][N][hidden] fp32."""
+    assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n, \
+        f"{what}: expected a dense fp32 tensor of {n} elements, got {t.dtype} {tuple(t.shape)} strides {t.stride()}"
+
+
 def flash_attn_fwd(qkv, nh, scale, out, lse, out32=None):
     """qkv [B,N,1,3*hidden] bf16 -> out [B,N,1,hidden] = softmax(scale q k^T) v per (image, head); lse fp32 [B*nh, N] (base 2);
     out32: optional dense fp32 copy of out (for the backward's delta)."""
     B, N, _, C3 = qkv.shape
     hs = C3 // 3
+    _dense_f32(lse, B * nh * N, "lse")
+    if out32 is not None:
+        _dense_f32(out32, B * N * hs, "out32")
     d = L.FlashDesc(B, N, nh, hs // nh, geom(qkv)[4], geom(out)[4], scale)
     e = qkv.element_size()
     L.check(L.load().usseg_flash_attn_fwd(C.byref(d), qkv.data_ptr(), qkv.data_ptr() + hs * e, qkv.data_ptr() + 2 * hs * e, out.data_ptr(),
@@ -1132,6 +1141,9 @@ def flash_attn_bwd(qkv, nh, scale, out, d_out, lse, delta, dqkv, out32=None):
     B, N, _, C3 = qkv.shape
     hs = C3 // 3
     assert geom(dqkv)[4] == geom(qkv)[4] and geom(d_out)[4] == geom(out)[4]
+    for t, n, what in ((lse, B * nh * N, "lse"), (delta, B * nh * N, "delta"), (out32, B * N * hs, "out32")):
+        if t is not None:
+            _dense_f32(t, n, what)
     d = L.FlashDesc(B, N, nh, hs // nh, geom(qkv)[4], geom(out)[4], scale)
     e = qkv.element_size()
     L.check(L.load().usseg_flash_attn_bwd(C.byref(d), qkv.data_ptr(), qkv.data_ptr() + hs * e, qkv.data_ptr() + 2 * hs * e, out.data_ptr(),
@@ -1190,6 +1202,8 @@ def window_attn_fwd(qkv, table, heads, ws, shift, out):
 
 def window_attn_bwd(qkv, dout, table, heads, ws, shift, dqkv, dtable):
     B, H, W, C3, ldq = geom(qkv)
+    # the kernel writes dqkv with qkv's row stride
+    assert tuple(dqkv.shape) == tuple(qkv.shape) and geom(dqkv)[4] == ldq, "dqkv must have qkv's shape and row stride"
     lib = L.load()
     rows = torch.empty(int(lib.usseg_window_attn_bwd_ws_floats(B, H, W, heads, ws)), dtype=torch.float32, device=qkv.device)
     L.check(lib.usseg_window_attn_bwd(qkv.data_ptr(), ldq, dout.data_ptr(), geom(dout)[4], table.data_ptr(), B, H, W, C3 // 3, heads, ws, shift,
@@ -1205,7 +1219,7 @@ def token_mean_fwd(x):
 
 
 def token_mean_bwd(dy, like):
-    B, H, W, Cc, ld = geom(like)
-    dx = torch.empty_like(like)
-    L.check(L.load().usseg_token_mean_bwd(dy.data_ptr(), B, H * W, Cc, ld, dx.data_ptr(), _stream()), "token_mean_bwd")
+    B, H, W, Cc, _ = geom(like)
+    dx = torch.empty(like.shape, dtype=like.dtype, device=like.device)      # dense: the kernel writes it with dx's own row stride
+    L.check(L.load().usseg_token_mean_bwd(dy.data_ptr(), B, H * W, Cc, geom(dx)[4], dx.data_ptr(), _stream()), "token_mean_bwd")
     return dx
