@@ -752,6 +752,28 @@ int usseg_prof_enable(int32_t kind_mask, int32_t capacity);
 int usseg_prof_read(int32_t kind, double* total_ms, int64_t* launches);
 int usseg_prof_disable(void);
 
+/* ---- offline preprocessing of one raw scan (prep.hip; DataFilePlayGround.output2DImages mode 1, DataFilePlayGround.py:286-393) ----------
+ * Every cardiac cycle of one .mat file in one chain of launches, fp64 like the reference; the cv2 resize / GaussianBlur rules the kernels
+ * restate are in DESIGN.md section 4h.  Output size USSEG_PREP_H x USSEG_PREP_W (cv2.resize(.., (80, 256))).  Every value is written by
+ * one lane with a fixed operation order: bitwise reproducible.  All buffers are dense and row-major.
+ * frames: fp64 [C][10][H0][W0], plane c*10+k = displacement[:, :, start_c + k] (k < 5: the "real" frames, else "imag"; :312-318).
+ * usseg_prep_cycle_stats -> stats fp64 [C*10][2]: the plane's mean (numpy's x.mean(axis=0).mean(axis=0): an ordered column sum / H0,
+ *   then an ordered sum of the column means / W0) and safe_max = max|x - mean| with 0 -> 1 (:368-376).  col_ws: fp64 [C*10][3][W0]. */
+#define USSEG_PREP_H 256
+#define USSEG_PREP_W 80
+int usseg_prep_cycle_stats(const double* frames, int32_t C, int32_t H0, int32_t W0, double* col_ws, double* stats, usseg_stream_t stream);
+/* The label and the gate at USSEG_PREP_H x USSEG_PREP_W (:330-343).  brain: fp64 [Hb][Wb]; gate[p] = 1 where the resized brain mask is
+ * exactly 0.  objective 0: label = gate ? 0 : 1 (blood, normal, ws unused, may be NULL).  objective 1: blood, normal fp64 [Hm][Wm]; the
+ * fp32 label where(blood > normal, 2, 1) (NaN compares false) goes through GaussianBlur 9x9 sigma 4, the re-set to 2 where blood > normal,
+ * GaussianBlur 3x3 sigma 2, the re-set, a fp32 resize and label = gate ? 0 : that.  ws: fp32 [2][Hm*Wm] (objective 1 only). */
+int usseg_prep_label(const double* brain, int32_t Hb, int32_t Wb, const double* blood, const double* normal, int32_t Hm, int32_t Wm,
+                     int32_t objective, float* ws, float* label, uint8_t* gate, usseg_stream_t stream);
+/* out fp64 [C][USSEG_PREP_H][USSEG_PREP_W][12], the reference's image per cycle (:393): 0 the label; 1..10 plane c*10+k resized, each
+ * bilinear tap normalised with stats before the blend and 0 where gate is set for objective 1 (:384-388); 11 the resized map
+ * mean_f log10(bmode[c][.][.][f]), never gated (:327, :351, :381).  bmode: fp64 [C][Hq][Wq][F], cycle c = bModeNorm[:, :, :, c]. */
+int usseg_prep_assemble(const double* frames, const double* stats, int32_t C, int32_t H0, int32_t W0, const double* bmode, int32_t Hq,
+                        int32_t Wq, int32_t F, const float* label, const uint8_t* gate, int32_t objective, double* out, usseg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,244 @@
+"""The reference's offline data preparation ``DataFilePlayGround.output2DImages`` (DataFilePlayGround.py:249-515): a patient's raw ``.mat``
+scans -> the ``TrainingData.npy`` / ``TestingData.npy`` [N,1,256,80,12] arrays and their paths that ``Dataset_2``, ``MainNumpy``,
+``MainParallel`` and ``TBIEvaluator`` read.  Channel 0 is the label, 1-10 the normalised displacement frames of one cardiac cycle, 11 the
+B-mode image.  Folders ``brainMask/`` (objective 0) and ``bleed/`` (objective 1) as in the reference.
+
+The numeric work of a file runs on the device, every cycle of the file at once (csrc/prep.hip): ``process_file`` gathers the 10*C frames
+the file's cycles use into one buffer with the B-mode stack and the masks, makes one host-to-device copy and enqueues three short steps on
+the current stream - per-plane statistics, the label and gate, and the assembly of the 12 channels - with no host synchronisation.  The
+host keeps ``loadmat``, the file walk, the split and the saves.
+
+cv2 is not part of this stack.  The kernels and ``resize_area`` restate the cv2 functions the reference calls, from these rules (a
+restatement of cv2's documented behaviour, not checked against cv2 itself):
+  * ``resize`` INTER_LINEAR, per axis: ``inv = dsize/ssize``, ``scale = 1.0/inv`` (double); ``f = float32((d+0.5)*scale - 0.5)``,
+    ``s = floor(f)``, ``f -= s`` (float32).  ``s < 0`` -> ``s, f = 0, 0``; ``s >= ssize-1`` -> ``s, f = ssize-1, 0`` and only the single
+    horizontal tap ``S[s]`` is used.  Weights float32 ``(1-f, f)``.  The horizontal pass first, then the vertical
+    ``b0*row(s) + b1*row(min(s+1, ssize-1))``.  float64 input: the weights are applied in double; float32 input: all in float32.
+  * ``GaussianBlur(ksize, sigma)`` on float32: ``t_i = float32(exp(-x_i^2/(2 sigma^2)))``, ``w_i = float32(t_i * (1/sum t))``;
+    separable, rows then columns, border BORDER_REFLECT_101 (``dcb|abcd|cba``).
+  * ``resize`` INTER_AREA (``FetchPolarAxis`` only, host NumPy): box averages when neither axis grows, else the linear scheme with the
+    area coefficients ``s = floor(d*scale)``, ``f = (d+1) - (s+1)*inv``, ``f = 0 if f <= 0 else f - floor(f)``.
+
+Deliberate deviations from the reference:
+  * one process: patients in the shuffled order, the ``.mat`` files of a patient in sorted order (the reference forks one child per
+    patient and appends in whatever order the children finish, and walks a patient's files in ``os.listdir`` order);
+  * ``seed=None`` draws the final shuffle's seed as the reference does (``np.random.randint(0, 1e5)``); a given ``seed`` reproduces the
+    output exactly;
+  * every input array is converted to float64 first, integer and boolean masks included (cv2's 8-bit fixed-point resize is not
+    restated; the reference's masks carry NaNs, so they are floating point), and ``log10`` is taken in float64;
+  * a file that lacks a field, has a cycle window that starts before frame 0 or runs past the last frame, or whose ``bModeNorm`` is not
+    4-D with a slice per cycle raises a ``ValueError`` naming the file (the reference fails inside a child process or mis-slices);
+  * the output folder's parent is created if it is missing.
+"""
+from __future__ import annotations
+
+import argparse
+import math
+import os
+import random
+from typing import List, Tuple
+
+import numpy as np
+import torch
+
+from . import ops
+
+OUT_H, OUT_W = ops.PREP_H, ops.PREP_W
+PATIENT_SEED = 20          # sklearn.utils.shuffle(pathlist, random_state=20), :444
+BAD_PATIENTS = (1, 14, 22, 23, 27, 28, 32, 34, 35, 36, 37, 38, 39, 44, 49, 69, 71, 78, 82, 90, 98, 101, 121, 124, 128, 133, 136, 928)  # :278
+FIELDS = ("normalMask", "bloodMask", "brainMask", "bModeNorm", "displacement", "hrTimes")
+
+
+def permutation(n: int, seed: int) -> np.ndarray:
+    """The order ``sklearn.utils.shuffle(x, random_state=seed)`` puts n rows in: ``np.random.RandomState(seed).permutation(n)``."""
+    return np.random.RandomState(seed).permutation(n)
+
+
+def patient_plan(iteration: int, rawDataPath: str) -> List[Tuple[str, int, bool]]:
+    """The patients ``output2DImages`` processes, in its order: (folder name, index in the shuffled list, goes to the test set).
+    The list is every entry of ``rawDataPath``, sorted, then shuffled with random_state 20 (:442-444); a bad patient (:278-279,
+    ``int(name[-3:])``) is left out but keeps its index; a patient is a test patient iff index % 10 == iteration % 10 (:397)."""
+    names = np.sort(os.listdir(rawDataPath))
+    names = names[permutation(len(names), PATIENT_SEED)]
+    plan = []
+    for index, name in enumerate(names):
+        if int(name[-3:]) in BAD_PATIENTS:
+            continue
+        plan.append((str(name), index, index % 10 == iteration % 10))
+    return plan
+
+
+def _load(path: str):
+    """Read and check one file; -> host float64 (frames [C,10,H0,W0], bmode [C,Hq,Wq,F], brain, blood, normal)."""
+    from scipy.io import loadmat
+    mat = loadmat(path)
+    missing = [k for k in FIELDS if k not in mat]
+    if missing:
+        raise ValueError(f"{path}: missing {', '.join(missing)}")
+    f64 = lambda k: np.asarray(mat[k]).astype(np.float64)
+    disp, hr, bmode = f64("displacement"), f64("hrTimes"), f64("bModeNorm")
+    brain, blood, normal = f64("brainMask"), f64("bloodMask"), f64("normalMask")
+    if disp.ndim != 3:
+        raise ValueError(f"{path}: displacement must be [H, W, T], is {disp.shape}")
+    if hr.ndim != 2 or hr.shape[0] < 1 or hr.shape[1] < 1:
+        raise ValueError(f"{path}: hrTimes must be [1, cycles + 1], is {hr.shape}")
+    C, T = hr.shape[1] - 1, disp.shape[2]
+    if bmode.ndim != 4 or bmode.shape[3] < C or 0 in bmode.shape[:3]:
+        raise ValueError(f"{path}: bModeNorm must be [H, W, F, >= {C}], is {bmode.shape}")
+    for k, m in (("brainMask", brain), ("bloodMask", blood), ("normalMask", normal)):
+        if m.ndim != 2 or 0 in m.shape:
+            raise ValueError(f"{path}: {k} must be a non-empty 2-D array, is {m.shape}")
+    if blood.shape != normal.shape:
+        raise ValueError(f"{path}: bloodMask {blood.shape} and normalMask {normal.shape} differ in shape")
+    frames = np.empty((C, 10) + disp.shape[:2], np.float64)
+    for h in range(C):
+        start = int(math.ceil(30 * hr[0, h]))          # :316
+        if start < 0 or start + 10 > T:
+            raise ValueError(f"{path}: cycle {h} takes frames {start}..{start + 9}, the file has {T}")
+        frames[h] = np.moveaxis(disp[:, :, start:start + 10], 2, 0)
+    return frames, np.ascontiguousarray(np.moveaxis(bmode[:, :, :, :C], 3, 0)), brain, blood, normal
+
+
+def process_file(path: str, objective: int, device="cuda") -> Tuple[torch.Tensor, str]:
+    """One ``.mat`` file -> (images, name): images a device float64 [C,1,256,80,12], one per cardiac cycle, as the reference's inner
+    loop builds them (:294-393, mode 1); name = the file name's first 17 characters (:291).  Enqueued on the current stream."""
+    if objective not in (0, 1):
+        raise ValueError(f"objective must be 0 (brain mask) or 1 (bleed), got {objective}")
+    frames, bmode, brain, blood, normal = _load(path)
+    name = os.path.basename(path)[0:17]
+    device = torch.device(device)
+    C = frames.shape[0]
+    if C == 0:
+        return torch.empty((0, 1, OUT_H, OUT_W, 12), dtype=torch.float64, device=device), name
+    parts = [frames, bmode, brain] + ([blood, normal] if objective == 1 else [])
+    dev = torch.from_numpy(np.concatenate([p.ravel() for p in parts])).to(device)         # the one host-to-device copy
+    views, off = [], 0
+    for p in parts:
+        views.append(dev[off:off + p.size].view(p.shape))
+        off += p.size
+    frames_d, bmode_d, brain_d = views[:3]
+    stats = ops.prep_cycle_stats(frames_d)
+    label, gate = ops.prep_label(brain_d, objective, *views[3:])
+    return ops.prep_assemble(frames_d, stats, bmode_d, label, gate, objective), name
+
+
+def _stack(images: List[torch.Tensor], names: List[str], seed: int):
+    """Concatenate, shuffle with ``seed`` (sklearn.utils.shuffle's order, :476-479) and bring to the host."""
+    perm = permutation(len(names), seed)
+    if images:
+        data = torch.cat(images)[torch.as_tensor(perm, device=images[0].device)].cpu().numpy()
+    else:
+        data = np.zeros((0, 1, OUT_H, OUT_W, 12), np.float64)
+    paths = np.array(names, dtype=str).reshape(-1, 1)[perm]
+    return data, paths
+
+
+def build_arrays(iteration: int, objective: int, rawDataPath: str, *, seed=None, device="cuda"):
+    """-> (train [N,1,256,80,12] float64, test [M,1,256,80,12] float64, train_paths [N,1] str, test_paths [M,1] str), the four arrays
+    ``output2DImages`` saves.  The final shuffle uses ``seed`` for the training rows and ``seed // 17`` for the test rows (:475-479)."""
+    if seed is None:
+        seed = np.random.randint(0, int(1e5))
+    tr, te, tr_names, te_names = [], [], [], []
+    for name, _, is_test in patient_plan(iteration, rawDataPath):
+        folder = os.path.join(rawDataPath, name)
+        for file in sorted(os.listdir(folder)):
+            if ".mat" not in file:
+                continue
+            images, pathName = process_file(os.path.join(folder, file), objective, device)
+            (te if is_test else tr).append(images)
+            (te_names if is_test else tr_names).extend([pathName] * images.shape[0])
+    train, train_paths = _stack(tr, tr_names, seed)
+    test, test_paths = _stack(te, te_names, seed // 17)
+    return train, test, train_paths, test_paths
+
+
+def output2DImages(iteration, objective, rawDataPath, savePath, *, seed=None):
+    """The reference's output2DImages (:249-493): ``savePath/brainMask`` (objective 0) or ``savePath/bleed`` (objective 1) gets
+    TrainingData.npy, TestingData.npy, TrainingPaths.npy and TestingPaths.npy.  A folder that already holds files is left as it is."""
+    dataFolder = os.path.join(savePath, "brainMask" if objective == 0 else "bleed")
+    if os.path.isdir(dataFolder) and len(os.listdir(dataFolder)) != 0:
+        print(str(dataFolder) + " contains data. End of data processing")
+        return
+    os.makedirs(dataFolder, exist_ok=True)
+    train, test, train_paths, test_paths = build_arrays(iteration, objective, rawDataPath, seed=seed)
+    print("training {}".format(train.shape))
+    print("testing {}".format(test.shape))
+    print("saved in : {}".format(savePath))
+    np.save(os.path.join(dataFolder, "TrainingData.npy"), train)
+    np.save(os.path.join(dataFolder, "TestingData.npy"), test)
+    np.save(os.path.join(dataFolder, "TrainingPaths.npy"), train_paths)
+    np.save(os.path.join(dataFolder, "TestingPaths.npy"), test_paths)
+
+
+# ---------------------------------------------------------------------------------------------------------- the display axis
+def _area_weights(ssize: int, dsize: int, box: bool) -> np.ndarray:
+    """[dsize, ssize] float64 matrix of cv2's INTER_AREA weights along one axis (float32 coefficients)."""
+    inv = dsize / ssize
+    scale = 1.0 / inv
+    Wt = np.zeros((dsize, ssize), np.float64)
+    for d in range(dsize):
+        if box:
+            fs1 = d * scale
+            fs2 = fs1 + scale
+            cell = min(scale, ssize - fs1)
+            s2 = min(math.floor(fs2), ssize - 1)
+            s1 = min(math.ceil(fs1), s2)
+            if s1 - fs1 > 1e-3:
+                Wt[d, s1 - 1] += np.float32((s1 - fs1) / cell)
+            for s in range(s1, s2):
+                Wt[d, s] += np.float32(1.0 / cell)
+            if fs2 - s2 > 1e-3:
+                Wt[d, s2] += np.float32(min(min(fs2 - s2, 1.0), cell) / cell)
+        else:
+            s = math.floor(d * scale)
+            f = np.float32((d + 1) - (s + 1) * inv)
+            f = np.float32(0.0) if f <= 0 else f - np.float32(math.floor(f))
+            if s >= ssize - 1:
+                Wt[d, ssize - 1] = 1.0
+            else:
+                Wt[d, s], Wt[d, s + 1] = np.float32(1.0) - f, f
+    return Wt
+
+
+def resize_area(src, dsize_hw=(OUT_H, OUT_W)) -> np.ndarray:
+    """cv2.resize(src, (W, H), interpolation=INTER_AREA) of a 2-D array, in float64 (see the module docstring)."""
+    src = np.asarray(src, np.float64)
+    if src.ndim != 2:
+        raise ValueError(f"resize_area takes a 2-D array, got {src.shape}")
+    (H, W), (h, w) = src.shape, dsize_hw
+    box = H >= h and W >= w
+    return _area_weights(H, h, box) @ src @ _area_weights(W, w, box).T
+
+
+def FetchPolarAxis(datapath, axisPath):
+    """:86-100: the file's xAxis and zAxis resized to 256x80 with INTER_AREA, +100 and -4, saved as axis/xAxis.npy and axis/yAxis.npy."""
+    from scipy.io import loadmat
+    mat = loadmat(datapath)
+    xaxis = resize_area(mat["xAxis"]) + 100
+    yaxis = resize_area(mat["zAxis"]) - 4
+    print("saved axis info in : {}".format(axisPath))
+    np.save(os.path.join(axisPath, "xAxis.npy"), xaxis)
+    np.save(os.path.join(axisPath, "yAxis.npy"), yaxis)
+
+
+def main(argv=None):
+    """:496-515: both objectives, then the display axis from a file of patient DoD009."""
+    ap = argparse.ArgumentParser(description="Raw .mat scans -> the training / test arrays of the brain-mask and bleed models.")
+    ap.add_argument("raw", help="folder of patient folders (DoD001, ...) holding .mat files")
+    ap.add_argument("save", help="output folder: brainMask/, bleed/ and axis/ are created in it")
+    ap.add_argument("--iteration", type=int, default=1, help="patients with index %% 10 == iteration %% 10 form the test set")
+    ap.add_argument("--seed", type=int, default=None, help="seed of the final shuffle (default: drawn, as in the reference)")
+    a = ap.parse_args(argv)
+    os.makedirs(a.save, exist_ok=True)
+    output2DImages(a.iteration, 0, a.raw, a.save, seed=a.seed)
+    output2DImages(a.iteration, 1, a.raw, a.save, seed=a.seed)
+    axisPath = os.path.join(a.save, "axis")
+    if not os.path.isdir(axisPath):
+        os.mkdir(axisPath)
+        rng = random if a.seed is None else random.Random(a.seed)
+        files = sorted(os.listdir(os.path.join(a.raw, "DoD009")))
+        FetchPolarAxis(os.path.join(a.raw, "DoD009", rng.choice(files)), axisPath)
+
+
+if __name__ == "__main__":
+    main()

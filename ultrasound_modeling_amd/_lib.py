@@ -230,6 +230,9 @@ _PROTOS = {
     "usseg_prof_enable": (C.c_int, [c_i32, c_i32]),
     "usseg_prof_read": (C.c_int, [c_i32, P(C.c_double), P(c_i64)]),
     "usseg_prof_disable": (C.c_int, []),
+    "usseg_prep_cycle_stats": (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "usseg_prep_label": (C.c_int, [c_vp, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "usseg_prep_assemble": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp]),
 }
 EXPORTED_SYMBOLS = tuple(_PROTOS)
 

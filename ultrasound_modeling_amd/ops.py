@@ -1223,3 +1223,62 @@ def token_mean_bwd(dy, like):
     dx = torch.empty(like.shape, dtype=like.dtype, device=like.device)      # dense: the kernel writes it with dx's own row stride
     L.check(L.load().usseg_token_mean_bwd(dy.data_ptr(), B, H * W, Cc, geom(dx)[4], dx.data_ptr(), _stream()), "token_mean_bwd")
     return dx
+
+
+# ------------------------------------------------------------------------------------------------ offline preprocessing (prep.hip)
+PREP_H, PREP_W = 256, 80     # USSEG_PREP_H, USSEG_PREP_W
+
+
+def _prep_check(t, name, dtype, ndim):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.dim() == ndim and t.is_contiguous()):
+        raise ValueError(f"{name} must be a contiguous {dtype} cuda tensor of {ndim} dims")
+
+
+def prep_cycle_stats(frames):
+    """frames fp64 [C,10,H0,W0] -> stats fp64 [C*10,2]: each plane's mean and safe_max (DataFilePlayGround.py:368-376)."""
+    _prep_check(frames, "frames", torch.float64, 4)
+    Cc, K, H0, W0 = frames.shape
+    if K != 10:
+        raise ValueError(f"frames must hold 10 planes per cycle, has {K}")
+    col = torch.empty((Cc * 10, 3, W0), dtype=torch.float64, device=frames.device)
+    stats = torch.empty((Cc * 10, 2), dtype=torch.float64, device=frames.device)
+    L.check(L.load().usseg_prep_cycle_stats(frames.data_ptr(), Cc, H0, W0, col.data_ptr(), stats.data_ptr(), _stream()), "prep_cycle_stats")
+    return stats
+
+
+def prep_label(brain, objective, blood=None, normal=None):
+    """The label fp32 [256,80] and the gate uint8 [256,80] (1 where the resized brain mask is 0) of one file (DataFilePlayGround.py:330-343).
+    brain fp64 [Hb,Wb]; objective 1 also takes blood and normal fp64 [Hm,Wm]."""
+    _prep_check(brain, "brain", torch.float64, 2)
+    Hm = Wm = 0
+    ws = None
+    if objective == 1:
+        _prep_check(blood, "blood", torch.float64, 2)
+        _prep_check(normal, "normal", torch.float64, 2)
+        if blood.shape != normal.shape:
+            raise ValueError(f"blood {tuple(blood.shape)} and normal {tuple(normal.shape)} masks differ in shape")
+        Hm, Wm = blood.shape
+        ws = torch.empty((2, Hm * Wm), dtype=torch.float32, device=brain.device)
+    label = torch.empty((PREP_H, PREP_W), dtype=torch.float32, device=brain.device)
+    gate = torch.empty((PREP_H, PREP_W), dtype=torch.uint8, device=brain.device)
+    L.check(L.load().usseg_prep_label(brain.data_ptr(), brain.shape[0], brain.shape[1], _ptr(blood if objective == 1 else None),
+                                      _ptr(normal if objective == 1 else None), Hm, Wm, objective, _ptr(ws), label.data_ptr(), gate.data_ptr(),
+                                      _stream()), "prep_label")
+    return label, gate
+
+
+def prep_assemble(frames, stats, bmode, label, gate, objective):
+    """The images of every cycle of one file: fp64 [C,1,256,80,12] (DataFilePlayGround.py:353-393).  frames fp64 [C,10,H0,W0], stats from
+    prep_cycle_stats, bmode fp64 [C,Hq,Wq,F] (bModeNorm with the cycle axis first), label / gate from prep_label."""
+    _prep_check(frames, "frames", torch.float64, 4)
+    _prep_check(stats, "stats", torch.float64, 2)
+    _prep_check(bmode, "bmode", torch.float64, 4)
+    _prep_check(label, "label", torch.float32, 2)
+    _prep_check(gate, "gate", torch.uint8, 2)
+    Cc, _, H0, W0 = frames.shape
+    if tuple(stats.shape) != (Cc * 10, 2) or bmode.shape[0] != Cc or tuple(label.shape) != (PREP_H, PREP_W) or label.shape != gate.shape:
+        raise ValueError("prep_assemble: stats, bmode, label and gate do not match the frames")
+    out = torch.empty((Cc, 1, PREP_H, PREP_W, 12), dtype=torch.float64, device=frames.device)
+    L.check(L.load().usseg_prep_assemble(frames.data_ptr(), stats.data_ptr(), Cc, H0, W0, bmode.data_ptr(), bmode.shape[1], bmode.shape[2],
+                                         bmode.shape[3], label.data_ptr(), gate.data_ptr(), objective, out.data_ptr(), _stream()), "prep_assemble")
+    return out
