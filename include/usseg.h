@@ -774,6 +774,26 @@ int usseg_prep_label(const double* brain, int32_t Hb, int32_t Wb, const double* 
 int usseg_prep_assemble(const double* frames, const double* stats, int32_t C, int32_t H0, int32_t W0, const double* bmode, int32_t Hq,
                         int32_t Wq, int32_t F, const float* label, const uint8_t* gate, int32_t objective, double* out, usseg_stream_t stream);
 
+/* ---- the evaluator's cone figures (cone.hip; TBIEvaluator.Display, TBIEvaluator.py:276-355 of the reference) ---------------------------
+ * pcolormesh(X, Y, C[:-1, :-1], shading='flat') scan-converted at px_per_unit pixels per axis unit, then colour-mapped; DESIGN.md
+ * section 4i.  All arithmetic fp64 without fused multiply-adds; every result is order-independent: bitwise reproducible.
+ * usseg_cone_index: X, Y fp64 [H][W] (H, W >= 2); quad q = i*(W-1) + j has the vertices (i,j), (i,j+1), (i+1,j+1), (i+1,j).  Pixel
+ * (r, c) of index int32 [Hp][Wp] samples (xmin + (c+0.5)/ppu, ymin + (r+0.5)/ppu) and holds the largest q whose nonzero winding number
+ * there is not 0 (half-open crossing rule), or -1.  Hp*Wp*4 bytes must fit int32.  Non-finite quads cover nothing. */
+int usseg_cone_index(const double* X, const double* Y, int32_t H, int32_t W, double xmin, double ymin, double ppu, int32_t Hp, int32_t Wp,
+                     int32_t* index, usseg_stream_t stream);
+/* bmode fp64 [B][HW] -> range fp64 [B][2]: np.histogram(bmode[b], bins=25)[1][[2, -2]] (first + k*((last-first)/25), first/last = min/max
+ * widened by 0.5 when equal); nonfinite int32 [B]: bit 0 where the image holds a NaN or an infinity, bit 1 where the 26 edges do not
+ * strictly increase (np.histogram raises on both). */
+int usseg_cone_range(const double* bmode, int32_t B, int32_t HW, double* range, int32_t* nonfinite, usseg_stream_t stream);
+/* out uint8 [B][2*Hp+gap][2*Wp+gap][3], white background: panel 0 (top left) prob_map fp32, 1 label fp64, 2 bleed fp32 (all [B][H][W],
+ * LUT 0, ranges[2p], ranges[2p+1] (a HOST array fp64 [3][2])), 3 (bottom right) bmode fp64 [B][H][W], LUT 1, bmode_range [B][2] on the
+ * device (usseg_cone_range's output).  luts: uint8 [2][256][3] on the device.  The pixel of quad (i, j) shows the value at (i, j);
+ * k = clamp(floor((v - vmin)/(vmax - vmin) * 256), 0, 255), 0 when vmax == vmin; a NaN or infinite value is white. */
+int usseg_cone_render(const int32_t* index, int32_t Hp, int32_t Wp, int32_t gap, const float* prob_map, const double* label, const float* bleed,
+                      const double* bmode, int32_t B, int32_t H, int32_t W, const double* ranges, const double* bmode_range, const uint8_t* luts,
+                      uint8_t* out, usseg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,125 @@
+"""Timing of the evaluator's cone figures (TBIEvaluator.ConeGeometry / render_figures / Display) on the synthetic 256x80 fan
+(r = 5..150, theta = +-0.7 rad, integer axes: 290 x 386 panels at 2 px per unit) (diagnostic).
+
+    python tools/time_cone.py                    # the table below, one JSON line
+    python tools/time_cone.py --trace            # a few index builds and render batches, for a kernel trace:
+                                                 # rocprofv3 --kernel-trace --stats -- python tools/time_cone.py --trace
+
+    index_ms           ConeGeometry's index build (memset + usseg_cone_index), host clock around a synchronised launch
+    render_us          one 16-image batch on the device: usseg_cone_range + usseg_cone_render, device events, inputs resident
+    render_GBps        the batch's figure bytes (16 x 596 x 788 x 3 = 22.5 MB written) plus the planes read, over render_us
+    figures_per_s      Display end to end: upload, render, download and PNG compression in the thread pool, files on local disk
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+H, W = 256, 80
+
+
+def fan():
+    r = np.linspace(5.0, 150.0, H)[:, None]
+    th = np.linspace(-0.7, 0.7, W)[None, :]
+    return r * np.sin(th) + 100, r * np.cos(th) - 4
+
+
+def result(N, seed=0):
+    from ultrasound_modeling_amd.TBIEvaluator import PolarResult
+    rng = np.random.default_rng(seed)
+    return PolarResult(rng.uniform(0, 2, (N, H, W)).astype(np.float32), rng.uniform(0, 1, (N, H, W)).astype(np.float32), None,
+                       rng.integers(0, 3, (N, H, W)).astype(np.float64), -np.abs(rng.standard_normal((N, H, W))) * 30,
+                       np.array([f"img{i}" for i in range(N)]))
+
+
+def table(args):
+    from ultrasound_modeling_amd import ops
+    from ultrasound_modeling_amd.TBIEvaluator import PANEL_RANGES, ConeGeometry, Display
+    X, Y = fan()
+    out = {"grid": [H, W], "px_per_unit": args.ppu}
+    geo = ConeGeometry(X, Y, px_per_unit=args.ppu)
+    torch.cuda.synchronize()
+    t = []
+    for _ in range(args.repeats):
+        t0 = time.perf_counter()
+        geo = ConeGeometry(X, Y, px_per_unit=args.ppu)
+        torch.cuda.synchronize()
+        t.append((time.perf_counter() - t0) * 1e3)
+    out["panel"] = list(geo.panel)
+    out["figure"] = list(geo.figure_shape)
+    out["index_ms"] = statistics.median(t)
+
+    B = 16
+    res = result(B)
+    dev = [torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in (res.prob_map, res.label, res.bleed_prob, res.bmode)]
+    luts = geo.luts()
+
+    def batch():
+        rg, _ = ops.cone_range(dev[3])
+        return ops.cone_render(geo.index, dev[0], dev[1], dev[2], dev[3], PANEL_RANGES, rg, luts, geo.gap)
+    for _ in range(5):
+        batch()
+    torch.cuda.synchronize()
+    per = []
+    for _ in range(args.repeats):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(args.calls):
+            batch()
+        e1.record()
+        e1.synchronize()
+        per.append(e0.elapsed_time(e1) * 1e3 / args.calls)
+    out["render_us"] = statistics.median(per)
+    out["render_us_min_max"] = [min(per), max(per)]
+    written = B * int(np.prod(geo.figure_shape))
+    read = sum(d.numel() * d.element_size() for d in dev) + geo.index.numel() * 4
+    out["render_bytes"] = [written, read]
+    out["render_GBps"] = (written + read) / (out["render_us"] * 1e-6) / 1e9
+
+    N = args.figures
+    res = result(N, seed=1)
+    with tempfile.TemporaryDirectory() as d:
+        Display(result(B, seed=2), geo, d, stamp=False)            # warm-up: colormap tables, thread pool, first PNGs
+        rates = []
+        for k in range(args.e2e_repeats):
+            t0 = time.perf_counter()
+            paths = Display(res, geo, os.path.join(d, str(k)), stamp=False)
+            rates.append(N / (time.perf_counter() - t0))
+        out["png_bytes_per_figure"] = int(np.mean([os.path.getsize(p) for p in paths]))
+    out["figures"] = N
+    out["figures_per_s"] = statistics.median(rates)
+    out["figures_per_s_min_max"] = [min(rates), max(rates)]
+    print(f"index {out['index_ms']:.3f} ms; render {out['render_us']:.1f} us per 16-image batch ({out['render_GBps']:.0f} GB/s); "
+          f"Display {out['figures_per_s']:.1f} figures/s ({N} figures, {out['png_bytes_per_figure']} B per PNG)", flush=True)
+    print(json.dumps(out), flush=True)
+
+
+def trace(args):
+    from ultrasound_modeling_amd.TBIEvaluator import ConeGeometry, render_figures
+    X, Y = fan()
+    res = result(32)
+    for _ in range(3):
+        geo = ConeGeometry(X, Y, px_per_unit=args.ppu)
+        render_figures(res, geo, batch_size=16)
+    torch.cuda.synchronize()
+    print("trace: 3 x (index build + 2 render batches of 16)", flush=True)
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--ppu", type=float, default=2.0)
+    ap.add_argument("--calls", type=int, default=50)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--figures", type=int, default=256)
+    ap.add_argument("--e2e-repeats", type=int, default=3)
+    ap.add_argument("--trace", action="store_true")
+    a = ap.parse_args()
+    trace(a) if a.trace else table(a)

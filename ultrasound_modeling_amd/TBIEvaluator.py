@@ -9,11 +9,35 @@
 ``Cascade`` runs it on the device for a batch: one input cast serves both models, the gate and the maps are one launch each
 (csrc/cascade.hip), nothing returns to the host in between, and ``capture_predict_graph`` (``step.PredictDriver``) records the whole
 cascade as ONE HIP graph.  ``Polar_Model`` is the batched form of the reference's ``Polar_Model(sAll=True)``, which starts one OS process
-per image and reloads both models in each.  The plotting (``Display``) stays out: this module draws nothing, writes no file, and reads
-no file when imported.
+per image and reloads both models in each.
+
+The figures (``Display``, :254-372 with the ``dispDict`` state the reference runs in): a 2x2 figure per image of four ``pcolormesh``
+panels on the scan geometry of ``axis/xAxis.npy`` / ``axis/yAxis.npy`` (cast with ``astype(int)``, :19-24) - Prediction (``prob_map``,
+magma, 0..2), the label (magma, 0..2), Probability Bleed (``bleed_prob``, magma, 0..1) and bMode (``binary``, from
+``np.histogram(bMode, bins=25)`` edge 2 to edge -2).  ``ConeGeometry`` scan-converts the quads once (csrc/cone.hip: the largest
+row-major quad whose nonzero winding number at the pixel centre is not 0, the values ``C[:-1, :-1]`` that matplotlib < 3.5 drew,
+y down); ``render_figures`` colour-maps all four panels of a batch in one launch after one range launch; ``Display`` writes the PNGs
+(a stdlib writer, compressed in a thread pool).  ``python -m ultrasound_modeling_amd.TBIEvaluator`` is the reference's module-level run.
+Deliberate deviations from the reference's pictures:
+  - no titles, axes, ticks or fonts; the panels sit on white, ``gap`` pixels apart;
+  - the panel size is set by ``px_per_unit`` (pixels per axis unit), not by matplotlib's figure layout;
+  - a pixel shows the quad that covers its centre, where Agg's non-antialiased fill decides by its own coverage rule (the two agree
+    within one pixel: tests/test_cpu_cone.py), and the colours are matplotlib's ``bytes=True`` tables, which truncate where Agg rounds
+    (a channel can be one lower);
+  - a bMode image that holds a NaN or an infinity, or spans a range too small for 25 bins, raises ``ValueError``, as
+    ``np.histogram`` does; NaN / infinite values of the other panels are left white (pcolormesh masks them);
+  - files are overwritten, the folder is created with its parents, and ``stamp=False`` drops the ``%f`` suffix.
+Importing this module draws nothing, writes no file and reads no file; matplotlib is imported only for its colormap tables.
 """
 from __future__ import annotations
 
+import argparse
+import binascii
+import datetime
+import os
+import struct
+import zlib
+from concurrent.futures import ThreadPoolExecutor
 from typing import NamedTuple, Optional
 
 import numpy as np
@@ -163,3 +187,191 @@ def Polar_Model(data, cascade: Cascade, names=None, batch_size=16):
         if mask is not None:
             mask[lo:lo + n] = out.mask[:n].cpu().numpy()
     return PolarResult(prob_map, bleed_prob, mask, label, bmode, None if names is None else np.asarray(names))
+
+
+# ---------------------------------------------------------------------------------------------------------- the figures
+PANEL_RANGES = ((0.0, 2.0), (0.0, 2.0), (0.0, 1.0))     # Prediction, label, Probability Bleed (:297, :304, :333); bMode per image
+GAP = 16                                                # white pixels between the panels
+
+
+def colormap_tables():
+    """uint8 [2,256,3]: matplotlib's magma and binary tables (``Colormap(range(256), bytes=True)``), read at run time."""
+    try:
+        import matplotlib
+    except ImportError as e:
+        raise RuntimeError("the evaluator's figures need matplotlib for the magma / binary colormap tables; it is not installed") from e
+    return np.stack([np.asarray(matplotlib.colormaps[n](range(256), bytes=True))[:, :3] for n in ("magma", "binary")]).astype(np.uint8)
+
+
+class ConeGeometry:
+    """The scan geometry of the figures: vertex grids ``xAxis``, ``yAxis`` [H,W] (the reference casts them with ``astype(int)``,
+    :23-24; ``int_axes=False`` keeps them as they are) and ``px_per_unit`` pixels per axis unit.  Builds the panel's index image on
+    ``device`` once (one ``usseg_cone_index`` launch): int32 [Hp,Wp], the quad each pixel shows or -1, with
+    Hp = ceil((ymax-ymin)*px_per_unit), Wp = ceil((xmax-xmin)*px_per_unit), row 0 at ymin (the inverted y axis, :300)."""
+
+    def __init__(self, xAxis, yAxis, px_per_unit=2, int_axes=True, device="cuda", gap=GAP):
+        X, Y = np.asarray(xAxis), np.asarray(yAxis)
+        if X.shape != Y.shape or X.ndim != 2 or min(X.shape) < 2:
+            raise ValueError(f"xAxis {X.shape} and yAxis {Y.shape} must be one [H,W] vertex grid with H, W >= 2")
+        if not (np.issubdtype(X.dtype, np.number) and np.issubdtype(Y.dtype, np.number)) or not (np.isfinite(X).all() and np.isfinite(Y).all()):
+            raise ValueError("xAxis and yAxis must hold finite numbers")
+        if int_axes:
+            X, Y = X.astype(int), Y.astype(int)
+        X, Y = np.ascontiguousarray(X, np.float64), np.ascontiguousarray(Y, np.float64)
+        ppu = float(px_per_unit)
+        if not (np.isfinite(ppu) and ppu > 0):
+            raise ValueError(f"px_per_unit must be a positive number, got {px_per_unit!r}")
+        gap = int(gap)
+        if gap < 0:
+            raise ValueError(f"gap must be >= 0, got {gap}")
+        self.xmin, self.ymin = float(X.min()), float(Y.min())
+        Hp, Wp = int(np.ceil((Y.max() - self.ymin) * ppu)), int(np.ceil((X.max() - self.xmin) * ppu))
+        if Hp < 1 or Wp < 1:
+            raise ValueError(f"the grid spans no area at px_per_unit {ppu} (panel {Hp} x {Wp})")
+        if Hp * Wp * 4 > ops._INT32_MAX or (2 * Hp + gap) * (2 * Wp + gap) * 3 > ops._INT32_MAX:
+            raise ValueError(f"a {Hp} x {Wp} panel at px_per_unit {ppu} overflows int32 byte offsets")
+        self.X, self.Y, self.px_per_unit, self.gap = X, Y, ppu, gap
+        self.grid = X.shape
+        self.panel = (Hp, Wp)
+        self.figure_shape = (2 * Hp + gap, 2 * Wp + gap, 3)
+        self.device = torch.device(device)
+        self.index = ops.cone_index(torch.from_numpy(X).to(self.device), torch.from_numpy(Y).to(self.device), self.xmin, self.ymin, ppu,
+                                    Hp, Wp)
+        self._luts = None
+
+    @classmethod
+    def from_dir(cls, axis_dir, **kw):
+        """Read ``xAxis.npy`` and ``yAxis.npy`` (``DataFilePlayGround.FetchPolarAxis``'s output) from ``axis_dir``."""
+        return cls(np.load(os.path.join(axis_dir, "xAxis.npy")), np.load(os.path.join(axis_dir, "yAxis.npy")), **kw)
+
+    def luts(self):
+        if self._luts is None:
+            self._luts = torch.from_numpy(colormap_tables()).to(self.device)
+        return self._luts
+
+
+def _check_result(result, geometry, batch_size):
+    if int(batch_size) != batch_size or batch_size < 1:
+        raise ValueError(f"batch_size must be a positive integer, got {batch_size!r}")
+    planes = (result.prob_map, result.label, result.bleed_prob, result.bmode)
+    shapes = {np.shape(p) for p in planes}
+    if len(shapes) != 1 or len(next(iter(shapes))) != 3:
+        raise ValueError(f"prob_map, label, bleed_prob and bmode must be one [N,H,W] shape, got {[np.shape(p) for p in planes]}")
+    H, W = next(iter(shapes))[1:]
+    if (H, W) != tuple(geometry.grid):
+        raise ValueError(f"the maps are {H} x {W} but the geometry's vertex grid is {tuple(geometry.grid)}")
+
+
+def _render_batches(result: PolarResult, geometry: ConeGeometry, batch_size):
+    """-> iterator of (first index, valid images, uint8 [valid, *figure_shape] on the host): per batch one upload of the four planes,
+    one ``usseg_cone_range`` and one ``usseg_cone_render`` launch; the short last batch is padded as ``batches`` pads."""
+    _check_result(result, geometry, batch_size)
+    dev = geometry.device
+    luts = geometry.luts()
+    planes = [np.asarray(result.prob_map, np.float32), np.asarray(result.label, np.float64), np.asarray(result.bleed_prob, np.float32),
+              np.asarray(result.bmode, np.float64)]
+    split = [batches(p, batch_size) for p in planes]
+    for parts in zip(*split):
+        lo, n = parts[0][0], parts[0][1]
+        pm, lab, bp, bm = (torch.from_numpy(p[2]).to(dev) for p in parts)
+        rng, bad = ops.cone_range(bm)
+        out = ops.cone_render(geometry.index, pm, lab, bp, bm, PANEL_RANGES, rng, luts, geometry.gap)
+        bad = bad[:n].cpu().numpy()
+        if bad.any():
+            k = int(np.nonzero(bad)[0][0])
+            name = "" if result.names is None else f" ({result.names[lo + k]})"
+            why = "holds NaN or infinite values" if bad[k] & 1 else "spans too small a range for 25 finite-sized bins"
+            raise ValueError(f"the bMode plane of image {lo + k}{name} {why}: np.histogram cannot take its range")
+        yield lo, n, out[:n].cpu().numpy()
+
+
+def render_figures(result: PolarResult, geometry: ConeGeometry, batch_size=16):
+    """Every image's figure: uint8 [N, 2*Hp+gap, 2*Wp+gap, 3] (NumPy), panels Prediction | label over Probability Bleed | bMode."""
+    N = np.shape(result.prob_map)[0]
+    figs = np.empty((N,) + geometry.figure_shape, np.uint8)
+    for lo, n, f in _render_batches(result, geometry, batch_size):
+        figs[lo:lo + n] = f
+    return figs
+
+
+def write_png(path, rgb, level=6):
+    """uint8 [H,W,3] -> an 8-bit RGB PNG (filter 0 on every row, one zlib stream)."""
+    rgb = np.asarray(rgb)
+    if rgb.dtype != np.uint8 or rgb.ndim != 3 or rgb.shape[2] != 3 or min(rgb.shape[:2]) < 1:
+        raise ValueError(f"write_png takes uint8 [H,W,3], got {rgb.dtype} {rgb.shape}")
+    H, W = rgb.shape[:2]
+    raw = np.empty((H, 1 + 3 * W), np.uint8)
+    raw[:, 0] = 0
+    raw[:, 1:] = rgb.reshape(H, 3 * W)
+
+    def chunk(kind, data):
+        return struct.pack(">I", len(data)) + kind + data + struct.pack(">I", binascii.crc32(kind + data) & 0xFFFFFFFF)
+
+    png = (b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", W, H, 8, 2, 0, 0, 0)) +
+           chunk(b"IDAT", zlib.compress(raw.tobytes(), level)) + chunk(b"IEND", b""))
+    with open(path, "wb") as f:
+        f.write(png)
+
+
+def _names(result):
+    N = np.shape(result.prob_map)[0]
+    names = [str(i) for i in range(N)] if result.names is None else [str(n) for n in result.names]
+    if len(names) != N:
+        raise ValueError(f"{len(names)} names for {N} images")
+    for n in names:
+        if "/" in n or "\0" in n:
+            raise ValueError(f"image name {n!r} holds a '/' (or a NUL): it would not name a file in the output folder")
+    return names
+
+
+def Display(result: PolarResult, geometry: ConeGeometry, savePath, stamp=True, batch_size=16, workers=16):
+    """Write every image's figure to ``savePath/<%m%d-%H>/<str(name)><%f>.png`` (:346-351; ``str`` of the name as the reference
+    executes it, the brackets of a row of an [N,1] paths array included; the image index when ``result.names`` is None).
+    ``stamp=False`` drops the ``%f`` suffix.  Rendering runs on the device one batch ahead of the PNG compression, which a pool of at
+    most 16 threads does.  -> the list of paths written, in image order."""
+    names = _names(result)
+    _check_result(result, geometry, batch_size)
+    workers = max(1, min(16, int(workers), os.cpu_count() or 1))
+    paths = [None] * len(names)
+    with ThreadPoolExecutor(max_workers=workers) as pool:
+        jobs = []
+        for lo, n, figs in _render_batches(result, geometry, batch_size):
+            for k in range(n):
+                now = datetime.datetime.now()
+                folder = os.path.join(savePath, now.strftime("%m%d-%H"))
+                os.makedirs(folder, exist_ok=True)
+                paths[lo + k] = os.path.join(folder, names[lo + k] + (now.strftime("%f") if stamp else "") + ".png")
+                jobs.append(pool.submit(write_png, paths[lo + k], figs[k]))
+        for j in jobs:
+            j.result()
+    return paths
+
+
+def main(argv=None):
+    """The reference's module-level run (:375, ``Polar_Model(sAll=True)``): the test set through the cascade, then one figure per image."""
+    ap = argparse.ArgumentParser(description="Test images -> the evaluator's maps and one four-panel cone figure (PNG) per image.")
+    ap.add_argument("data", help="test data .npy [N, d1, d2, d3, 12] (DataFilePlayGround's output)")
+    ap.add_argument("paths", help="the image names .npy (one per test image)")
+    ap.add_argument("axis_dir", help="folder holding xAxis.npy and yAxis.npy")
+    ap.add_argument("out", help="output folder: <out>/<%%m%%d-%%H>/<name><%%f>.png")
+    ap.add_argument("--bleed", required=True, help="bleed model checkpoint (3 classes)")
+    ap.add_argument("--mask", default=None, help="brain-mask model checkpoint (2 classes): the use_brainMask=True cascade")
+    ap.add_argument("--batch", type=int, default=16, help="images per graph replay and per render launch")
+    ap.add_argument("--px-per-unit", type=float, default=2.0, help="panel pixels per axis unit")
+    ap.add_argument("--no-stamp", action="store_true", help="name files <name>.png, without the %%f suffix")
+    ap.add_argument("--transunet", action="store_true", help="the checkpoints are TBI_TransUNet models")
+    ap.add_argument("--use-vit", action="store_true", help="the checkpoints have the ViT bottleneck")
+    a = ap.parse_args(argv)
+    if a.batch < 1:
+        ap.error("--batch must be >= 1")
+    data = np.load(a.data)
+    names = np.load(a.paths)
+    cascade = Cascade.from_checkpoints(a.bleed, a.mask, batch_size=a.batch, use_vit=a.use_vit, transunet=a.transunet)
+    geometry = ConeGeometry.from_dir(a.axis_dir, px_per_unit=a.px_per_unit, device=cascade.device)
+    result = Polar_Model(data, cascade, names=names, batch_size=a.batch)
+    paths = Display(result, geometry, a.out, stamp=not a.no_stamp, batch_size=a.batch)
+    print(f"wrote {len(paths)} figures under {a.out}")
+
+
+if __name__ == "__main__":
+    main()

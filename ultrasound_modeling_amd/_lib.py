@@ -233,6 +233,10 @@ _PROTOS = {
     "usseg_prep_cycle_stats": (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "usseg_prep_label": (C.c_int, [c_vp, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "usseg_prep_assemble": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp]),
+    "usseg_cone_index": (C.c_int, [c_vp, c_vp, c_i32, c_i32, C.c_double, C.c_double, C.c_double, c_i32, c_i32, c_vp, c_vp]),
+    "usseg_cone_range": (C.c_int, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "usseg_cone_render": (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, P(C.c_double), c_vp, c_vp, c_vp,
+                                    c_vp]),
 }
 EXPORTED_SYMBOLS = tuple(_PROTOS)
 

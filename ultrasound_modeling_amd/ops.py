@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import math
 import os
 from typing import Optional, Tuple
 
@@ -1281,4 +1282,70 @@ def prep_assemble(frames, stats, bmode, label, gate, objective):
     out = torch.empty((Cc, 1, PREP_H, PREP_W, 12), dtype=torch.float64, device=frames.device)
     L.check(L.load().usseg_prep_assemble(frames.data_ptr(), stats.data_ptr(), Cc, H0, W0, bmode.data_ptr(), bmode.shape[1], bmode.shape[2],
                                          bmode.shape[3], label.data_ptr(), gate.data_ptr(), objective, out.data_ptr(), _stream()), "prep_assemble")
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ the evaluator's cone figures (cone.hip)
+_INT32_MAX = 2**31 - 1
+
+
+def cone_index(X, Y, xmin, ymin, px_per_unit, Hp, Wp):
+    """Which quad of the vertex grid X, Y (fp64 [H,W]) each pixel of a [Hp,Wp] panel shows: -> int32 [Hp,Wp], -1 for background.
+    Pixel (r, c) samples (xmin + (c+0.5)/px_per_unit, ymin + (r+0.5)/px_per_unit) (include/usseg.h, usseg_cone_index)."""
+    _prep_check(X, "X", torch.float64, 2)
+    _prep_check(Y, "Y", torch.float64, 2)
+    if X.shape != Y.shape or X.device != Y.device or min(X.shape) < 2:
+        raise ValueError(f"X {tuple(X.shape)} and Y {tuple(Y.shape)} must be one [H,W] grid (H, W >= 2) on one device")
+    if X.numel() * 8 > _INT32_MAX or not (1 <= Hp and 1 <= Wp and Hp * Wp * 4 <= _INT32_MAX):
+        raise ValueError(f"grid {tuple(X.shape)} / panel {Hp}x{Wp}: empty, or byte offsets overflow int32")
+    if not (math.isfinite(px_per_unit) and px_per_unit > 0 and math.isfinite(xmin) and math.isfinite(ymin)):
+        raise ValueError(f"bad origin ({xmin}, {ymin}) or px_per_unit {px_per_unit}")
+    index = torch.empty((Hp, Wp), dtype=torch.int32, device=X.device)
+    L.check(L.load().usseg_cone_index(X.data_ptr(), Y.data_ptr(), X.shape[0], X.shape[1], float(xmin), float(ymin), float(px_per_unit), Hp, Wp,
+                                      index.data_ptr(), _stream()), "cone_index")
+    return index
+
+
+def cone_range(bmode):
+    """bmode fp64 [B,H,W] -> (range fp64 [B,2]: np.histogram(bmode[b], bins=25)[1][[2, -2]], nonfinite int32 [B]: nonzero where
+    np.histogram would raise - bit 0 a NaN or an infinity, bit 1 edges that do not strictly increase)."""
+    _prep_check(bmode, "bmode", torch.float64, 3)
+    B = bmode.shape[0]
+    if not (1 <= B <= 65535) or bmode[0].numel() < 1:
+        raise ValueError(f"bmode {tuple(bmode.shape)}: 1..65535 non-empty images")
+    rng = torch.empty((B, 2), dtype=torch.float64, device=bmode.device)
+    bad = torch.empty((B,), dtype=torch.int32, device=bmode.device)
+    L.check(L.load().usseg_cone_range(bmode.data_ptr(), B, bmode[0].numel(), rng.data_ptr(), bad.data_ptr(), _stream()), "cone_range")
+    return rng, bad
+
+
+def cone_render(index, prob_map, label, bleed_prob, bmode, ranges, bmode_range, luts, gap):
+    """The four panels of every image: -> uint8 [B, 2*Hp+gap, 2*Wp+gap, 3] (usseg_cone_render).  index int32 [Hp,Wp] from cone_index;
+    prob_map, bleed_prob fp32 and label, bmode fp64 [B,H,W]; ranges: three (vmin, vmax) pairs of panels 0..2 (host numbers);
+    bmode_range fp64 [B,2] from cone_range; luts uint8 [2,256,3] (panels 0-2, panel 3)."""
+    _prep_check(index, "index", torch.int32, 2)
+    for name, t, dt in (("prob_map", prob_map, torch.float32), ("label", label, torch.float64), ("bleed_prob", bleed_prob, torch.float32),
+                        ("bmode", bmode, torch.float64)):
+        _prep_check(t, name, dt, 3)
+        if t.shape != prob_map.shape:
+            raise ValueError(f"{name} {tuple(t.shape)} and prob_map {tuple(prob_map.shape)} differ in shape")
+    _prep_check(bmode_range, "bmode_range", torch.float64, 2)
+    _prep_check(luts, "luts", torch.uint8, 3)
+    B, H, W = prob_map.shape
+    Hp, Wp = index.shape
+    if tuple(bmode_range.shape) != (B, 2) or tuple(luts.shape) != (2, 256, 3):
+        raise ValueError(f"bmode_range {tuple(bmode_range.shape)} must be [{B},2] and luts {tuple(luts.shape)} [2,256,3]")
+    if len({t.device for t in (index, prob_map, label, bleed_prob, bmode, bmode_range, luts)}) != 1:
+        raise ValueError("cone_render: the tensors are on more than one device")
+    r = [float(v) for pair in ranges for v in pair]
+    if len(r) != 6:
+        raise ValueError(f"ranges must be three (vmin, vmax) pairs, got {ranges!r}")
+    gap = int(gap)
+    OH, OW = 2 * Hp + gap, 2 * Wp + gap
+    if gap < 0 or H < 2 or W < 2 or OH * OW * 3 > _INT32_MAX or H * W * 8 > _INT32_MAX:
+        raise ValueError(f"cone_render: bad gap {gap} or planes [{B},{H},{W}], or a {OH}x{OW} figure overflows int32 byte offsets")
+    out = torch.empty((B, OH, OW, 3), dtype=torch.uint8, device=index.device)
+    L.check(L.load().usseg_cone_render(index.data_ptr(), Hp, Wp, gap, prob_map.data_ptr(), label.data_ptr(), bleed_prob.data_ptr(),
+                                       bmode.data_ptr(), B, H, W, (C.c_double * 6)(*r), bmode_range.data_ptr(), luts.data_ptr(), out.data_ptr(),
+                                       _stream()), "cone_render")
     return out
