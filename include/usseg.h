@@ -768,6 +768,15 @@ int usseg_prep_cycle_stats(const double* frames, int32_t C, int32_t H0, int32_t 
  * GaussianBlur 3x3 sigma 2, the re-set, a fp32 resize and label = gate ? 0 : that.  ws: fp32 [2][Hm*Wm] (objective 1 only). */
 int usseg_prep_label(const double* brain, int32_t Hb, int32_t Wb, const double* blood, const double* normal, int32_t Hm, int32_t Wm,
                      int32_t objective, float* ws, float* label, uint8_t* gate, usseg_stream_t stream);
+/* The thick-mask label of PizzaPlayGround.py (:92-97) and DataPreprocessing.py (:134-146): label fp32 and gate uint8 at
+ * USSEG_PREP_H x USSEG_PREP_W from brain fp64 [Hb][Wb] and blood (bloodMaskThick) fp64 [Hm][Wm], no blur and no normal mask.  gate[p] = 1
+ * where the fp64-resized brain mask is exactly 0, as usseg_prep_label; label = gate ? 0 : v with
+ *   order 0 (PizzaPlayGround): each tap float(blood + 1.0), then the resize in float32 arithmetic (cv2's float32 path);
+ *   order 1 (DataPreprocessing, objective 1): the resize of blood with the weights applied in double, then v = float(that + 1.0).
+ * NaN in blood propagates through the taps it reaches (a NaN tap of weight 0 included).  One lane per output pixel, no workspace, one
+ * launch.  Errors: a null pointer, Hb, Wb, Hm or Wm < 1, order other than 0 or 1. */
+int usseg_prep_label_thick(const double* brain, int32_t Hb, int32_t Wb, const double* blood, int32_t Hm, int32_t Wm, int32_t order,
+                           float* label, uint8_t* gate, usseg_stream_t stream);
 /* out fp64 [C][USSEG_PREP_H][USSEG_PREP_W][12], the reference's image per cycle (:393): 0 the label; 1..10 plane c*10+k resized, each
  * bilinear tap normalised with stats before the blend and 0 where gate is set for objective 1 (:384-388); 11 the resized map
  * mean_f log10(bmode[c][.][.][f]), never gated (:327, :351, :381).  bmode: fp64 [C][Hq][Wq][F], cycle c = bModeNorm[:, :, :, c]. */

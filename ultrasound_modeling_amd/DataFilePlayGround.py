@@ -68,35 +68,61 @@ def patient_plan(iteration: int, rawDataPath: str) -> List[Tuple[str, int, bool]
     return plan
 
 
-def _load(path: str):
-    """Read and check one file; -> host float64 (frames [C,10,H0,W0], bmode [C,Hq,Wq,F], brain, blood, normal)."""
-    from scipy.io import loadmat
-    mat = loadmat(path)
-    missing = [k for k in FIELDS if k not in mat]
+def _require(path: str, mat, fields) -> None:
+    missing = [k for k in fields if k not in mat]
     if missing:
         raise ValueError(f"{path}: missing {', '.join(missing)}")
+
+
+def _check(path: str, mat, masks):
+    """The shape checks of a loaded file; -> float64 (displacement, hrTimes, bModeNorm, [the fields named by masks])."""
     f64 = lambda k: np.asarray(mat[k]).astype(np.float64)
     disp, hr, bmode = f64("displacement"), f64("hrTimes"), f64("bModeNorm")
-    brain, blood, normal = f64("brainMask"), f64("bloodMask"), f64("normalMask")
+    ms = [f64(k) for k in masks]
     if disp.ndim != 3:
         raise ValueError(f"{path}: displacement must be [H, W, T], is {disp.shape}")
     if hr.ndim != 2 or hr.shape[0] < 1 or hr.shape[1] < 1:
         raise ValueError(f"{path}: hrTimes must be [1, cycles + 1], is {hr.shape}")
-    C, T = hr.shape[1] - 1, disp.shape[2]
+    C = hr.shape[1] - 1
     if bmode.ndim != 4 or bmode.shape[3] < C or 0 in bmode.shape[:3]:
         raise ValueError(f"{path}: bModeNorm must be [H, W, F, >= {C}], is {bmode.shape}")
-    for k, m in (("brainMask", brain), ("bloodMask", blood), ("normalMask", normal)):
+    for k, m in zip(masks, ms):
         if m.ndim != 2 or 0 in m.shape:
             raise ValueError(f"{path}: {k} must be a non-empty 2-D array, is {m.shape}")
-    if blood.shape != normal.shape:
-        raise ValueError(f"{path}: bloodMask {blood.shape} and normalMask {normal.shape} differ in shape")
+    return disp, hr, bmode, ms
+
+
+def _gather(path: str, disp, hr, bmode):
+    """-> host float64 (frames [C,10,H0,W0], bmode [C,Hq,Wq,F]): the 10 frames each cycle's window takes (:316) and its B-mode slice."""
+    C, T = hr.shape[1] - 1, disp.shape[2]
     frames = np.empty((C, 10) + disp.shape[:2], np.float64)
     for h in range(C):
         start = int(math.ceil(30 * hr[0, h]))          # :316
         if start < 0 or start + 10 > T:
             raise ValueError(f"{path}: cycle {h} takes frames {start}..{start + 9}, the file has {T}")
         frames[h] = np.moveaxis(disp[:, :, start:start + 10], 2, 0)
-    return frames, np.ascontiguousarray(np.moveaxis(bmode[:, :, :, :C], 3, 0)), brain, blood, normal
+    return frames, np.ascontiguousarray(np.moveaxis(bmode[:, :, :, :C], 3, 0))
+
+
+def _load(path: str):
+    """Read and check one file; -> host float64 (frames [C,10,H0,W0], bmode [C,Hq,Wq,F], brain, blood, normal)."""
+    from scipy.io import loadmat
+    mat = loadmat(path)
+    _require(path, mat, FIELDS)
+    disp, hr, bmode, (brain, blood, normal) = _check(path, mat, ("brainMask", "bloodMask", "normalMask"))
+    if blood.shape != normal.shape:
+        raise ValueError(f"{path}: bloodMask {blood.shape} and normalMask {normal.shape} differ in shape")
+    return _gather(path, disp, hr, bmode) + (brain, blood, normal)
+
+
+def _upload(parts, device):
+    """One host-to-device copy of the host float64 arrays ``parts``; -> a device view of each."""
+    dev = torch.from_numpy(np.concatenate([p.ravel() for p in parts])).to(device)
+    views, off = [], 0
+    for p in parts:
+        views.append(dev[off:off + p.size].view(p.shape))
+        off += p.size
+    return views
 
 
 def process_file(path: str, objective: int, device="cuda") -> Tuple[torch.Tensor, str]:
@@ -111,11 +137,7 @@ def process_file(path: str, objective: int, device="cuda") -> Tuple[torch.Tensor
     if C == 0:
         return torch.empty((0, 1, OUT_H, OUT_W, 12), dtype=torch.float64, device=device), name
     parts = [frames, bmode, brain] + ([blood, normal] if objective == 1 else [])
-    dev = torch.from_numpy(np.concatenate([p.ravel() for p in parts])).to(device)         # the one host-to-device copy
-    views, off = [], 0
-    for p in parts:
-        views.append(dev[off:off + p.size].view(p.shape))
-        off += p.size
+    views = _upload(parts, device)                                                         # the one host-to-device copy
     frames_d, bmode_d, brain_d = views[:3]
     stats = ops.prep_cycle_stats(frames_d)
     label, gate = ops.prep_label(brain_d, objective, *views[3:])

@@ -232,6 +232,7 @@ _PROTOS = {
     "usseg_prof_disable": (C.c_int, []),
     "usseg_prep_cycle_stats": (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "usseg_prep_label": (C.c_int, [c_vp, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "usseg_prep_label_thick": (C.c_int, [c_vp, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "usseg_prep_assemble": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp]),
     "usseg_cone_index": (C.c_int, [c_vp, c_vp, c_i32, c_i32, C.c_double, C.c_double, C.c_double, c_i32, c_i32, c_vp, c_vp]),
     "usseg_cone_range": (C.c_int, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]),

@@ -141,6 +141,17 @@ __global__ __launch_bounds__(256) void prep_blur_kernel(const float* __restrict_
   }
 }
 
+// The fp64 INTER_LINEAR resize of an fp64 [H][W] mask at output pixel (y, x) of 256x80: weights applied in double.
+__device__ __forceinline__ double resize_f64_at(const double* __restrict__ m, int H, int W, int y, int x) {
+#pragma clang fp contract(off)
+  const Taps ty = lin_taps(y, kOH, H), tx = lin_taps(x, kOW, W);
+  const double* r0 = m + (int64_t)ty.i0 * W;
+  const double* r1 = m + (int64_t)ty.i1 * W;
+  const double h0 = tx.two ? r0[tx.i0] * (double)tx.w0 + r0[tx.i1] * (double)tx.w1 : r0[tx.i0];
+  const double h1 = tx.two ? r1[tx.i0] * (double)tx.w0 + r1[tx.i1] * (double)tx.w1 : r1[tx.i0];
+  return h0 * (double)ty.w0 + h1 * (double)ty.w1;
+}
+
 // One lane per output pixel: the brain mask resized (fp64, :330) gives the gate (== 0); the label is 0 there, else 1 (objective 0,
 // :333) or the blurred fp32 label resized in fp32 (objective 1, :342-343).
 __global__ __launch_bounds__(256) void prep_label_kernel(const double* __restrict__ brain, int Hb, int Wb, const float* __restrict__ lab,
@@ -149,13 +160,7 @@ __global__ __launch_bounds__(256) void prep_label_kernel(const double* __restric
   const int total = kOH * kOW;
   for (int i = blockIdx.x * kThreads + threadIdx.x; i < total; i += gridDim.x * kThreads) {
     const int y = i / kOW, x = i - y * kOW;
-    const Taps ty = lin_taps(y, kOH, Hb), tx = lin_taps(x, kOW, Wb);
-    const double* r0 = brain + (int64_t)ty.i0 * Wb;
-    const double* r1 = brain + (int64_t)ty.i1 * Wb;
-    const double h0 = tx.two ? r0[tx.i0] * (double)tx.w0 + r0[tx.i1] * (double)tx.w1 : r0[tx.i0];
-    const double h1 = tx.two ? r1[tx.i0] * (double)tx.w0 + r1[tx.i1] * (double)tx.w1 : r1[tx.i0];
-    const double bm = h0 * (double)ty.w0 + h1 * (double)ty.w1;
-    const bool g = bm == 0.0;
+    const bool g = resize_f64_at(brain, Hb, Wb, y, x) == 0.0;
     float v = 1.f;
     if (lab) {
       const Taps sy = lin_taps(y, kOH, Hm), sx = lin_taps(x, kOW, Wm);
@@ -210,6 +215,44 @@ extern "C" int usseg_prep_label(const double* brain, int32_t Hb, int32_t Wb, con
   hipLaunchKernelGGL(prep_label_kernel, dim3(prep_grid(kOH * kOW)), dim3(kThreads), 0, s, brain, (int)Hb, (int)Wb, lab, (int)Hm, (int)Wm,
                      label, gate);
   return usseg_check_launch("prep_label");
+}
+
+// ---------------------------------------------------------------------------------------------------------------- the thick-mask label
+// The label of PizzaPlayGround (:92-97) and DataPreprocessing (:134-146), both from bloodMaskThick with no blur: one lane per output
+// pixel, each tap computed on the fly (no workspace).  Gate as prep_label_kernel; the label is 0 there, else
+//   order 0: float(blood + 1) per tap (the +1 in double), then the fp32 resize: cv2's float32 path on label.astype('float32');
+//   order 1: the fp64 resize of blood, then float(that + 1.0).
+__global__ __launch_bounds__(256) void prep_label_thick_kernel(const double* __restrict__ brain, int Hb, int Wb, const double* __restrict__ blood,
+                                                               int Hm, int Wm, int order, float* __restrict__ label, uint8_t* __restrict__ gate) {
+#pragma clang fp contract(off)
+  const int total = kOH * kOW;
+  for (int i = blockIdx.x * kThreads + threadIdx.x; i < total; i += gridDim.x * kThreads) {
+    const int y = i / kOW, x = i - y * kOW;
+    const bool g = resize_f64_at(brain, Hb, Wb, y, x) == 0.0;
+    float v;
+    if (order == 0) {
+      const Taps sy = lin_taps(y, kOH, Hm), sx = lin_taps(x, kOW, Wm);
+      auto tap = [&](int r, int c) { return (float)(blood[(int64_t)r * Wm + c] + 1.0); };
+      const float g0 = sx.two ? tap(sy.i0, sx.i0) * sx.w0 + tap(sy.i0, sx.i1) * sx.w1 : tap(sy.i0, sx.i0);
+      const float g1 = sx.two ? tap(sy.i1, sx.i0) * sx.w0 + tap(sy.i1, sx.i1) * sx.w1 : tap(sy.i1, sx.i0);
+      v = g0 * sy.w0 + g1 * sy.w1;
+    } else {
+      v = (float)(resize_f64_at(blood, Hm, Wm, y, x) + 1.0);
+    }
+    label[i] = g ? 0.f : v;
+    gate[i] = (uint8_t)g;
+  }
+}
+
+extern "C" int usseg_prep_label_thick(const double* brain, int32_t Hb, int32_t Wb, const double* blood, int32_t Hm, int32_t Wm, int32_t order,
+                                      float* label, uint8_t* gate, usseg_stream_t stream) {
+  USSEG_CHECK_ARG(brain && blood && label && gate, "prep_label_thick: null pointer");
+  USSEG_CHECK_ARG(Hb > 0 && Wb > 0, "prep_label_thick: bad brain-mask geometry (Hb, Wb > 0)");
+  USSEG_CHECK_ARG(Hm > 0 && Wm > 0, "prep_label_thick: bad blood-mask geometry (Hm, Wm > 0)");
+  USSEG_CHECK_ARG(order == 0 || order == 1, "prep_label_thick: order must be 0 or 1");
+  hipLaunchKernelGGL(prep_label_thick_kernel, dim3(prep_grid(kOH * kOW)), dim3(kThreads), 0, (hipStream_t)stream, brain, (int)Hb, (int)Wb,
+                     blood, (int)Hm, (int)Wm, (int)order, label, gate);
+  return usseg_check_launch("prep_label_thick");
 }
 
 // ---------------------------------------------------------------------------------------------------------------- assembly

@@ -1268,6 +1268,22 @@ def prep_label(brain, objective, blood=None, normal=None):
     return label, gate
 
 
+def prep_label_thick(brain, blood, order):
+    """The label fp32 [256,80] and the gate uint8 [256,80] from bloodMaskThick, no blur (PizzaPlayGround.py:92-97, order 0;
+    DataPreprocessing.py:134-146, order 1).  brain fp64 [Hb,Wb], blood fp64 [Hm,Wm]; the rules are in include/usseg.h."""
+    _prep_check(brain, "brain", torch.float64, 2)
+    _prep_check(blood, "blood", torch.float64, 2)
+    if order not in (0, 1):
+        raise ValueError(f"order must be 0 (PizzaPlayGround) or 1 (DataPreprocessing), got {order!r}")
+    if brain.device != blood.device:
+        raise ValueError("prep_label_thick: brain and blood are on different devices")
+    label = torch.empty((PREP_H, PREP_W), dtype=torch.float32, device=brain.device)
+    gate = torch.empty((PREP_H, PREP_W), dtype=torch.uint8, device=brain.device)
+    L.check(L.load().usseg_prep_label_thick(brain.data_ptr(), brain.shape[0], brain.shape[1], blood.data_ptr(), blood.shape[0], blood.shape[1],
+                                            int(order), label.data_ptr(), gate.data_ptr(), _stream()), "prep_label_thick")
+    return label, gate
+
+
 def prep_assemble(frames, stats, bmode, label, gate, objective):
     """The images of every cycle of one file: fp64 [C,1,256,80,12] (DataFilePlayGround.py:353-393).  frames fp64 [C,10,H0,W0], stats from
     prep_cycle_stats, bmode fp64 [C,Hq,Wq,F] (bModeNorm with the cycle axis first), label / gate from prep_label."""
