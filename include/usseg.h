@@ -13,9 +13,10 @@
  *    never synchronises and never throws.  Mutable host state is THREAD-LOCAL: the error string; the queue of
  *    deferred finishing reductions of every stream between usseg_defer_begin() and usseg_defer_end() (defer.hip);
  *    the opt-in launch timer of usseg_prof_* (runtime.hip) - so host threads that drive different streams do not
- *    share any of it (a stream's begin / launches / flush / end come from one thread).  The only process-wide state
- *    is immutable after first use: the USSEG_* planner switches, each read from the environment once (DESIGN.md
- *    section 4), and the per-kernel "dynamic LDS size set" latches;
+ *    share any of it (a stream's begin / launches / flush / end come from one thread).  Process-wide state: the USSEG_*
+ *    planner switches, each read from the environment once and immutable after first use; and the
+ *    dynamic-LDS opt-in table (runtime.hip), guarded by a mutex, which records per (device, kernel) the largest size
+ *    granted - a failed opt-in is returned by the call that needed it;
  *  - one producer per destination between two flushes is NOT required: deferred finishes that share a
  *    destination are issued as separate, stream-ordered launches (defer.hip);
  *  - all work is enqueued on the hipStream_t passed in (graph-capture safe);

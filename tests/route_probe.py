@@ -13,7 +13,11 @@ kink rule that test_gpu_norm_routes.py states once in its docstring.
 
 attn_ref / window_ref / ln_wide_ref restate the attention kernels and the wide LayerNorm in fp64 with the magnitudes and the
 score-error terms that test_gpu_attn_routes.py states once in its docstring; acheck bounds an output on the device.
+
+small_deferral(floats, first_producer=True) defers the finishing reductions of the current stream into a partial-row region of only
+`floats` floats, so that a test can place a launch's regions against the end of a full region.
 """
+import contextlib
 import math
 
 import pytest
@@ -72,6 +76,28 @@ def kernels(fn):
     if not names:
         pytest.fail("the profiler recorded no device kernel for this call: the route cannot be checked")
     return out, names
+
+
+@contextlib.contextmanager
+def small_deferral(floats, first_producer=True):
+    """A deferral context (usseg_defer_begin) on the current stream with a partial-row region of `floats` floats and no slab region;
+    with `first_producer`, a one-workgroup LayerNorm backward (64 pixels x 8 channels: 24 floats of partial rows) first takes the
+    region's first 64 floats.  The queued finishes run when the block ends."""
+    from ultrasound_modeling_amd import _lib as L
+    from ultrasound_modeling_amd import ops
+    region = torch.empty(floats, dtype=torch.float32, device=DEV)
+    if first_producer:
+        x, dy = (to_dev(bf(torch.linspace(-2, 2, 512, dtype=torch.float64).reshape(1, 8, 8, 8) * k))[1] for k in (1, -1))
+        v = torch.ones(8, device=DEV)
+        g = [torch.zeros(8, device=DEV) for _ in range(3)]
+    h = torch.cuda.current_stream().cuda_stream
+    L.check(L.load().usseg_defer_begin(h, region.data_ptr(), floats, None, 0), "defer_begin")
+    try:
+        if first_producer:
+            ops.norm_act_bwd(x, dy, 8, v, v, torch.empty_like(x), g[0], g[1], 0, 1, EPS, ops.ACT_LRELU, 0.3, dbias=g[2])
+        yield
+    finally:
+        L.check(L.load().usseg_defer_end(h), "defer_end")
 
 
 def short(name):

@@ -18,6 +18,7 @@ import pytest
 import torch
 
 import usseg_oracle as O
+from route_probe import routed, small_deferral
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -501,15 +502,24 @@ def test_residual_S_stage_layer_by_layer(world, stage):
         dsc_d = dev(g_of(rec.act_after(rec.norm[pre + "convtmp_scbn"][1])))
         scn = st.convtmp_scbn
 
-        def run(fused):
+        def run(fused, defer_floats=0):
             net.flat.zero_grad()
             sa_s, sa_dg = ops.splitattn_bwd(d, yd, dout_d, params, grp.mlp_g, g, s, ws, None)
             dcat_ = ops.new_act(B, H, W, grp.Up + oc, DEV)
             if fused:
                 dv_ = torch.empty_like(v_raw_o)
                 grads_ = (grp.dg2, grp.dbe2, grp.db2, grp.dg1, grp.dbe1, grp.db1, scn.gamma.grad, scn.beta.grad, st.convtmp_sc.bias.grad)
-                ops.cardinal_bwd(dout_d, dsc_d, v_raw_o, u_raw_o, sc_raw_o, grp.w2_d, grp.g2, grp.be2, grp.g1, grp.be1, scn.gamma.data, scn.beta.data,
-                                 sa_s, sa_dg, 3.0, dv_, dcat_, grads_, grp.cin_p, grp.P, grp.cv11, grp.cvkk, grp.Up, grp.Vp, oc, 1e-3, a)
+                launch = lambda: ops.cardinal_bwd(dout_d, dsc_d, v_raw_o, u_raw_o, sc_raw_o, grp.w2_d, grp.g2, grp.be2, grp.g1, grp.be1, scn.gamma.data,
+                                                  scn.beta.data, sa_s, sa_dg, 3.0, dv_, dcat_, grads_, grp.cin_p, grp.P, grp.cv11, grp.cvkk, grp.Up,
+                                                  grp.Vp, oc, 1e-3, a)
+                if defer_floats:
+                    def deferred():
+                        with small_deferral(defer_floats):
+                            launch()
+                    _, names = routed(deferred, "cardinal_bwd_kernel<", "reduce_finish_batched_kernel")
+                    assert "reduce_finish_kernel" not in names, names   # all three regions deferred, none in the caller's workspace
+                else:
+                    launch()
             else:
                 dv_ = ops.norm_act_bwd_sa(v_raw_o, dout_d, grp.V, grp.g2, grp.be2, torch.empty_like(v_raw_o), grp.dg2, grp.dbe2, 0, 3, 1e-3,
                                           ops.ACT_LRELU, a, sa_s, sa_dg, 3.0, dbias=grp.db2)
@@ -523,6 +533,18 @@ def test_residual_S_stage_layer_by_layer(world, stage):
             return dv_, dcat_, vecs
         dv_f, dcat_f, vec_f = run(True)
         dv_u, dcat_u, vec_u = run(False)
+        # the three partial-row regions of the launch are reserved together: behind a first producer (64 floats), a deferral region of
+        # exactly their size holds the first two but not the third, so the reservation flushes once and then places all three (the
+        # shortcut's region requested on its own would go to offset 0 after the flush, across the first).  G workgroup pairs: the larger of
+        # the 8x8-tile and 64-pixel shortcut-tile counts while that is at most 256 (cardinal.hip launch_bwd).  Bit for bit the undeferred launch.
+        G = max(-(-H // 8) * -(-W // 8) * B, -(-B * H * W // 64))
+        assert G <= 256
+        n2, n1, nsc = 3 * G * grp.Vp, 3 * G * grp.Up, 3 * G * oc
+        assert nsc > 64
+        dv_d, dcat_d, vec_d = run(True, -(-n2 // 64) * 64 + -(-n1 // 64) * 64 + nsc)
+        for nm, f_, d_ in zip(("dv", "dcat", "dgamma2", "dbeta2", "dbias2", "dgamma1", "dbeta1", "dbias1", "dgamma_sc", "dbeta_sc", "dbias_sc"),
+                              [dv_f, dcat_f] + vec_f, [dv_d, dcat_d] + vec_d):
+            assert torch.equal(f_, d_), f"fused bwd with deferred finishes: {nm} differs from the undeferred launch"
         cat = lambda ts: torch.cat([t.detach() for t in ts], 3)
         # dv: the oracle stores the re-weighting's backward (radix*s*dout + dg) in bf16 before the norm backward; both product paths form it in
         # fp32 registers, so each is compared with the oracle at the bar the UNFUSED launch needs, and with each other at the plain bar below

@@ -53,7 +53,7 @@ import torch
 
 import usseg_oracle as O
 from route_probe import (ACTS, EPS, U_BF16, U_F32, act_f, bf, c_f32, check, check_norm_bwd, kname, ng_of, norm_ref, routed, sa_reference,
-                         seam_data, to_dev)
+                         seam_data, small_deferral, to_dev)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -353,9 +353,9 @@ def test_ln_tile_fused(gen, geom):
     run_fused_bwd(gen, f"tile fused {geom}", (2, 128, 128), CG * NG, NG, "lrelu", (f"ln_bwd_tile_kernel<{CP}, {CG}, {NG}, true>", "reduce_finish_kernel"))
 
 
-@pytest.mark.parametrize("ca,cb", [(64, 30), (128, 63)], ids=["stage1", "stage2"])
-def test_ln_pair(gen, ca, cb):
-    """The shortcut norm (A) and conv2_bn with the re-weighting's backward (B) in one ln_bwd_pair_kernel launch; both bounded."""
+def ln_pair_case(gen, ca, cb):
+    """The shortcut norm (A) and conv2_bn with the re-weighting's backward (B) of one ln_bwd_pair_kernel launch: (outputs() -> fresh
+    (dxa, dxb, [dgamma, dbeta, dbias of A, then of B]), launch(dxa, dxb, outs), check(dxa, dxb, outs) - every element bounded)."""
     from ultrasound_modeling_amd import ops
     B, H, W = 2, 128, 128
     M, cpb, HW = B * H * W, (cb + 7) // 8 * 8, H * W
@@ -363,25 +363,43 @@ def test_ln_pair(gen, ca, cb):
     xa, dya, xb, dob = (seam_data(gen, B, H, W, c) for c in (ca, ca, cb, cb))
     ga, ba, gb, bb = vec(gen, ca, neg=True), vec(gen, ca, 0.0, 0.2), vec(gen, cb, neg=True), vec(gen, cb, 0.0, 0.2)
     s, dgv = sa_vectors(gen, B, cb, mult)
-    outs = [torch.zeros(c, device=DEV) for c in (ca, ca, ca, cpb, cpb, cpb)]
-    dxa, dxb = torch.full((B, H, W, ca), NAN, dtype=torch.bfloat16, device=DEV), torch.full((B, H, W, cpb), NAN, dtype=torch.bfloat16, device=DEV)
-    want = "ln_bwd_pair_kernel<8, 64, 1, false, 4, 10, 3, true>" if ca == 64 else "ln_bwd_pair_kernel<16, 128, 1, false, 8, 21, 3, true>"
-    ok, _ = routed(lambda: ops.norm_act_bwd_pair(to_dev(xa)[1], to_dev(dya)[1], ca, ga.float().to(DEV), ba.float().to(DEV), dxa, *outs[:3],
-                                                 to_dev(xb)[1], to_dev(dob)[1], cb, 3, padded(gb, cpb), padded(bb, cpb), dxb, *outs[3:],
-                                                 s.float().to(DEV), dgv.float().to(DEV), mult, EPS, alpha), want)
+
+    def outputs():
+        return (torch.full((B, H, W, ca), NAN, dtype=torch.bfloat16, device=DEV), torch.full((B, H, W, cpb), NAN, dtype=torch.bfloat16, device=DEV),
+                [torch.zeros(c, device=DEV) for c in (ca, ca, ca, cpb, cpb, cpb)])
+
+    def launch(dxa, dxb, outs):
+        return ops.norm_act_bwd_pair(to_dev(xa)[1], to_dev(dya)[1], ca, ga.float().to(DEV), ba.float().to(DEV), dxa, *outs[:3], to_dev(xb)[1],
+                                     to_dev(dob)[1], cb, 3, padded(gb, cpb), padded(bb, cpb), dxb, *outs[3:], s.float().to(DEV), dgv.float().to(DEV),
+                                     mult, EPS, alpha)
+
+    def check(dxa, dxb, outs):
+        torch.cuda.synchronize()
+        ra = norm_ref(xa.reshape(M, ca).to(DEV), ga.to(DEV), ba.to(DEV), "lrelu", dy=dya.reshape(M, ca).to(DEV))
+        check_norm_bwd("pair A", M, ca, ra, dxa.reshape(M, ca), *outs[:3])
+        se, ge = s.to(DEV).repeat_interleave(HW, 0), dgv.to(DEV).repeat_interleave(HW, 0)
+        do = dob.reshape(M, cb).to(DEV)
+        rb = norm_ref(xb.reshape(M, cb).to(DEV), gb.to(DEV), bb.to(DEV), "lrelu", 3, dy=mult * se * do + ge)
+        mb = norm_ref(xb.reshape(M, cb).to(DEV), gb.to(DEV), bb.to(DEV), "lrelu", 3, dy=mult * se * do.abs() + ge.abs())
+        for k in ("dxmag", "dxext", "dgmag", "dbmag", "dgext", "dbext"):
+            rb[k] = mb[k]
+        rb["kink"] = rb["kink"] | mb["kink"]
+        check_norm_bwd("pair B", M, cb, rb, dxb[..., :cb].reshape(M, cb), *outs[3:])
+        assert dxb[..., cb:].abs().max().item() == 0, "pad channels"
+    return outputs, launch, check
+
+
+LN_PAIR_KERNEL = {64: "ln_bwd_pair_kernel<8, 64, 1, false, 4, 10, 3, true>", 128: "ln_bwd_pair_kernel<16, 128, 1, false, 8, 21, 3, true>"}
+
+
+@pytest.mark.parametrize("ca,cb", [(64, 30), (128, 63)], ids=["stage1", "stage2"])
+def test_ln_pair(gen, ca, cb):
+    """The shortcut norm (A) and conv2_bn with the re-weighting's backward (B) in one ln_bwd_pair_kernel launch; both bounded."""
+    outputs, launch, check_pair = ln_pair_case(gen, ca, cb)
+    bufs = outputs()
+    ok, _ = routed(lambda: launch(*bufs), LN_PAIR_KERNEL[ca])
     assert ok
-    torch.cuda.synchronize()
-    ra = norm_ref(xa.reshape(M, ca).to(DEV), ga.to(DEV), ba.to(DEV), "lrelu", dy=dya.reshape(M, ca).to(DEV))
-    check_norm_bwd("pair A", M, ca, ra, dxa.reshape(M, ca), *outs[:3])
-    se, ge = s.to(DEV).repeat_interleave(HW, 0), dgv.to(DEV).repeat_interleave(HW, 0)
-    do = dob.reshape(M, cb).to(DEV)
-    rb = norm_ref(xb.reshape(M, cb).to(DEV), gb.to(DEV), bb.to(DEV), "lrelu", 3, dy=mult * se * do + ge)
-    mb = norm_ref(xb.reshape(M, cb).to(DEV), gb.to(DEV), bb.to(DEV), "lrelu", 3, dy=mult * se * do.abs() + ge.abs())
-    for k in ("dxmag", "dxext", "dgmag", "dbmag", "dgext", "dbext"):
-        rb[k] = mb[k]
-    rb["kink"] = rb["kink"] | mb["kink"]
-    check_norm_bwd("pair B", M, cb, rb, dxb[..., :cb].reshape(M, cb), *outs[3:])
-    assert dxb[..., cb:].abs().max().item() == 0, "pad channels"
+    check_pair(*bufs)
 
 
 def test_norm_deferred_finish(gen):
@@ -403,6 +421,31 @@ def test_norm_deferred_finish(gen):
     torch.cuda.synchronize()
     ref = norm_ref(x.reshape(M, C).to(DEV), gamma.to(DEV), beta.to(DEV), "elu", dy=dy.reshape(M, C).to(DEV))
     check_norm_bwd("deferred", M, C, ref, dx[..., :C].reshape(M, C), dg, db, dbias)
+
+
+@pytest.mark.parametrize("ca,cb,G", [(64, 30, 512), (128, 63, 256)], ids=["stage1", "stage2"])
+def test_ln_pair_deferred_regions(gen, ca, cb, G):
+    """The two partial-row regions of an ln_bwd_pair_kernel launch are reserved together.  Behind a first producer (64 floats), a
+    deferral region of exactly their size holds A but not A and B, so the reservation flushes once and then places both; requesting B
+    on its own after A would flush and put B at offset 0, across A (B > 64 floats).  G = workgroups of each role (one per 64-pixel tile,
+    at most 512 at 4 per CU (stage 1: 38 KB of LDS) or 256 at 2 (stage 2: 54 KB), cardinal.hip launch_ln_pair); A = G*3*ca floats,
+    B = G*3*roundup(cb, 8).  Every output equals the undeferred launch bit for bit (both finishes sum in reduce_finish_body's order)."""
+    outputs, launch, check_pair = ln_pair_case(gen, ca, cb)
+    ref = outputs()
+    assert launch(*ref)
+    got = outputs()
+    na, nb = G * 3 * ca, G * 3 * ((cb + 7) // 8 * 8)
+    assert na % 64 == 0 and nb > 64
+
+    def run():
+        with small_deferral(na + nb):
+            assert launch(*got)
+    _, names = routed(run, LN_PAIR_KERNEL[ca], "reduce_finish_batched_kernel")
+    assert "reduce_finish_kernel" not in names, names      # both regions were deferred, none fell back to the caller's workspace
+    torch.cuda.synchronize()
+    for what, a, b in zip(("dxa", "dxb", "dgamma A", "dbeta A", "dbias A", "dgamma B", "dbeta B", "dbias B"), ref[:2] + tuple(ref[2]), got[:2] + tuple(got[2])):
+        assert torch.equal(a, b), f"deferred pair: {what} differs from the undeferred launch"
+    check_pair(*got)
 
 
 # ------------------------------------------------------------------------------------------------ BN + act + 2x2 pool

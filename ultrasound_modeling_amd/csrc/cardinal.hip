@@ -204,16 +204,13 @@ template <int CIN, int CV11, int CVKK, int OC, bool STASH = true>
 int launch_fwd(const CardFwd& p, hipStream_t s) {
   using Cfg = CardCfg<CIN, CV11, CVKK, OC>;
   const void* const kernel = STASH ? (const void*)cardinal_fwd_kernel<CIN, CV11, CVKK, OC> : (const void*)cardinal_fwd_infer_kernel<CIN, CV11, CVKK, OC>;
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS_B);
-    attr_done = true;
-  }
+  const char* const what = STASH ? "cardinal_fwd" : "cardinal_fwd_infer";
+  if (usseg_lds_opt_in(kernel, Cfg::LDS_B)) return usseg_check_launch(what);
   const int slot = usseg_prof_start(4, s);       // timed as a fused tile kernel (usseg_prof kind 4): convs + norms in one launch
   if constexpr (STASH) hipLaunchKernelGGL((cardinal_fwd_kernel<CIN, CV11, CVKK, OC>), dim3(p.ntiles, p.B, 2), dim3(256), Cfg::LDS_B, s, p);
   else hipLaunchKernelGGL((cardinal_fwd_infer_kernel<CIN, CV11, CVKK, OC>), dim3(p.ntiles, p.B, 2), dim3(256), Cfg::LDS_B, s, p);
   usseg_prof_stop(4, slot, s);
-  return usseg_check_launch(STASH ? "cardinal_fwd" : "cardinal_fwd_infer");
+  return usseg_check_launch(what);
 }
 
 }  // namespace
@@ -490,11 +487,7 @@ __global__ __launch_bounds__(256) void ln_bwd_tile_kernel(const LnTile P) {
 template <int CP, int CG, int NG, bool FUSE>
 int launch_lnb(const LnTileArgs& a, float* dgamma, float* dbeta, float* dbias, float* caller_ws, hipStream_t s) {
   using Cfg = LnbCfg<CP, CG, NG, FUSE>;
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)ln_bwd_tile_kernel<CP, CG, NG, FUSE>, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS_B);
-    attr_done = true;
-  }
+  if (usseg_lds_opt_in((const void*)ln_bwd_tile_kernel<CP, CG, NG, FUSE>, Cfg::LDS_B)) return 1;   // taken: the caller's usseg_check_launch reports it
   LnTile P;
   P.a = a;
   P.ntiles = (int)((a.M + 63) / 64);
@@ -857,11 +850,7 @@ template <int CIN, int CV11, int CVKK, int OC>
 int launch_bwd(CardBwd& p, float* dg2, float* dbe2, float* db2, float* dg1, float* dbe1, float* db1, float* dgsc, float* dbesc, float* dbsc,
                float* caller_ws, hipStream_t s) {
   using Cfg = CardBwdCfg<CV11, CVKK, OC>;
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)cardinal_bwd_kernel<CIN, CV11, CVKK, OC>, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS_B);
-    attr_done = true;
-  }
+  if (usseg_lds_opt_in((const void*)cardinal_bwd_kernel<CIN, CV11, CVKK, OC>, Cfg::LDS_B)) return usseg_check_launch("cardinal_bwd");
   // workgroup pairs (cardinal tile walker, shortcut tile walker): as many as are resident at once, at most one per tile
   static const int g_env = getenv("USSEG_CARD_BWD_G") ? atoi(getenv("USSEG_CARD_BWD_G")) : 0;
   const int per_cu = 160 * 1024 / (2 * Cfg::LDS_B) > 0 ? 160 * 1024 / (2 * Cfg::LDS_B) : 1;
@@ -873,10 +862,10 @@ int launch_bwd(CardBwd& p, float* dg2, float* dbe2, float* db2, float* dg1, floa
   while (G > 1 && (int64_t)G * 3 * (VP + UP + OC) > (int64_t)USSEG_REDUCE_MAX_BLOCKS * 3 * 512) G >>= 1;   // the three partial-row regions fit usseg_reduce_ws_floats()
   p.G = G;
   // three partial-row regions (private ones while the finishing reductions are deferred); caller_ws holds all three otherwise
-  const int64_t n2 = (int64_t)G * 3 * VP, n1 = (int64_t)G * 3 * UP, nsc = (int64_t)G * 3 * OC;
-  p.ws2 = usseg_defer_reduce_ws(s, caller_ws, n2);
-  p.ws1 = usseg_defer_reduce_ws(s, caller_ws + n2, n1);
-  p.sc.ws = usseg_defer_reduce_ws(s, caller_ws + n2 + n1, nsc);
+  const int64_t need[3] = {(int64_t)G * 3 * VP, (int64_t)G * 3 * UP, (int64_t)G * 3 * OC};
+  float* ws[3];
+  usseg_defer_reduce_ws_n(s, caller_ws, need, 3, ws);
+  p.ws2 = ws[0]; p.ws1 = ws[1]; p.sc.ws = ws[2];
   const int slot = usseg_prof_start(4, s);       // timed as a fused tile kernel (kind 4)
   hipLaunchKernelGGL((cardinal_bwd_kernel<CIN, CV11, CVKK, OC>), dim3(2 * G), dim3(256), Cfg::LDS_B, s, p);
   usseg_prof_stop(4, slot, s);
@@ -907,20 +896,17 @@ int launch_ln_pair(LnPair& P, float* const* ga, float* const* gb, float* caller_
   using CA = LnbCfg<CPA, CGA, NGA, FA>;
   using CB = LnbCfg<CPB, CGB, NGB, FB>;
   constexpr int LDS = CA::LDS_B > CB::LDS_B ? CA::LDS_B : CB::LDS_B;
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)ln_bwd_pair_kernel<CPA, CGA, NGA, FA, CPB, CGB, NGB, FB>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    attr_done = true;
-  }
+  if (usseg_lds_opt_in((const void*)ln_bwd_pair_kernel<CPA, CGA, NGA, FA, CPB, CGB, NGB, FB>, LDS)) return 1;   // taken: as launch_lnb
   const int per_cu = LDS > 80 * 1024 ? 1 : (LDS > 40 * 1024 ? 2 : 4);      // workgroups of EACH role per CU
   const int most = P.ntiles_a > P.ntiles_b ? P.ntiles_a : P.ntiles_b;
   int G = 128 * per_cu;
   if (G > most) G = most;
   if (G > USSEG_REDUCE_MAX_BLOCKS) G = USSEG_REDUCE_MAX_BLOCKS;
   P.G = G;
-  const int64_t na = (int64_t)G * 3 * CA::CPH, nb = (int64_t)G * 3 * CB::CPH;
-  P.a.ws = usseg_defer_reduce_ws(s, caller_ws, na);
-  P.b.ws = usseg_defer_reduce_ws(s, caller_ws + na, nb);
+  const int64_t need[2] = {(int64_t)G * 3 * CA::CPH, (int64_t)G * 3 * CB::CPH};
+  float* ws[2];
+  usseg_defer_reduce_ws_n(s, caller_ws, need, 2, ws);
+  P.a.ws = ws[0]; P.b.ws = ws[1];
   hipLaunchKernelGGL((ln_bwd_pair_kernel<CPA, CGA, NGA, FA, CPB, CGB, NGB, FB>), dim3(2 * G), dim3(256), LDS, s, P);
   usseg_launch_reduce_finish(P.a.ws, 1, G, 3, CA::CPH, P.a.C, 1.f, ga[0], ga[1], ga[2], s, 0);
   usseg_launch_reduce_finish(P.b.ws, 1, G, 3, CB::CPH, P.b.C, 1.f, gb[0], gb[1], gb[2], s, 0);

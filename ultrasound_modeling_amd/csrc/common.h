@@ -439,6 +439,10 @@ void usseg_set_error(const char* fmt, ...);
     }                                              \
   } while (0)
 int usseg_check_launch(const char* what);
+// Lets `kernel` use `bytes` of dynamic LDS (beyond the default limit) on the current device: hipFuncSetAttribute once per (device, kernel) and size,
+// thread-safe.  On failure it sets the error text and returns USSEG_ERR_LAUNCH; the caller skips the launch, and this thread's next
+// usseg_check_launch returns USSEG_ERR_LAUNCH too, so launchers that return void or "took the launch" need no status of their own.
+int usseg_lds_opt_in(const void* kernel, int bytes);
 // opt-in per-launch timing: returns an event slot (>=0) after recording its start event, or -1 when disabled
 // LayerNorm + LeakyReLU backward on the lane-per-pixel tile kernel (cardinal.hip); returns 0 if it has no instantiation for the geometry
 struct LnTileArgs {
@@ -492,8 +496,10 @@ int usseg_try_launch_wgrad_halo(const WgHaloGeom* g, int njobs, float* ws, int64
 int conv2d_wgrad_impl(const UssegConvDesc* d, const void* x, const void* dy, float* dw, const UssegWgradDst* dst, float* ws, int64_t ws_floats,
                       const UssegTapMask& mask, usseg_stream_t stream);
 
-// deferral of the finishing reductions (defer.hip): workspace regions for producers between usseg_defer_begin and _flush
+// deferral of the finishing reductions (defer.hip): workspace regions for producers between usseg_defer_begin and _flush; a launch
+// with several regions reserves them in one call (caller_ws holds them back to back when nothing is deferred)
 float* usseg_defer_reduce_ws(hipStream_t s, float* caller_ws, int64_t need);
+void usseg_defer_reduce_ws_n(hipStream_t s, float* caller_ws, const int64_t* need, int n, float** out);
 float* usseg_defer_wgrad_ws(hipStream_t s, float* caller_ws, int64_t caller_floats, int64_t* avail);
 // out (identity or mapped) += sum over the split slabs ws[split][slab_floats] (wgrad_halo.hip)
 void usseg_launch_wgrad_finish(const float* ws, int splits, int64_t slab_floats, float* out, const WgMap& map, int Ma, int Nb, hipStream_t s);

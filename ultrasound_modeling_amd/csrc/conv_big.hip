@@ -456,11 +456,7 @@ static int nt_for(int nout) { return nout <= 16 ? 1 : (nout <= 32 ? 2 : 4); }
 
 template <int NT, int NS, int NW = 4>
 static void big_launch_t(const BigParams& P, dim3 grid, size_t dyn, hipStream_t s) {
-  static bool attr_done = false;   // > 64 KB of LDS per workgroup needs the opt-in (one-time host call, never a stream op)
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)conv_big_kernel<NT, NS, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_done = true;
-  }
+  if (usseg_lds_opt_in((const void*)conv_big_kernel<NT, NS, NW>, 160 * 1024)) return;
   hipLaunchKernelGGL((conv_big_kernel<NT, NS, NW>), grid, dim3(64 * NW), dyn, s, P);
 }
 
@@ -504,11 +500,7 @@ static void big_launch(BigParams& P, int njobs, int nt, int PX, hipStream_t s, i
 
 template <int NT, int NS, bool RES = false>
 static void stream_launch_t(const BigParams& P, dim3 grid, size_t dyn, int fast_wait, hipStream_t s) {
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)conv_stream_kernel<NT, NS, RES>, hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024);   // + 1 KB static
-    attr_done = true;
-  }
+  if (usseg_lds_opt_in((const void*)conv_stream_kernel<NT, NS, RES>, 158 * 1024)) return;   // + 1 KB static
   hipLaunchKernelGGL((conv_stream_kernel<NT, NS, RES>), grid, dim3(256), dyn, s, P, fast_wait);
 }
 

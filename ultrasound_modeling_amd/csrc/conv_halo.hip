@@ -395,16 +395,12 @@ static int halo_launch(HaloMulti& P, int njobs, hipStream_t s) {
     int pgx = ((gx + gpb - 1) / gpb + 7) & ~7;       // a multiple of 8: workgroups per XCD = pgx / 8
     gpb = (((gx + 7) >> 3) + (pgx >> 3) - 1) / (pgx >> 3);   // groups per workgroup under the per-XCD split
     if (gpb > 16) { pgx = ((((gx + 7) >> 3) + 15) / 16) * 8; gpb = 16; }
-    static bool attr_done = false;   // > 64 KB of LDS per workgroup needs the opt-in (one-time host call, never a stream op)
-    if (!attr_done) {
-      (void)hipFuncSetAttribute((const void*)conv_halo_persist_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-      (void)hipFuncSetAttribute((const void*)conv_halo_persist_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-      (void)hipFuncSetAttribute((const void*)conv_halo_persist_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-      attr_done = true;
+    const void* const kernel = nt == 1 ? (const void*)conv_halo_persist_kernel<1> : (nt == 2 ? (const void*)conv_halo_persist_kernel<2> : (const void*)conv_halo_persist_kernel<4>);
+    if (usseg_lds_opt_in(kernel, 96 * 1024) == USSEG_OK) {   // (on failure: taken, the caller's usseg_check_launch reports it)
+      if (nt == 1) hipLaunchKernelGGL(conv_halo_persist_kernel<1>, dim3(pgx, gy, njobs), dim3(256), dyn, s, P, gpb);
+      else if (nt == 2) hipLaunchKernelGGL(conv_halo_persist_kernel<2>, dim3(pgx, gy, njobs), dim3(256), dyn, s, P, gpb);
+      else hipLaunchKernelGGL(conv_halo_persist_kernel<4>, dim3(pgx, gy, njobs), dim3(256), dyn, s, P, gpb);
     }
-    if (nt == 1) hipLaunchKernelGGL(conv_halo_persist_kernel<1>, dim3(pgx, gy, njobs), dim3(256), dyn, s, P, gpb);
-    else if (nt == 2) hipLaunchKernelGGL(conv_halo_persist_kernel<2>, dim3(pgx, gy, njobs), dim3(256), dyn, s, P, gpb);
-    else hipLaunchKernelGGL(conv_halo_persist_kernel<4>, dim3(pgx, gy, njobs), dim3(256), dyn, s, P, gpb);
     usseg_prof_stop(1, slot, s);
     return 1;
   }

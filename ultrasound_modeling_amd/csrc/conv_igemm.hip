@@ -594,11 +594,7 @@ template <int NT, int NSTAGE>
 static void igemm_dma_persist_launch_t(const IgemmParams& p, dim3 grid, hipStream_t s) {
   constexpr int BNP = 16 * NT < 32 ? 32 : 16 * NT;
   const size_t dyn = (size_t)NSTAGE * (128 + BNP) * 128;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)igemm_dma_persist_kernel<NT, NSTAGE>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-    attr = true;
-  }
+  if (usseg_lds_opt_in((const void*)igemm_dma_persist_kernel<NT, NSTAGE>, 128 * 1024)) return;
   hipLaunchKernelGGL((igemm_dma_persist_kernel<NT, NSTAGE>), grid, dim3(256), dyn, s, p);
 }
 
@@ -606,11 +602,7 @@ template <int NT, int NSTAGE>
 static void igemm_dma_launch_t(const IgemmParams& p, dim3 grid, hipStream_t s) {
   constexpr int BNP = 16 * NT < 32 ? 32 : 16 * NT;
   const size_t dyn = (size_t)NSTAGE * (128 + BNP) * 128;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)igemm_dma_kernel<NT, NSTAGE>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-    attr = true;
-  }
+  if (usseg_lds_opt_in((const void*)igemm_dma_kernel<NT, NSTAGE>, 128 * 1024)) return;
   hipLaunchKernelGGL((igemm_dma_kernel<NT, NSTAGE>), grid, dim3(256), dyn, s, p);
 }
 
@@ -681,12 +673,8 @@ static int launch_igemm(const IgemmParams& p_in, hipStream_t s) {
 #define USSEG_IGEMM_LAUNCH(NT_, KC_)                                                                                         \
   do {                                                                                                                         \
     const size_t dyn = (size_t)2 * (128 + 16 * NT_) * (KC_ * 8 + 8) * sizeof(bf16_t) + 128 * sizeof(int);                      \
-    static bool attr = false;                                                                                                  \
-    if (!attr) {                                                                                                               \
-      (void)hipFuncSetAttribute((const void*)igemm_kernel<NT_, KC_>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);   \
-      attr = true;                                                                                                             \
-    }                                                                                                                          \
-    hipLaunchKernelGGL((igemm_kernel<NT_, KC_>), grid, block, dyn, s, p);                                                      \
+    if (usseg_lds_opt_in((const void*)igemm_kernel<NT_, KC_>, 96 * 1024) == USSEG_OK)                                          \
+      hipLaunchKernelGGL((igemm_kernel<NT_, KC_>), grid, block, dyn, s, p);                                                    \
   } while (0)
   if (kc == 8) {
     if (nt == 1) USSEG_IGEMM_LAUNCH(1, 8); else if (nt == 2) USSEG_IGEMM_LAUNCH(2, 8); else if (nt == 4) USSEG_IGEMM_LAUNCH(4, 8); else USSEG_IGEMM_LAUNCH(8, 8);

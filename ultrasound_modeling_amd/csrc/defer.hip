@@ -229,13 +229,25 @@ static void flush_wgrad(DeferCtx& c) {
   c.wused = 0;
 }
 
-// Workspace for `need` floats of per-workgroup partial rows: the caller's own ws, or (deferring) a private region.
-float* usseg_defer_reduce_ws(hipStream_t s, float* caller_ws, int64_t need) {
+// Workspace for the n partial-row regions of one launch (need[i] floats each): the caller's own ws, laid out back to back, or
+// (deferring) private regions reserved together.  A flush, if one is needed, comes before any region is handed out: a region
+// handed out before it would stay in use while the bump allocation starts over beneath it.
+void usseg_defer_reduce_ws_n(hipStream_t s, float* caller_ws, const int64_t* need, int n, float** out) {
   DeferCtx* c = find_ctx(s);
-  if (!c || !c->rws || need > c->rcap) return caller_ws;
-  if (c->rused + need > c->rcap) flush_reduce(*c);
-  float* r = c->rws + c->rused;
-  c->rused += (need + 63) & ~(int64_t)63;
+  int64_t span = 0;   // the private regions start 64-float aligned: end of the last one
+  for (int i = 0; i < n; ++i) span = ((span + 63) & ~(int64_t)63) + need[i];
+  const bool defer = c && c->rws && span <= c->rcap;
+  if (defer && c->rused + span > c->rcap) flush_reduce(*c);
+  float* r = defer ? c->rws + c->rused : caller_ws;
+  for (int i = 0; i < n; ++i) {
+    out[i] = r;
+    r += defer ? (need[i] + 63) & ~(int64_t)63 : need[i];
+  }
+  if (defer) c->rused += (span + 63) & ~(int64_t)63;
+}
+float* usseg_defer_reduce_ws(hipStream_t s, float* caller_ws, int64_t need) {
+  float* r;
+  usseg_defer_reduce_ws_n(s, caller_ws, &need, 1, &r);
   return r;
 }
 

@@ -1,8 +1,11 @@
 // Error reporting for the C ABI: a thread-local message, never an exception or an exit.
 #include <stdarg.h>
+#include <map>
+#include <mutex>
 #include "common.h"
 
 static thread_local char g_err[512] = "";
+static thread_local bool g_opt_in_failed = false;   // a failed usseg_lds_opt_in, reported by this thread's next usseg_check_launch
 
 void usseg_set_error(const char* fmt, ...) {
   va_list ap;
@@ -11,8 +14,32 @@ void usseg_set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
+int usseg_lds_opt_in(const void* kernel, int bytes) {
+  static std::mutex mu;
+  static std::map<std::pair<int, const void*>, int> granted;   // (device, kernel) -> the largest size set so far
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e == hipSuccess) {
+    std::lock_guard<std::mutex> lock(mu);
+    int& have = granted[{dev, kernel}];
+    if (bytes <= have) return USSEG_OK;
+    e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e == hipSuccess) {
+      have = bytes;
+      return USSEG_OK;
+    }
+  }
+  usseg_set_error("dynamic LDS opt-in of kernel %p to %d bytes on device %d failed: %s", kernel, bytes, dev, hipGetErrorString(e));
+  g_opt_in_failed = true;
+  return USSEG_ERR_LAUNCH;
+}
+
 int usseg_check_launch(const char* what) {
   hipError_t e = hipGetLastError();
+  if (g_opt_in_failed) {      // the launch was skipped; usseg_lds_opt_in wrote the message
+    g_opt_in_failed = false;
+    return USSEG_ERR_LAUNCH;
+  }
   if (e != hipSuccess) {
     usseg_set_error("%s: launch failed: %s", what, hipGetErrorString(e));
     return USSEG_ERR_LAUNCH;

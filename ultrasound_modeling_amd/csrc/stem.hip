@@ -367,11 +367,7 @@ extern "C" int usseg_stem_fwd(int32_t B, int32_t H, int32_t W, const void* x, in
   p.B = B; p.H = H; p.W = W; p.ldx = ldx; p.alpha = alpha; p.eps = eps;
   p.tiles_x = (W + T - 1) / T;
   p.ntiles = p.tiles_x * ((H + TH - 1) / TH);
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)stem_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_B);
-    attr_done = true;
-  }
+  if (usseg_lds_opt_in((const void*)stem_fwd_kernel, LDS_B)) return usseg_check_launch("stem_fwd");
   hipStream_t s = (hipStream_t)stream;
   const int slot = usseg_prof_start(4, s);
   hipLaunchKernelGGL(stem_fwd_kernel, dim3(p.ntiles, B), dim3(256), LDS_B, s, p);
@@ -393,11 +389,7 @@ extern "C" int usseg_stem_fwd_infer(int32_t B, int32_t H, int32_t W, const void*
   p.B = B; p.H = H; p.W = W; p.ldx = ldx; p.alpha = alpha; p.eps = eps;
   p.tiles_x = (W + T - 1) / T;
   p.ntiles = p.tiles_x * ((H + TH - 1) / TH);
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)stem_fwd_infer_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_B);
-    attr_done = true;
-  }
+  if (usseg_lds_opt_in((const void*)stem_fwd_infer_kernel, LDS_B)) return usseg_check_launch("stem_fwd_infer");
   hipStream_t s = (hipStream_t)stream;
   const int slot = usseg_prof_start(4, s);
   hipLaunchKernelGGL(stem_fwd_infer_kernel, dim3(p.ntiles, B), dim3(256), LDS_B, s, p);

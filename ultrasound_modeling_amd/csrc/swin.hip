@@ -208,7 +208,7 @@ static void ln_wide_launch(const LnWide& p, unsigned grid, hipStream_t s) {
   const size_t dyn = BWD ? (size_t)4 * p.C * sizeof(float) : 0;
 #define LNW(NK_)                                                                                                             \
   {                                                                                                                          \
-    if (BWD && dyn > 48 * 1024) (void)hipFuncSetAttribute((const void*)ln_wide_kernel<NK_, BWD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn); \
+    if (BWD && dyn > 48 * 1024 && usseg_lds_opt_in((const void*)ln_wide_kernel<NK_, BWD>, (int)dyn)) return;                \
     hipLaunchKernelGGL((ln_wide_kernel<NK_, BWD>), dim3(grid), dim3(256), dyn, s, p);                                        \
   }
   if (nk <= 1) LNW(1) else if (nk <= 2) LNW(2) else if (nk <= 4) LNW(4) else LNW(8)
@@ -754,7 +754,7 @@ static int wa_launch(const WinAttn& p, hipStream_t s) {
   const dim3 grid(nW, p.heads, p.B);
 #define WAL(WS_)                                                                                                                     \
   {                                                                                                                                  \
-    if (dyn > 48 * 1024) (void)hipFuncSetAttribute((const void*)window_attn_kernel<BWD, WS_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);   \
+    if (dyn > 48 * 1024 && usseg_lds_opt_in((const void*)window_attn_kernel<BWD, WS_>, (int)dyn)) return 0;                          \
     hipLaunchKernelGGL((window_attn_kernel<BWD, WS_>), grid, dim3(64), dyn, s, p);                                                  \
   }
   if (p.ws == 2) WAL(2) else if (p.ws == 4) WAL(4) else if (p.ws == 8) WAL(8) else return 0;

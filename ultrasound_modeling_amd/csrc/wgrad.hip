@@ -375,11 +375,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_dma_kernel(const WgradParams p, 
 template <int TM, int NSTAGE>
 static void wgrad_dma_launch_t(const WgradParams& p, dim3 grid, hipStream_t s) {
   const size_t dyn = (size_t)NSTAGE * 2 * 64 * 64 * TM * 2;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)wgrad_dma_kernel<TM, NSTAGE>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-    attr = true;
-  }
+  if (usseg_lds_opt_in((const void*)wgrad_dma_kernel<TM, NSTAGE>, 128 * 1024)) return;
   hipLaunchKernelGGL((wgrad_dma_kernel<TM, NSTAGE>), grid, dim3(256), dyn, s, p, 1.0f / (float)(p.Hg * p.Wg), 1.0f / (float)p.Wg);
 }
 
