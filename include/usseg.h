@@ -557,6 +557,36 @@ int usseg_cascade_gate(const float* probs, int32_t C_mask, int64_t M, const void
 int usseg_cascade_maps(const float* probs, int32_t C, int64_t M, float* prob_map, float* bleed_prob, usseg_stream_t stream);
 int usseg_loss_from_probs(const UssegLossDesc* d, const float* probs, const float* y_true, const float* scale, float* loss,
                           usseg_stream_t stream);
+/* ---- class loss: VisionTransformer.my_loss_cat and its focal variant (VisionTransformer.py:259-280) ----------------------------
+ * The reference's second loss for Arch B, as executed.  Per pixel, with probabilities p[c], labels y[c], s = label_smoothing:
+ *     ys[c] = y[c]*(1 - s) + s/C
+ *     pc[c] = clip(p[c], clip_eps, 1 - clip_eps)            (:266; NOT divided by the class sum, unlike Keras' CCE of loss_kind 0)
+ *     l     = -factor * sum_c w[c] * ys[c] * (1 - pc[c])^gamma * log(pc[c])
+ *     d l / d p[c] = factor*w[c]*ys[c]*(gamma*(1-pc)^(gamma-1)*log(pc) - (1-pc)^gamma/pc) for clip_eps < p[c] < 1 - clip_eps, else 0
+ * my_loss_cat as committed (:270): factor 3, w = class_factor, gamma 0.  Its focal line (:272-273,277): factor 1, w = 1, gamma = alpha.
+ * gamma is 0 (no pow and no 1 - pc evaluated) or lies in [1, 8] (below 1 the derivative is unbounded at the clip edge); w[c] and factor
+ * are finite and >= 0; only w[0..C) is read.  The struct travels BY VALUE with the launch, so a captured graph holds its numbers.
+ * The three entry points below are the class-loss forms of the three above; the descriptor must say loss_kind 2 and its
+ * label_smoothing, clip_eps, inv_global_batch and geometry mean what they mean there.  The scalar is
+ * inv_global_batch * sum over all pixels of l, through the same ordered sum (loss: USSEG_ACC_FLOATS floats, [0] OVERWRITTEN);
+ * dlogits = d scalar / d logits. */
+typedef struct UssegClassLoss {
+  float w[8];   /* per-class weight */
+  float gamma;  /* focal exponent: 0, or 1..8 */
+  float factor; /* the reference's 3 ("if using class factor") or 1 */
+} UssegClassLoss;
+int usseg_softmax_loss_fwd_bwd_cl(const UssegLossDesc* d, const UssegClassLoss* cl, const float* logits, const float* y_true, float* probs,
+                                  float* loss, void* dlogits, usseg_stream_t stream);
+/* Fused head: gamma == 0 and gamma > 0 are separate instantiations of the kernel (the loss is a compile-time property of it).
+ * USSEG_ERR_UNSUPPORTED - nothing launched - under the same conditions as the function above. */
+int usseg_head_quad_softmax_loss_cl(const void* x, int32_t B, int32_t h, int32_t w, int32_t Cin_phys, int32_t ldx, const void* wq, const float* bias,
+                                    int32_t C, const float* y_true, float* probs, float* loss, void* dlogits, float label_smoothing, float clip_eps,
+                                    float inv_global_batch, const UssegClassLoss* cl, usseg_stream_t stream);
+/* On PROBABILITIES (fp32 [M][C], like y_true).  as_map == 0: the scalar (compute_loss with this loss).  as_map != 0: loss is [HW] floats,
+ * map[hw] = sum_b l[b][hw] (what my_loss_cat returns, :270 axis=[0,3]); inv_global_batch is not applied; one thread owns a pixel and walks
+ * the batch in order. */
+int usseg_loss_from_probs_cl(const UssegLossDesc* d, const UssegClassLoss* cl, const float* probs, const float* y_true, float* loss,
+                             int32_t as_map, usseg_stream_t stream);
 /* The <= 4-class head Conv2DTranspose(k x k, stride 2, 'same') (Decoder.py:120 k=3; TBI_ResNest.py:124 k=4) in "quad" form: a
  * stride-1 convolution at the INPUT resolution whose 16 output channels are (output parity class)*4 + n, run by
  * usseg_conv2d_fwd/dgrad/wgrad as a 3x3 conv (each parity uses <= 2x2 of the stencil taps, the rest are zero).  With

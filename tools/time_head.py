@@ -1,0 +1,73 @@
+"""Times the fused head launch (head conv + softmax + loss + d loss / d logits, csrc/attn_loss_optim.hip head_quad_loss_kernel) at the bench
+shape with tools/time_conv.py's method: `reps` launches captured into one HIP graph, replayed three times between two events.
+usage: python tools/time_head.py [--lib PATH] [--rounds N] [B h w Cin C]
+  --lib PATH: time that build of the library instead (e.g. the parent commit's, which has only the CategoricalCrossentropy entry point);
+  each variant is timed `rounds` times, so the run-to-run spread stands beside every number."""
+import argparse
+import ctypes as C
+import sys
+
+import torch
+
+sys.path.insert(0, ".")
+from ultrasound_modeling_amd import _lib as L
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--lib", default=L.LIB_PATH)
+ap.add_argument("--rounds", type=int, default=5)
+ap.add_argument("--reps", type=int, default=30)
+ap.add_argument("shape", nargs="*", type=int, default=[16, 128, 128, 72, 3])
+a = ap.parse_args()
+B, h, w, Cin, NC = a.shape
+lib = C.CDLL(a.lib)
+vp, i32, f32 = C.c_void_p, C.c_int32, C.c_float
+lib.usseg_head_quad_softmax_loss.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp, f32, f32, f32, vp]
+has_cl = hasattr(lib, "usseg_head_quad_softmax_loss_cl")
+if has_cl:
+    lib.usseg_head_quad_softmax_loss_cl.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp, f32, f32, f32, C.POINTER(L.ClassLoss), vp]
+
+g = torch.Generator().manual_seed(0)
+x = torch.randn(B, h, w, Cin, generator=g).to(torch.bfloat16).cuda()
+wq = (torch.randn(16, 9 * Cin, generator=g) / (9 * Cin) ** 0.5).to(torch.bfloat16).cuda()
+bias = torch.zeros(4).cuda()
+y = torch.softmax(torch.randn(B, 2 * h, 2 * w, NC, generator=g), -1).cuda()
+probs = torch.empty(B, 2 * h, 2 * w, NC).cuda()
+loss = torch.zeros(2050).cuda()
+dl = torch.empty(B, h, w, 16, dtype=torch.bfloat16).cuda()
+
+
+def launch(cl):
+    s = torch.cuda.current_stream().cuda_stream
+    args = [x.data_ptr(), B, h, w, Cin, Cin, wq.data_ptr(), bias.data_ptr(), NC, y.data_ptr(), probs.data_ptr(), loss.data_ptr(), dl.data_ptr(), 0.1, 1e-7,
+            1.0 / B]
+    rc = lib.usseg_head_quad_softmax_loss(*args, s) if cl is None else lib.usseg_head_quad_softmax_loss_cl(*args, C.byref(cl), s)
+    assert rc == 0, rc
+
+
+def t(fn, reps):
+    for _ in range(3):
+        fn()
+    torch.cuda.synchronize()
+    gr = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(gr):
+        for _ in range(reps):
+            fn()
+    gr.replay()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(3):
+        gr.replay()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / (3 * reps) * 1e3
+
+
+variants = [("cce (loss_kind 0)", None)]
+if has_cl:
+    cf = (C.c_float * 8)(0.06329, 0.027567, 0.90914)
+    variants += [("my_loss_cat (gamma 0)", L.ClassLoss(cf, 0.0, 3.0)), ("focal (gamma 2)", L.ClassLoss((C.c_float * 8)(*([1.0] * 8)), 2.0, 1.0))]
+print(f"{a.lib}: fused head {B}x{h}x{w} {Cin} channels, {NC} classes")
+for name, cl in variants:
+    ts = [t(lambda: launch(cl), a.reps) for _ in range(a.rounds)]
+    print(f"  {name:24s} {min(ts):7.2f} us min, {sorted(ts)[len(ts) // 2]:7.2f} median, {max(ts):7.2f} max   [{' '.join(f'{v:.2f}' for v in ts)}]")

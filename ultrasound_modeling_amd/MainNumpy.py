@@ -96,6 +96,21 @@ class Process(object):
         return m["f1"]
 
 
+def main(train_path, val_path, save_path=None, epochs=50, batch_size=32, num_classes=3, *, loss="cce"):
+    """MainNumpy.py:150-177 with the paths as arguments: ``VisionTransformer(32, img_size=(256, 80))`` over a ``Dataset_2.Dataset``,
+    50 epochs, then a save if ``save_path`` is given.  ``loss``: the model's ``loss=`` ("cce", "my_loss_cat", "focal")."""
+    from .Dataset_2 import Dataset
+    from .VisionTransformer import VisionTransformer
+    dataset = Dataset(train_path, val_path, num_classes)
+    neuralnet = VisionTransformer(batch_size, img_size=input_size, num_classes=num_classes, loss=loss)
+    print(len(neuralnet.visionModel.layers))
+    process = Process(batch_size=batch_size, num_classes=num_classes)
+    process.training(neuralnet=neuralnet, dataset=dataset, epochs=epochs)
+    if save_path is not None:
+        neuralnet.visionModel.save(save_path)
+    return neuralnet, process
+
+
 def reference_schedule() -> PiecewiseConstantDecay:
     """MainNumpy.py:83-84."""
     return PiecewiseConstantDecay([2000, 4000, 8000, 10000, 15000], [1e-0, 3e-1, 1e-1, 3e-2, 1e-2, 3e-3])

@@ -18,7 +18,7 @@ The epoch driver (``Process.training`` / ``test`` / ``mirrored_train_step`` / ``
 MainParallel.py:24-176,201-220) runs any model with ``train_step`` / ``step`` / ``empty_step`` (``VisionTransformer``) over a
 ``Dataset.Dataset``, one process per replica:
     python -m torch.distributed.run --nproc_per_node N -m ultrasound_modeling_amd.MainParallel TRAIN VAL [--save P] [--epochs N]
-        [--batch-size B] [--no-vit]
+        [--batch-size B] [--no-vit] [--loss {cce,my_loss_cat,focal}]
 (world size 1 runs without the launcher).  As the reference executes: epochs count from 0; ``test`` runs after EVERY epoch (:72); the
 test loss is the plain sum over the test batches (:89 is commented out); test batches are ``batch_size`` images (:155) split like the
 training batches; each replica's loss is divided by the GLOBAL batch (``VisionTransformer.batch_size``, a short last batch included,
@@ -276,9 +276,11 @@ class Process(object):
         return float(total)
 
 
-def main(train_path, val_path, save_path=None, epochs=51, batch_size=64, use_vit=True, *, seed=0, schedule=False, capture_graph=True):
+def main(train_path, val_path, save_path=None, epochs=51, batch_size=64, use_vit=True, *, seed=0, schedule=False, capture_graph=True,
+         loss="cce"):
     """MainParallel.py:201-216 with the paths as arguments: ``VisionTransformer(batch_size=64)`` with the ViT bottleneck, 51 epochs,
     then rank 0 saves if ``save_path`` is given.  Every rank seeds ``random`` with ``seed``, so all draw the same augmentations.
+    ``loss``: the model's ``loss=`` ("cce", "my_loss_cat", "focal"); every replica divides it by the global batch all the same.
     Under ``nccl`` the model lives on ``cuda:LOCAL_RANK``; the ``USSEG_DIST_BACKEND=gloo`` rehearsal keeps every rank on device 0."""
     from .Dataset import Dataset
     from .VisionTransformer import VisionTransformer
@@ -289,7 +291,7 @@ def main(train_path, val_path, save_path=None, epochs=51, batch_size=64, use_vit
     random.seed(seed)
     dataset = Dataset(train_path, val_path, batch_size, device=device)
     neuralnet = VisionTransformer(batch_size, img_size=(dataset.height, dataset.width), in_channels=dataset.channel, use_vit=use_vit,
-                                  device=str(device))
+                                  device=str(device), loss=loss)
     if rank == 0:
         print(len(neuralnet.visionModel.layers))
     process = Process(batch_size, schedule=schedule, capture_graph=capture_graph)
@@ -312,9 +314,11 @@ def _cli(argv=None):
     ap.add_argument("--seed", type=int, default=0, help="augmentation draws (the same on every rank)")
     ap.add_argument("--schedule", action="store_true", help="install the MainParallel.py:74-79 rate schedule once")
     ap.add_argument("--no-graph", action="store_true", help="run every step eagerly")
+    ap.add_argument("--loss", choices=("cce", "my_loss_cat", "focal"), default="cce",
+                    help="the model's loss: CategoricalCrossentropy (the reference's), its class-weighted my_loss_cat, or the focal variant")
     a = ap.parse_args(argv)
     main(a.train, a.val, a.save, epochs=a.epochs, batch_size=a.batch_size, use_vit=not a.no_vit, seed=a.seed, schedule=a.schedule,
-         capture_graph=not a.no_graph)
+         capture_graph=not a.no_graph, loss=a.loss)
     if dist.is_initialized():
         dist.barrier()
         dist.destroy_process_group()

@@ -49,9 +49,12 @@ class VisionTransformer(_VisionTransformer):
     """TBI_TransUNet.py:532-592.  Note the reference's argument order here: batch_size comes LAST (:533)."""
 
     def __init__(self, img_size=(256, 80), num_classes=3, learning_rate=1e-3, weight_decay=1e-4, batch_size=16, *,
-                 in_channels: int = 10, device: Optional[str] = None, seed: Optional[int] = 0, adamw: bool = False):
+                 in_channels: int = 10, device: Optional[str] = None, seed: Optional[int] = 0, adamw: bool = False,
+                 loss: str = "cce", class_factor=None, focal_gamma=None):
+        """``loss`` / ``class_factor`` / ``focal_gamma``: as in the newer model (``VisionTransformer.VisionTransformer``), with this file's
+        reduction - the mean over the B*H*W pixels of the batch."""
         super().__init__(batch_size, img_size, num_classes, learning_rate, weight_decay, in_channels=in_channels, use_vit=True,
-                         device=device, seed=seed, transunet=True, adamw=adamw)
+                         device=device, seed=seed, transunet=True, adamw=adamw, loss=loss, class_factor=class_factor, focal_gamma=focal_gamma)
 
     def step(self, x, y, train=False):
         """TBI_TransUNet.py:571-588 -> (loss, probabilities); ``train=True`` also clips and applies the gradients."""
@@ -174,10 +177,11 @@ def test(neuralnet, dataset, epoch):
     return r["f1"]
 
 
-def main(train_path, val_path, save_path=None, epochs=51, batch_size=16):
-    """:997-1010 with the paths as arguments: 256x80x10 input, batch 16, 51 epochs, then a save if ``save_path`` is given."""
+def main(train_path, val_path, save_path=None, epochs=51, batch_size=16, *, loss="cce"):
+    """:997-1010 with the paths as arguments: 256x80x10 input, batch 16, 51 epochs, then a save if ``save_path`` is given.
+    ``loss``: the model's ``loss=`` ("cce", "my_loss_cat", "focal")."""
     dataset = Dataset(train_path, val_path)
-    neuralnet = VisionTransformer(img_size=input_size, num_classes=3, learning_rate=1e-3, batch_size=batch_size)
+    neuralnet = VisionTransformer(img_size=input_size, num_classes=3, learning_rate=1e-3, batch_size=batch_size, loss=loss)
     print(len(neuralnet.visionModel.layers))
     training(neuralnet=neuralnet, dataset=dataset, epochs=epochs, batch_size=batch_size)
     if save_path is not None:

@@ -305,10 +305,13 @@ class Transformer(nn.Module):
         self.embeddings.backward(d_hidden, d_feats)
 
 
+LOSSES = ("cce", "my_loss_cat", "focal")
+
+
 class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
     def __init__(self, batch_size, img_size=(256, 80), num_classes=3, learning_rate=1e-3, weight_decay=1e-4, *,
                  in_channels: int = 10, use_vit: bool = False, device: Optional[str] = None, seed: Optional[int] = 0,
-                 transunet: bool = False, adamw: bool = False):
+                 transunet: bool = False, adamw: bool = False, loss: str = "cce", class_factor=None, focal_gamma=None):
         """``transunet=True`` builds the older self-contained copy of this model in TBI_TransUNet.py (BASELINE configs[3]):
         BatchNormalization where ResNest.py / Decoder.py use LayerNormalization (:304,426,465,472,503), conv_4 = 256 channels
         (:368), and the loss is CategoricalCrossentropy(label_smoothing=0.1) with the DEFAULT reduction - the mean over all
@@ -316,8 +319,36 @@ class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
 
         ``learning_rate`` may be a ``schedules.PiecewiseConstantDecay``.  ``adamw=True`` makes ``weight_decay`` (a float or a schedule)
         the decoupled weight decay of tfa.optimizers.AdamW, the optimiser the reference has commented out (:203); by default it stays
-        unused, as in the reference."""
+        unused, as in the reference.
+
+        ``loss`` is the reference's ``self.loss`` (:205-207), fixed at construction (a captured graph holds its numbers):
+          * ``"cce"`` (default): CategoricalCrossentropy(label_smoothing=0.1), as the reference compiles it;
+          * ``"my_loss_cat"``: the method the reference keeps one commented line away (:207, :259-280) as executed - factor 3,
+            ``self.class_factor`` per class, clipped probabilities NOT divided by their class sum;
+          * ``"focal"``: its commented focal line (:272-273, "-1 otherwise" :277) - factor 1, unit weights, exponent ``self.alpha`` = 2
+            unless ``focal_gamma`` (0, or 1..8) is given.  ``class_factor=`` given together with ``"focal"`` is the weighted focal loss with
+            factor 3: the one combination the reference's comments describe (:277) but no line of it ever ran.
+        ``class_factor`` (default the reference's [0.06329, 0.027567, 0.90914], :209) needs one entry per class wherever it is used.
+        Every loss is summed over the pixels and divided by the global batch (``transunet``: averaged over the B*H*W pixels).  The
+        loss is not part of a checkpoint (the reference fixes it in code)."""
         super().__init__()
+        if loss not in LOSSES:
+            raise ValueError(f"loss must be one of {LOSSES}, got {loss!r}")
+        if focal_gamma is not None and loss != "focal":
+            raise ValueError("focal_gamma only applies to loss='focal'")
+        self.alpha = 2                                                                  # :208
+        self.class_factor = [0.06329, 0.027567, 0.90914] if class_factor is None else [float(v) for v in class_factor]   # :209
+        if (loss == "my_loss_cat" or class_factor is not None) and len(self.class_factor) != num_classes:
+            raise ValueError(f"class_factor has {len(self.class_factor)} entries for {num_classes} classes")
+        self.loss_name = loss
+        if loss == "my_loss_cat":
+            self._class_loss = ops.class_loss(self.class_factor, 0.0, 3.0)              # :270
+        elif loss == "focal":
+            gamma = float(self.alpha if focal_gamma is None else focal_gamma)
+            weighted = class_factor is not None
+            self._class_loss = ops.class_loss(self.class_factor if weighted else [1.0] * num_classes, gamma, 3.0 if weighted else 1.0)   # :272-273,277
+        else:
+            self._class_loss = None
         if seed is not None:
             torch.manual_seed(seed)
         assert img_size[0] % 16 == 0 and img_size[1] % 16 == 0, "H and W must be multiples of 16 (four 2x2 poolings)"
@@ -431,12 +462,13 @@ class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
         # :205,:227 sum / GLOBAL batch; TBI_TransUNet.py:546 (default reduction): mean over the B*H*W pixels of the batch
         scale = 1.0 / float(B * H * W) if self.transunet else 1.0 / float(self.batch_size)
         if fused:       # head conv + softmax + loss in one launch (:142, :205, :225-229); falls back to the three launches if it has no kernel
-            if self.decoder._quad.forward_loss(xh, y, probs, self._loss, dlogits, label_smoothing=0.1, clip_eps=1e-7, inv_global_batch=scale):
+            kw = {} if self._class_loss is None else {"class_loss": self._class_loss}       # (no keyword: today's call of today's symbol)
+            if self.decoder._quad.forward_loss(xh, y, probs, self._loss, dlogits, label_smoothing=0.1, clip_eps=1e-7, inv_global_batch=scale, **kw):
                 return probs, dlogits
             logits = self.decoder._head_forward(xh)
             self.decoder._logits = logits
         ops.softmax_loss(logits, y, probs, self._loss, dlogits, HW=H * W, C_classes=self.num_classes, loss_kind=0,
-                         label_smoothing=0.1, clip_eps=1e-7, inv_global_batch=scale, quad_w=qw)
+                         label_smoothing=0.1, clip_eps=1e-7, inv_global_batch=scale, quad_w=qw, class_loss=self._class_loss)
         return probs, dlogits
 
     def _predict_body(self, x):
@@ -459,15 +491,29 @@ class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
             return probs
 
     def compute_loss(self, y_true, y_pred):
-        """VisionTransformer.py:225-227: CategoricalCrossentropy(label_smoothing=0.1, reduction NONE) on PROBABILITIES, summed
-        and divided by the global batch size -> scalar.  (train_step/step use the fused softmax+loss kernel instead.)"""
+        """VisionTransformer.py:225-227: ``self.loss`` - CategoricalCrossentropy(label_smoothing=0.1, reduction NONE) by default, the
+        class loss under ``loss="my_loss_cat"`` / ``"focal"`` - on PROBABILITIES, summed and divided by the global batch size
+        -> scalar.  (train_step/step use the fused softmax+loss kernel instead.)"""
         y_true, y_pred = self._prep_y(y_true), self._prep_y(y_pred)
         H, W = y_pred.shape[1], y_pred.shape[2]
         loss = torch.empty(ops.ACC_FLOATS, dtype=torch.float32, device=self.device)
         ops.fill_f32(loss, 0.0)
         ops.loss_from_probs(y_pred, y_true, loss, HW=H * W, C_classes=y_pred.shape[-1], loss_kind=0, label_smoothing=0.1, clip_eps=1e-7,
-                            inv_global_batch=1.0 / float(self.batch_size))
+                            inv_global_batch=1.0 / float(self.batch_size), class_loss=self._class_loss)
         return loss[0].clone()
+
+    def my_loss_cat(self, y_true, y_pred):
+        """VisionTransformer.py:259-280 as committed, whatever ``loss=`` says: on PROBABILITIES [B,H,W,classes] -> the fp32 [H,W] map
+        -3 * sum over batch and classes of y_smoothed * log(clip(p, 1e-7, 1 - 1e-7)) * class_factor (:270, axis=[0,3]).  ``y_true``
+        is left as it was (the reference's in-place smoothing, :262-263, acts on its own tensor)."""
+        if len(self.class_factor) != y_pred.shape[-1]:
+            raise ValueError(f"class_factor has {len(self.class_factor)} entries for {y_pred.shape[-1]} classes")
+        y_true, y_pred = self._prep_y(y_true), self._prep_y(y_pred)
+        H, W = y_pred.shape[1], y_pred.shape[2]
+        out = torch.empty((H, W), dtype=torch.float32, device=self.device)
+        ops.loss_from_probs(y_pred, y_true, out, HW=H * W, C_classes=y_pred.shape[-1], label_smoothing=0.1, clip_eps=1e-7,
+                            class_loss=ops.class_loss(self.class_factor, 0.0, 3.0), as_map=True)
+        return out
 
     def step(self, x, y):
         """Evaluation step (:248-254): -> (loss, probs)."""
@@ -494,7 +540,7 @@ class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
         return [self.flat.flat] + self.optimizer.state_tensors() + bn
 
     def train_step(self, x, y):
-        """One optimisation step (:235-246): -> (loss, probs).  Loss = sum of per-pixel CCE / GLOBAL batch size.
+        """One optimisation step (:235-246): -> (loss, probs).  Loss = sum of the per-pixel loss (CCE unless ``loss=`` chose another) / GLOBAL batch size.
         After ``capture_graph`` the returned loss and probabilities are the captured step's static buffers: valid until the next call
         (a clone of the scalar would be one more dispatch - 4.6 us - behind every replay).  An input whose shape, dtype, strides or device
         differ from the captured ones runs eagerly."""

@@ -84,6 +84,11 @@ class GemmDesc(C.Structure):
                 ("xs1", c_i64), ("xs2", c_i64), ("ws1", c_i64), ("ws2", c_i64), ("ys1", c_i64), ("ys2", c_i64), ("flags", c_i32)]
 
 
+class ClassLoss(C.Structure):
+    """UssegClassLoss: VisionTransformer.my_loss_cat and its focal variant (usseg.h); passed by reference, copied into the launch."""
+    _fields_ = [("w", c_f32 * 8), ("gamma", c_f32), ("factor", c_f32)]
+
+
 class FlashDesc(C.Structure):
     _fields_ = [("B", c_i32), ("N", c_i32), ("H", c_i32), ("head_dim", c_i32), ("ld_qkv", c_i32), ("ld_o", c_i32), ("scale", c_f32)]
 
@@ -184,6 +189,10 @@ _PROTOS = {
     "usseg_softmax_loss_fwd_bwd": (C.c_int, [P(LossDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "usseg_head_quad_softmax_loss": (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_f32, c_f32, c_f32, c_vp]),
     "usseg_loss_from_probs": (C.c_int, [P(LossDesc), c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "usseg_softmax_loss_fwd_bwd_cl": (C.c_int, [P(LossDesc), P(ClassLoss), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "usseg_head_quad_softmax_loss_cl": (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_f32, c_f32, c_f32,
+                                                  P(ClassLoss), c_vp]),
+    "usseg_loss_from_probs_cl": (C.c_int, [P(LossDesc), P(ClassLoss), c_vp, c_vp, c_vp, c_i32, c_vp]),
     "usseg_quad_bias_expand": (C.c_int, [c_vp, c_i32, c_i32, c_vp, c_vp]),
     "usseg_space_to_depth2": (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp]),
     "usseg_tconv_quad_fwd": (C.c_int, [P(ConvDesc), c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),

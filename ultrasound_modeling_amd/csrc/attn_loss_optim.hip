@@ -2,6 +2,7 @@
 // and the optimiser (global-norm clip + Adam) for gfx950.  The big tensors are streamed 16 bytes per lane; the
 // MLP is a few hundred FLOPs per workgroup and runs in fp32 out of LDS.
 #include "common.h"
+#include <cmath>
 
 static inline int lanes_per_pixel(int chunks) {
   int l = 1;
@@ -632,10 +633,29 @@ extern "C" int usseg_splitattn_apply_bwd_dy(const UssegSplitAttnDesc* d, const v
 // One pixel: softmax, probabilities out, loss term (returned) and d(sum loss)/d logits.
 // CC = compile-time class count (0 = read d.C): with a run-time C the per-class register arrays are indexed through select chains
 // (600 v_cndmask + 480 s_cselect in the ISA, 36 us for 1M pixels); the reference's 3 classes get the unrolled form.
-template <int CC>
+// The class loss (usseg.h, UssegClassLoss) as the kernels take it: fw[c] = factor * w[c], folded on the host.
+struct ClassLossK { float fw[8]; float gamma; };
+// One class of one pixel: its loss term (returned) and d term / d p (dLdp), both times `scale`.  FOCAL = false is my_loss_cat as committed
+// (VisionTransformer.py:270): no pow, no 1 - pc.  The gradient is zero where p was clipped (the open interval of loss_kind 0).
+template <bool FOCAL>
+__device__ __forceinline__ float class_loss_term(float p, float ys, float fw, float gamma, float eps, float scale, float& dLdp) {
+  const float pc = fminf(fmaxf(p, eps), 1.f - eps);
+  const float lg = __logf(pc);
+  const bool inside = p > eps && p < 1.f - eps;
+  const float t = fw * ys * scale;
+  if (!FOCAL) {
+    dLdp = inside ? -t / pc : 0.f;
+    return -t * lg;
+  }
+  const float om = 1.f - pc;                          // > 0: the entry points refuse a clip_eps that 1 - clip_eps rounds away in fp32
+  const float pw = __expf(gamma * __logf(om));        // (1 - pc)^gamma
+  dLdp = inside ? t * (gamma * (pw / om) * lg - pw / pc) : 0.f;
+  return -t * pw * lg;
+}
+template <int CC, bool CL = false>
 __device__ __forceinline__ float softmax_loss_pixel(const UssegLossDesc& d, int b, int hw, const float* __restrict__ logits,
                                                     const float* __restrict__ y_true, const float* __restrict__ scale, float* __restrict__ probs,
-                                                    bf16_t* __restrict__ dlogits) {
+                                                    bf16_t* __restrict__ dlogits, const ClassLossK* cl = nullptr) {
   const int C = CC ? CC : d.C;
   const int64_t m = (int64_t)b * d.HW + hw;      // (image, pixel) come from the grid: no 64-bit division per pixel
   float z[8], p[8], yt[8];
@@ -659,7 +679,18 @@ __device__ __forceinline__ float softmax_loss_pixel(const UssegLossDesc& d, int 
   _Pragma("unroll") for (int c = 0; c < C; ++c) yt[c] = y_true[m * C + c];
   float dLdp[8];
   float l = 0.f;
-  if (d.loss_kind == 0) {
+  if (CL) {
+    // loss_kind 2: VisionTransformer.my_loss_cat / its focal line (VisionTransformer.py:259-280; usseg.h UssegClassLoss)
+    if (cl->gamma == 0.f) {
+      _Pragma("unroll") for (int c = 0; c < C; ++c)
+        l += class_loss_term<false>(p[c], yt[c] * (1.f - d.label_smoothing) + d.label_smoothing / (float)C, cl->fw[c], 0.f, d.clip_eps,
+                                    d.inv_global_batch, dLdp[c]);
+    } else {
+      _Pragma("unroll") for (int c = 0; c < C; ++c)
+        l += class_loss_term<true>(p[c], yt[c] * (1.f - d.label_smoothing) + d.label_smoothing / (float)C, cl->fw[c], cl->gamma, d.clip_eps,
+                                   d.inv_global_batch, dLdp[c]);
+    }
+  } else if (d.loss_kind == 0) {
     // CategoricalCrossentropy(label_smoothing) on probabilities (VisionTransformer.py:205)
     float S = 0.f;
     _Pragma("unroll") for (int c = 0; c < C; ++c) S += p[c];
@@ -701,16 +732,22 @@ __device__ __forceinline__ float softmax_loss_pixel(const UssegLossDesc& d, int 
 
 // Reproducible reductions: loss_kind 0 sums the workgroup totals in workgroup order (grid_ordered_sum, loss = [USSEG_ACC_FLOATS]);
 // loss_kind 1 gives every pixel of the [H,W] map to ONE thread that walks the batch in order (no atomics on the map).
-template <int CC>
+// loss_kind 2 (the class loss, CL = true) takes the scalar form too; its parameters are the last kernel argument, an empty struct for loss_kind 0 / 1.
+template <bool CL> struct ClassLossArg {};
+template <> struct ClassLossArg<true> : ClassLossK {};
+__device__ __forceinline__ const ClassLossK* class_loss_ptr(const ClassLossArg<false>&) { return nullptr; }
+__device__ __forceinline__ const ClassLossK* class_loss_ptr(const ClassLossArg<true>& a) { return &a; }
+template <int CC, bool CL = false>
 __global__ __launch_bounds__(256) void softmax_loss_kernel(const UssegLossDesc d, const float* __restrict__ logits, const float* __restrict__ y_true,
                                                             const float* __restrict__ scale, float* __restrict__ probs, float* loss,
-                                                            bf16_t* __restrict__ dlogits) {
+                                                            bf16_t* __restrict__ dlogits, const ClassLossArg<CL> cla) {
   __shared__ float red[4];
+  const ClassLossK* cl = class_loss_ptr(cla);
   if (d.loss_kind == 1 && y_true) {
     const int nb = (int)(d.M / d.HW);
     for (int64_t hw = (int64_t)blockIdx.x * 256 + threadIdx.x; hw < d.HW; hw += (int64_t)gridDim.x * 256) {
       float l = 0.f;
-      for (int b = 0; b < nb; ++b) l += softmax_loss_pixel<CC>(d, b, (int)hw, logits, y_true, scale, probs, dlogits);
+      for (int b = 0; b < nb; ++b) l += softmax_loss_pixel<CC, CL>(d, b, (int)hw, logits, y_true, scale, probs, dlogits, cl);
       loss[hw] = l;
     }
     return;
@@ -722,10 +759,10 @@ __global__ __launch_bounds__(256) void softmax_loss_kernel(const UssegLossDesc d
   for (; hw + 3 * stride < d.HW; hw += 4 * stride) {
     float l4[4];
 #pragma unroll
-    for (int u = 0; u < 4; ++u) l4[u] = softmax_loss_pixel<CC>(d, b, hw + u * stride, logits, y_true, scale, probs, dlogits);
+    for (int u = 0; u < 4; ++u) l4[u] = softmax_loss_pixel<CC, CL>(d, b, hw + u * stride, logits, y_true, scale, probs, dlogits, cl);
     lsum += (l4[0] + l4[1]) + (l4[2] + l4[3]);
   }
-  for (; hw < d.HW; hw += stride) lsum += softmax_loss_pixel<CC>(d, b, hw, logits, y_true, scale, probs, dlogits);
+  for (; hw < d.HW; hw += stride) lsum += softmax_loss_pixel<CC, CL>(d, b, hw, logits, y_true, scale, probs, dlogits, cl);
   if (y_true) {
     for (int msk = 32; msk >= 1; msk >>= 1) lsum += __shfl_xor(lsum, msk, 64);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = lsum;
@@ -734,33 +771,86 @@ __global__ __launch_bounds__(256) void softmax_loss_kernel(const UssegLossDesc d
   }
 }
 
-extern "C" int usseg_softmax_loss_fwd_bwd(const UssegLossDesc* d, const float* logits, const float* y_true, const float* scale, float* probs,
-                                          float* loss, void* dlogits, usseg_stream_t stream) {
+// The argument checks of the class-loss entry points (each before any launch, each with its own message) and the host-side fold fw = factor * w.
+static int class_loss_args(const char* who, const UssegClassLoss* cl, int C, int maxC, ClassLossK* k) {
+  USSEG_CHECK_ARG(cl, "%s: null class-loss struct", who);
+  USSEG_CHECK_ARG(C >= 1 && C <= maxC, "%s: 1 <= C <= %d", who, maxC);
+  USSEG_CHECK_ARG(cl->gamma == 0.f || (cl->gamma >= 1.f && cl->gamma <= 8.f), "%s: gamma must be 0 or lie in [1, 8]", who);
+  USSEG_CHECK_ARG(std::isfinite(cl->factor) && cl->factor >= 0.f, "%s: factor must be finite and >= 0", who);
+  for (int c = 0; c < C; ++c) USSEG_CHECK_ARG(std::isfinite(cl->w[c]) && cl->w[c] >= 0.f, "%s: class weights must be finite and >= 0", who);
+  for (int c = 0; c < 8; ++c) k->fw[c] = c < C ? cl->factor * cl->w[c] : 0.f;
+  k->gamma = cl->gamma;
+  return USSEG_OK;
+}
+static int class_loss_desc(const char* who, const UssegLossDesc* d) {
+  USSEG_CHECK_ARG(d->loss_kind == 2, "%s: the descriptor must say loss_kind 2", who);
+  USSEG_CHECK_ARG(d->clip_eps > 0.f && 1.f - d->clip_eps < 1.f && d->clip_eps < 0.5f, "%s: clip_eps must be > 0 and representable below 1 in fp32", who);
+  return USSEG_OK;
+}
+
+// The pointer / layout checks and the grid shared by usseg_softmax_loss_fwd_bwd and its class-loss form (*empty: nothing to launch).
+static int softmax_loss_check(const UssegLossDesc* d, const float* logits, const float* y_true, const float* probs, const float* loss,
+                              const void* dlogits) {
   USSEG_CHECK_ARG(d && logits && probs, "null pointer");
   USSEG_CHECK_ARG(d->C >= 1 && d->C <= 8 && d->ldl >= d->C, "softmax_loss: 1 <= C <= 8");
   USSEG_CHECK_ARG(!y_true || loss, "loss pointer required with y_true");
   USSEG_CHECK_ARG(d->quad_w == 0 || (d->C <= 4 && d->ldl == 16 && d->quad_w % 2 == 0 && d->HW % (2 * d->quad_w) == 0),
                   "softmax_loss: quad layout needs C <= 4, ldl == 16, even H and W");
   USSEG_CHECK_ARG(!dlogits || (d->lddl == (d->quad_w ? 16 : 8)), "dlogits stride must be 8 (16 in the quad layout)");
-  USSEG_CHECK_ARG(d->loss_kind == 0 || (d->loss_kind == 1 && scale), "loss_kind 1 needs scale");
-  if (d->M <= 0) return USSEG_OK;
+  return USSEG_OK;
+}
+static int softmax_loss_grid(const UssegLossDesc* d, bool map_form, dim3* grid, bool* empty) {
+  *empty = d->M <= 0;
+  if (*empty) return USSEG_OK;
   USSEG_CHECK_ARG(d->HW > 0 && d->M % d->HW == 0, "softmax_loss: M must be a multiple of HW");
   USSEG_CHECK_ARG(d->HW < (1 << 30) && d->M / d->HW <= 65535, "softmax_loss: image too large");
   const int nb = (int)(d->M / d->HW);
-  dim3 grid;
-  if (y_true && d->loss_kind == 1) {
+  if (map_form) {
     int64_t g = cdiv64(d->HW, 256);
-    grid = dim3((unsigned)(g > 2048 ? 2048 : g));
+    *grid = dim3((unsigned)(g > 2048 ? 2048 : g));
   } else {
     static const int ppt = getenv("USSEG_LOSS_PPT") ? atoi(getenv("USSEG_LOSS_PPT")) : 4;
     int64_t g = cdiv64(d->HW, 256 * ppt);          // <= 2048 workgroups in all: the slots of the ordered sum
     if (g * nb > 2048) g = 2048 / nb > 0 ? 2048 / nb : 1;
     USSEG_CHECK_ARG(g * nb <= 2048, "softmax_loss: more than 2048 images");
-    grid = dim3((unsigned)g, (unsigned)nb);
+    *grid = dim3((unsigned)g, (unsigned)nb);
   }
-  if (d->C == 3) hipLaunchKernelGGL(softmax_loss_kernel<3>, grid, dim3(256), 0, (hipStream_t)stream, *d, logits, y_true, scale, probs, loss, (bf16_t*)dlogits);
-  else hipLaunchKernelGGL(softmax_loss_kernel<0>, grid, dim3(256), 0, (hipStream_t)stream, *d, logits, y_true, scale, probs, loss, (bf16_t*)dlogits);
+  return USSEG_OK;
+}
+
+extern "C" int usseg_softmax_loss_fwd_bwd(const UssegLossDesc* d, const float* logits, const float* y_true, const float* scale, float* probs,
+                                          float* loss, void* dlogits, usseg_stream_t stream) {
+  dim3 grid;
+  bool empty;
+  int rc = softmax_loss_check(d, logits, y_true, probs, loss, dlogits);
+  if (rc) return rc;
+  USSEG_CHECK_ARG(d->loss_kind == 0 || (d->loss_kind == 1 && scale), "loss_kind 1 needs scale");
+  rc = softmax_loss_grid(d, y_true && d->loss_kind == 1, &grid, &empty);
+  if (rc || empty) return rc;
+  if (d->C == 3) hipLaunchKernelGGL(softmax_loss_kernel<3>, grid, dim3(256), 0, (hipStream_t)stream, *d, logits, y_true, scale, probs, loss, (bf16_t*)dlogits, ClassLossArg<false>{});
+  else hipLaunchKernelGGL(softmax_loss_kernel<0>, grid, dim3(256), 0, (hipStream_t)stream, *d, logits, y_true, scale, probs, loss, (bf16_t*)dlogits, ClassLossArg<false>{});
   return usseg_check_launch("softmax_loss");
+}
+
+extern "C" int usseg_softmax_loss_fwd_bwd_cl(const UssegLossDesc* d, const UssegClassLoss* cl, const float* logits, const float* y_true, float* probs,
+                                             float* loss, void* dlogits, usseg_stream_t stream) {
+  dim3 grid;
+  bool empty;
+  ClassLossK k;
+  USSEG_CHECK_ARG(d, "softmax_loss_cl: null descriptor");
+  int rc = class_loss_args("softmax_loss_cl", cl, d->C, d->quad_w ? 4 : 8, &k);
+  if (rc) return rc;
+  if ((rc = class_loss_desc("softmax_loss_cl", d))) return rc;
+  USSEG_CHECK_ARG(!dlogits || y_true, "softmax_loss_cl: dlogits needs y_true");
+  if ((rc = softmax_loss_check(d, logits, y_true, probs, loss, dlogits))) return rc;
+  rc = softmax_loss_grid(d, false, &grid, &empty);
+  if (rc || empty) return rc;
+  ClassLossArg<true> a;
+  static_cast<ClassLossK&>(a) = k;
+  const float* no_scale = nullptr;
+  if (d->C == 3) hipLaunchKernelGGL((softmax_loss_kernel<3, true>), grid, dim3(256), 0, (hipStream_t)stream, *d, logits, y_true, no_scale, probs, loss, (bf16_t*)dlogits, a);
+  else hipLaunchKernelGGL((softmax_loss_kernel<0, true>), grid, dim3(256), 0, (hipStream_t)stream, *d, logits, y_true, no_scale, probs, loss, (bf16_t*)dlogits, a);
+  return usseg_check_launch("softmax_loss_cl");
 }
 
 // ---- the quad-form head, its softmax and the loss in ONE launch -------------------------------------------------------------------
@@ -777,8 +867,12 @@ struct HeadQuad {
   int32_t B, h, w, ldx, tiles_x, C;
   float label_smoothing, clip_eps, inv_global_batch;
 };
-template <int CC, int CP>
-__global__ __launch_bounds__(256) void head_quad_loss_kernel(const HeadQuad p) {      // (72 channels: 192 VGPRs, two workgroups per CU; a bound of three spills)
+// The loss is a compile-time property of the kernel: LK 0 = CategoricalCrossentropy (loss_kind 0, argument type HeadQuad: the instantiations
+// that existed before the class loss, unchanged), LK 2 = the class loss with gamma == 0, LK 3 = with gamma > 0 (both loss_kind 2 of the ABI;
+// argument type HeadQuadCL, which appends fw = factor * w and gamma).
+struct HeadQuadCL : HeadQuad { float fw[4]; float gamma; };
+template <int CC, int CP, int LK, class PT>
+__global__ __launch_bounds__(256) void head_quad_loss_kernel(const PT p) {      // (72 channels: 192 VGPRs, two workgroups per CU; a bound of three spills)
 #if defined(__HIP_DEVICE_COMPILE__)
   constexpr int TW = 16, HWD = TW + 2, CH = CP / 8, KTOT = 9 * CP, KS = (KTOT + 31) / 32, NIT = (HWD * HWD * CH + 255) / 256;
   __shared__ __attribute__((aligned(16))) bf16_t XT[HWD * HWD * CP];        // the halo tile [18*18][CP]
@@ -865,7 +959,26 @@ __global__ __launch_bounds__(256) void head_quad_loss_kernel(const HeadQuad p) {
       const float inv = 1.f / sum;
 #pragma unroll
       for (int c = 0; c < CC; ++c) { pr[c] *= inv; p.probs[m * CC + c] = pr[c]; }
-      if (p.y_true) {       // CategoricalCrossentropy(label_smoothing) on probabilities: the arithmetic of softmax_loss_pixel, loss_kind 0
+      if constexpr (LK != 0) {
+        if (p.y_true) {     // the class loss: the arithmetic of softmax_loss_pixel, loss_kind 2 (class_loss_term)
+          float dLdp[4], l = 0.f;
+#pragma unroll
+          for (int c = 0; c < CC; ++c)
+            l += class_loss_term<LK == 3>(pr[c], ytv[i][c] * (1.f - p.label_smoothing) + p.label_smoothing / (float)CC, p.fw[c], p.gamma, p.clip_eps,
+                                          p.inv_global_batch, dLdp[c]);
+          lsum += l;
+          if (p.dl) {
+            float dot = 0.f, o[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int c = 0; c < CC; ++c) dot += dLdp[c] * pr[c];
+#pragma unroll
+            for (int c = 0; c < CC; ++c) o[c] = pr[c] * (dLdp[c] - dot);
+            uint2 v;
+            v.x = pack2bf(o[0], o[1]); v.y = pack2bf(o[2], o[3]);
+            *reinterpret_cast<uint2*>(p.dl + (((int64_t)b * p.h + gy) * p.w + gx) * 16 + 4 * q) = v;
+          }
+        }
+      } else if (p.y_true) {       // CategoricalCrossentropy(label_smoothing) on probabilities: the arithmetic of softmax_loss_pixel, loss_kind 0
         float u[4], dLdp[4];
         const float* yt = ytv[i];
         float S = 0.f, ubar = 0.f, l = 0.f;
@@ -902,44 +1015,78 @@ __global__ __launch_bounds__(256) void head_quad_loss_kernel(const HeadQuad p) {
   }
 #endif
 }
-template <int CC, int CP>
-static void head_quad_launch(const HeadQuad& p, dim3 grid, hipStream_t s) {
-  hipLaunchKernelGGL((head_quad_loss_kernel<CC, CP>), grid, dim3(256), 0, s, p);
+template <int CC, int CP, int LK, class PT>
+static void head_quad_launch(const PT& p, dim3 grid, hipStream_t s) {
+  hipLaunchKernelGGL((head_quad_loss_kernel<CC, CP, LK, PT>), grid, dim3(256), 0, s, p);
 }
-template <int CP>
-static void head_quad_launch_c(const HeadQuad& p, dim3 grid, hipStream_t s) {
+template <int CP, int LK, class PT>
+static void head_quad_launch_c(const PT& p, dim3 grid, hipStream_t s) {
   switch (p.C) {
-    case 1: head_quad_launch<1, CP>(p, grid, s); break;
-    case 2: head_quad_launch<2, CP>(p, grid, s); break;
-    case 3: head_quad_launch<3, CP>(p, grid, s); break;
-    default: head_quad_launch<4, CP>(p, grid, s); break;
+    case 1: head_quad_launch<1, CP, LK>(p, grid, s); break;
+    case 2: head_quad_launch<2, CP, LK>(p, grid, s); break;
+    case 3: head_quad_launch<3, CP, LK>(p, grid, s); break;
+    default: head_quad_launch<4, CP, LK>(p, grid, s); break;
   }
 }
-extern "C" int usseg_head_quad_softmax_loss(const void* x, int32_t B, int32_t h, int32_t w, int32_t Cin_phys, int32_t ldx, const void* wq, const float* bias, int32_t C,
-                                            const float* y_true, float* probs, float* loss, void* dlogits, float label_smoothing, float clip_eps,
-                                            float inv_global_batch, usseg_stream_t stream) {
+// The checks, the parameter block and the grid shared by usseg_head_quad_softmax_loss and its class-loss form.
+static int head_quad_plan(HeadQuad* p, dim3* grid, const void* x, int32_t B, int32_t h, int32_t w, int32_t Cin_phys, int32_t ldx, const void* wq,
+                          const float* bias, int32_t C, const float* y_true, float* probs, float* loss, void* dlogits, float label_smoothing,
+                          float clip_eps, float inv_global_batch) {
   USSEG_CHECK_ARG(x && wq && bias && probs && B > 0 && h > 0 && w > 0 && Cin_phys >= 8 && Cin_phys % 8 == 0 && ldx >= Cin_phys && ldx % 8 == 0 && C >= 1 && C <= 4,
                   "head_quad_softmax_loss: bad arguments");
   USSEG_CHECK_ARG(!y_true || loss, "head_quad_softmax_loss: loss pointer required with y_true");
   USSEG_CHECK_ARG(!dlogits || y_true, "head_quad_softmax_loss: dlogits needs y_true");
-  HeadQuad p = {};
-  p.x = (const bf16_t*)x; p.wq = (const bf16_t*)wq; p.bias = bias; p.y_true = y_true; p.probs = probs; p.loss = loss; p.dl = (bf16_t*)dlogits;
-  p.B = B; p.h = h; p.w = w; p.ldx = ldx; p.C = C; p.tiles_x = (w + 15) / 16;
-  p.label_smoothing = label_smoothing; p.clip_eps = clip_eps; p.inv_global_batch = inv_global_batch;
-  const int64_t tiles = (int64_t)p.tiles_x * ((h + 15) / 16);
+  p->x = (const bf16_t*)x; p->wq = (const bf16_t*)wq; p->bias = bias; p->y_true = y_true; p->probs = probs; p->loss = loss; p->dl = (bf16_t*)dlogits;
+  p->B = B; p->h = h; p->w = w; p->ldx = ldx; p->C = C; p->tiles_x = (w + 15) / 16;
+  p->label_smoothing = label_smoothing; p->clip_eps = clip_eps; p->inv_global_batch = inv_global_batch;
+  const int64_t tiles = (int64_t)p->tiles_x * ((h + 15) / 16);
   // instantiated for the head widths of the models (Decoder.py: 16 channels + the re-injected 56 = 72; 16 for a plain head); more workgroups
   // than the ordered sum has slots, or another width: the caller runs conv + softmax_loss
   if (tiles * B > USSEG_ACC_FLOATS - 2 || B > 65535 || (Cin_phys != 16 && Cin_phys != 72)) {
     usseg_set_error("head_quad_softmax_loss: no fused kernel for this size");
     return USSEG_ERR_UNSUPPORTED;
   }
-  const dim3 grid((unsigned)tiles, (unsigned)B);
+  *grid = dim3((unsigned)tiles, (unsigned)B);
+  return USSEG_OK;
+}
+extern "C" int usseg_head_quad_softmax_loss(const void* x, int32_t B, int32_t h, int32_t w, int32_t Cin_phys, int32_t ldx, const void* wq, const float* bias, int32_t C,
+                                            const float* y_true, float* probs, float* loss, void* dlogits, float label_smoothing, float clip_eps,
+                                            float inv_global_batch, usseg_stream_t stream) {
+  HeadQuad p = {};
+  dim3 grid;
+  const int rc = head_quad_plan(&p, &grid, x, B, h, w, Cin_phys, ldx, wq, bias, C, y_true, probs, loss, dlogits, label_smoothing, clip_eps, inv_global_batch);
+  if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
   const int slot = usseg_prof_start(4, s);       // timed with the fused tile kernels (a conv + what follows it in one launch)
-  if (Cin_phys == 72) head_quad_launch_c<72>(p, grid, s);
-  else head_quad_launch_c<16>(p, grid, s);
+  if (Cin_phys == 72) head_quad_launch_c<72, 0>(p, grid, s);
+  else head_quad_launch_c<16, 0>(p, grid, s);
   usseg_prof_stop(4, slot, s);
   return usseg_check_launch("head_quad_softmax_loss");
+}
+extern "C" int usseg_head_quad_softmax_loss_cl(const void* x, int32_t B, int32_t h, int32_t w, int32_t Cin_phys, int32_t ldx, const void* wq, const float* bias,
+                                               int32_t C, const float* y_true, float* probs, float* loss, void* dlogits, float label_smoothing,
+                                               float clip_eps, float inv_global_batch, const UssegClassLoss* cl, usseg_stream_t stream) {
+  ClassLossK k;
+  int rc = class_loss_args("head_quad_softmax_loss_cl", cl, C, 4, &k);
+  if (rc) return rc;
+  USSEG_CHECK_ARG(clip_eps > 0.f && 1.f - clip_eps < 1.f && clip_eps < 0.5f, "head_quad_softmax_loss_cl: clip_eps must be > 0 and representable below 1 in fp32");
+  HeadQuadCL p = {};
+  dim3 grid;
+  if ((rc = head_quad_plan(&p, &grid, x, B, h, w, Cin_phys, ldx, wq, bias, C, y_true, probs, loss, dlogits, label_smoothing, clip_eps, inv_global_batch)))
+    return rc;
+  for (int c = 0; c < 4; ++c) p.fw[c] = k.fw[c];
+  p.gamma = k.gamma;
+  hipStream_t s = (hipStream_t)stream;
+  const int slot = usseg_prof_start(4, s);
+  if (k.gamma == 0.f) {
+    if (Cin_phys == 72) head_quad_launch_c<72, 2>(p, grid, s);
+    else head_quad_launch_c<16, 2>(p, grid, s);
+  } else {
+    if (Cin_phys == 72) head_quad_launch_c<72, 3>(p, grid, s);
+    else head_quad_launch_c<16, 3>(p, grid, s);
+  }
+  usseg_prof_stop(4, slot, s);
+  return usseg_check_launch("head_quad_softmax_loss_cl");
 }
 
 // compute_loss / my_loss_cat on probabilities (the reference's public loss methods): same arithmetic as the fused kernel above
@@ -981,6 +1128,53 @@ __global__ __launch_bounds__(256) void loss_from_probs_kernel(const UssegLossDes
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = lsum;
   __syncthreads();
   grid_ordered_sum((red[0] + red[1]) + (red[2] + red[3]), loss, gridDim.x);
+}
+// The class loss on probabilities: the scalar (ordered sum), or the [HW] map with one thread owning a pixel and walking the batch in order.
+__device__ __forceinline__ float class_loss_from_probs_pixel(const UssegLossDesc& d, const ClassLossK& cl, int64_t m, const float* probs,
+                                                             const float* y_true, float scale) {
+  float l = 0.f, unused;
+  for (int c = 0; c < d.C; ++c) {
+    const float ys = y_true[m * d.C + c] * (1.f - d.label_smoothing) + d.label_smoothing / (float)d.C;
+    l += cl.gamma == 0.f ? class_loss_term<false>(probs[m * d.C + c], ys, cl.fw[c], 0.f, d.clip_eps, scale, unused)
+                         : class_loss_term<true>(probs[m * d.C + c], ys, cl.fw[c], cl.gamma, d.clip_eps, scale, unused);
+  }
+  return l;
+}
+__global__ __launch_bounds__(256) void loss_from_probs_cl_kernel(const UssegLossDesc d, const ClassLossK cl, const float* probs, const float* y_true,
+                                                                  float* loss, int as_map) {
+  __shared__ float red[4];
+  if (as_map) {
+    const int nb = (int)(d.M / d.HW);
+    for (int64_t hw = (int64_t)blockIdx.x * 256 + threadIdx.x; hw < d.HW; hw += (int64_t)gridDim.x * 256) {
+      float l = 0.f;
+      for (int b = 0; b < nb; ++b) l += class_loss_from_probs_pixel(d, cl, (int64_t)b * d.HW + hw, probs, y_true, 1.f);
+      loss[hw] = l;
+    }
+    return;
+  }
+  float lsum = 0.f;
+  for (int64_t m = (int64_t)blockIdx.x * 256 + threadIdx.x; m < d.M; m += (int64_t)gridDim.x * 256)
+    lsum += class_loss_from_probs_pixel(d, cl, m, probs, y_true, d.inv_global_batch);
+  for (int msk = 32; msk >= 1; msk >>= 1) lsum += __shfl_xor(lsum, msk, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = lsum;
+  __syncthreads();
+  grid_ordered_sum((red[0] + red[1]) + (red[2] + red[3]), loss, gridDim.x);
+}
+extern "C" int usseg_loss_from_probs_cl(const UssegLossDesc* d, const UssegClassLoss* cl, const float* probs, const float* y_true, float* loss,
+                                        int32_t as_map, usseg_stream_t stream) {
+  ClassLossK k;
+  USSEG_CHECK_ARG(d, "loss_from_probs_cl: null descriptor");
+  int rc = class_loss_args("loss_from_probs_cl", cl, d->C, 8, &k);
+  if (rc) return rc;
+  if ((rc = class_loss_desc("loss_from_probs_cl", d))) return rc;
+  USSEG_CHECK_ARG(probs && y_true && loss, "loss_from_probs_cl: null pointer");
+  USSEG_CHECK_ARG(d->HW > 0, "loss_from_probs_cl: HW must be positive");
+  if (d->M <= 0) return USSEG_OK;
+  USSEG_CHECK_ARG(d->M % d->HW == 0, "loss_from_probs_cl: M must be a multiple of HW");
+  int64_t g = as_map ? cdiv64(d->HW, 256) : cdiv64(d->M, 256 * 4);
+  if (g > 2048) g = 2048;
+  hipLaunchKernelGGL(loss_from_probs_cl_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, *d, k, probs, y_true, loss, (int)as_map);
+  return usseg_check_launch("loss_from_probs_cl");
 }
 extern "C" int usseg_loss_from_probs(const UssegLossDesc* d, const float* probs, const float* y_true, const float* scale, float* loss,
                                      usseg_stream_t stream) {

@@ -294,7 +294,8 @@ class QuadHead:
 
     def forward_loss(self, x, y_true, probs, loss, dlogits, **kw) -> bool:
         """The head conv, its softmax and the loss in ONE launch (csrc/attn_loss_optim.hip head_quad_loss_kernel); leaves the state ``forward``
-        leaves.  False - nothing done - when there is no fused kernel for this size (ordered-sum slots, LDS)."""
+        leaves.  False - nothing done - when there is no fused kernel for this size (ordered-sum slots, LDS).  ``class_loss=ops.class_loss(...)``
+        among the keywords selects that loss instead of CategoricalCrossentropy (its own instantiations of the same kernel)."""
         if not ops.head_quad_softmax_loss(x, self.wq_f, self.head.bias.data, self.head.cout, y_true, probs, loss, dlogits, **kw):
             return False
         self._x = self.head._x = x

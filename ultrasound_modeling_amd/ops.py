@@ -1005,35 +1005,73 @@ def splitattn_bwd(d: SplitAttnDesc, y, dout, params, grads, g, s, ws, dy):
 
 
 # ------------------------------------------------------------------------------------------------ head softmax + loss
+def class_loss(w, gamma=0.0, factor=1.0) -> L.ClassLoss:
+    """A ``UssegClassLoss`` (usseg.h): l = -factor * sum_c w[c] * y_smoothed[c] * (1 - p[c])^gamma * log p[c] on clipped, un-normalised
+    probabilities - VisionTransformer.my_loss_cat (factor 3, w = class_factor, gamma 0) and its focal line (factor 1, w = 1, gamma = alpha).
+    ValueError for what the library would refuse: more than 8 weights, a gamma that is neither 0 nor in [1, 8], a negative or non-finite number."""
+    w = [float(v) for v in w]
+    gamma, factor = float(gamma), float(factor)
+    if not 1 <= len(w) <= 8:
+        raise ValueError(f"class loss: 1 to 8 class weights, got {len(w)}")
+    if not (gamma == 0.0 or 1.0 <= gamma <= 8.0):
+        raise ValueError(f"class loss: gamma must be 0 or lie in [1, 8], got {gamma}")
+    if not all(math.isfinite(v) and v >= 0.0 for v in w + [factor]):
+        raise ValueError(f"class loss: weights and factor must be finite and >= 0, got {w}, {factor}")
+    return L.ClassLoss((L.c_f32 * 8)(*w), gamma, factor)
+
+
 def softmax_loss(logits, y_true, probs, loss, dlogits, *, HW, C_classes, loss_kind=0, label_smoothing=0.1, clip_eps=1e-7,
-                 inv_global_batch=1.0, scale=None, quad_w=0):
+                 inv_global_batch=1.0, scale=None, quad_w=0, class_loss=None):
     """logits fp32 [..., ldl]; y_true fp32 [..., C] or None; probs fp32 [..., C]; dlogits bf16 [..., 8] or None.
-    ``quad_w`` = full-resolution width when logits / dlogits are in the head's space-to-depth layout [B,H/2,W/2,16]."""
+    ``quad_w`` = full-resolution width when logits / dlogits are in the head's space-to-depth layout [B,H/2,W/2,16].
+    ``class_loss`` (``ops.class_loss(...)``): the loss is loss_kind 2, the scalar form of that class loss, instead of ``loss_kind``."""
     M = probs.numel() // C_classes
     ldl = logits.shape[-1]
+    if class_loss is not None:
+        assert scale is None and (loss is None or loss.numel() >= ACC_FLOATS)
+        d = LossDesc(M, HW, C_classes, ldl, 16 if quad_w else 8, 2, label_smoothing, clip_eps, inv_global_batch, quad_w)
+        L.check(L.load().usseg_softmax_loss_fwd_bwd_cl(C.byref(d), C.byref(class_loss), logits.data_ptr(), _ptr(y_true), probs.data_ptr(), _ptr(loss),
+                                                       _ptr(dlogits), _stream()), "softmax_loss_cl")
+        return
     assert loss is None or loss_kind == 1 or loss.numel() >= ACC_FLOATS, "the scalar loss accumulates through a USSEG_ACC_FLOATS buffer"
     d = LossDesc(M, HW, C_classes, ldl, 16 if quad_w else 8, loss_kind, label_smoothing, clip_eps, inv_global_batch, quad_w)
     L.check(L.load().usseg_softmax_loss_fwd_bwd(C.byref(d), logits.data_ptr(), _ptr(y_true), _ptr(scale), probs.data_ptr(), _ptr(loss),
                                                 _ptr(dlogits), _stream()), "softmax_loss")
 
 
-def head_quad_softmax_loss(x, wq, bias, C_classes, y_true, probs, loss, dlogits, *, label_smoothing=0.1, clip_eps=1e-7, inv_global_batch=1.0) -> bool:
-    """The quad-form head conv + softmax + loss (loss_kind 0) in one launch; x [B,h,w,Cin_phys] bf16, wq [16][9*Cin_phys], probs [B,2h,2w,C] fp32,
+def head_quad_softmax_loss(x, wq, bias, C_classes, y_true, probs, loss, dlogits, *, label_smoothing=0.1, clip_eps=1e-7, inv_global_batch=1.0,
+                           class_loss=None) -> bool:
+    """The quad-form head conv + softmax + loss (loss_kind 0, or the class loss ``class_loss``) in one launch; x [B,h,w,Cin_phys] bf16,
+    wq [16][9*Cin_phys], probs [B,2h,2w,C] fp32,
     dlogits bf16 [B,h,w,16] or None.  False - nothing launched - when there is no fused kernel for the size (ordered-sum slots, LDS)."""
     B, h, w, Cx, ldx = geom(x)
     assert tuple(wq.shape) == (16, 9 * Cx) and (loss is None or loss.numel() >= ACC_FLOATS)
-    rc = L.load().usseg_head_quad_softmax_loss(x.data_ptr(), B, h, w, Cx, ldx, wq.data_ptr(), bias.data_ptr(), C_classes, _ptr(y_true), probs.data_ptr(),
-                                               _ptr(loss), _ptr(dlogits), label_smoothing, clip_eps, inv_global_batch, _stream())
+    if class_loss is not None:
+        rc = L.load().usseg_head_quad_softmax_loss_cl(x.data_ptr(), B, h, w, Cx, ldx, wq.data_ptr(), bias.data_ptr(), C_classes, _ptr(y_true),
+                                                      probs.data_ptr(), _ptr(loss), _ptr(dlogits), label_smoothing, clip_eps, inv_global_batch,
+                                                      C.byref(class_loss), _stream())
+    else:
+        rc = L.load().usseg_head_quad_softmax_loss(x.data_ptr(), B, h, w, Cx, ldx, wq.data_ptr(), bias.data_ptr(), C_classes, _ptr(y_true), probs.data_ptr(),
+                                                   _ptr(loss), _ptr(dlogits), label_smoothing, clip_eps, inv_global_batch, _stream())
     if rc == -2:
         return False
     L.check(rc, "head_quad_softmax_loss")
     return True
 
 
-def loss_from_probs(probs, y_true, loss, *, HW, C_classes, loss_kind=0, label_smoothing=0.1, clip_eps=1e-7, inv_global_batch=1.0, scale=None):
-    """The reference's public loss methods on PROBABILITIES (compute_loss / my_loss_cat); ``loss`` (pre-zeroed) accumulates."""
+def loss_from_probs(probs, y_true, loss, *, HW, C_classes, loss_kind=0, label_smoothing=0.1, clip_eps=1e-7, inv_global_batch=1.0, scale=None,
+                    class_loss=None, as_map=False):
+    """The reference's public loss methods on PROBABILITIES (compute_loss / my_loss_cat); ``loss`` (pre-zeroed) accumulates.
+    ``class_loss``: that class loss (loss_kind 2) instead - the scalar in ``loss[0]``, or with ``as_map`` the [HW] map summed over the batch
+    (VisionTransformer.my_loss_cat's return value; ``inv_global_batch`` is not applied to it)."""
     assert probs.dtype == torch.float32 and y_true.dtype == torch.float32 and probs.is_contiguous() and y_true.is_contiguous()
     M = probs.numel() // C_classes
+    if class_loss is not None:
+        assert scale is None and loss.numel() >= (HW if as_map else ACC_FLOATS)
+        d = LossDesc(M, HW, C_classes, C_classes, 8, 2, label_smoothing, clip_eps, inv_global_batch, 0)
+        L.check(L.load().usseg_loss_from_probs_cl(C.byref(d), C.byref(class_loss), probs.data_ptr(), y_true.data_ptr(), loss.data_ptr(), int(as_map),
+                                                  _stream()), "loss_from_probs_cl")
+        return
     assert loss_kind == 1 or loss.numel() >= ACC_FLOATS
     d = LossDesc(M, HW, C_classes, C_classes, 8, loss_kind, label_smoothing, clip_eps, inv_global_batch, 0)
     L.check(L.load().usseg_loss_from_probs(C.byref(d), probs.data_ptr(), y_true.data_ptr(), _ptr(scale), loss.data_ptr(), _stream()),
