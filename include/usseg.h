@@ -388,7 +388,8 @@ int usseg_bn_batch_stats(const void* x, int64_t M, int32_t C, int32_t ldx, float
 int usseg_bn_train_bwd_fix(const void* x, void* dx, int64_t M, int32_t C, int32_t Cphys, int32_t ldx, int32_t lddx, const float* gamma,
                            const float* mean, const float* var, float eps, const float* tg, const float* tb, usseg_stream_t stream);
 
-/* ---- plain activation (conv1 + LeakyReLU, ResNest.py:39-40; TBI_ResNest.py:83-87) ------------- */
+/* ---- plain activation (conv1 + LeakyReLU, ResNest.py:39-40; TBI_ResNest.py:83-87) -------------
+ * y may be x, and dx may be dy (same stride): every 16-byte chunk is read and written by exactly one thread, once. */
 int usseg_act_fwd(const void* x, int64_t M, int32_t C, int32_t ldx, int32_t ldy, int32_t act, float alpha, void* y,
                   usseg_stream_t stream);
 int usseg_act_bwd(const void* x, const void* dy, int64_t M, int32_t C, int32_t ldx, int32_t lddy, int32_t lddx,

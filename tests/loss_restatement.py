@@ -55,7 +55,7 @@ def per_pixel(y_true, y_pred, w, gamma, factor):
     y_true *= 1.0 - SMOOTH                                                                   # :262
     y_true += SMOOTH / C                                                                     # :263
     y_pred = torch.clamp(y_pred, LO, HI)                                                     # :266
-    cf = torch.as_tensor(w, dtype=torch.float64)
+    cf = torch.as_tensor(w, dtype=torch.float64, device=y_pred.device)
     if gamma == 0:
         return -factor * torch.sum(y_true * torch.log(y_pred) * cf, dim=-1)                  # :270 (axis 3)
     return -factor * torch.sum(y_true * torch.log(y_pred) * torch.pow(1.0 - y_pred, gamma) * cf, dim=-1)   # :272-273 (axis 3)

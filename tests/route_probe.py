@@ -64,6 +64,16 @@ def to_dev(x64, ld=None, off=0, fill=0.0):
     return buf, buf[..., off:off + cp]
 
 
+def nan_view(B, H, W, cp, ld, off):
+    """A NaN-filled device bf16 buffer [B,H,W,ld] and its channel-slice view [..., off:off+cp] (an output written through the view)."""
+    buf = torch.full((B, H, W, ld), float("nan"), dtype=torch.bfloat16, device=DEV)
+    return buf, buf[..., off:off + cp]
+
+
+def outside_untouched(buf, off, cp, what):
+    assert torch.isnan(buf[..., :off].float()).all() and torch.isnan(buf[..., off + cp:].float()).all(), f"{what}: outside the view"
+
+
 def kernels(fn):
     from torch.profiler import ProfilerActivity, profile
     torch.cuda.synchronize()
@@ -98,6 +108,19 @@ def small_deferral(floats, first_producer=True):
         yield
     finally:
         L.check(L.load().usseg_defer_end(h), "defer_end")
+
+
+def no_launch(fn):
+    """fn() must raise before launching anything on the device."""
+    from torch.profiler import ProfilerActivity, profile
+    from ultrasound_modeling_amd._lib import UssegError
+    torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CUDA]) as prof:
+        with pytest.raises(UssegError):
+            fn()
+        torch.cuda.synchronize()
+    names = [e.name for e in prof.events() if e.device_type != torch.autograd.DeviceType.CPU and not e.name.lower().startswith(("memcpy", "memset"))]
+    assert not names, names
 
 
 def short(name):
@@ -344,12 +367,12 @@ def sa_reference(y, dout, prm, P, R, Cg, Hd, mult, norm_mode, act, sigmoid):
 
 
 # ------------------------------------------------------------------------------------------------ attention restatement (fp64)
-def acheck(what, y, ref, mag, u, c, extra=None):
+def acheck(what, y, ref, mag, u, c, extra=None, tiny=TINY):
     """|y - ref| <= c*u*mag + extra + tiny for every element, evaluated on y's device (NaN fails); prints and returns the worst
     ratio err / bound.  mag may be None (the bound is extra alone)."""
     y = y.detach().double()
     ref = ref.detach().double().to(y.device)
-    lim = torch.full_like(ref, TINY)
+    lim = torch.full_like(ref, tiny)
     if mag is not None:
         lim = lim + c * u * mag.detach().double().to(y.device)
     if extra is not None:

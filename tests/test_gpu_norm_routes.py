@@ -52,8 +52,8 @@ import pytest
 import torch
 
 import usseg_oracle as O
-from route_probe import (ACTS, EPS, U_BF16, U_F32, act_f, bf, c_f32, check, check_norm_bwd, kname, ng_of, norm_ref, routed, sa_reference,
-                         seam_data, small_deferral, to_dev)
+from route_probe import (ACTS, EPS, U_BF16, U_F32, act_f, bf, c_f32, check, check_norm_bwd, kname, nan_view, ng_of, no_launch, norm_ref, outside_untouched,
+                         routed, sa_reference, seam_data, small_deferral, to_dev)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -69,15 +69,6 @@ def vec(gen, n, base=1.0, sc=0.3, neg=False):
 
 def padded(v, cp):
     return torch.cat([v.float(), torch.zeros(cp - v.numel())]).to(DEV)
-
-
-def nan_view(B, H, W, cp, ld, off):
-    buf = torch.full((B, H, W, ld), NAN, dtype=torch.bfloat16, device=DEV)
-    return buf, buf[..., off:off + cp]
-
-
-def outside_untouched(buf, off, cp, what):
-    assert torch.isnan(buf[..., :off].float()).all() and torch.isnan(buf[..., off + cp:].float()).all(), f"{what}: outside the view"
 
 
 # ------------------------------------------------------------------------------------------------ streaming LayerNorm
@@ -588,19 +579,6 @@ def test_split_attention(gen, B, H, W, P, R, radix, Cg, Hd, norm_mode, act, gap)
     for nm, got, want, mag in zip(("dw1", "db1", "dgamma", "dbeta", "dw2", "db2"), grads, r["grads"], r["gmags"]):
         check(f"sa {B}x{HW} {nm}", got, want, mag, U_F32, c_f32(B * HW))
     outside_untouched(dbuf, 8, Cop, "dout")
-
-
-def no_launch(fn):
-    """fn() must raise before launching anything on the device."""
-    from torch.profiler import ProfilerActivity, profile
-    from ultrasound_modeling_amd._lib import UssegError
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CUDA]) as prof:
-        with pytest.raises(UssegError):
-            fn()
-        torch.cuda.synchronize()
-    names = [e.name for e in prof.events() if e.device_type != torch.autograd.DeviceType.CPU and not e.name.lower().startswith(("memcpy", "memset"))]
-    assert not names, names
 
 
 @pytest.mark.parametrize("Cg,Hd,R", [(129, 8, 1), (8, 65, 1), (8, 4, 5)], ids=["cg129", "hd65", "r5"])

@@ -729,7 +729,9 @@ def avgpool2_fwd(x, out):
 
 
 def avgpool2_bwd(dy, dx, add=None, db=None):
-    """``db``: optional fp32 vector that receives the column sums of dx (the bias gradient of the conv in front of the pool)."""
+    """``db``: optional fp32 vector to which the column sums of the stored dx are ADDED (the bias gradient of the conv in front of the pool).
+    Up to 512 channels one fused kernel writes dx and the sums; wider rows (up to colsum's 16384 channels) take the plain backward followed by a
+    ``colsum`` launch over dx - the same sums, added to ``db`` in the same way."""
     B, H, W, Cc, lddx = geom(dx)
     ldadd = geom(add)[4] if add is not None else 0
     if db is not None and Cc <= 512:
@@ -738,6 +740,8 @@ def avgpool2_bwd(dy, dx, add=None, db=None):
         return dx
     L.check(L.load().usseg_avgpool2_bwd(dy.data_ptr(), B, H, W, Cc, geom(dy)[4], lddx, _ptr(add), ldadd, dx.data_ptr(),
                                         _stream()), "avgpool2_bwd")
+    if db is not None:      # rows wider than the fused kernel's 512 channels: the column sums of the stored dx in a launch of their own
+        colsum(dx, db)
     return dx
 
 
