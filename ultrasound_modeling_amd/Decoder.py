@@ -8,25 +8,25 @@ state) are copied in.
 """
 from __future__ import annotations
 
-import os
 from typing import List, Optional
 
 import torch
 import torch.nn as nn
 
+from . import knobs
 from . import ops
 from .layers import (KERAS_BN_EPS, KERAS_LRELU_ALPHA, AveragePooling2D, BatchNormalization, Conv2D, Conv2DTranspose, LayerNormalization,
                      LeakyReLU, QuadHead, QuadTConv)
 from .ops import ACT_LRELU, ACT_NONE, BF16, roundup
 
 
-_FUSED_DGRAD = os.environ.get("USSEG_FUSED_DGRAD", "1") != "0"
-_BRANCH4 = os.environ.get("USSEG_BRANCH4", "1") != "0"     # the 1x1 branch of a DecoderBlock stage as a fourth job of its multi-job conv launch
-_QUAD_UP = os.environ.get("USSEG_QUAD_UP", "0") != "0"
+_FUSED_DGRAD = knobs.get("USSEG_FUSED_DGRAD")
+_BRANCH4 = knobs.get("USSEG_BRANCH4")     # the 1x1 branch of a DecoderBlock stage as a fourth job of its multi-job conv launch
+_QUAD_UP = knobs.get("USSEG_QUAD_UP")
 # Inference-mode BatchNorm folded into the producing conv: its scale goes into the PACKED forward operand (W' = W*gamma*rstd per output
 # channel), its shift replaces the bias, LeakyReLU rides in the plain epilogue - no norm launch and no pre-norm tensor in the forward
 # pass; the backward pass recovers what it needs from the activated output (norm backward mode 2).
-_FOLD_BN = os.environ.get("USSEG_FOLD_BN", "1") != "0"
+_FOLD_BN = knobs.get("USSEG_FOLD_BN")
 
 
 class DecoderBlock(nn.Module):
@@ -261,7 +261,7 @@ class DecoderCup(nn.Module):
         self.head = Conv2DTranspose(cin, num_classes, 3)                              # :120 (softmax fused downstream)
         # <= 4 classes: the head runs in "quad" form - a 2x2-tap conv at the input resolution whose 16 channels are the four
         # output parities (one HBM-bound launch each way instead of a 4-class gather GEMM and a 9-tap per-tap weight gradient)
-        self.quad_head = num_classes <= 4 and os.environ.get("USSEG_QUAD_HEAD", "1") != "0"
+        self.quad_head = num_classes <= 4 and knobs.get("USSEG_QUAD_HEAD")
         self._quad = QuadHead(self.head) if self.quad_head else None
 
     def on_finalize(self, device):

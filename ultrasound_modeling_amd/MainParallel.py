@@ -48,6 +48,7 @@ from typing import Optional, Tuple
 
 import torch
 import torch.distributed as dist
+from . import knobs
 
 
 def init_distributed(backend: Optional[str] = None) -> Tuple[int, int, int]:
@@ -61,7 +62,7 @@ def init_distributed(backend: Optional[str] = None) -> Tuple[int, int, int]:
         if backend is None:
             # USSEG_DIST_BACKEND=gloo: rehearsal of the multi-process path on a box with fewer GPUs than ranks (the ranks then
             # share a device and the exchange goes through host memory - correctness only, never a measurement)
-            backend = os.environ.get("USSEG_DIST_BACKEND") or ("nccl" if torch.cuda.is_available() else "gloo")   # "nccl" is RCCL on ROCm
+            backend = knobs.get("USSEG_DIST_BACKEND") or ("nccl" if torch.cuda.is_available() else "gloo")   # "nccl" is RCCL on ROCm
         if backend == "nccl":
             torch.cuda.set_device(local)
         dist.init_process_group(backend=backend, rank=rank, world_size=world)
@@ -125,7 +126,7 @@ class MirroredTrainer:
             if hasattr(net, "repack"):
                 net.repack()
             if chunks is None:
-                chunks = int(os.environ.get("USSEG_DP_CHUNKS", "0")) or 1
+                chunks = knobs.get("USSEG_DP_CHUNKS") or 1
             net.grad_sync = GradSync(group, chunks)
 
     def train_step(self, x_local, y_local):

@@ -18,12 +18,12 @@ How a ``residual_S`` stage is executed (ResNest.py:89-104):
 from __future__ import annotations
 
 import contextlib
-import os
 from typing import List
 
 import torch
 import torch.nn as nn
 
+from . import knobs
 from . import ops
 from .layers import (KERAS_LN_EPS, KERAS_LRELU_ALPHA, AveragePooling2D, BatchNormalization, Conv2D, LayerNormalization,
                      LeakyReLU, _Workspace)
@@ -39,21 +39,21 @@ from .ops import ACT_LRELU, ACT_NONE, BF16, roundup
 # stream costs more than it hides (3.03 / 3.06 ms), all four 3.12 ms - the side stream still carries the decoder's weight gradients then.
 # (with the ViT bottleneck - TBI_TransUNet.py, 512x512 - the side stream carries the ViT's weight gradients instead and 12 is 2.5 % slower than 0:
 # the wrapper sets ``ResNest.stage_lazy`` to 0 there.)  USSEG_ENC_LAZY overrides both.
-_STAGE_LAZY_ENV = os.environ.get("USSEG_ENC_LAZY")
-_STAGE_LAZY = int(_STAGE_LAZY_ENV) if _STAGE_LAZY_ENV is not None else 12
-_FOLD_BN = os.environ.get("USSEG_FOLD_BN", "1") != "0"
+_STAGE_LAZY_ENV = knobs.get("USSEG_ENC_LAZY")
+_STAGE_LAZY = _STAGE_LAZY_ENV if _STAGE_LAZY_ENV is not None else 12
+_FOLD_BN = knobs.get("USSEG_FOLD_BN")
 # the cardinal group + shortcut of a stage as ONE launch (csrc/cardinal.hip); 0 = the six unfused launches (the cross-check of the tests)
-_FUSED_CARDINAL = os.environ.get("USSEG_FUSED_CARDINAL", "1") != "0"
-_FUSED_CARDINAL_BWD = os.environ.get("USSEG_FUSED_CARDINAL_BWD", "1") != "0"     # ... and its backward chain + the shortcut norm's backward as one launch
+_FUSED_CARDINAL = knobs.get("USSEG_FUSED_CARDINAL")
+_FUSED_CARDINAL_BWD = knobs.get("USSEG_FUSED_CARDINAL_BWD")     # ... and its backward chain + the shortcut norm's backward as one launch
 # The fused backward launch holds one 8x8 tile per workgroup with ~200-500 registers per lane (one or two workgroups per CU): it wins where a
 # stage has few tiles per CU (16x16 and 32x32 at batch 16: 49 vs 64 and 58 vs 71 us) and loses to the streaming norm kernels on the large stages
 # (125 vs 66 us at 64x64, 201 vs 92 us at 128x128: 16 rounds of 10-us tiles).
-_CARD_BWD_MAX_PX = int(os.environ.get("USSEG_CARD_BWD_MAX_PX", "32768"))
-_LN_PAIR = os.environ.get("USSEG_LN_PAIR", "1") != "0"      # shortcut norm backward + conv2_bn backward of the large stages in one launch
-_FUSED_STEM_BWD = os.environ.get("USSEG_FUSED_STEM_BWD", "1") != "0"     # stem backward-data passes fused with the norm / activation backward in front
-_STEM_WGRAD_MERGE = os.environ.get("USSEG_STEM_WGRAD_MERGE", "1") != "0"   # the stem's three weight gradients in one multi-job launch
-_FUSED_STEM = os.environ.get("USSEG_FUSED_STEM", "1") != "0"             # the stem (three convs, two norms, pool) as one launch (csrc/stem.hip)
-_MERGED_DGRAD = os.environ.get("USSEG_MERGED_DGRAD", "1") != "0"     # one backward-data GEMM for a stage's grouped 1x1 and shortcut 1x1
+_CARD_BWD_MAX_PX = knobs.get("USSEG_CARD_BWD_MAX_PX")
+_LN_PAIR = knobs.get("USSEG_LN_PAIR")      # shortcut norm backward + conv2_bn backward of the large stages in one launch
+_FUSED_STEM_BWD = knobs.get("USSEG_FUSED_STEM_BWD")     # stem backward-data passes fused with the norm / activation backward in front
+_STEM_WGRAD_MERGE = knobs.get("USSEG_STEM_WGRAD_MERGE")   # the stem's three weight gradients in one multi-job launch
+_FUSED_STEM = knobs.get("USSEG_FUSED_STEM")             # the stem (three convs, two norms, pool) as one launch (csrc/stem.hip)
+_MERGED_DGRAD = knobs.get("USSEG_MERGED_DGRAD")     # one backward-data GEMM for a stage's grouped 1x1 and shortcut 1x1
 
 
 def _span(t: torch.Tensor, n: int) -> torch.Tensor:

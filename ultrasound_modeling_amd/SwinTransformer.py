@@ -27,19 +27,19 @@ The storage type is bf16 (the build's choice for every path; BASELINE quotes fp1
 from __future__ import annotations
 
 import contextlib
-import os
 from typing import List, Optional
 
 import torch
 import torch.nn as nn
 
 from .step import TrainStepDriver
+from . import knobs
 from . import ops
 from .flat import AdamClip, FlatParams
 from .layers import _FUSE_LN_RES, Conv2D
 from .ops import ACT_GELU, ACT_NONE, BF16, roundup
 
-_LAZY_BLOCK = os.environ.get("USSEG_SWIN_LAZY", "1") != "0"     # per-block lazy weight gradients (ops.lazy_wgrads)
+_LAZY_BLOCK = knobs.get("USSEG_SWIN_LAZY")     # per-block lazy weight gradients (ops.lazy_wgrads)
 
 CFGS = {   # SwinTransformer.py:8-21
     "swin_tiny_224": dict(input_size=(224, 224), window_size=4, embed_dim=96, depths=[2, 2, 6, 2], num_heads=[3, 6, 12, 24]),

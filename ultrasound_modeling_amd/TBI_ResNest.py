@@ -22,6 +22,7 @@ from typing import List, Optional
 import torch
 import torch.nn as nn
 
+from . import knobs
 from . import ops
 from .flat import AdamClip, FlatParams
 from .layers import (KERAS_BN_EPS, KERAS_ELU_ALPHA, AveragePooling2D, BatchNormalization, Conv2D, Conv2DTranspose, QuadHead, QuadTConv,
@@ -29,9 +30,9 @@ from .layers import (KERAS_BN_EPS, KERAS_ELU_ALPHA, AveragePooling2D, BatchNorma
 from .ops import ACT_ELU, ACT_NONE, ACT_RELU, BF16, roundup
 from .step import PredictDriver, TrainStepDriver, inference_norms
 
-_STEM_WGRAD_MERGE = os.environ.get("USSEG_STEM_WGRAD_MERGE", "1") != "0"   # the stem's three weight gradients in one multi-job launch (as ResNest.py's)
+_STEM_WGRAD_MERGE = knobs.get("USSEG_STEM_WGRAD_MERGE")   # the stem's three weight gradients in one multi-job launch (as ResNest.py's)
 _PREDICT_SALT = 1 << 31     # the dropout seeds of predict calls: apart from training (salt 0) and the numbered evaluation calls
-_STAGE_LAZY = os.environ.get("USSEG_STAGE_LAZY", "1") != "0"    # per-stage lazy weight gradients (ops.lazy_wgrads) in the backward pass: -1.5 %
+_STAGE_LAZY = knobs.get("USSEG_STAGE_LAZY")    # per-stage lazy weight gradients (ops.lazy_wgrads) in the backward pass: -1.5 %
 
 
 def _span(t: torch.Tensor, n: int) -> torch.Tensor:
@@ -280,10 +281,10 @@ class _ResModel(nn.Module):
             add(name + "_bn", BatchNormalization(oc))                                # :213
             cin = oc + sk
         add("f_tran", Conv2DTranspose(cin, num_class, 4, **G))                       # :124
-        self._quad = QuadHead(self.f_tran) if (num_class <= 4 and os.environ.get("USSEG_QUAD_HEAD", "1") != "0") else None
+        self._quad = QuadHead(self.f_tran) if (num_class <= 4 and knobs.get("USSEG_QUAD_HEAD")) else None
         # the five 4x4 stride-2 up-convolutions (:210) as tap-masked convs on space-to-depth tensors
         self._qt = {}
-        if os.environ.get("USSEG_QUAD_TCONV", "0") != "0":      # built and parity-tested; with 768-1024 input channels both paths are MFMA-heavy and the quad form measured 5 % slower (11.6 vs 11.0 ms), so off by default
+        if knobs.get("USSEG_QUAD_TCONV"):      # built and parity-tested; with 768-1024 input channels both paths are MFMA-heavy and the quad form measured 5 % slower (11.6 vs 11.0 ms), so off by default
             for name, oc, drop in self.UPS:
                 object.__setattr__(self, "_qt_" + name, QuadTConv(getattr(self, name + "_t_conv")))
                 self._qt[name] = getattr(self, "_qt_" + name)

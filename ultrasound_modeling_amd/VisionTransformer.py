@@ -14,12 +14,12 @@ actually build; its variables carry the reference's attribute paths (``transform
 from __future__ import annotations
 
 import contextlib
-import os
 from typing import Optional
 
 import torch
 import torch.nn as nn
 
+from . import knobs
 from . import ops
 from . import Decoder as _DEC
 from . import ResNest as _ENC
@@ -28,13 +28,13 @@ from .flat import AdamClip, FlatParams
 from .layers import BatchNormalization, Conv2D, LayerNormalization, _Workspace
 from .ResNest import ResNest, cardinal, residual_S
 
-_FUSED_HEAD = os.environ.get("USSEG_FUSED_HEAD", "1") != "0"      # quad-form head conv + softmax + loss as one launch (csrc/attn_loss_optim.hip)
+_FUSED_HEAD = knobs.get("USSEG_FUSED_HEAD")      # quad-form head conv + softmax + loss as one launch (csrc/attn_loss_optim.hip)
 from .ops import BF16, roundup
 from .step import PredictDriver, TrainStepDriver, inference_norms
 
 input_size = (256, 80)   # VisionTransformer.py:7
-_VIT_LAZY = os.environ.get("USSEG_VIT_LAZY", "enc")              # ops.lazy_wgrads over the whole encoder ("enc"), per block, or "0"
-_FUSED_ATTN = os.environ.get("USSEG_FUSED_ATTN", "1") != "0"   # train-step attention on csrc/flash_attn.hip (head size 128)
+_VIT_LAZY = knobs.get("USSEG_VIT_LAZY")              # ops.lazy_wgrads over the whole encoder ("enc"), per block, or "0"
+_FUSED_ATTN = knobs.get("USSEG_FUSED_ATTN")   # train-step attention on csrc/flash_attn.hip (head size 128)
 
 
 def repack_all(root: nn.Module):

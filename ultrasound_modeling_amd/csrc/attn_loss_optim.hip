@@ -809,7 +809,7 @@ static int softmax_loss_grid(const UssegLossDesc* d, bool map_form, dim3* grid, 
     int64_t g = cdiv64(d->HW, 256);
     *grid = dim3((unsigned)(g > 2048 ? 2048 : g));
   } else {
-    static const int ppt = getenv("USSEG_LOSS_PPT") ? atoi(getenv("USSEG_LOSS_PPT")) : 4;
+    const int ppt = knob<K_LOSS_PPT>();
     int64_t g = cdiv64(d->HW, 256 * ppt);          // <= 2048 workgroups in all: the slots of the ordered sum
     if (g * nb > 2048) g = 2048 / nb > 0 ? 2048 / nb : 1;
     USSEG_CHECK_ARG(g * nb <= 2048, "softmax_loss: more than 2048 images");

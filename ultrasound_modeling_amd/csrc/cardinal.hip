@@ -852,7 +852,7 @@ int launch_bwd(CardBwd& p, float* dg2, float* dbe2, float* db2, float* dg1, floa
   using Cfg = CardBwdCfg<CV11, CVKK, OC>;
   if (usseg_lds_opt_in((const void*)cardinal_bwd_kernel<CIN, CV11, CVKK, OC>, Cfg::LDS_B)) return usseg_check_launch("cardinal_bwd");
   // workgroup pairs (cardinal tile walker, shortcut tile walker): as many as are resident at once, at most one per tile
-  static const int g_env = getenv("USSEG_CARD_BWD_G") ? atoi(getenv("USSEG_CARD_BWD_G")) : 0;
+  const int g_env = knob<K_CARD_BWD_G>();
   const int per_cu = 160 * 1024 / (2 * Cfg::LDS_B) > 0 ? 160 * 1024 / (2 * Cfg::LDS_B) : 1;
   const int most = p.ntiles > p.sc_tiles ? p.ntiles : p.sc_tiles;
   int G = g_env > 0 ? g_env : 256 * per_cu;
@@ -916,12 +916,12 @@ int launch_ln_pair(LnPair& P, float* const* ga, float* const* gb, float* caller_
 }  // namespace
 
 int usseg_try_ln_bwd_tile(const LnTileArgs& a, float* dgamma, float* dbeta, float* dbias, float* caller_ws, hipStream_t s) {
-  static const int off = getenv("USSEG_LN_TILE") && atoi(getenv("USSEG_LN_TILE")) == 0;
+  const int off = knob<K_LN_TILE>() == 0;
   if (off || a.M <= 0 || a.M >= (1ll << 31)) return 0;
   const bool fuse = a.sa_s != nullptr;
   // a 64-pixel tile is one long dependency chain per workgroup: it beats the streaming kernel (one pixel on 4-16 lanes, mask FMAs) once the
   // tensor has several tiles per CU to overlap (measured: 2x on 128x128 / 64x64 x 16 images, slower below ~32k pixels)
-  static const int64_t min_px = getenv("USSEG_LN_TILE_MIN") ? atoll(getenv("USSEG_LN_TILE_MIN")) : 32768;
+  const int64_t min_px = knob<K_LN_TILE_MIN>();
   if (a.M < min_px || (fuse && a.HW % 64 != 0)) return 0;
   const int cg = a.G > 0 ? a.C / a.G : 0;
 #define LNB(CPv, CGv, NGv)                                                                                                  \
@@ -937,8 +937,8 @@ int usseg_try_ln_bwd_tile(const LnTileArgs& a, float* dgamma, float* dbeta, floa
 // A = the shortcut norm (one group of Oc channels), B = conv2_bn with the re-weighting's backward folded in (3 groups of cvkk): the two
 // stages whose tensors are large enough for the tile kernels (ResNest.py stages 1 and 2 at 256x256).  0: no instantiation, nothing launched.
 int usseg_try_ln_bwd_pair(const LnTileArgs& a, float* const* ga, const LnTileArgs& b, float* const* gb, float* caller_ws, hipStream_t s) {
-  static const int off = getenv("USSEG_LN_PAIR") && atoi(getenv("USSEG_LN_PAIR")) == 0;
-  static const int64_t min_px = getenv("USSEG_LN_TILE_MIN") ? atoll(getenv("USSEG_LN_TILE_MIN")) : 32768;
+  const int off = knob<K_LN_PAIR>() == 0;
+  const int64_t min_px = knob<K_LN_TILE_MIN>();
   if (off || a.M < min_px || b.M < min_px || a.M >= (1ll << 31) || b.M >= (1ll << 31)) return 0;
   if (a.sa_s || !b.sa_s || b.HW % 64 != 0 || a.G != 1 || b.G != 3) return 0;
   LnPair P;

@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include "../../include/usseg.h"
+#include "knobs.h"
 
 typedef unsigned short bf16_t;  // raw bf16 bits
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;  // one MFMA A/B fragment (4 VGPRs)

@@ -418,7 +418,7 @@ __global__ __launch_bounds__(256, 2) void conv_stream_kernel(const BigParams P, 
 
 // Fills a job from a pass for a PX-pixel tile; returns 0 if the pass does not fit that tiling.
 static int big_fill_job(BigJob& p, const ConvPass& g, int PX, int any_cin = 0) {
-  static const int min_cin = getenv("USSEG_BIG_MIN_CIN") ? atoi(getenv("USSEG_BIG_MIN_CIN")) : 33;
+  const int min_cin = knob<K_BIG_MIN_CIN>();
   const int B = g.B, H = g.H, W = g.W, d = g.d, ldx = g.ldx;
   if (d < 1 || H % d || W % d || (g.Cin < min_cin && !any_cin)) return 0;
   const int Hl = H / d, Wl = W / d;
@@ -474,7 +474,7 @@ static void big_launch(BigParams& P, int njobs, int nt, int PX, hipStream_t s, i
   // chunk's DMA in flight under this chunk's MFMAs) wins: -10...-15 % on concats_2 256->512 @16x16, conv_more and the decoder's
   // 512->64 branches at batch 16 and 32 (tools/bench_conv.py, round 2), +15...+30 % when forced on the 1024-workgroup launches.
   // USSEG_BIG_STAGES: 0 = this rule (default), 1 / 2 = forced.
-  static const int stages_env = getenv("USSEG_BIG_STAGES") ? atoi(getenv("USSEG_BIG_STAGES")) : 0;
+  const int stages_env = knob<K_BIG_STAGES>();
   int64_t total_wg = 0;
   for (int j = 0; j < njobs; ++j) total_wg += (int64_t)P.job[j].gx * P.job[j].gy;
   const int nstages = stages_env == 2 ? 2 : (stages_env == 1 ? 1 : (total_wg <= 512 ? 2 : 1));
@@ -512,16 +512,15 @@ struct StreamPlan {
   unsigned wgx, gy;
 };
 static int stream_plan(const ConvPass& g, StreamPlan& sp) {
-  static const int mode = getenv("USSEG_STREAM") ? atoi(getenv("USSEG_STREAM")) : 1;
-  static const int px_env = getenv("USSEG_STREAM_PX") ? atoi(getenv("USSEG_STREAM_PX")) : 0;
+  const int mode = knob<K_STREAM>();
+  const int px_env = knob<K_STREAM_PX>();
   // read per call (not cached): the parity tests use these two to drive small shapes through many steps per workgroup
-  const char* ms_env = getenv("USSEG_STREAM_MIN_STEPS");
-  const char* wgx_env = getenv("USSEG_STREAM_WGX");
-  const int min_steps = ms_env ? atoi(ms_env) : 1;
-  static const int occ_env = getenv("USSEG_STREAM_OCC") ? atoi(getenv("USSEG_STREAM_OCC")) : 0;
+  const int min_steps = knob<K_STREAM_MIN_STEPS>();
+  const int wgx_env = knob<K_STREAM_WGX>();
+  const int occ_env = knob<K_STREAM_OCC>();
   if (!mode || g.mask.group_ch) return 0;
   // its epilogue is bias + activation + bf16 store (no loads inside the streaming loop), or the RES variant with a preloaded residual
-  static const int res_env = getenv("USSEG_STREAM_RES") ? atoi(getenv("USSEG_STREAM_RES")) : 1;
+  const int res_env = knob<K_STREAM_RES>();
   if (g.out_f32 || g.accumulate || g.scale) return 0;
   if (g.res && (!res_env || (g.ldr & 3))) return 0;
   const int nt = nt_for(g.Nout);
@@ -542,7 +541,7 @@ static int stream_plan(const ConvPass& g, StreamPlan& sp) {
     if (occ < 1) continue;
     int wgx = (256 * occ / gy) & ~7;             // one resident wave of workgroups, a multiple of 8 (per-XCD walk)
     if (wgx < 8) wgx = 8;
-    if (wgx_env && atoi(wgx_env) >= 8) wgx = atoi(wgx_env) & ~7;
+    if (wgx_env >= 8) wgx = wgx_env & ~7;
     const int gpx = (p.npatches + 7) / 8;        // groups per XCD
     int per_wg = (gpx + wgx / 8 - 1) / (wgx / 8);
     if (per_wg * nchunks < min_steps && !px_env) continue;   // too few steps to amortise the weights: the tiled kernels win
@@ -590,16 +589,15 @@ static bool stream_same_plan(const StreamPlan& a, const StreamPlan& b) {
 
 // Chooses the kernel and the tile (pixels per workgroup, channel tile) and launches; 0 if no tiling fits or the launch would be too small.
 int usseg_try_launch_conv_big(const ConvPass* g, int njobs, hipStream_t s) {
-  static const int mode = getenv("USSEG_BIG") ? atoi(getenv("USSEG_BIG")) : 1;
-  static const int px_env = getenv("USSEG_BIG_PX") ? atoi(getenv("USSEG_BIG_PX")) : 0;
-  static const int nt_env = getenv("USSEG_BIG_NT") ? atoi(getenv("USSEG_BIG_NT")) : 0;
-  static const int min_wg = getenv("USSEG_BIG_MIN_WG") ? atoi(getenv("USSEG_BIG_MIN_WG")) : 128;
-  static const int wg_min = getenv("USSEG_BIG_WG_TILE") ? atoi(getenv("USSEG_BIG_WG_TILE")) : 512;
+  const int mode = knob<K_BIG>();
+  const int px_env = knob<K_BIG_PX>();
+  const int nt_env = knob<K_BIG_NT>();
+  const int min_wg = knob<K_BIG_MIN_WG>();
+  const int wg_min = knob<K_BIG_WG_TILE>();
   if (!mode || njobs < 1 || njobs > 4) return 0;
   {   // HBM-bound jobs whose weights fit in LDS: the streaming kernel, one full-chip launch per job
-    static const int multi = getenv("USSEG_STREAM_MULTI") ? atoi(getenv("USSEG_STREAM_MULTI")) : 1;
-    const char* merge_env = getenv("USSEG_STREAM_MERGE");      // read per call: the parity test flips it inside one process
-    const int merge = merge_env ? atoi(merge_env) : 1;         // jobs of one plan in ONE launch (0: a launch per job)
+    const int multi = knob<K_STREAM_MULTI>();
+    const int merge = knob<K_STREAM_MERGE>();      // jobs of one plan in ONE launch (0: a launch per job); read per call: the parity test flips it inside one process
     bool all = (njobs == 1 || multi) && njobs <= 4;
     StreamPlan sp[4];
     for (int j = 0; j < njobs && all; ++j) all = stream_plan(g[j], sp[j]) != 0;
@@ -642,9 +640,8 @@ int usseg_try_launch_conv_big(const ConvPass* g, int njobs, hipStream_t s) {
   // waves per CU, half the weight-stage traffic (read per call: the parity tests force it with USSEG_BIG_W8=2)
   int w8 = 0;
   {
-    const char* w8e = getenv("USSEG_BIG_W8");
-    const int w8_mode = w8e ? atoi(w8e) : 1;
-    static const int w8_min = getenv("USSEG_BIG_W8_MIN") ? atoi(getenv("USSEG_BIG_W8_MIN")) : 128;
+    const int w8_mode = knob<K_BIG_W8>();
+    const int w8_min = knob<K_BIG_W8_MIN>();
     if (w8_mode && best_px == 128) {
       bool ok = true;
       int64_t wg = 0;

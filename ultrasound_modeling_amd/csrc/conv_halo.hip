@@ -375,13 +375,13 @@ static int halo_launch(HaloMulti& P, int njobs, hipStream_t s) {
   const int gy = (Nout + 16 * nt - 1) / (16 * nt);
   const int slot = usseg_prof_start(1, s);
   // persistent variant: the tile's whole weight operand fits in 46 KB of LDS and there are pixel groups to amortise it over
-  static const int no_persist = getenv("USSEG_NO_PERSIST") != nullptr;
+  const int no_persist = knob<K_NO_PERSIST>();
   const size_t wbytes = (size_t)p0.nchunks * 9 * 16 * nt * 40 * sizeof(bf16_t);
   if (!no_persist && wbytes <= 46080 && gx >= 1024) {
     const size_t dyn = wbytes + (size_t)maxhp * 40 * sizeof(bf16_t);   // weights + the largest halo tile of the jobs
     // One resident wave of workgroups: `occ` per CU by LDS (160 KB) and by the launch bounds.  A second, partly filled wave
     // would cost a whole extra pass (3 resident + 1024 workgroups used to run as 768 + 256).
-    static const int occ_env = getenv("USSEG_PERSIST_OCC") ? atoi(getenv("USSEG_PERSIST_OCC")) : 0;
+    const int occ_env = knob<K_PERSIST_OCC>();
     int occ = (int)((160 * 1024) / (dyn + 3072 + 256));
     const int occ_max = nt <= 2 ? 4 : 2;
     if (occ > occ_max) occ = occ_max;
@@ -414,7 +414,7 @@ static int halo_launch(HaloMulti& P, int njobs, hipStream_t s) {
 // Returns 1 and launches if every pass fits the halo kernel and they share the grid shape, 0 if the caller must use another kernel.
 // (The passes' tap masks are ignored: masked taps carry zero weights.)
 int usseg_try_launch_conv_halo(const ConvPass* g, int njobs, hipStream_t s) {
-  static const int disabled = getenv("USSEG_NO_HALO") != nullptr;
+  const int disabled = knob<K_NO_HALO>();
   if (disabled || njobs < 1 || njobs > 4) return 0;
   HaloMulti P;
   for (int j = 0; j < njobs; ++j)

@@ -615,25 +615,25 @@ static int launch_igemm(const IgemmParams& p_in, hipStream_t s) {
   const unsigned gz = p.cls_mode ? 4 : (p.nb2 > 0 ? (unsigned)p.nbatch : 1);
   // channel tile: the widest that covers Nout, narrowed while the launch has fewer workgroups than CUs (the 16x16 stages
   // are 32 pixel tiles: a 128-channel tile leaves 3/4 of the chip idle - the b0.up backward-data ran 63 us on 64 workgroups)
-  static const int wg_min = getenv("USSEG_IGEMM_WG_MIN") ? atoi(getenv("USSEG_IGEMM_WG_MIN")) : 256;
+  const int wg_min = knob<K_IGEMM_WG_MIN>();
   int nt = p.Nout <= 16 ? 1 : (p.Nout <= 32 ? 2 : (p.Nout <= 64 ? 4 : 8));
   while (nt > 2 && gx * ((p.Nout + 16 * nt - 1) / (16 * nt)) * gz < wg_min) nt >>= 1;
   const unsigned gy = (unsigned)((p.Nout + 16 * nt - 1) / (16 * nt));
   // K step 64 when the K loop is long enough to amortise the bigger stage (>= 16 chunks of 8 channels)
-  static const int kc_env = getenv("USSEG_IGEMM_KC") ? atoi(getenv("USSEG_IGEMM_KC")) : 0;
+  const int kc_env = knob<K_IGEMM_KC>();
   const int kc = kc_env ? kc_env : (p.ntaps * p.cpt >= 16 ? 8 : 4);
   const dim3 grid((unsigned)gx, gy, gz);
   const int slot = usseg_prof_start(1, s);
   {   // plain mode with a K loop worth a stage ring: the LDS-DMA variant
-    static const int dma = getenv("USSEG_IGEMM_DMA") ? atoi(getenv("USSEG_IGEMM_DMA")) : 1;
+    const int dma = knob<K_IGEMM_DMA>();
     const int64_t nb = cdiv64(p.M, (int64_t)p.Hg * p.Wg);
     const bool fits = nb * p.Hi * p.Wi * p.ldx * 2 < 0x7fff0000ll && (int64_t)p.Nw * p.Kw * 2 < 0x7fff0000ll &&
                       p.M < (1 << 23) && nb * p.Hi * p.Wi < (1 << 23) && nb * p.Ho * p.Wo < (1 << 23);   // fdivmod_px / signed 24-bit multiplies in the row decodes
     const int k_chunks = p.cls_mode ? 4 * p.cpt : p.ntaps * p.cpt;   // a parity class has up to four taps
-    static const int dma_min = getenv("USSEG_IGEMM_DMA_MIN") ? atoi(getenv("USSEG_IGEMM_DMA_MIN")) : 4;
-    static const int dma_batched = getenv("USSEG_IGEMM_DMA_BATCHED") ? atoi(getenv("USSEG_IGEMM_DMA_BATCHED")) : 1;
+    const int dma_min = knob<K_IGEMM_DMA_MIN>();
+    const int dma_batched = knob<K_IGEMM_DMA_BATCHED>();
     const bool bat_ok = p.nb2 <= 0 || (dma_batched && !p.cls_mode && (p.xs1 | p.xs2 | p.ws1 | p.ws2) % 8 == 0);   // 16-byte aligned batch bases
-    static const int xcd_env = getenv("USSEG_IGEMM_XCD") ? atoi(getenv("USSEG_IGEMM_XCD")) : 1;
+    const int xcd_env = knob<K_IGEMM_XCD>();
     p.xcd_remap = 0;
     if (dma && bat_ok && k_chunks >= dma_min && fits) {
       // activation-heavy launches only (pixels >= 16 x output channels: the operand worth sharing is the activation tile).  Measured per
@@ -641,7 +641,7 @@ static int launch_igemm(const IgemmParams& p_in, hipStream_t s) {
       // GEMMs (8192 tokens x 512-2048 channels, weight-heavy) it cost 0.5 %, hence the rule
       p.xcd_remap = xcd_env && p.nb2 <= 0 && (int64_t)gx * gy * gz < (1ll << 20) && (int64_t)gy * gz > 1 && (xcd_env > 1 || p.M >= 16 * (int64_t)p.Nout);
       // short K loops with several pixel tiles per resident workgroup slot: the persistent form
-      static const int persist = getenv("USSEG_IGEMM_PERSIST") ? atoi(getenv("USSEG_IGEMM_PERSIST")) : 1;
+      const int persist = knob<K_IGEMM_PERSIST>();
       const int nks = (p.ntaps * p.cpt + 7) / 8;
       const bool plain = !p.cls_mode && p.nb2 <= 0 && !p.res && !p.accumulate && !p.scale && !p.out_f32;
       const int64_t slots_x = 512 / (int64_t)gy;      // two workgroups per CU resident
@@ -657,8 +657,8 @@ static int launch_igemm(const IgemmParams& p_in, hipStream_t s) {
       // 128-channel tiles: two stages (64 KB, two workgroups per CU) by default; a launch that puts at most one workgroup on a CU
       // anyway and has a long K loop (the dense layers of the ViT / Swin: 8192 tokens x 2048 -> 512 is 256 workgroups x 32 steps)
       // is bound by the DMA latency of its single prefetched stage: it gets a deeper ring instead
-      static const int st8 = getenv("USSEG_IGEMM_STAGES8") ? atoi(getenv("USSEG_IGEMM_STAGES8")) : 4;   // 4 stages: cfg4 11.01 -> 10.92 ms, the others unchanged (2 = off)
-      static const int st8_wg = getenv("USSEG_IGEMM_STAGES8_WG") ? atoi(getenv("USSEG_IGEMM_STAGES8_WG")) : 256;
+      const int st8 = knob<K_IGEMM_STAGES8>();   // 4 stages: cfg4 11.01 -> 10.92 ms, the others unchanged (2 = off)
+      const int st8_wg = knob<K_IGEMM_STAGES8_WG>();
       const bool deep = nt == 8 && st8 > 2 && (int64_t)gx * gy * gz <= st8_wg && nks >= 8;
       if (nt == 1) igemm_dma_launch_t<1, 3>(p, grid, s);
       else if (nt == 2) igemm_dma_launch_t<2, 3>(p, grid, s);

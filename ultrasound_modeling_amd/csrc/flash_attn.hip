@@ -507,7 +507,7 @@ __global__ __launch_bounds__(64 * NW, 1) void flash_bwd_dkv_kernel(const FlashPa
 // backward at 8 x 1024 tokens x 4 heads against 70 / 144 us for 2 = 4 waves x 32; 0 = 4 waves x 16, 64 per workgroup, when 128-query
 // workgroups would not fill the 256 CUs (16 images x 256 tokens: 13.8 / 30.5 us against 16.5 / 36.5).
 static int fa_variant(const UssegFlashDesc* d) {
-  static const int v = getenv("USSEG_FLASH_TILE") ? atoi(getenv("USSEG_FLASH_TILE")) : -1;
+  const int v = knob<K_FLASH_TILE>();
   if (v >= 0) return v;
   return (int64_t)d->B * d->H * ((d->N + 127) / 128) >= 256 ? 1 : 0;
 }

@@ -740,7 +740,7 @@ template <bool BWD>
 static int wa_launch(const WinAttn& p, hipStream_t s) {
   const int N = p.ws * p.ws, nW = (p.H / p.ws) * (p.W / p.ws);
   const size_t dyn = sizeof(float) * ((size_t)(BWD ? 4 : 3) * N * (p.d + 1) + (BWD ? 2 * (size_t)N * (N + 1) : 0));
-  static const int no_mfma = getenv("USSEG_WINATTN_MFMA") && atoi(getenv("USSEG_WINATTN_MFMA")) == 0;
+  const int no_mfma = knob<K_WINATTN_MFMA>() == 0;
   if (p.ws == 8 && p.d == 32 && !no_mfma) {
     // windows per block: a power of two dividing nW that still fills the chip (the forward holds 8 one-wave blocks per CU, the
     // backward 2: 78 KB of LDS); the backward gains most - one bias-table reduction per block instead of one per window

@@ -381,12 +381,12 @@ static void wgrad_dma_launch_t(const WgradParams& p, dim3 grid, hipStream_t s) {
 
 static int launch_wgrad(WgradParams& p, int ntaps, float* ws, int64_t ws_floats, hipStream_t s) {
   // LDS-DMA variant: unbatched launches whose operands fit 32-bit byte offsets and whose pixel count fits the float division
-  static const int dma_env = getenv("USSEG_WGRAD_DMA") ? atoi(getenv("USSEG_WGRAD_DMA")) : 1;
+  const int dma_env = knob<K_WGRAD_DMA>();
   const bool dma = dma_env && p.nb2 <= 0 && p.M < (1 << 24) && (int64_t)p.Hg * p.Wg < (1 << 23) && (int64_t)p.B * p.Ha * p.Wa < (1 << 24) && (int64_t)p.B * p.Hb * p.Wb < (1 << 24) &&   // (24-bit multiplies in the pixel decode)
                    (int64_t)p.B * p.Ha * p.Wa * p.lda * 2 < 0x7fff0000ll &&
                    (int64_t)p.B * p.Hb * p.Wb * p.ldb * 2 < 0x7fff0000ll && p.lda % 8 == 0 && p.ldb % 8 == 0;
   // 128x128 tiles when both channel counts exceed one 64-wide tile (split-K supplies the workgroups if the tiles are few)
-  static const int tm_env = getenv("USSEG_WGRAD_TM") ? atoi(getenv("USSEG_WGRAD_TM")) : 0;
+  const int tm_env = knob<K_WGRAD_TM>();
   int tm = 1;
   if (dma && p.Ma > 64 && p.Nb > 64) tm = 2;
   if (dma && tm_env) tm = tm_env;
@@ -399,8 +399,8 @@ static int launch_wgrad(WgradParams& p, int ntaps, float* ws, int64_t ws_floats,
   // swept on the four bench configurations (target 2048/1024/512/384/256/128 x slab cap 8/4/2): the round-1 setting (2048, 8) made
   // 16-32 splits of the big dense gradients of the ViT / Swin layers, whose slabs then dominate (wgrad_finish 580 us per cfg4 step);
   // (512, 4): Arch B 3.735 -> 3.70 ms, cfg4 11.52 -> 11.11, cfg5 12.44 -> 11.87, Arch A unchanged; 128 is 2-10 % slower everywhere
-  static const int wg_target = getenv("USSEG_WGD_TARGET") ? atoi(getenv("USSEG_WGD_TARGET")) : 512;
-  static const int slab_cap = getenv("USSEG_WGD_CAP") ? atoi(getenv("USSEG_WGD_CAP")) : 4;
+  const int wg_target = knob<K_WGD_TARGET>();
+  const int slab_cap = knob<K_WGD_CAP>();
   int64_t want = (wg_target + tiles - 1) / tiles;
   int64_t max_splits = cdiv64(p.M, 256);
   if (want > max_splits) want = max_splits;
@@ -425,7 +425,7 @@ static int launch_wgrad(WgradParams& p, int ntaps, float* ws, int64_t ws_floats,
   {
     // wave quantisation (see wgrad_halo_launch): 3 (64x64 tiles) or 2 (128x128) workgroups per CU resident; near the target pick
     // the split count with the cheapest rounds x (K steps per workgroup + fixed cost) estimate
-    static const int quant = getenv("USSEG_WG_QUANT") ? atoi(getenv("USSEG_WG_QUANT")) : 1;
+    const int quant = knob<K_WG_QUANT>();
     const int64_t hi_cap = p.ws ? (want * 2 < cap_splits ? want * 2 : cap_splits) : want;   // within the slab traffic cap; without slabs (atomics) never more splits
     if (quant && dma && want > 1) {
       const int64_t slots = 256 * (tm == 2 ? 2 : 3);
@@ -445,17 +445,17 @@ static int launch_wgrad(WgradParams& p, int ntaps, float* ws, int64_t ws_floats,
   int64_t splits = cdiv64(p.M, p.chunk);
   const int slot = usseg_prof_start(2, s);
   const dim3 grid((unsigned)splits, (unsigned)(p.mtiles * p.ntiles), (unsigned)ntaps);
-  static const int dbg = getenv("USSEG_WGRAD_DEBUG") != nullptr;
+  const int dbg = knob<K_WGRAD_DEBUG>();
   if (dbg) fprintf(stderr, "[wgrad] M %lld (B %d Hg %d Wg %d) Ma %d Nb %d taps %d tm %d splits %lld chunk %lld slab %s asy %d bsy %d lda %d ldb %d\n", (long long)p.M, p.B, p.Hg, p.Wg,
                    p.Ma, p.Nb, ntaps, tm, (long long)splits, (long long)p.chunk, p.ws ? "yes" : "no", p.asy, p.bsy, p.lda, p.ldb);
   {
-    static const int pow2_env = getenv("USSEG_WGRAD_POW2") ? atoi(getenv("USSEG_WGRAD_POW2")) : 1;
+    const int pow2_env = knob<K_WGRAD_POW2>();
     auto lg = [](int v) { int l = 0; while ((1 << l) < v) ++l; return (1 << l) == v ? l : -1; };
     p.lw = pow2_env ? lg(p.Wg) : -1;
     p.lh = pow2_env ? lg(p.Hg) : -1;
     if (p.lw < 0 || p.lh < 0) p.lw = p.lh = -1;
   }
-  static const int xcd_env = getenv("USSEG_WGRAD_XCD") ? atoi(getenv("USSEG_WGRAD_XCD")) : 1;
+  const int xcd_env = knob<K_WGRAD_XCD>();
   p.xcd_remap = dma && xcd_env && p.nb2 <= 0 && (int64_t)splits * p.mtiles * p.ntiles * ntaps < (1ll << 20) && (p.mtiles * p.ntiles * ntaps > 1);
   if (dma) {
     if (tm == 2) wgrad_dma_launch_t<2, 2>(p, grid, s);
@@ -599,7 +599,7 @@ extern "C" int usseg_gemm_tn_batched(const UssegGemmDesc* d, const void* a, cons
   p.chunk = ((d->K + 63) / 64) * 64;                     // one split: the batch already fills the chip
   p.ntaps = 1;
   const int slot = usseg_prof_start(2, (hipStream_t)stream);
-  static const int dma_env = getenv("USSEG_WGRAD_DMA") ? atoi(getenv("USSEG_WGRAD_DMA")) : 1;
+  const int dma_env = knob<K_WGRAD_DMA>();
   const bool dma = dma_env && d->K < (1 << 23) && (int64_t)d->K * d->ldx * 2 < 0x7fff0000ll && (int64_t)d->K * d->ldw * 2 < 0x7fff0000ll &&
                    (d->xs1 | d->xs2 | d->ws1 | d->ws2) % 8 == 0;
   const dim3 grid(1, (unsigned)(p.mtiles * p.ntiles), (unsigned)(d->nb1 * d->nb2));

@@ -373,7 +373,7 @@ __global__ __launch_bounds__(256 * NTG, NTG == 1 ? 2 : 1) void wgrad_halo_kernel
 // differ as long as the jobs take the same tile shape and the same number of tiles (the stem's three convs: 32x32, 16x32 and 8x16 channels are
 // one 32x32 tile each) - as one grid; returns 0 if the geometry does not fit (the caller then launches the jobs one at a time).
 int usseg_try_launch_wgrad_halo(const WgHaloGeom* gm, int njobs, float* ws, int64_t ws_floats, hipStream_t s) {
-  static const int disabled = getenv("USSEG_NO_HALO") != nullptr;
+  const int disabled = knob<K_NO_HALO>();
   if (disabled || njobs < 1 || njobs > 4) return 0;
   WgHaloMulti P;
   const int Ma = gm[0].Ma, Nb = gm[0].Nb;     // job 0 decides the tile shape; every job must land in the same shape class with the same tile count
@@ -446,10 +446,10 @@ int usseg_try_launch_wgrad_halo(const WgHaloGeom* gm, int njobs, float* ws, int6
   for (int j = 0; j < njobs; ++j) in_bytes += (int64_t)gm[j].B * gm[j].H * gm[j].W * (gm[j].Ma + gm[j].Nb) * 2;
   in_bytes /= njobs;
   const int64_t slab_bytes = slab * 4;
-  static const int wg_target = getenv("USSEG_WG_TARGET") ? atoi(getenv("USSEG_WG_TARGET")) : 256;   // round 3 sweep (128 / 192 / 256 / 384 / 512 / 768): 256 is -25 us on Arch B (half the slabs for wgrad_finish), neutral on A / T
+  const int wg_target = knob<K_WG_TARGET>();   // round 3 sweep (128 / 192 / 256 / 384 / 512 / 768): 256 is -25 us on Arch B (half the slabs for wgrad_finish), neutral on A / T
   int splits = (wg_target + tiles * njobs - 1) / (tiles * njobs);
   int max_splits = (ngroups + 1) / 2;
-  static const int slab_cap = getenv("USSEG_SLAB_CAP") ? atoi(getenv("USSEG_SLAB_CAP")) : 2;
+  const int slab_cap = knob<K_SLAB_CAP>();
   const int64_t traffic_cap = slab_cap * in_bytes / slab_bytes < 4 ? 4 : slab_cap * in_bytes / slab_bytes;
   if (max_splits > traffic_cap) max_splits = (int)traffic_cap;
   if (!ws) max_splits = (ngroups + 15) / 16;
@@ -460,7 +460,7 @@ int usseg_try_launch_wgrad_halo(const WgHaloGeom* gm, int njobs, float* ws, int6
     // Wave quantisation: the 64x64 shape runs one workgroup per CU (8 waves), the others two, so a launch of 528 workgroups
     // is three rounds of 256 where 504 would be two.  Around the target, pick the split count with the cheapest
     // rounds x (groups per workgroup + fixed cost) estimate (fixed cost ~ 3 group times: prologue + slab epilogue).
-    static const int quant = getenv("USSEG_WG_QUANT") ? atoi(getenv("USSEG_WG_QUANT")) : 1;
+    const int quant = knob<K_WG_QUANT>();
     if (quant && max_splits > 1) {
       const int slots = 256 * (shape == 0 ? 1 : 2);
       const int64_t tj = (int64_t)tiles * njobs;
@@ -501,13 +501,13 @@ int usseg_try_launch_wgrad_halo(const WgHaloGeom* gm, int njobs, float* ws, int6
     for (int c = 0; c < 4; ++c) P.job[0].tapmask[c] = qm.mask[c];
   }
   const dim3 grid(splits, tiles, njobs);
-  static const int xcd_env = getenv("USSEG_WGHALO_XCD") ? atoi(getenv("USSEG_WGHALO_XCD")) : 1;
+  const int xcd_env = knob<K_WGHALO_XCD>();
   P.xcd_remap = xcd_env && tiles * njobs > 1 && (int64_t)splits * tiles * njobs < (1ll << 20);     // (fdiv() in the remap)
-  static const int dbg = getenv("USSEG_WGRAD_DEBUG") != nullptr;
+  const int dbg = knob<K_WGRAD_DEBUG>();
   if (dbg) fprintf(stderr, "[wgrad_halo] B %d H %d W %d d %d Ma %d Nb %d jobs %d shape %d tiles %d ngroups %d splits %d gpb %d max_splits %d traffic_cap %lld slab_MB %.2f in_MB %.2f\n",
                    gm[0].B, gm[0].H, gm[0].W, gm[0].d, Ma, Nb, njobs, shape, tiles, ngroups, splits, gpb, max_splits, (long long)traffic_cap, slab_bytes / 1e6, in_bytes / 1e6);
   const int slot = usseg_prof_start(2, s);
-  static const int pf = getenv("USSEG_WGRAD_PF") ? atoi(getenv("USSEG_WGRAD_PF")) : 1;
+  const int pf = knob<K_WGRAD_PF>();
   if (shape == 1) {
     if (pf) { if (masked) hipLaunchKernelGGL((wgrad_halo_kernel<2, 1, 1, true, 1, true>), grid, dim3(256), 0, s, P); else hipLaunchKernelGGL((wgrad_halo_kernel<2, 1, 1, true, 1, false>), grid, dim3(256), 0, s, P); }
     else { if (masked) hipLaunchKernelGGL((wgrad_halo_kernel<2, 1, 1, false, 1, true>), grid, dim3(256), 0, s, P); else hipLaunchKernelGGL((wgrad_halo_kernel<2, 1, 1, false, 1, false>), grid, dim3(256), 0, s, P); }
@@ -518,7 +518,7 @@ int usseg_try_launch_wgrad_halo(const WgHaloGeom* gm, int njobs, float* ws, int6
     if (pf) { if (masked) hipLaunchKernelGGL((wgrad_halo_kernel<4, 1, 2, true, 1, true>), grid, dim3(256), 0, s, P); else hipLaunchKernelGGL((wgrad_halo_kernel<4, 1, 2, true, 1, false>), grid, dim3(256), 0, s, P); }
     else { if (masked) hipLaunchKernelGGL((wgrad_halo_kernel<4, 1, 2, false, 1, true>), grid, dim3(256), 0, s, P); else hipLaunchKernelGGL((wgrad_halo_kernel<4, 1, 2, false, 1, false>), grid, dim3(256), 0, s, P); }
   } else {
-    static const int tg8 = getenv("USSEG_WGRAD_8W") ? atoi(getenv("USSEG_WGRAD_8W")) : 1;
+    const int tg8 = knob<K_WGRAD_8W>();
     if (tg8) { if (masked) hipLaunchKernelGGL((wgrad_halo_kernel<2, 2, 2, true, 2, true>), grid, dim3(512), 0, s, P); else hipLaunchKernelGGL((wgrad_halo_kernel<2, 2, 2, true, 2, false>), grid, dim3(512), 0, s, P); }
     else { if (masked) hipLaunchKernelGGL((wgrad_halo_kernel<2, 2, 2, false, 1, true>), grid, dim3(256), 0, s, P); else hipLaunchKernelGGL((wgrad_halo_kernel<2, 2, 2, false, 1, false>), grid, dim3(256), 0, s, P); }
   }
@@ -539,8 +539,7 @@ int usseg_try_launch_tconv_wgrad_halo(const bf16_t* x, const bf16_t* dy, const W
                                       int lddy, int k, float* ws, int64_t ws_floats, hipStream_t s) {
   // Built and parity-tested, off by default: with 4 of 9 taps live per class the 64x64 halo tile is staging-bound and loses to the
   // per-tap LDS-DMA kernel with 128x128 tiles (Arch A 9.20 vs 8.78 ms, Arch B 4.32 vs 4.22 ms per step).
-  const char* en = getenv("USSEG_TCONV_HALO");   // read per call: the parity test flips it inside one process
-  const int enabled = en ? atoi(en) : 0;
+  const int enabled = knob<K_TCONV_HALO>();   // read per call: the parity test flips it inside one process
   if (!enabled || map.nblocks < 1 || (k != 3 && k != 4)) return 0;
   const int pad = k == 4 ? 1 : 0;
   WgHaloGeom g[4];

@@ -11,16 +11,16 @@ Activations are bf16 ``[B,H,W,Cphys]`` with Cphys = roundup(C, 8) and zero pad c
 from __future__ import annotations
 
 import math
-import os
 from typing import Optional
 
 import torch
 import torch.nn as nn
 
+from . import knobs
 from . import ops
 from .ops import ACT_ELU, ACT_LRELU, ACT_NONE, ACT_RELU, BF16, roundup
 
-_FUSE_LN_RES = os.environ.get("USSEG_FUSE_LN_RES", "1") != "0"    # LayerNorm backward + residual add in one pass (transformer blocks)
+_FUSE_LN_RES = knobs.get("USSEG_FUSE_LN_RES")    # LayerNorm backward + residual add in one pass (transformer blocks)
 
 KERAS_LRELU_ALPHA = 0.3   # tf.keras.layers.LeakyReLU() default
 KERAS_ELU_ALPHA = 1.0

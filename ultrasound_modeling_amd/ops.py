@@ -17,6 +17,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib as L
+from . import knobs
 from ._lib import (ACCUMULATE, ACT_ELU, ACT_GELU, ACT_LRELU, ACT_NONE, ACT_RELU, OUT_F32, CardinalDesc, ConvDesc, GemmDesc, LossDesc, NormDesc,
                    SplitAttnDesc, SplitAttnGrads, SplitAttnParams)
 
@@ -65,8 +66,8 @@ def _fork_allowed(max_hw_queues: Optional[str]) -> bool:
 class _Side:
     # read once, like the HIP runtime itself, which takes the setting when it loads (with torch, before this module)
     fork = _fork_allowed(os.environ.get("GPU_MAX_HW_QUEUES"))
-    enabled = os.environ.get("USSEG_SIDE_STREAM", "0") != "0"
-    defer = os.environ.get("USSEG_DEFER", "1") != "0"
+    enabled = knobs.get("USSEG_SIDE_STREAM")
+    defer = knobs.get("USSEG_DEFER")
     depth = 0
     stream = None
     keep = []
@@ -161,7 +162,7 @@ def side_stream(*keep):
 # ``wgrad_later`` are only collected; at the end of the block they all run on the side stream behind ONE fork, beside whatever the
 # main stream does next (the encoder's backward pass), and join at the end of the overlap region.  The per-layer fork of
 # ``side_stream`` (USSEG_SIDE_STREAM=1) costs a cross-stream edge per launch, which made it slower than a single stream.
-_LAZY = os.environ.get("USSEG_LAZY_WGRAD", "1") != "0"
+_LAZY = knobs.get("USSEG_LAZY_WGRAD")
 _lazy_q = None
 
 
