@@ -588,6 +588,52 @@ int usseg_head_quad_softmax_loss_cl(const void* x, int32_t B, int32_t h, int32_t
  * the batch in order. */
 int usseg_loss_from_probs_cl(const UssegLossDesc* d, const UssegClassLoss* cl, const float* probs, const float* y_true, float* loss,
                              int32_t as_map, usseg_stream_t stream);
+/* ---- region-overlap losses: soft Dice / Tversky, optionally plus CategoricalCrossentropy (csrc/overlap_loss.hip) ------------------
+ * Not in the reference: the loss family people training a segmenter on rare classes reach for first.  On the head's fp32 probabilities
+ * p[m][c] and the labels y[m][c] exactly as passed (no label smoothing in the overlap term; soft labels allowed), m over the M pixels
+ * of THIS call, s = smooth, a = alpha, b = beta, g = power:
+ *     I_c = sum_m p*y      P_c = sum_m p      Y_c = sum_m y
+ *     N_c = I_c + s        D_c = (1-a-b)*I_c + a*P_c + b*Y_c + s        T_c = N_c / D_c
+ *     L_ov = sum_c w[c] * (1 - T_c)^g
+ *     loss = ce_weight * CCE + ov_weight * ov_scale * L_ov
+ * CCE is loss_kind 0 above, exactly: Keras normalisation, clip_eps, label_smoothing, times inv_global_batch.  a = b = 0.5 is soft Dice
+ * in the convention (2*I + 2*s)/(P + Y + 2*s): s is added to the numerator and to the denominator of the HALVED textbook fraction, so
+ * the textbook smoothing constant is 2*s.  power is 1, or lies in [1, 4] (below 1, (1-T)^(g-1) is unbounded at T = 1: refused);
+ * smooth > 0; alpha, beta, w[c], ov_weight, ce_weight finite and >= 0; only w[0..C) is read; C <= 4.  ov_scale (finite, >= 0) is the
+ * caller's data-parallel weight of this call's overlap term: with the replicas' gradients SUM-reduced, B_local / global batch makes the
+ * result the batch-weighted mean of the replicas' overlap losses (1 on one device).
+ *     d loss / d p_c(m) = A_c*y_c(m) + B_c (+ the CCE term),   k_c = ov_weight*ov_scale*w[c]*g*(1-T_c)^(g-1),
+ *     A_c = -k_c*(D_c - (1-a-b)*N_c)/D_c^2,   B_c = k_c*a*N_c/D_c^2;   dlogit_j = p_j*(G_j - sum_c p_c*G_c), fp32, ONE bf16 rounding.
+ * The gradient at a pixel depends on sums over all pixels, so there are two launches behind a probabilities-only forward
+ * (usseg_head_quad_softmax_loss / usseg_softmax_loss_fwd_bwd with y_true = NULL):
+ *   usseg_overlap_loss_sums   reads probs and y_true (fp32 [M][C], 16-byte aligned) once; acc[0] = the scalar loss (OVERWRITTEN);
+ *                             acc[2] = the CCE pixel sum; acc[4+c] = A_c; acc[8+c] = B_c; acc[16+c], [20+c], [24+c], [28+c] = I_c, P_c, Y_c, T_c.
+ *   usseg_overlap_loss_bwd    reads probs, y_true and acc[4..12); writes dlogits bf16 [M][8] (lddl 8), or with quad_w the
+ *                             space-to-depth layout [B][H/2][W/2][16] (lddl 16) of UssegLossDesc; pad channels are exactly zero.
+ * acc names acc_floats floats, USSEG_OVERLAP_ACC_FLOATS to hold every grid: [1] is a ticket counter (zero between calls), [32 + 16*b + k]
+ * workgroup b's partial of value k.  The 3C + 1 totals are bitwise reproducible: fixed per-thread, per-wave and per-workgroup orders, the
+ * partials published by a returning agent-scope exchange, and the last workgroup to arrive adds them in workgroup order (no float atomics,
+ * no workgroup waits for another).  Zero the buffer once at allocation; no per-call zeroing.  The grid rule, part of the contract because
+ * the rounding-error bound of the totals follows from it: usseg_overlap_loss_grid(M) = clamp(ceil(ceil(M/4)/256), 1, 512) workgroups of
+ * 256 threads; a thread adds groups of 4 consecutive pixels, group index striding by 256*grid.
+ * Of the descriptor only M, HW, C, lddl, quad_w, label_smoothing, clip_eps and inv_global_batch are read (M <= 2^29, a multiple of HW; M = 0
+ * gives loss 0 and no backward launch).  The struct travels BY VALUE with the launches, so a captured graph holds its numbers.  Every
+ * argument is checked before any launch (USSEG_ERR_BAD_ARG with usseg_last_error text), an accumulator too small for the grid included. */
+typedef struct UssegOverlapLoss {
+  float w[8];      /* per-class weight */
+  float alpha;     /* weight of the false positives (P - I) in the denominator */
+  float beta;      /* weight of the false negatives (Y - I) */
+  float smooth;    /* s > 0 */
+  float power;     /* g: 1, or in [1, 4] */
+  float ov_weight; /* weight of the overlap term */
+  float ce_weight; /* weight of the CCE term; 0: not evaluated */
+} UssegOverlapLoss;
+#define USSEG_OVERLAP_ACC_FLOATS 8224 /* 32 + 16 * 512 workgroups */
+int usseg_overlap_loss_grid(int64_t M);
+int usseg_overlap_loss_sums(const UssegLossDesc* d, const UssegOverlapLoss* ol, float ov_scale, const float* probs, const float* y_true,
+                            float* acc, int64_t acc_floats, usseg_stream_t stream);
+int usseg_overlap_loss_bwd(const UssegLossDesc* d, const UssegOverlapLoss* ol, const float* probs, const float* y_true, const float* acc,
+                           int64_t acc_floats, void* dlogits, usseg_stream_t stream);
 /* The <= 4-class head Conv2DTranspose(k x k, stride 2, 'same') (Decoder.py:120 k=3; TBI_ResNest.py:124 k=4) in "quad" form: a
  * stride-1 convolution at the INPUT resolution whose 16 output channels are (output parity class)*4 + n, run by
  * usseg_conv2d_fwd/dgrad/wgrad as a 3x3 conv (each parity uses <= 2x2 of the stencil taps, the rest are zero).  With

@@ -2,7 +2,10 @@
 shape with tools/time_conv.py's method: `reps` launches captured into one HIP graph, replayed three times between two events.
 usage: python tools/time_head.py [--lib PATH] [--rounds N] [B h w Cin C]
   --lib PATH: time that build of the library instead (e.g. the parent commit's, which has only the CategoricalCrossentropy entry point);
-  each variant is timed `rounds` times, so the run-to-run spread stands beside every number."""
+  each variant is timed `rounds` times, so the run-to-run spread stands beside every number.
+With a library that has the region-overlap losses (csrc/overlap_loss.hip) it also times, in the same process, the path they take - the
+probabilities-only head launch, the sums pass and the backward pass, together and one by one - and the softmax_loss kernel on the same
+pixels, and prints each kernel's achieved bytes/s against the bytes it must move."""
 import argparse
 import ctypes as C
 import sys
@@ -71,3 +74,46 @@ print(f"{a.lib}: fused head {B}x{h}x{w} {Cin} channels, {NC} classes")
 for name, cl in variants:
     ts = [t(lambda: launch(cl), a.reps) for _ in range(a.rounds)]
     print(f"  {name:24s} {min(ts):7.2f} us min, {sorted(ts)[len(ts) // 2]:7.2f} median, {max(ts):7.2f} max   [{' '.join(f'{v:.2f}' for v in ts)}]")
+
+if hasattr(lib, "usseg_overlap_loss_sums"):
+    i64 = C.c_int64
+    lib.usseg_overlap_loss_sums.argtypes = [C.POINTER(L.LossDesc), C.POINTER(L.OverlapLoss), f32, vp, vp, vp, i64, vp]
+    lib.usseg_overlap_loss_bwd.argtypes = [C.POINTER(L.LossDesc), C.POINTER(L.OverlapLoss), vp, vp, vp, i64, vp, vp]
+    lib.usseg_softmax_loss_fwd_bwd.argtypes = [C.POINTER(L.LossDesc), vp, vp, vp, vp, vp, vp, vp]
+    H, W = 2 * h, 2 * w
+    M = B * H * W
+    from ultrasound_modeling_amd import ops
+    acc = torch.zeros(ops.OVERLAP_ACC_FLOATS).cuda()
+    logits = torch.randn(B, h, w, 16, generator=g).cuda()
+    stream = lambda: torch.cuda.current_stream().cuda_stream
+    dq = L.LossDesc(M, H * W, NC, 16, 16, 0, 0.1, 1e-7, 1.0 / B, W)
+
+    def head_probs_only():
+        rc = lib.usseg_head_quad_softmax_loss(x.data_ptr(), B, h, w, Cin, Cin, wq.data_ptr(), bias.data_ptr(), NC, None, probs.data_ptr(), None, None, 0.1, 1e-7,
+                                              1.0 / B, stream())
+        assert rc == 0, rc
+
+    def sums(ol):
+        assert lib.usseg_overlap_loss_sums(C.byref(dq), C.byref(ol), 1.0, probs.data_ptr(), y.data_ptr(), acc.data_ptr(), acc.numel(), stream()) == 0
+
+    def bwd(ol):
+        assert lib.usseg_overlap_loss_bwd(C.byref(dq), C.byref(ol), probs.data_ptr(), y.data_ptr(), acc.data_ptr(), acc.numel(), dl.data_ptr(), stream()) == 0
+
+    def softmax_loss():
+        assert lib.usseg_softmax_loss_fwd_bwd(C.byref(dq), logits.data_ptr(), y.data_ptr(), None, probs.data_ptr(), loss.data_ptr(), dl.data_ptr(), stream()) == 0
+
+    def row(name, fn, nbytes=None):
+        ts = [t(fn, a.reps) for _ in range(a.rounds)]
+        med = sorted(ts)[len(ts) // 2]
+        bw = "" if nbytes is None else f"   {nbytes / 1e6:6.1f} MB -> {nbytes / med / 1e6:5.2f} TB/s"
+        print(f"  {name:40s} {min(ts):7.2f} us min, {med:7.2f} median, {max(ts):7.2f} max{bw}")
+
+    uw = (C.c_float * 8)(*([1.0 / NC] * NC))
+    rd = 2 * M * NC * 4
+    row("head, probabilities only", head_probs_only)
+    for name, ol in (("dice", L.OverlapLoss(uw, 0.5, 0.5, 1.0, 1.0, 1.0, 0.0)), ("dice_ce", L.OverlapLoss(uw, 0.5, 0.5, 1.0, 1.0, 1.0, 1.0))):
+        row(f"{name}: head + sums + bwd", lambda: (head_probs_only(), sums(ol), bwd(ol)))
+        row(f"{name}: sums (pass 1)", lambda: sums(ol), rd)
+        row(f"{name}: bwd (pass 2)", lambda: bwd(ol), rd + M * 8)
+    # softmax_loss_kernel: quad fp32 logits read (64 B per 2x2 pixels = 16 B a pixel), labels read AND probabilities written (2 * M*NC*4), dlogits written (8 B a pixel)
+    row("softmax_loss (quad logits, cce)", softmax_loss, M * 16 + 2 * M * NC * 4 + M * 8)

@@ -21,7 +21,7 @@ from __future__ import annotations
 
 import torch
 
-from .metrics import SegMetrics
+from .metrics import SegMetrics, dice_line
 from .schedules import PiecewiseConstantDecay
 
 input_size = (256, 80)      # :12
@@ -91,18 +91,22 @@ class Process(object):
         print("f1 = {}".format(m["f1"]))
         print("precision = {}".format(m["precision"]))
         print("recall = {}".format(m["recall"]))
+        dice = dice_line(neuralnet, self.metrics)
+        if dice is not None:                                    # only with loss="dice" / "tversky" / "dice_ce"
+            print("dice per class = {}".format(dice))
         self.history.append(dict(m, phase="test", epoch=epoch, loss=total_loss))
         self.metrics.reset_states()                                                              # :142-146
         return m["f1"]
 
 
-def main(train_path, val_path, save_path=None, epochs=50, batch_size=32, num_classes=3, *, loss="cce"):
+def main(train_path, val_path, save_path=None, epochs=50, batch_size=32, num_classes=3, *, loss="cce", overlap=None):
     """MainNumpy.py:150-177 with the paths as arguments: ``VisionTransformer(32, img_size=(256, 80))`` over a ``Dataset_2.Dataset``,
-    50 epochs, then a save if ``save_path`` is given.  ``loss``: the model's ``loss=`` ("cce", "my_loss_cat", "focal")."""
+    50 epochs, then a save if ``save_path`` is given.  ``loss``: the model's ``loss=`` ("cce", "my_loss_cat", "focal", "dice", "tversky",
+    "dice_ce"); ``overlap``: the settings of the last three (``VisionTransformer(overlap=...)``), which also add a per-class Dice line to the test report."""
     from .Dataset_2 import Dataset
-    from .VisionTransformer import VisionTransformer
+    from .VisionTransformer import VisionTransformer, overlap_settings
     dataset = Dataset(train_path, val_path, num_classes)
-    neuralnet = VisionTransformer(batch_size, img_size=input_size, num_classes=num_classes, loss=loss)
+    neuralnet = VisionTransformer(batch_size, img_size=input_size, num_classes=num_classes, loss=loss, overlap=overlap_settings(loss, overlap))
     print(len(neuralnet.visionModel.layers))
     process = Process(batch_size=batch_size, num_classes=num_classes)
     process.training(neuralnet=neuralnet, dataset=dataset, epochs=epochs)

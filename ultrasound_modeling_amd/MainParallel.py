@@ -18,7 +18,7 @@ The epoch driver (``Process.training`` / ``test`` / ``mirrored_train_step`` / ``
 MainParallel.py:24-176,201-220) runs any model with ``train_step`` / ``step`` / ``empty_step`` (``VisionTransformer``) over a
 ``Dataset.Dataset``, one process per replica:
     python -m torch.distributed.run --nproc_per_node N -m ultrasound_modeling_amd.MainParallel TRAIN VAL [--save P] [--epochs N]
-        [--batch-size B] [--no-vit] [--loss {cce,my_loss_cat,focal}]
+        [--batch-size B] [--no-vit] [--loss {cce,my_loss_cat,focal,dice,tversky,dice_ce}]
 (world size 1 runs without the launcher).  As the reference executes: epochs count from 0; ``test`` runs after EVERY epoch (:72); the
 test loss is the plain sum over the test batches (:89 is commented out); test batches are ``batch_size`` images (:155) split like the
 training batches; each replica's loss is divided by the GLOBAL batch (``VisionTransformer.batch_size``, a short last batch included,
@@ -49,6 +49,7 @@ from typing import Optional, Tuple
 import torch
 import torch.distributed as dist
 from . import knobs
+from .metrics import dice_line
 
 
 def init_distributed(backend: Optional[str] = None) -> Tuple[int, int, int]:
@@ -224,6 +225,9 @@ class Process(object):
         self._print("f1 = {}".format(m["f1"]))
         self._print("precision = {}".format(m["precision"]))
         self._print("recall = {}".format(m["recall"]))
+        dice = dice_line(neuralnet, self.metrics)
+        if dice is not None:                                    # only with loss="dice" / "tversky" / "dice_ce"
+            self._print("dice per class = {}".format(dice))
         self.history.append(dict(m, phase="test", epoch=epoch, loss=total_loss))
         self.metrics.reset_states()                                                              # :110-114
         return m["f1"]
@@ -278,13 +282,15 @@ class Process(object):
 
 
 def main(train_path, val_path, save_path=None, epochs=51, batch_size=64, use_vit=True, *, seed=0, schedule=False, capture_graph=True,
-         loss="cce"):
+         loss="cce", overlap=None):
     """MainParallel.py:201-216 with the paths as arguments: ``VisionTransformer(batch_size=64)`` with the ViT bottleneck, 51 epochs,
     then rank 0 saves if ``save_path`` is given.  Every rank seeds ``random`` with ``seed``, so all draw the same augmentations.
-    ``loss``: the model's ``loss=`` ("cce", "my_loss_cat", "focal"); every replica divides it by the global batch all the same.
+    ``loss``: the model's ``loss=`` ("cce", "my_loss_cat", "focal"); every replica divides it by the global batch all the same.  The
+    region-overlap losses ("dice", "tversky", "dice_ce", settings in ``overlap``) are computed per replica on its own images and weighted by
+    local batch / global batch: the SUM of the replicas is their batch-weighted mean; they add a per-class Dice line to the test report.
     Under ``nccl`` the model lives on ``cuda:LOCAL_RANK``; the ``USSEG_DIST_BACKEND=gloo`` rehearsal keeps every rank on device 0."""
     from .Dataset import Dataset
-    from .VisionTransformer import VisionTransformer
+    from .VisionTransformer import VisionTransformer, overlap_settings
     rank, world, local = init_distributed()
     nccl = world > 1 and dist.get_backend() == "nccl"
     device = torch.device("cuda", local if nccl else 0)
@@ -292,7 +298,7 @@ def main(train_path, val_path, save_path=None, epochs=51, batch_size=64, use_vit
     random.seed(seed)
     dataset = Dataset(train_path, val_path, batch_size, device=device)
     neuralnet = VisionTransformer(batch_size, img_size=(dataset.height, dataset.width), in_channels=dataset.channel, use_vit=use_vit,
-                                  device=str(device), loss=loss)
+                                  device=str(device), loss=loss, overlap=overlap_settings(loss, overlap))
     if rank == 0:
         print(len(neuralnet.visionModel.layers))
     process = Process(batch_size, schedule=schedule, capture_graph=capture_graph)
@@ -315,8 +321,9 @@ def _cli(argv=None):
     ap.add_argument("--seed", type=int, default=0, help="augmentation draws (the same on every rank)")
     ap.add_argument("--schedule", action="store_true", help="install the MainParallel.py:74-79 rate schedule once")
     ap.add_argument("--no-graph", action="store_true", help="run every step eagerly")
-    ap.add_argument("--loss", choices=("cce", "my_loss_cat", "focal"), default="cce",
-                    help="the model's loss: CategoricalCrossentropy (the reference's), its class-weighted my_loss_cat, or the focal variant")
+    ap.add_argument("--loss", choices=("cce", "my_loss_cat", "focal", "dice", "tversky", "dice_ce"), default="cce",
+                    help="the model's loss: CategoricalCrossentropy (the reference's), its class-weighted my_loss_cat, the focal variant, or a "
+                         "region-overlap loss (soft Dice, Tversky 0.3 / 0.7, Dice + CCE)")
     a = ap.parse_args(argv)
     main(a.train, a.val, a.save, epochs=a.epochs, batch_size=a.batch_size, use_vit=not a.no_vit, seed=a.seed, schedule=a.schedule,
          capture_graph=not a.no_graph, loss=a.loss)

@@ -305,13 +305,42 @@ class Transformer(nn.Module):
         self.embeddings.backward(d_hidden, d_feats)
 
 
-LOSSES = ("cce", "my_loss_cat", "focal")
+LOSSES = ("cce", "my_loss_cat", "focal")             # the reference's own: per-pixel losses inside the fused head launch
+OVERLAP_LOSSES = ("dice", "tversky", "dice_ce")      # region-overlap losses (not in the reference): two launches behind the probabilities-only head
+
+
+def overlap_settings(loss, overlap):
+    """What the drivers hand the constructor: for a region-overlap loss with no settings given, the empty dict (every default)."""
+    return {} if overlap is None and loss in OVERLAP_LOSSES else overlap
+
+
+def overlap_config(loss, num_classes, overlap):
+    """``loss`` in OVERLAP_LOSSES and the ``overlap`` settings (dict or None) -> ``ops.overlap_loss(...)``; ValueError for a bad or
+    contradictory combination."""
+    cfg = dict(overlap or {})
+    unknown = [k for k in cfg if k not in ops.OVERLAP_KEYS]
+    if unknown:
+        raise ValueError(f"overlap: unknown settings {unknown}; known: {ops.OVERLAP_KEYS}")
+    if loss != "tversky" and ("alpha" in cfg or "beta" in cfg):
+        raise ValueError(f"overlap: alpha / beta belong to loss='tversky'; '{loss}' is alpha = beta = 0.5")
+    if loss != "dice_ce" and cfg.get("ce_weight", 0.0) != 0.0:
+        raise ValueError(f"overlap: a cross-entropy term needs loss='dice_ce', not '{loss}'")
+    if loss == "dice_ce" and cfg.get("ce_weight", 1.0) == 0.0:
+        raise ValueError("overlap: loss='dice_ce' with ce_weight = 0 is loss='dice'")
+    w = cfg.get("class_weight")
+    w = [1.0 / num_classes] * num_classes if w is None else [float(v) for v in w]
+    if len(w) != num_classes:
+        raise ValueError(f"overlap: class_weight has {len(w)} entries for {num_classes} classes")
+    a, b = (0.3, 0.7) if loss == "tversky" else (0.5, 0.5)
+    return ops.overlap_loss(w, cfg.get("alpha", a), cfg.get("beta", b), cfg.get("smooth", 1.0), cfg.get("power", 1.0), cfg.get("ov_weight", 1.0),
+                            cfg.get("ce_weight", 1.0 if loss == "dice_ce" else 0.0))
 
 
 class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
     def __init__(self, batch_size, img_size=(256, 80), num_classes=3, learning_rate=1e-3, weight_decay=1e-4, *,
                  in_channels: int = 10, use_vit: bool = False, device: Optional[str] = None, seed: Optional[int] = 0,
-                 transunet: bool = False, adamw: bool = False, loss: str = "cce", class_factor=None, focal_gamma=None):
+                 transunet: bool = False, adamw: bool = False, loss: str = "cce", class_factor=None, focal_gamma=None,
+                 overlap=None, alpha=None, beta=None, smooth=None, power=None, class_weight=None, ce_weight=None, ov_weight=None):
         """``transunet=True`` builds the older self-contained copy of this model in TBI_TransUNet.py (BASELINE configs[3]):
         BatchNormalization where ResNest.py / Decoder.py use LayerNormalization (:304,426,465,472,503), conv_4 = 256 channels
         (:368), and the loss is CategoricalCrossentropy(label_smoothing=0.1) with the DEFAULT reduction - the mean over all
@@ -330,10 +359,30 @@ class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
             factor 3: the one combination the reference's comments describe (:277) but no line of it ever ran.
         ``class_factor`` (default the reference's [0.06329, 0.027567, 0.90914], :209) needs one entry per class wherever it is used.
         Every loss is summed over the pixels and divided by the global batch (``transunet``: averaged over the B*H*W pixels).  The
-        loss is not part of a checkpoint (the reference fixes it in code)."""
+        loss is not part of a checkpoint (the reference fixes it in code).
+
+        Region-overlap losses (not in the reference; DESIGN.md section 8, usseg.h ``UssegOverlapLoss``), on the probabilities and labels of the
+        images THIS replica holds: ``"dice"`` (soft Dice), ``"tversky"`` (alpha 0.3 / beta 0.7 unless given), ``"dice_ce"`` (Dice plus the
+        default CCE with ``ce_weight`` 1).  They are selected by the name TOGETHER WITH their settings: ``overlap={}`` takes every default, and the
+        bare name with neither ``overlap`` nor a keyword stays the ValueError it was before these losses existed (callers and a test rely on
+        ``loss="dice"`` alone being refused; the drivers' ``main(loss=...)`` pass ``{}`` themselves).  ``overlap`` - a dict, or the same names as keywords - sets ``alpha, beta`` (tversky only),
+        ``smooth`` (1), ``power`` (1, up to 4), ``class_weight`` (uniform 1/classes), ``ov_weight`` (1), ``ce_weight`` (dice_ce only).  The
+        overlap term is weighted by local batch / global batch (``transunet``: 1), so SUM-reduced replicas train on the batch-weighted mean."""
         super().__init__()
-        if loss not in LOSSES:
-            raise ValueError(f"loss must be one of {LOSSES}, got {loss!r}")
+        if loss not in LOSSES + OVERLAP_LOSSES:
+            raise ValueError(f"loss must be one of {LOSSES + OVERLAP_LOSSES}, got {loss!r}")
+        given = dict(alpha=alpha, beta=beta, smooth=smooth, power=power, class_weight=class_weight, ce_weight=ce_weight, ov_weight=ov_weight)
+        overlap_kw = {k: v for k, v in given.items() if v is not None}      # (the keyword ``alpha`` is Tversky's; ``self.alpha`` below is the focal exponent, :208)
+        if overlap is not None and overlap_kw:
+            raise ValueError("give the overlap settings as overlap={...} or as keywords, not both")
+        overlap = overlap if overlap is not None else (overlap_kw or None)
+        if overlap is not None and loss not in OVERLAP_LOSSES:
+            raise ValueError(f"overlap settings only apply to loss in {OVERLAP_LOSSES}")
+        if loss in OVERLAP_LOSSES and overlap is None:
+            raise ValueError(f"loss={loss!r} needs its settings: overlap={{}} for the defaults, or any of {ops.OVERLAP_KEYS}")
+        if loss in OVERLAP_LOSSES and (class_factor is not None or focal_gamma is not None):
+            raise ValueError(f"class_factor / focal_gamma do not apply to loss='{loss}' (its weights are overlap['class_weight'])")
+        self._overlap = overlap_config(loss, num_classes, overlap) if loss in OVERLAP_LOSSES else None
         if focal_gamma is not None and loss != "focal":
             raise ValueError("focal_gamma only applies to loss='focal'")
         self.alpha = 2                                                                  # :208
@@ -368,9 +417,15 @@ class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
         self.flat = FlatParams(self, self.device)
         self.optimizer = AdamClip(self.flat, lr=learning_rate, clip_norm=1.0,          # :204,:244
                                   weight_decay=weight_decay if adamw else None)
-        self._loss = torch.zeros(ops.ACC_FLOATS, dtype=torch.float32, device=self.device)   # [0] = the scalar loss
+        self._loss = torch.zeros(ops.ACC_FLOATS if self._overlap is None else ops.OVERLAP_ACC_FLOATS, dtype=torch.float32,
+                                 device=self.device)                                         # [0] = the scalar loss
         self.grad_sync = None                   # set by the data-parallel wrapper: callable(flat_grad)
         self._graph = None
+
+    @property
+    def overlap_loss(self):
+        """The ``UssegOverlapLoss`` this model trains with (``loss="dice"`` / ``"tversky"`` / ``"dice_ce"``), or None for a per-pixel loss."""
+        return self._overlap
 
     # ------------------------------------------------------------------ parameters in / out (Keras names)
     @property
@@ -461,6 +516,8 @@ class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
             dlogits = ops.new_act(B, H // 2, W // 2, 16, self.device) if qw else ops.new_act(B, H, W, 8, self.device)
         # :205,:227 sum / GLOBAL batch; TBI_TransUNet.py:546 (default reduction): mean over the B*H*W pixels of the batch
         scale = 1.0 / float(B * H * W) if self.transunet else 1.0 / float(self.batch_size)
+        if self._overlap is not None:
+            return self._forward_overlap(xh, logits, y, probs, dlogits, scale)
         if fused:       # head conv + softmax + loss in one launch (:142, :205, :225-229); falls back to the three launches if it has no kernel
             kw = {} if self._class_loss is None else {"class_loss": self._class_loss}       # (no keyword: today's call of today's symbol)
             if self.decoder._quad.forward_loss(xh, y, probs, self._loss, dlogits, label_smoothing=0.1, clip_eps=1e-7, inv_global_batch=scale, **kw):
@@ -469,6 +526,21 @@ class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
             self.decoder._logits = logits
         ops.softmax_loss(logits, y, probs, self._loss, dlogits, HW=H * W, C_classes=self.num_classes, loss_kind=0,
                          label_smoothing=0.1, clip_eps=1e-7, inv_global_batch=scale, quad_w=qw, class_loss=self._class_loss)
+        return probs, dlogits
+
+    def _forward_overlap(self, xh, logits, y, probs, dlogits, scale):
+        """The region-overlap losses: today's probabilities-only head launch(es), then the sums pass (scalar loss and backward coefficients into
+        ``self._loss``), then - for a training step - the backward pass that writes ``dlogits``."""
+        B, H, W, C = probs.shape
+        if xh is not None and not self.decoder._quad.forward_loss(xh, None, probs, None, None):
+            logits = self.decoder._head_forward(xh)
+            self.decoder._logits = logits
+        if logits is not None:
+            ops.softmax_loss(logits, None, probs, None, None, HW=H * W, C_classes=C, quad_w=self.decoder.quad_w)
+        kw = dict(overlap=self._overlap, HW=H * W, C_classes=C, label_smoothing=0.1, clip_eps=1e-7, inv_global_batch=scale)
+        ops.overlap_loss_sums(probs, y, self._loss, ov_scale=1.0 if self.transunet else float(B) / float(self.batch_size), **kw)
+        if dlogits is not None:
+            ops.overlap_loss_bwd(probs, y, self._loss, dlogits, quad_w=self.decoder.quad_w, **kw)
         return probs, dlogits
 
     def _predict_body(self, x):
@@ -496,6 +568,12 @@ class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
         -> scalar.  (train_step/step use the fused softmax+loss kernel instead.)"""
         y_true, y_pred = self._prep_y(y_true), self._prep_y(y_pred)
         H, W = y_pred.shape[1], y_pred.shape[2]
+        if self._overlap is not None:       # the overlap loss of THESE tensors, weighted as a step weights a batch of their size
+            acc = torch.zeros(ops.OVERLAP_ACC_FLOATS, dtype=torch.float32, device=self.device)
+            ops.overlap_loss_sums(y_pred, y_true, acc, overlap=self._overlap, HW=H * W, C_classes=y_pred.shape[-1], label_smoothing=0.1, clip_eps=1e-7,
+                                  ov_scale=1.0 if self.transunet else float(y_pred.shape[0]) / float(self.batch_size),
+                                  inv_global_batch=1.0 / float(self.batch_size))
+            return acc[0].clone()
         loss = torch.empty(ops.ACC_FLOATS, dtype=torch.float32, device=self.device)
         ops.fill_f32(loss, 0.0)
         ops.loss_from_probs(y_pred, y_true, loss, HW=H * W, C_classes=y_pred.shape[-1], loss_kind=0, label_smoothing=0.1, clip_eps=1e-7,

@@ -90,6 +90,12 @@ class ClassLoss(C.Structure):
     _fields_ = [("w", c_f32 * 8), ("gamma", c_f32), ("factor", c_f32)]
 
 
+class OverlapLoss(C.Structure):
+    """UssegOverlapLoss: soft Dice / Tversky, optionally plus CategoricalCrossentropy (usseg.h); passed by reference, copied into the launches."""
+    _fields_ = [("w", c_f32 * 8), ("alpha", c_f32), ("beta", c_f32), ("smooth", c_f32), ("power", c_f32), ("ov_weight", c_f32),
+                ("ce_weight", c_f32)]
+
+
 class FlashDesc(C.Structure):
     _fields_ = [("B", c_i32), ("N", c_i32), ("H", c_i32), ("head_dim", c_i32), ("ld_qkv", c_i32), ("ld_o", c_i32), ("scale", c_f32)]
 
@@ -194,6 +200,9 @@ _PROTOS = {
     "usseg_head_quad_softmax_loss_cl": (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_f32, c_f32, c_f32,
                                                   P(ClassLoss), c_vp]),
     "usseg_loss_from_probs_cl": (C.c_int, [P(LossDesc), P(ClassLoss), c_vp, c_vp, c_vp, c_i32, c_vp]),
+    "usseg_overlap_loss_grid": (C.c_int, [c_i64]),
+    "usseg_overlap_loss_sums": (C.c_int, [P(LossDesc), P(OverlapLoss), c_f32, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "usseg_overlap_loss_bwd": (C.c_int, [P(LossDesc), P(OverlapLoss), c_vp, c_vp, c_vp, c_i64, c_vp, c_vp]),
     "usseg_quad_bias_expand": (C.c_int, [c_vp, c_i32, c_i32, c_vp, c_vp]),
     "usseg_space_to_depth2": (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp]),
     "usseg_tconv_quad_fwd": (C.c_int, [P(ConvDesc), c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),

@@ -21,7 +21,7 @@ import torch
 from ._lib import SEG_COUNTS
 from .ops import seg_counts  # noqa: F401  (the kernel wrapper; re-exported here)
 
-__all__ = ["SEG_COUNTS", "SegMetrics", "counts_to_metrics", "seg_counts"]
+__all__ = ["SEG_COUNTS", "SegMetrics", "counts_to_metrics", "dice_per_class", "dice_line", "seg_counts"]
 
 
 def _div_no_nan(a: float, b: float) -> float:
@@ -59,6 +59,30 @@ def counts_to_metrics(counts, num_classes: int = 3) -> Dict[str, float]:
             "mean_iou": _div_no_nan(iou, valid)}
 
 
+def dice_per_class(counts, num_classes: int = 3):
+    """Counter buffer -> the (hard) Dice score of every class from the confusion matrix the counters already hold:
+    ``2*cm[c][c] / (row_c + col_c)``, div_no_nan (0.0 for a class that neither occurs nor is predicted).  Entry 2 is the class-2 (bleed)
+    score the ``c2`` pair of the reference does not give (that pair is the last image column, see above).  Same ``ValueError`` as
+    ``counts_to_metrics`` for invalid elements."""
+    nc = int(num_classes)
+    if not 1 <= nc <= 4:
+        raise ValueError(f"num_classes must be 1..4, got {nc}")
+    c = [int(v) for v in torch.as_tensor(counts).reshape(-1)[:SEG_COUNTS].cpu().tolist()]
+    invalid = c[6 + nc * nc]
+    if invalid:
+        raise ValueError(f"{invalid} invalid elements: a class outside [0, {nc}) or a prediction outside [0, 1] (TF raises for both)")
+    cm = [c[6 + i * nc:6 + (i + 1) * nc] for i in range(nc)]          # cm[true][pred]
+    return [_div_no_nan(2.0 * cm[k][k], sum(cm[k]) + sum(row[k] for row in cm)) for k in range(nc)]
+
+
+def dice_line(neuralnet, seg_metrics):
+    """The drivers' extra report line: the per-class Dice list when the model trains with a region-overlap loss, else None (nothing is
+    printed); the history keeps its keys either way."""
+    if getattr(neuralnet, "overlap_loss", None) is None:      # (models without the property - Arch A - have no overlap loss)
+        return None
+    return seg_metrics.dice()
+
+
 class SegMetrics:
     """The drivers' five Keras metric objects as ONE counter buffer: ``update_state`` is one launch, ``result`` one copy to the
     host, ``reset_states`` one fill.  ``round=True`` is the MainNumpy / TBI_TransUNet / MainParallel scoring (tf.math.round of
@@ -83,6 +107,10 @@ class SegMetrics:
 
     def result(self) -> Dict[str, float]:
         return counts_to_metrics(self.counts.cpu(), self.num_classes)
+
+    def dice(self):
+        """Per-class Dice of the counters so far (``dice_per_class``); call after ``reduce`` under data parallelism."""
+        return dice_per_class(self.counts.cpu(), self.num_classes)
 
     def reset_states(self) -> None:
         self.counts.zero_()

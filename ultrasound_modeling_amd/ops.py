@@ -1083,6 +1083,57 @@ def loss_from_probs(probs, y_true, loss, *, HW, C_classes, loss_kind=0, label_sm
             "loss_from_probs")
 
 
+# ------------------------------------------------------------------------------------------------ soft Dice / Tversky (+ CCE)
+OVERLAP_ACC_FLOATS = 8224   # USSEG_OVERLAP_ACC_FLOATS: [0] loss, [1] ticket, [2] CCE sum, [4..12) A_c, B_c, [16..32) I, P, Y, T, [32 + 16*b + k] partials
+OVERLAP_KEYS = ("alpha", "beta", "smooth", "power", "class_weight", "ce_weight", "ov_weight")
+
+
+def overlap_loss(class_weight, alpha=0.5, beta=0.5, smooth=1.0, power=1.0, ov_weight=1.0, ce_weight=0.0) -> L.OverlapLoss:
+    """A ``UssegOverlapLoss`` (usseg.h): loss = ce_weight * CCE + ov_weight * ov_scale * sum_c w[c] * (1 - T_c)^power with the Tversky index
+    T_c = (I_c + s) / ((1-a-b)*I_c + a*P_c + b*Y_c + s); alpha = beta = 0.5 is soft Dice.  ValueError for what the library would refuse:
+    more than 4 weights, a power outside [1, 4], smooth <= 0, a negative or non-finite number - and for a loss with both weights zero."""
+    w = [float(v) for v in class_weight]
+    alpha, beta, smooth, power, ov_weight, ce_weight = (float(v) for v in (alpha, beta, smooth, power, ov_weight, ce_weight))
+    if not 1 <= len(w) <= 4:
+        raise ValueError(f"overlap loss: 1 to 4 class weights, got {len(w)}")
+    if not 1.0 <= power <= 4.0:
+        raise ValueError(f"overlap loss: power must lie in [1, 4], got {power}")
+    if not (math.isfinite(smooth) and smooth > 0.0):
+        raise ValueError(f"overlap loss: smooth must be finite and > 0, got {smooth}")
+    if not all(math.isfinite(v) and v >= 0.0 for v in w + [alpha, beta, ov_weight, ce_weight]):
+        raise ValueError(f"overlap loss: weights, alpha and beta must be finite and >= 0, got {w}, {alpha}, {beta}, {ov_weight}, {ce_weight}")
+    if ov_weight == 0.0 and ce_weight == 0.0:
+        raise ValueError("overlap loss: ov_weight and ce_weight are both zero")
+    return L.OverlapLoss((L.c_f32 * 8)(*w), alpha, beta, smooth, power, ov_weight, ce_weight)
+
+
+def overlap_loss_grid(M: int) -> int:
+    """Workgroups of the sums pass for M pixels (usseg.h: the grid rule its rounding-error bound follows from)."""
+    return int(L.load().usseg_overlap_loss_grid(int(M)))
+
+
+def _overlap_desc(probs, y_true, HW, C_classes, lddl, label_smoothing, clip_eps, inv_global_batch, quad_w):
+    assert probs.dtype == torch.float32 and y_true.dtype == torch.float32 and probs.is_contiguous() and y_true.is_contiguous()
+    assert probs.shape == y_true.shape
+    return LossDesc(probs.numel() // C_classes, HW, C_classes, C_classes, lddl, 0, label_smoothing, clip_eps, inv_global_batch, quad_w)
+
+
+def overlap_loss_sums(probs, y_true, acc, *, overlap, HW, C_classes, ov_scale=1.0, label_smoothing=0.1, clip_eps=1e-7, inv_global_batch=1.0):
+    """Pass 1 on PROBABILITIES fp32 [..., C]: ``acc`` (fp32 [OVERLAP_ACC_FLOATS], zeroed once at allocation) receives the scalar loss in [0],
+    the backward coefficients in [4..12) and the totals I, P, Y, T per class from [16], all bitwise reproducible."""
+    d = _overlap_desc(probs, y_true, HW, C_classes, 8, label_smoothing, clip_eps, inv_global_batch, 0)
+    L.check(L.load().usseg_overlap_loss_sums(C.byref(d), C.byref(overlap), ov_scale, probs.data_ptr(), y_true.data_ptr(), acc.data_ptr(), acc.numel(),
+                                             _stream()), "overlap_loss_sums")
+
+
+def overlap_loss_bwd(probs, y_true, acc, dlogits, *, overlap, HW, C_classes, label_smoothing=0.1, clip_eps=1e-7, inv_global_batch=1.0, quad_w=0):
+    """Pass 2: d loss / d logits (bf16 [..., 8], or [B,H/2,W/2,16] with ``quad_w`` = the full-resolution width) from the probabilities, the labels and
+    the coefficients ``overlap_loss_sums`` left in ``acc``."""
+    d = _overlap_desc(probs, y_true, HW, C_classes, 16 if quad_w else 8, label_smoothing, clip_eps, inv_global_batch, quad_w)
+    L.check(L.load().usseg_overlap_loss_bwd(C.byref(d), C.byref(overlap), probs.data_ptr(), y_true.data_ptr(), acc.data_ptr(), acc.numel(),
+                                            dlogits.data_ptr(), _stream()), "overlap_loss_bwd")
+
+
 def quad_bias_expand(bias, C_logical, out):
     L.check(L.load().usseg_quad_bias_expand(bias.data_ptr(), C_logical, out.numel() // 4, out.data_ptr(), _stream()), "quad_bias_expand")
 
