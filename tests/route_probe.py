@@ -12,7 +12,9 @@ norm_ref / check_norm_bwd restate the LayerNorm / BatchNorm + activation forward
 kink rule that test_gpu_norm_routes.py states once in its docstring.
 
 attn_ref / window_ref / ln_wide_ref restate the attention kernels and the wide LayerNorm in fp64 with the magnitudes and the
-score-error terms that test_gpu_attn_routes.py states once in its docstring; acheck bounds an output on the device.
+score-error terms that test_gpu_attn_routes.py states once in its docstring; acheck bounds an output on the device (with `skip`, all
+but the kink-excluded elements).  seam_data(..., seam=8, cols=True) places the last image's values next to the row AND column seams of a
+2-D tile kernel (test_gpu_fused_routes.py).
 
 small_deferral(floats, first_producer=True) defers the finishing reductions of the current stream into a partial-row region of only
 `floats` floats, so that a test can place a launch's regions against the end of a full region.
@@ -38,14 +40,16 @@ def bf(t):
     return t.to(torch.bfloat16).to(torch.float64)
 
 
-def seam_data(gen, B, H, W, C, scale=1.0):
-    """bf16-exact fp64 NHWC data with one large element and a last image that is zero except near the 16-row seams."""
+def seam_data(gen, B, H, W, C, scale=1.0, seam=16, cols=False):
+    """bf16-exact fp64 NHWC data with one large element and a last image that is zero except near the `seam`-row seams (16 by default)
+    and in the last two rows; with `cols`, also kept next to the `seam`-column seams and in the last two columns (2-D tile kernels)."""
     x = bf(torch.randn(B, H, W, C, generator=gen, dtype=torch.float64) * scale)
     if B > 1 and H > 4:
-        keep = torch.zeros(H, dtype=torch.bool)
-        for r in range(H):
-            keep[r] = r % 16 in (0, 15) or r >= H - 2
-        x[B - 1, ~keep] = 0
+        near = lambda n: torch.tensor([r % seam in (0, seam - 1) or r >= n - 2 for r in range(n)])
+        keep = near(H)[:, None].expand(H, W)
+        if cols:
+            keep = keep | near(W)[None, :]
+        x[B - 1][~keep] = 0
     x[B - 1, H - 1, W - 1, C - 1] = 64 * scale      # the last element of the tensor: the ragged tail of every walk
     x[0, H // 2, 0, 0] = -48 * scale
     return x
@@ -367,9 +371,9 @@ def sa_reference(y, dout, prm, P, R, Cg, Hd, mult, norm_mode, act, sigmoid):
 
 
 # ------------------------------------------------------------------------------------------------ attention restatement (fp64)
-def acheck(what, y, ref, mag, u, c, extra=None, tiny=TINY):
-    """|y - ref| <= c*u*mag + extra + tiny for every element, evaluated on y's device (NaN fails); prints and returns the worst
-    ratio err / bound.  mag may be None (the bound is extra alone)."""
+def acheck(what, y, ref, mag, u, c, extra=None, tiny=TINY, skip=None):
+    """|y - ref| <= c*u*mag + extra + tiny for every element (not in the boolean `skip`), evaluated on y's device (NaN fails); prints
+    and returns the worst ratio err / bound.  mag may be None (the bound is extra alone)."""
     y = y.detach().double()
     ref = ref.detach().double().to(y.device)
     lim = torch.full_like(ref, tiny)
@@ -380,7 +384,11 @@ def acheck(what, y, ref, mag, u, c, extra=None, tiny=TINY):
     assert y.shape == ref.shape == lim.shape, (what, y.shape, ref.shape, lim.shape)
     err = (y - ref).abs()
     bad = ~(err <= lim)
-    ratio = (err / lim).nan_to_num(nan=float("inf")).max().item() if y.numel() else 0.0
+    ratios = (err / lim).nan_to_num(nan=float("inf"))
+    if skip is not None:
+        keep = ~skip.to(y.device).reshape(y.shape)
+        bad, ratios = bad & keep, ratios * keep
+    ratio = ratios.max().item() if y.numel() else 0.0
     print(f"\n  bound {what}: worst ratio {ratio:.3f}", end="")
     if bad.any():
         first = tuple(bad.nonzero()[0].tolist())

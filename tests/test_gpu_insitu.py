@@ -461,6 +461,7 @@ def test_residual_S_stage_layer_by_layer(world, stage):
         dcat[..., grp.Up:] = dev(dys2[3])
         dxm = ops.conv2d_dgrad(dcat, st.wcat_d, 1, 1, ops.new_act(B, H, W, grp.cin_p, DEV))
         check("merged 1x1 backward-data (cardinal group + shortcut)", dxm[..., :grp.cin], bf(gx_both), worst=worst)
+    # (per-element bounds and multi-tile walks of both fused launches below: test_gpu_fused_routes.py)
     # ---- the fused launch (csrc/cardinal.hip): grouped 1x1 -> LN -> LeakyReLU -> grouped 3x3 -> LN -> LeakyReLU (+ pooled rows) and the
     # shortcut 1x1 -> LN -> LeakyReLU from ONE read of the stage input.  Its only input is x, so the later tensors are compared with the
     # oracle's own chain (same bf16 storage points): a value that lands on the other side of a rounding boundary moves the tensors behind it.

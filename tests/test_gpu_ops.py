@@ -1146,7 +1146,7 @@ def test_ordered_sum_of_a_loss_map(gen, n):
 def test_fused_cardinal_forward_equals_the_unfused_launches(gen, cin, cv11, cvkk, oc, B, H, W):
     """csrc/cardinal.hip on ragged geometries (the native 256x80 grid gives 64x20, 32x10, 16x5 stages; tiles are 8x8): every output of
     the fused launch against the six launches it replaces (same packed operands, same rounding points), incl. pad channels and the
-    pooled partial rows."""
+    pooled partial rows.  Per-element bounds on seam data and a larger tile decode: test_gpu_fused_routes.py."""
     from ultrasound_modeling_amd import ops
     P = 3
     U, V = P * cv11, P * cvkk
@@ -1219,7 +1219,8 @@ def test_fused_stem_is_bit_identical_to_its_four_launches(gen, B, H, W):
 def test_fused_cardinal_backward_equals_the_unfused_launches(gen, cin, cv11, cvkk, oc, B, H, W):
     """csrc/cardinal.hip backward (K3) on ragged geometries: dv, du_raw, dsc_raw and the nine per-channel gradient vectors of the ONE fused
     launch against the four launches it replaces (norm_act_bwd_sa -> conv2d_dgrad 3x3 -> norm_act_bwd | norm_act_bwd of the shortcut) on the
-    same inputs and packed operands; same rounding points (dv and du are bf16 where the unfused launches store them)."""
+    same inputs and packed operands; same rounding points (dv and du are bf16 where the unfused launches store them).  Per-element bounds
+    and the persistent walk (more tiles than workgroup pairs): test_gpu_fused_routes.py."""
     from ultrasound_modeling_amd import ops
     P = 3
     U, V = P * cv11, P * cvkk
