@@ -861,6 +861,46 @@ int usseg_prep_label_thick(const double* brain, int32_t Hb, int32_t Wb, const do
 int usseg_prep_assemble(const double* frames, const double* stats, int32_t C, int32_t H0, int32_t W0, const double* bmode, int32_t Hq,
                         int32_t Wq, int32_t F, const float* label, const uint8_t* gate, int32_t objective, double* out, usseg_stream_t stream);
 
+/* ---- DataFilePlayGround.dataAug on the device (prep_aug.hip; DataFilePlayGround.py:177-246 of the reference, as executed) ---------------
+ * Records are dense fp64 [N][H][W][C], H, W >= 4, C >= 3: channel 0 the label, 1..C-2 the displacement frames, C-1 the B-mode image.
+ * DESIGN.md section 4h defines every step.  All arithmetic fp64 without fused multiply-adds, the order statistics exact: bitwise
+ * reproducible.
+ *
+ * usseg_select_ranks_f64: x fp64 [N][n] -> out fp64 [N][R], out[s][i] = the value of rank ranks[i] (0 = the smallest) of segment s, by a
+ *   radix select on the order-preserving 64-bit key of a double with -0.0 folded onto +0.0 (a zero is returned as +0.0; NaNs sort by
+ *   their bits, positive ones last).  ranks is a HOST array of R <= 4 values in [0, n), the same for every segment.  active (device int32
+ *   [N], nullable): a segment whose entry is 0 is skipped and its out row left untouched.  One workgroup per (segment, rank), LDS integer
+ *   histograms, no grid-wide wait.  Errors: a null pointer, N outside [1, 65535], n outside [1, 2^31), R outside [1, 4], a rank outside
+ *   [0, n). */
+int usseg_select_ranks_f64(const double* x, int32_t N, int64_t n, const int32_t* ranks, int32_t R, const int32_t* active, double* out,
+                           usseg_stream_t stream);
+#define USSEG_PREP_AUG_PARTIALS 64
+typedef struct UssegPrepAugSample {
+  int32_t do_flip, do_reduc, do_contrast, do_clip;
+  int32_t clip[4];                               /* r, c, ra, ca */
+  int32_t do_rotate, rot_slot;                   /* rot_slot: this sample's place in rot_list / the coefficient buffer */
+  int32_t do_shift, shift_r, shift_c, shift_dir;
+  int32_t do_noise, reserved;
+  uint64_t seed;                                 /* of the generated noise */
+  double rot[6];                                 /* R00, R01, R10, R11, offset0, offset1: source (y, x) = R (i, j) + offset */
+} UssegPrepAugSample;
+typedef struct UssegPrepAugDesc {
+  int32_t N, H, W, C;
+  int32_t n_rot;                                 /* entries of rot_list: the samples that rotate */
+  int32_t k_lo, k_hi;                            /* floor of the 2nd / 98th percentile's position among the H*W*C values ... */
+  double g_lo, g_hi;                             /* ... and its fraction (numpy's linear rule) */
+  double zH, zW;                                 /* z^(H-1), z^(W-1), z = sqrt(3) - 2 */
+} UssegPrepAugDesc;
+/* The workspace of usseg_prep_aug in doubles, -1 on a bad argument. */
+int64_t usseg_prep_aug_ws_doubles(int32_t N, int32_t H, int32_t W, int32_t C, int32_t n_rot);
+/* out[n] = dataAug(x[n]) with the draws samples_dev[n] (device table), seven launches whatever N and the draws are.  x is not modified.
+ * rot_list_dev: device int32, its first n_rot entries the samples with do_rotate in rising order (at least one readable entry).  noise:
+ * the unit Gaussian field fp64 [N][H][W][C-1] or NULL (then a counter-based generator seeded per sample); noise_out (nullable, same shape)
+ * receives the field that was used, 0 where a sample takes none.  Errors: a null pointer, geometry, H*W*C >= 2^31, n_rot outside [0, N],
+ * ranks outside the record, weights outside [0, 1), non-finite zH / zW, a workspace below usseg_prep_aug_ws_doubles. */
+int usseg_prep_aug(const UssegPrepAugDesc* d, const UssegPrepAugSample* samples_dev, const int32_t* rot_list_dev, const double* x,
+                   const double* noise, double* ws, int64_t ws_doubles, double* out, double* noise_out, usseg_stream_t stream);
+
 /* ---- the evaluator's cone figures (cone.hip; TBIEvaluator.Display, TBIEvaluator.py:276-355 of the reference) ---------------------------
  * pcolormesh(X, Y, C[:-1, :-1], shading='flat') scan-converted at px_per_unit pixels per axis unit, then colour-mapped; DESIGN.md
  * section 4i.  All arithmetic fp64 without fused multiply-adds; every result is order-independent: bitwise reproducible.

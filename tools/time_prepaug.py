@@ -1,0 +1,72 @@
+"""Timing of DataFilePlayGround.dataAug_batch (csrc/prep_aug.hip) on one [64, 256, 80, 12] batch with every step on, next to the host cost
+of the same batch through the NumPy / scipy restatement of tests/prepaug_restatement.py (diagnostic).
+
+    python tools/time_prepaug.py                 # one JSON line
+    python tools/time_prepaug.py --trace         # a few batches, for a kernel trace:
+                                                 # rocprofv3 --kernel-trace --stats -- python tools/time_prepaug.py --trace
+
+    device_ms          one batch on the device, device events around `calls` batches: the table upload, the workspace allocation and the seven launches
+    host_ms            the same batch through the restatement, one record after the other on one core (`--host-records` of them, scaled)
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+N, H, W, Cc = 64, 256, 80, 12
+
+
+def batch(seed=0):
+    import prepaug_restatement as R
+    rng = np.random.default_rng(seed)
+    x = np.stack([R.record(rng, H, W, Cc) for _ in range(N)])
+    sets = [R.params(flip=True, reduc=True, contrast=True, clip=(100 + k, 30, 30, 15), rotate=True, angle=(k % 11) / 5, shift=(k % 31, k % 13, k % 2),
+                     noise=True, seed=k) for k in range(N)]
+    return x, sets, rng.standard_normal((N, H, W, Cc - 1))
+
+
+def main(a):
+    import prepaug_restatement as R
+    from ultrasound_modeling_amd.DataFilePlayGround import dataAug_batch
+    x, sets, field = batch()
+    xd = torch.from_numpy(x).cuda()
+    for _ in range(3):
+        dataAug_batch(xd, sets)
+    torch.cuda.synchronize()
+    if a.trace:
+        print("trace: 3 batches", flush=True)
+        return
+    per = []
+    for _ in range(a.repeats):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(a.calls):
+            dataAug_batch(xd, sets)
+        e1.record()
+        e1.synchronize()
+        per.append(e0.elapsed_time(e1) / a.calls)
+    t0 = time.perf_counter()
+    for k in range(a.host_records):
+        R.dataAug(x[k], sets[k], field[k])
+    host = (time.perf_counter() - t0) * 1e3 * N / a.host_records
+    out = {"batch": [N, H, W, Cc], "device_ms": statistics.median(per), "device_ms_min_max": [min(per), max(per)], "host_ms": host,
+           "host_records_timed": a.host_records, "record_bytes": int(x.nbytes)}
+    print(f"device {out['device_ms']:.3f} ms per batch ({min(per):.3f} .. {max(per):.3f}); restatement on the host {host:.0f} ms per batch", flush=True)
+    print(json.dumps(out), flush=True)
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--calls", type=int, default=10)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--host-records", type=int, default=4)
+    ap.add_argument("--trace", action="store_true")
+    main(ap.parse_args())

@@ -56,6 +56,17 @@ class AugDesc(C.Structure):
     _fields_ = [("B", c_i32), ("H", c_i32), ("W", c_i32), ("C", c_i32), ("Cphys", c_i32), ("num_classes", c_i32)]
 
 
+class PrepAugSample(C.Structure):
+    _fields_ = [("do_flip", c_i32), ("do_reduc", c_i32), ("do_contrast", c_i32), ("do_clip", c_i32), ("clip", c_i32 * 4), ("do_rotate", c_i32),
+                ("rot_slot", c_i32), ("do_shift", c_i32), ("shift_r", c_i32), ("shift_c", c_i32), ("shift_dir", c_i32), ("do_noise", c_i32),
+                ("reserved", c_i32), ("seed", C.c_uint64), ("rot", C.c_double * 6)]
+
+
+class PrepAugDesc(C.Structure):
+    _fields_ = [("N", c_i32), ("H", c_i32), ("W", c_i32), ("C", c_i32), ("n_rot", c_i32), ("k_lo", c_i32), ("k_hi", c_i32),
+                ("g_lo", C.c_double), ("g_hi", C.c_double), ("zH", C.c_double), ("zW", C.c_double)]
+
+
 class NormDesc(C.Structure):
     _fields_ = [("M", c_i64), ("C", c_i32), ("Cphys", c_i32), ("ldx", c_i32), ("ldy", c_i32), ("G", c_i32),
                 ("mode", c_i32), ("eps", c_f32), ("act", c_i32), ("alpha", c_f32), ("lddx", c_i32)]
@@ -253,6 +264,9 @@ _PROTOS = {
     "usseg_prep_label": (C.c_int, [c_vp, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "usseg_prep_label_thick": (C.c_int, [c_vp, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "usseg_prep_assemble": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp]),
+    "usseg_select_ranks_f64": (C.c_int, [c_vp, c_i32, c_i64, P(c_i32), c_i32, c_vp, c_vp, c_vp]),
+    "usseg_prep_aug_ws_doubles": (c_i64, [c_i32, c_i32, c_i32, c_i32, c_i32]),
+    "usseg_prep_aug": (C.c_int, [P(PrepAugDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
     "usseg_cone_index": (C.c_int, [c_vp, c_vp, c_i32, c_i32, C.c_double, C.c_double, C.c_double, c_i32, c_i32, c_vp, c_vp]),
     "usseg_cone_range": (C.c_int, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "usseg_cone_render": (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, P(C.c_double), c_vp, c_vp, c_vp,

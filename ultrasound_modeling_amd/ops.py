@@ -1378,6 +1378,48 @@ def prep_label_thick(brain, blood, order):
     return label, gate
 
 
+def select_ranks_f64(x, ranks, active=None):
+    """x fp64 [N,n] -> fp64 [N,len(ranks)]: the value of each rank (0 = the smallest, at most 4 ranks) of every row, exact (a radix select
+    on the device; a zero comes back as +0.0).  active (int32 [N], optional): rows whose entry is 0 are skipped and come back as NaN."""
+    _prep_check(x, "x", torch.float64, 2)
+    ranks = [int(r) for r in ranks]
+    if active is not None:
+        _prep_check(active, "active", torch.int32, 1)
+        if active.shape[0] != x.shape[0] or active.device != x.device:
+            raise ValueError("select_ranks_f64: active must hold one entry per row of x, on its device")
+    out = torch.full((x.shape[0], len(ranks)), float("nan"), dtype=torch.float64, device=x.device)
+    L.check(L.load().usseg_select_ranks_f64(x.data_ptr(), x.shape[0], x.shape[1], (C.c_int32 * max(len(ranks), 1))(*ranks), len(ranks),
+                                            _ptr(active), out.data_ptr(), _stream()), "select_ranks_f64")
+    return out
+
+
+def prep_aug(images, table, rot_list, n_rot, k_lo, g_lo, k_hi, g_hi, zH, zW, noise=None, noise_out=None):
+    """DataFilePlayGround.dataAug of a batch in seven launches (csrc/prep_aug.hip): images fp64 [N,H,W,Cc] -> a new fp64 [N,H,W,Cc].
+    table: uint8 tensor holding N UssegPrepAugSample; rot_list int32 [>= max(n_rot, 1)]; (k, g) the floor and fraction of the 2nd and 98th
+    percentile's position among H*W*Cc values; zH, zW = (sqrt(3)-2)^(H-1), ^(W-1); noise / noise_out fp64 [N,H,W,Cc-1] or None."""
+    _prep_check(images, "images", torch.float64, 4)
+    _prep_check(table, "table", torch.uint8, 1)
+    _prep_check(rot_list, "rot_list", torch.int32, 1)
+    N, H, W, Cc = images.shape
+    if table.numel() != N * C.sizeof(L.PrepAugSample) or rot_list.numel() < max(n_rot, 1):
+        raise ValueError("prep_aug: table or rot_list does not match the batch")
+    for t, name in ((noise, "noise"), (noise_out, "noise_out")):
+        if t is not None:
+            _prep_check(t, name, torch.float64, 4)
+            if tuple(t.shape) != (N, H, W, Cc - 1):
+                raise ValueError(f"prep_aug: {name} must be [N, H, W, Cc-1] = {(N, H, W, Cc - 1)}, is {tuple(t.shape)}")
+    lib = L.load()
+    need = lib.usseg_prep_aug_ws_doubles(N, H, W, Cc, n_rot)
+    if need < 0:
+        raise ValueError(f"prep_aug: bad geometry {tuple(images.shape)}, n_rot {n_rot}")
+    ws = torch.empty(need, dtype=torch.float64, device=images.device)
+    out = torch.empty_like(images)
+    d = L.PrepAugDesc(N, H, W, Cc, n_rot, k_lo, k_hi, g_lo, g_hi, zH, zW)
+    L.check(lib.usseg_prep_aug(C.byref(d), table.data_ptr(), rot_list.data_ptr(), images.data_ptr(), _ptr(noise), ws.data_ptr(), need,
+                               out.data_ptr(), _ptr(noise_out), _stream()), "prep_aug")
+    return out
+
+
 def prep_assemble(frames, stats, bmode, label, gate, objective):
     """The images of every cycle of one file: fp64 [C,1,256,80,12] (DataFilePlayGround.py:353-393).  frames fp64 [C,10,H0,W0], stats from
     prep_cycle_stats, bmode fp64 [C,Hq,Wq,F] (bModeNorm with the cycle axis first), label / gate from prep_label."""
