@@ -192,7 +192,10 @@ int usseg_tconv2d_wgrad(const UssegConvDesc* d, const void* x, const void* dy, f
 int usseg_pack_weight(const float* src, int64_t sT, int64_t sN, int64_t sK, int32_t T, int32_t Nn, int32_t Kk,
                       void* dst, int32_t Kw, int32_t tap_stride, int32_t n_off, int32_t k_off,
                       usseg_stream_t stream);
-/* All packs of a model in one launch: `jobs_dev` is a DEVICE array of njobs descriptors (same fields as above). */
+/* All packs of a model in one launch: `jobs_dev` is a DEVICE array of njobs descriptors (same fields as above).  usseg_pack_weight refuses
+ * k_off + Kk > tap_stride and T*tap_stride > Kw; the two batched forms cannot read the device table and check nothing: a job may place its
+ * segment at any k_off with Kk <= tap_stride and k_off + (T-1)*tap_stride + Kk <= Kw (the quad operands and the decoder's concatenated
+ * backward-data operand do), and the jobs of one launch must write disjoint elements. */
 typedef struct UssegPackJob {
   const float* src;
   void* dst;
@@ -641,7 +644,9 @@ int usseg_overlap_loss_bwd(const UssegLossDesc* d, const UssegOverlapLoss* ol, c
  * the bias and the gradients between the Keras variables and that form: bias16[cls*4+n] = bias[n];
  * dbias[n] += sum_cls d16[cls*4+n] (head, Np = 4);  grad[kh][kw][n][c] += dq[(di+1)*3+(dj+1)][c][(a*2+b)*Np+n], dq = [9][Cin_phys][4*Np]. */
 int usseg_quad_bias_expand(const float* bias, int32_t C, int32_t Np, float* out /* [4*Np] */, usseg_stream_t stream);
-int usseg_quad_bias_fold(const float* d16, int32_t C, float* dbias, usseg_stream_t stream);
+/* d16 is [4][4] - the head's own Np = 4, whatever Np the other helpers are given: dbias[n] += d16[n] + d16[4+n] + d16[8+n] + d16[12+n], n < C <= 4.
+ * (usseg_quad_head_fold strides its d16 by the Np it is passed; the two agree bit for bit at Np = 4.) */
+int usseg_quad_bias_fold(const float* d16 /* [4][4] */, int32_t C, float* dbias, usseg_stream_t stream);
 int usseg_tconv_quad_unpack(const float* dq, int32_t Cin_phys, int32_t Cin, int32_t Cout, int32_t Np, int32_t ksize, float* grad,
                             usseg_stream_t stream);
 /* usseg_tconv_quad_unpack + usseg_quad_bias_fold (with d16 = [4][Np] column sums) as ONE launch: the tail of the quad-form head's backward. */
