@@ -637,6 +637,55 @@ int usseg_overlap_loss_sums(const UssegLossDesc* d, const UssegOverlapLoss* ol, 
                             float* acc, int64_t acc_floats, usseg_stream_t stream);
 int usseg_overlap_loss_bwd(const UssegLossDesc* d, const UssegOverlapLoss* ol, const float* probs, const float* y_true, const float* acc,
                            int64_t acc_floats, void* dlogits, usseg_stream_t stream);
+/* ---- exact Euclidean distance maps (csrc/sdf.hip) ------------------------------------------------------------------------------------
+ * usseg_sdf_labels: y_true fp32 [B,H,W,C] - the labels exactly as the loss kernels get them, C <= 4, soft labels allowed - -> phi fp32
+ * [B,H,W,C], the layout of probs.  Per image and class the mask is y_c > thr (NaN is outside the mask).  With d(A) at a pixel the Euclidean
+ * distance to the nearest pixel of the set A:
+ *     outside the mask  phi = d(mask)              (the first pixel outside is 1)
+ *     inside the mask   phi = 1 - d(not mask)      (the first pixel inside is 0)
+ * which is Kervadec et al.'s signed distance map, scipy form  edt(~m)*~m - (edt(m) - 1)*m.  A class with no mask pixel in that image has
+ * phi = 0 everywhere - and so has a class that covers the WHOLE image: a deliberate deviation (SciPy's distance_transform_edt of an image
+ * without a background pixel is an arbitrary ramp; a class without a boundary has no boundary term).  Exactness is part of the contract:
+ * squared distances are computed in int32 and are exact, and phi is the fp64 value (the square root of that integer; 1 minus it inside the
+ * mask) rounded ONCE to fp32 - outside the mask the correctly rounded fp32 square root (double rounding is innocuous for square roots of
+ * integers below 2^31).  A second call gives the same bits.
+ * H and W each lie in [1, 8192], B in [0, 65535], B*H*W <= 2^29; anything else is USSEG_ERR_BAD_ARG before any launch, like a workspace
+ * (16-byte aligned) of fewer than usseg_sdf_ws_bytes(B,H,W,C) bytes (-1 for a shape the transform refuses).  Nothing allocates; two launches.
+ *
+ * usseg_surface_dist: a, b uint8 [N,H,W] masks, nonzero = inside.  The surface S(m) is the set of mask pixels with at least one 4-neighbour
+ * outside the mask, out-of-image counting as outside (medpy's / SciPy's  m & ~binary_erosion(m, border_value=0)).  Per image
+ *     counters int64 [N,4] = |S(a)|, |S(b)|, max over S(a) of the SQUARED distance to S(b), max over S(b) of the squared distance to S(a)
+ *     sums     fp64  [N,2] = sum over S(a) of the distance to S(b), sum over S(b) of the distance to S(a)
+ * When either surface is empty both maxima are -1 and both sums 0.  The sums are bitwise reproducible: one workgroup per image and
+ * direction, a thread adds its pixels in index order, the 256 partial sums are added as a fixed tree; no float atomics.  Hausdorff distance
+ * = sqrt(max of the two maxima); average symmetric surface distance (medpy) = mean of sums[0]/|S(a)| and sums[1]/|S(b)|.  HD95 needs a
+ * per-image selection and is not provided.  Same limits as above with N for B; workspace usseg_surface_ws_bytes(N,H,W). */
+int64_t usseg_sdf_ws_bytes(int32_t B, int32_t H, int32_t W, int32_t C);
+int usseg_sdf_labels(const float* y_true, int32_t B, int32_t H, int32_t W, int32_t C, float thr, float* phi, void* ws, int64_t ws_bytes,
+                     usseg_stream_t stream);
+int64_t usseg_surface_ws_bytes(int32_t N, int32_t H, int32_t W);
+int usseg_surface_dist(const uint8_t* a, const uint8_t* b, int32_t N, int32_t H, int32_t W, int64_t* counters, double* sums, void* ws,
+                       int64_t ws_bytes, usseg_stream_t stream);
+/* ---- the boundary term on top of the region-overlap losses (Kervadec et al.; csrc/overlap_loss.hip) ------------------------------------
+ *     L_B = wb * ov_scale * (1/M) * sum_m sum_c u[c] * p_c(m) * phi_c(m)          loss = (the overlap loss above) + L_B
+ * phi fp32 [M][C] (16-byte aligned) is usseg_sdf_labels' map of the same labels, M the pixels of this call, u[c] per-class weights (finite,
+ * >= 0; only u[0..C) is read), ov_scale the same data-parallel factor the overlap term takes, and wb the boundary weight - read from DEVICE
+ * memory when the kernel runs, so a captured graph follows a weight that grows during training.  The two entry points take everything
+ * usseg_overlap_loss_sums / _bwd take and are further instantiations of the same two kernels:
+ *   usseg_overlap_boundary_loss_sums   acc[0] = overlap loss + L_B;  acc[12] = L_B alone;  acc[13] = wb*ov_scale/M, the coefficient of
+ *                                      u[c]*phi_c(m) in G_c(m);  every other slot as usseg_overlap_loss_sums leaves it.  The one extra total
+ *                                      rides in the same ordered reduction (3C + 2 values a workgroup).
+ *   usseg_overlap_boundary_loss_bwd    G_c(m) = A_c*y_c(m) + B_c + acc[13]*u[c]*phi_c(m) (+ the CCE term) in dlogit_j = p_j*(G_j - sum_c p_c*G_c):
+ *                                      still ONE bf16 rounding of the fp32 value.  Reads acc[4..12) and acc[13].
+ * With *wb == 0 the loss and every dlogits element equal the plain pair's bit for bit (pass 2 skips the summand when acc[13] is zero). */
+typedef struct UssegBoundaryLoss {
+  float u[8]; /* per-class weight of the boundary term */
+} UssegBoundaryLoss;
+int usseg_overlap_boundary_loss_sums(const UssegLossDesc* d, const UssegOverlapLoss* ol, float ov_scale, const float* probs, const float* y_true,
+                                     const float* phi, const UssegBoundaryLoss* bl, const float* wb, float* acc, int64_t acc_floats,
+                                     usseg_stream_t stream);
+int usseg_overlap_boundary_loss_bwd(const UssegLossDesc* d, const UssegOverlapLoss* ol, const float* probs, const float* y_true, const float* phi,
+                                    const UssegBoundaryLoss* bl, const float* acc, int64_t acc_floats, void* dlogits, usseg_stream_t stream);
 /* The <= 4-class head Conv2DTranspose(k x k, stride 2, 'same') (Decoder.py:120 k=3; TBI_ResNest.py:124 k=4) in "quad" form: a
  * stride-1 convolution at the INPUT resolution whose 16 output channels are (output parity class)*4 + n, run by
  * usseg_conv2d_fwd/dgrad/wgrad as a 3x3 conv (each parity uses <= 2x2 of the stencil taps, the rest are zero).  With

@@ -39,8 +39,9 @@ class Process(object):
         self.test_iter = 0
         self.history = []
 
-    def training(self, neuralnet, dataset, epochs):
-        """MainNumpy.py:31-88 -> None; one dict per epoch in ``self.history`` (``phase`` "train")."""
+    def training(self, neuralnet, dataset, epochs, *, boundary_ramp=None):
+        """MainNumpy.py:31-88 -> None; one dict per epoch in ``self.history`` (``phase`` "train").  ``boundary_ramp`` (default off): added to the model's boundary
+        weight after each epoch - Kervadec et al.'s rebalancing; the weight is a device float, so a captured graph follows it."""
         print("\nTraining to %d epochs (%d of minibatch size)" % (epochs, self.batch_size))
         iteration = 0
         prev_loss = 0
@@ -68,6 +69,8 @@ class Process(object):
                 print("Model is throwing a fit")
                 print(class_score)
             prev_loss = loss
+            if boundary_ramp is not None:
+                neuralnet.set_boundary_weight(neuralnet.boundary_weight + float(boundary_ramp))
             if epoch % 5 == 0:
                 self.test(neuralnet, dataset, epoch)
             # :83-88 (the learning-rate "schedule"): installed before the first step with schedule=True, see the module docstring
@@ -99,14 +102,16 @@ class Process(object):
         return m["f1"]
 
 
-def main(train_path, val_path, save_path=None, epochs=50, batch_size=32, num_classes=3, *, loss="cce", overlap=None):
+def main(train_path, val_path, save_path=None, epochs=50, batch_size=32, num_classes=3, *, loss="cce", overlap=None, boundary=None):
     """MainNumpy.py:150-177 with the paths as arguments: ``VisionTransformer(32, img_size=(256, 80))`` over a ``Dataset_2.Dataset``,
     50 epochs, then a save if ``save_path`` is given.  ``loss``: the model's ``loss=`` ("cce", "my_loss_cat", "focal", "dice", "tversky",
-    "dice_ce"); ``overlap``: the settings of the last three (``VisionTransformer(overlap=...)``), which also add a per-class Dice line to the test report."""
+    "dice_ce"); ``overlap``: the settings of the last three (``VisionTransformer(overlap=...)``), which also add a per-class Dice line to the test report;
+    ``boundary``: the boundary term on top of one of those three (``VisionTransformer(boundary=...)``)."""
     from .Dataset_2 import Dataset
     from .VisionTransformer import VisionTransformer, overlap_settings
     dataset = Dataset(train_path, val_path, num_classes)
-    neuralnet = VisionTransformer(batch_size, img_size=input_size, num_classes=num_classes, loss=loss, overlap=overlap_settings(loss, overlap))
+    neuralnet = VisionTransformer(batch_size, img_size=input_size, num_classes=num_classes, loss=loss, overlap=overlap_settings(loss, overlap),
+                                  boundary=boundary)
     print(len(neuralnet.visionModel.layers))
     process = Process(batch_size=batch_size, num_classes=num_classes)
     process.training(neuralnet=neuralnet, dataset=dataset, epochs=epochs)

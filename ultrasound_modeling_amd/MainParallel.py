@@ -190,8 +190,9 @@ class Process(object):
         if self.trainer is None or self.trainer.rank == 0:
             print(*args, **kwargs)
 
-    def training(self, neuralnet, dataset, epochs, batch_size):
-        """MainParallel.py:41-79 -> None."""
+    def training(self, neuralnet, dataset, epochs, batch_size, *, boundary_ramp=None):
+        """MainParallel.py:41-79 -> None.  ``boundary_ramp`` (default off): added to the model's boundary
+        weight after each epoch - Kervadec et al.'s rebalancing; the weight is a device float, so a captured graph follows it."""
         assert batch_size == self.batch_size == dataset.BATCH_SIZE, "one global batch size for the driver, the dataset and the model"
         self._mirror(neuralnet)
         self._print("\nTraining to %d epochs (%d of minibatch size)" % (epochs, batch_size))
@@ -212,6 +213,8 @@ class Process(object):
             if prev_loss == loss:
                 self._print("Model is throwing a fit")
             prev_loss = loss
+            if boundary_ramp is not None:
+                neuralnet.set_boundary_weight(neuralnet.boundary_weight + float(boundary_ramp))
             self.test(neuralnet, dataset, epoch)                                                 # :72
 
     def test(self, neuralnet, dataset, epoch):
@@ -282,12 +285,13 @@ class Process(object):
 
 
 def main(train_path, val_path, save_path=None, epochs=51, batch_size=64, use_vit=True, *, seed=0, schedule=False, capture_graph=True,
-         loss="cce", overlap=None):
+         loss="cce", overlap=None, boundary=None):
     """MainParallel.py:201-216 with the paths as arguments: ``VisionTransformer(batch_size=64)`` with the ViT bottleneck, 51 epochs,
     then rank 0 saves if ``save_path`` is given.  Every rank seeds ``random`` with ``seed``, so all draw the same augmentations.
     ``loss``: the model's ``loss=`` ("cce", "my_loss_cat", "focal"); every replica divides it by the global batch all the same.  The
     region-overlap losses ("dice", "tversky", "dice_ce", settings in ``overlap``) are computed per replica on its own images and weighted by
     local batch / global batch: the SUM of the replicas is their batch-weighted mean; they add a per-class Dice line to the test report.
+    ``boundary`` (``VisionTransformer(boundary=...)``) adds the boundary term to one of those three, weighted per replica the same way.
     Under ``nccl`` the model lives on ``cuda:LOCAL_RANK``; the ``USSEG_DIST_BACKEND=gloo`` rehearsal keeps every rank on device 0."""
     from .Dataset import Dataset
     from .VisionTransformer import VisionTransformer, overlap_settings
@@ -298,7 +302,7 @@ def main(train_path, val_path, save_path=None, epochs=51, batch_size=64, use_vit
     random.seed(seed)
     dataset = Dataset(train_path, val_path, batch_size, device=device)
     neuralnet = VisionTransformer(batch_size, img_size=(dataset.height, dataset.width), in_channels=dataset.channel, use_vit=use_vit,
-                                  device=str(device), loss=loss, overlap=overlap_settings(loss, overlap))
+                                  device=str(device), loss=loss, overlap=overlap_settings(loss, overlap), boundary=boundary)
     if rank == 0:
         print(len(neuralnet.visionModel.layers))
     process = Process(batch_size, schedule=schedule, capture_graph=capture_graph)
@@ -324,9 +328,13 @@ def _cli(argv=None):
     ap.add_argument("--loss", choices=("cce", "my_loss_cat", "focal", "dice", "tversky", "dice_ce"), default="cce",
                     help="the model's loss: CategoricalCrossentropy (the reference's), its class-weighted my_loss_cat, the focal variant, or a "
                          "region-overlap loss (soft Dice, Tversky 0.3 / 0.7, Dice + CCE)")
+    ap.add_argument("--boundary-weight", type=float, default=None, metavar="W",
+                    help="add the boundary term (signed distance map of the labels times the probabilities) with weight W; needs a region-overlap --loss")
     a = ap.parse_args(argv)
+    if a.boundary_weight is not None and a.loss not in ("dice", "tversky", "dice_ce"):
+        raise SystemExit("--boundary-weight needs --loss dice, tversky or dice_ce")
     main(a.train, a.val, a.save, epochs=a.epochs, batch_size=a.batch_size, use_vit=not a.no_vit, seed=a.seed, schedule=a.schedule,
-         capture_graph=not a.no_graph, loss=a.loss)
+         capture_graph=not a.no_graph, loss=a.loss, boundary=None if a.boundary_weight is None else {"weight": a.boundary_weight})
     if dist.is_initialized():
         dist.barrier()
         dist.destroy_process_group()

@@ -189,6 +189,28 @@ def Polar_Model(data, cascade: Cascade, names=None, batch_size=16):
     return PolarResult(prob_map, bleed_prob, mask, label, bmode, None if names is None else np.asarray(names))
 
 
+# ---------------------------------------------------------------------------------------------------------- surface scores
+def surface_scores(result: PolarResult, threshold=0.5, device=None):
+    """Hausdorff and average symmetric surface distance of the bleed class, per image: the prediction ``result.bleed_prob > threshold``
+    against the label's class 2 (``label > 1.5``: ``label2vec``'s class-2 plane under the 0.5 rule).  -> ``metrics.surface_distances``' dict
+    (``hd`` / ``assd`` NaN for an image without a predicted or without a labelled bleed, ``n_a`` / ``n_b`` the two surface pixel counts)."""
+    from .metrics import surface_distances
+    return surface_distances(np.asarray(result.bleed_prob) > threshold, np.asarray(result.label) > 1.5, device=device)
+
+
+def write_surface_csv(path, result: PolarResult, threshold=0.5, device=None):
+    """One row per image: name, hd, assd, surface pixels of the prediction, surface pixels of the label.  -> the number of rows."""
+    import csv
+    s = surface_scores(result, threshold, device=device)
+    names = _names(result)
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(["name", "hd", "assd", "n_pred", "n_label"])
+        for i, n in enumerate(names):
+            w.writerow([n, repr(float(s["hd"][i])), repr(float(s["assd"][i])), int(s["n_a"][i]), int(s["n_b"][i])])
+    return len(names)
+
+
 # ---------------------------------------------------------------------------------------------------------- the figures
 PANEL_RANGES = ((0.0, 2.0), (0.0, 2.0), (0.0, 1.0))     # Prediction, label, Probability Bleed (:297, :304, :333); bMode per image
 GAP = 16                                                # white pixels between the panels
@@ -361,6 +383,8 @@ def main(argv=None):
     ap.add_argument("--no-stamp", action="store_true", help="name files <name>.png, without the %%f suffix")
     ap.add_argument("--transunet", action="store_true", help="the checkpoints are TBI_TransUNet models")
     ap.add_argument("--use-vit", action="store_true", help="the checkpoints have the ViT bottleneck")
+    ap.add_argument("--surface-csv", default=None, metavar="PATH",
+                    help="also write the bleed class's Hausdorff and average symmetric surface distance, one row per image")
     a = ap.parse_args(argv)
     if a.batch < 1:
         ap.error("--batch must be >= 1")
@@ -369,6 +393,9 @@ def main(argv=None):
     cascade = Cascade.from_checkpoints(a.bleed, a.mask, batch_size=a.batch, use_vit=a.use_vit, transunet=a.transunet)
     geometry = ConeGeometry.from_dir(a.axis_dir, px_per_unit=a.px_per_unit, device=cascade.device)
     result = Polar_Model(data, cascade, names=names, batch_size=a.batch)
+    if a.surface_csv is not None:
+        rows = write_surface_csv(a.surface_csv, result, device=cascade.device)
+        print(f"wrote {rows} surface-score rows to {a.surface_csv}")
     paths = Display(result, geometry, a.out, stamp=not a.no_stamp, batch_size=a.batch)
     print(f"wrote {len(paths)} figures under {a.out}")
 

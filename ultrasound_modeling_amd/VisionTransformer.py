@@ -14,6 +14,7 @@ actually build; its variables carry the reference's attribute paths (``transform
 from __future__ import annotations
 
 import contextlib
+import math
 from typing import Optional
 
 import torch
@@ -336,11 +337,40 @@ def overlap_config(loss, num_classes, overlap):
                             cfg.get("ce_weight", 1.0 if loss == "dice_ce" else 0.0))
 
 
+def boundary_config(loss, num_classes, boundary):
+    """The ``boundary`` settings (dict) of a model with ``loss`` in OVERLAP_LOSSES -> (weight, ``ops.boundary_loss(...)``, threshold); ValueError for
+    any other loss, an unknown key, a negative or non-finite weight, a wrong-length ``class_weight`` or a NaN threshold."""
+    if loss not in OVERLAP_LOSSES:
+        raise ValueError(f"boundary: the boundary term is an add-on to loss in {OVERLAP_LOSSES}, not to '{loss}'")
+    if not isinstance(boundary, dict):
+        raise ValueError(f"boundary: a dict of {ops.BOUNDARY_KEYS} ({{}} for the defaults), got {type(boundary).__name__}")
+    unknown = [k for k in boundary if k not in ops.BOUNDARY_KEYS]
+    if unknown:
+        raise ValueError(f"boundary: unknown settings {unknown}; known: {ops.BOUNDARY_KEYS}")
+    weight = _boundary_weight(boundary.get("weight", 0.01))
+    u = boundary.get("class_weight")
+    u = [0.0] + [1.0] * (num_classes - 1) if u is None else [float(v) for v in u]
+    if len(u) != num_classes:
+        raise ValueError(f"boundary: class_weight has {len(u)} entries for {num_classes} classes")
+    thr = float(boundary.get("threshold", 0.5))
+    if math.isnan(thr):
+        raise ValueError("boundary: threshold is NaN")
+    return weight, ops.boundary_loss(u), thr
+
+
+def _boundary_weight(w):
+    w = float(w)
+    if not (math.isfinite(w) and w >= 0.0):
+        raise ValueError(f"boundary: weight must be finite and >= 0, got {w}")
+    return w
+
+
 class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
     def __init__(self, batch_size, img_size=(256, 80), num_classes=3, learning_rate=1e-3, weight_decay=1e-4, *,
                  in_channels: int = 10, use_vit: bool = False, device: Optional[str] = None, seed: Optional[int] = 0,
                  transunet: bool = False, adamw: bool = False, loss: str = "cce", class_factor=None, focal_gamma=None,
-                 overlap=None, alpha=None, beta=None, smooth=None, power=None, class_weight=None, ce_weight=None, ov_weight=None):
+                 overlap=None, alpha=None, beta=None, smooth=None, power=None, class_weight=None, ce_weight=None, ov_weight=None,
+                 boundary=None):
         """``transunet=True`` builds the older self-contained copy of this model in TBI_TransUNet.py (BASELINE configs[3]):
         BatchNormalization where ResNest.py / Decoder.py use LayerNormalization (:304,426,465,472,503), conv_4 = 256 channels
         (:368), and the loss is CategoricalCrossentropy(label_smoothing=0.1) with the DEFAULT reduction - the mean over all
@@ -367,7 +397,13 @@ class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
         bare name with neither ``overlap`` nor a keyword stays the ValueError it was before these losses existed (callers and a test rely on
         ``loss="dice"`` alone being refused; the drivers' ``main(loss=...)`` pass ``{}`` themselves).  ``overlap`` - a dict, or the same names as keywords - sets ``alpha, beta`` (tversky only),
         ``smooth`` (1), ``power`` (1, up to 4), ``class_weight`` (uniform 1/classes), ``ov_weight`` (1), ``ce_weight`` (dice_ce only).  The
-        overlap term is weighted by local batch / global batch (``transunet``: 1), so SUM-reduced replicas train on the batch-weighted mean."""
+        overlap term is weighted by local batch / global batch (``transunet``: 1), so SUM-reduced replicas train on the batch-weighted mean.
+
+        ``boundary`` (a dict; only with a region-overlap loss) adds Kervadec et al.'s boundary term to it: weight * overlap factor * the mean over
+        the pixels of sum_c class_weight[c] * p_c * phi_c, phi the exact signed distance map of the labels (``ops.sdf_labels``, computed on the
+        device once per step).  Keys: ``weight`` (0.01), ``class_weight`` (0 for class 0, 1 for every other class), ``threshold`` (0.5: the mask
+        of a soft label).  ``boundary={}`` takes the defaults.  The weight lives on the device: ``set_boundary_weight`` reaches a captured graph's
+        next replay without a recapture, and a checkpoint keeps it."""
         super().__init__()
         if loss not in LOSSES + OVERLAP_LOSSES:
             raise ValueError(f"loss must be one of {LOSSES + OVERLAP_LOSSES}, got {loss!r}")
@@ -383,6 +419,7 @@ class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
         if loss in OVERLAP_LOSSES and (class_factor is not None or focal_gamma is not None):
             raise ValueError(f"class_factor / focal_gamma do not apply to loss='{loss}' (its weights are overlap['class_weight'])")
         self._overlap = overlap_config(loss, num_classes, overlap) if loss in OVERLAP_LOSSES else None
+        bnd = None if boundary is None else boundary_config(loss, num_classes, boundary)
         if focal_gamma is not None and loss != "focal":
             raise ValueError("focal_gamma only applies to loss='focal'")
         self.alpha = 2                                                                  # :208
@@ -419,8 +456,28 @@ class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
                                   weight_decay=weight_decay if adamw else None)
         self._loss = torch.zeros(ops.ACC_FLOATS if self._overlap is None else ops.OVERLAP_ACC_FLOATS, dtype=torch.float32,
                                  device=self.device)                                         # [0] = the scalar loss
+        self._boundary, self._boundary_thr, self._wb = None, 0.5, None
+        if bnd is not None:
+            self._boundary, self._boundary_thr = bnd[1], bnd[2]
+            self._wb = torch.full((1,), bnd[0], dtype=torch.float32, device=self.device)      # read by the sums kernel when it runs
         self.grad_sync = None                   # set by the data-parallel wrapper: callable(flat_grad)
         self._graph = None
+
+    @property
+    def boundary_loss(self):
+        """The ``UssegBoundaryLoss`` of a model built with ``boundary=``, or None."""
+        return self._boundary
+
+    @property
+    def boundary_weight(self):
+        """The boundary weight the next step uses, read from the device (synchronises); None without a boundary term."""
+        return None if self._wb is None else float(self._wb.item())
+
+    def set_boundary_weight(self, w):
+        """From the next step on, eager or replayed: the kernel reads the device float, so a captured graph needs no recapture."""
+        if self._wb is None:
+            raise ValueError("set_boundary_weight: the model was built without boundary=")
+        self._wb.fill_(_boundary_weight(w))
 
     @property
     def overlap_loss(self):
@@ -437,11 +494,16 @@ class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
         """model.save of a compiled Keras model (MainNumpy.py:177): variables, BN statistics AND the optimiser state."""
         d = self.export_params()
         d.update(self.optimizer.state_dict())
+        if self._wb is not None:
+            d["__boundary_weight__"] = self._wb.detach().clone()
         torch.save(d, path)
 
     def load(self, path):
         d = torch.load(path, map_location="cpu", weights_only=True)
         self.optimizer.load_state_dict({k: d.pop(k) for k in list(d) if k.startswith("__adam_")})
+        wb = d.pop("__boundary_weight__", None)      # (a checkpoint of a model without the term leaves the constructor's weight)
+        if wb is not None and self._wb is not None:
+            self._wb.copy_(wb.to(self._wb.device))
         self.load_params(d)
 
     @property
@@ -538,7 +600,14 @@ class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
         if logits is not None:
             ops.softmax_loss(logits, None, probs, None, None, HW=H * W, C_classes=C, quad_w=self.decoder.quad_w)
         kw = dict(overlap=self._overlap, HW=H * W, C_classes=C, label_smoothing=0.1, clip_eps=1e-7, inv_global_batch=scale)
-        ops.overlap_loss_sums(probs, y, self._loss, ov_scale=1.0 if self.transunet else float(B) / float(self.batch_size), **kw)
+        ov_scale = 1.0 if self.transunet else float(B) / float(self.batch_size)
+        if self._boundary is not None:          # the labels' distance map once per step, then the pair that carries the boundary term
+            phi = ops.sdf_labels(y, threshold=self._boundary_thr)
+            ops.overlap_boundary_loss_sums(probs, y, phi, self._loss, boundary=self._boundary, wb=self._wb, ov_scale=ov_scale, **kw)
+            if dlogits is not None:
+                ops.overlap_boundary_loss_bwd(probs, y, phi, self._loss, dlogits, boundary=self._boundary, quad_w=self.decoder.quad_w, **kw)
+            return probs, dlogits
+        ops.overlap_loss_sums(probs, y, self._loss, ov_scale=ov_scale, **kw)
         if dlogits is not None:
             ops.overlap_loss_bwd(probs, y, self._loss, dlogits, quad_w=self.decoder.quad_w, **kw)
         return probs, dlogits
@@ -570,9 +639,13 @@ class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
         H, W = y_pred.shape[1], y_pred.shape[2]
         if self._overlap is not None:       # the overlap loss of THESE tensors, weighted as a step weights a batch of their size
             acc = torch.zeros(ops.OVERLAP_ACC_FLOATS, dtype=torch.float32, device=self.device)
-            ops.overlap_loss_sums(y_pred, y_true, acc, overlap=self._overlap, HW=H * W, C_classes=y_pred.shape[-1], label_smoothing=0.1, clip_eps=1e-7,
-                                  ov_scale=1.0 if self.transunet else float(y_pred.shape[0]) / float(self.batch_size),
-                                  inv_global_batch=1.0 / float(self.batch_size))
+            kw = dict(overlap=self._overlap, HW=H * W, C_classes=y_pred.shape[-1], label_smoothing=0.1, clip_eps=1e-7,
+                      ov_scale=1.0 if self.transunet else float(y_pred.shape[0]) / float(self.batch_size), inv_global_batch=1.0 / float(self.batch_size))
+            if self._boundary is not None:
+                phi = ops.sdf_labels(y_true, threshold=self._boundary_thr)
+                ops.overlap_boundary_loss_sums(y_pred, y_true, phi, acc, boundary=self._boundary, wb=self._wb, **kw)
+            else:
+                ops.overlap_loss_sums(y_pred, y_true, acc, **kw)
             return acc[0].clone()
         loss = torch.empty(ops.ACC_FLOATS, dtype=torch.float32, device=self.device)
         ops.fill_f32(loss, 0.0)

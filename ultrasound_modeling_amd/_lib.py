@@ -107,6 +107,11 @@ class OverlapLoss(C.Structure):
                 ("ce_weight", c_f32)]
 
 
+class BoundaryLoss(C.Structure):
+    """UssegBoundaryLoss: the per-class weights of the boundary term (usseg.h); passed by reference, copied into the launches."""
+    _fields_ = [("u", c_f32 * 8)]
+
+
 class FlashDesc(C.Structure):
     _fields_ = [("B", c_i32), ("N", c_i32), ("H", c_i32), ("head_dim", c_i32), ("ld_qkv", c_i32), ("ld_o", c_i32), ("scale", c_f32)]
 
@@ -214,6 +219,12 @@ _PROTOS = {
     "usseg_overlap_loss_grid": (C.c_int, [c_i64]),
     "usseg_overlap_loss_sums": (C.c_int, [P(LossDesc), P(OverlapLoss), c_f32, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "usseg_overlap_loss_bwd": (C.c_int, [P(LossDesc), P(OverlapLoss), c_vp, c_vp, c_vp, c_i64, c_vp, c_vp]),
+    "usseg_sdf_ws_bytes": (c_i64, [c_i32, c_i32, c_i32, c_i32]),
+    "usseg_sdf_labels": (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp, c_i64, c_vp]),
+    "usseg_surface_ws_bytes": (c_i64, [c_i32, c_i32, c_i32]),
+    "usseg_surface_dist": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "usseg_overlap_boundary_loss_sums": (C.c_int, [P(LossDesc), P(OverlapLoss), c_f32, c_vp, c_vp, c_vp, P(BoundaryLoss), c_vp, c_vp, c_i64, c_vp]),
+    "usseg_overlap_boundary_loss_bwd": (C.c_int, [P(LossDesc), P(OverlapLoss), c_vp, c_vp, c_vp, P(BoundaryLoss), c_vp, c_i64, c_vp, c_vp]),
     "usseg_quad_bias_expand": (C.c_int, [c_vp, c_i32, c_i32, c_vp, c_vp]),
     "usseg_space_to_depth2": (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp]),
     "usseg_tconv_quad_fwd": (C.c_int, [P(ConvDesc), c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),

@@ -8,16 +8,22 @@
 // aligned, checked by the entry points); the last group of an M that is no multiple of 4 takes guarded scalar loads.
 // The CCE arithmetic restates loss_kind 0 of attn_loss_optim.hip (softmax_loss_pixel) rather than sharing it through a header: that
 // file's kernels stay instruction for instruction what they were.
+// The boundary term (usseg.h, UssegBoundaryLoss; BD instantiations of the same two kernels): L_B = wb*ov_scale/M * sum_m sum_c u_c*p_c*phi_c with
+// phi the signed distance map of the labels (sdf.hip).  Pass 1 carries one more total, reads wb from DEVICE memory, adds L_B to acc[0] and leaves
+// L_B in acc[12] and the coefficient wb*ov_scale/M in acc[13]; pass 2 adds acc[13]*u_c*phi_c(m) to G_c(m) in front of the ONE bf16 rounding - and
+// skips that summand when the coefficient is zero, so wb = 0 gives the bits of the plain pair.
 #include "common.h"
 #include <cmath>
 
-#define OV_HDR 32        // acc[0] loss, [1] ticket, [2] CCE pixel sum, [4..8) A_c, [8..12) B_c, [16..20) I_c, [20..24) P_c, [24..28) Y_c, [28..32) T_c
-#define OV_STRIDE 16     // floats per workgroup row of partials (3C + 1 <= 13 used): acc[OV_HDR + 16*b + k]
+#define OV_HDR 32        // acc[0] loss, [1] ticket, [2] CCE pixel sum, [4..8) A_c, [8..12) B_c, [12] L_B, [13] wb*ov_scale/M, [16..20) I_c, [20..24) P_c, [24..28) Y_c, [28..32) T_c
+#define OV_STRIDE 16     // floats per workgroup row of partials (3C + 2 <= 14 used): acc[OV_HDR + 16*b + k]
 #define OV_MAX_BLOCKS ((USSEG_OVERLAP_ACC_FLOATS - OV_HDR) / OV_STRIDE)
 static_assert(OV_MAX_BLOCKS == 512, "usseg.h documents the grid rule with 512 workgroups");
 
 // the parameters as the kernels take them, by value: ovk = ov_weight * ov_scale and cek = ce_weight * inv_global_batch folded on the host
 struct OverlapK { float w[4]; float alpha, beta, smooth, power, ovk, cek; };
+// the boundary term's arguments (BD instantiations only): u_c, bscale = ov_scale / M folded on the host, phi [M][C], the device float wb
+struct BoundaryK { float u[4]; float bscale; const float* phi; const float* wb; };
 
 template <int C>
 __device__ __forceinline__ void ov_load_group(const float* __restrict__ base, int g, int M, float (&v)[4 * C]) {
@@ -68,10 +74,10 @@ __device__ __forceinline__ float ov_cce_pixel(const float* p, const float* y, fl
 // issue before every partial is at the memory side), and the LAST workgroup to arrive adds the rows in a fixed order - thread (j, k) the
 // workgroups j, j+16, j+32, ... of value k, then thread k the sixteen j as a balanced tree.  No workgroup waits for another; no float
 // atomics; the ticket is back at zero when the kernel ends.  tools/check_ordered_sum.py checks the ISA of this sequence on every build.
-template <int C, bool CE>
-__global__ __launch_bounds__(256) void overlap_sums_kernel(const OverlapK k, const float* __restrict__ probs, const float* __restrict__ y_true,
-                                                            float* acc, int M, int ngroups, float ls, float eps) {
-  constexpr int K = 3 * C + 1;
+template <int C, bool CE, bool BD>
+__global__ __launch_bounds__(256) void overlap_sums_kernel(const OverlapK k, const BoundaryK bk, const float* __restrict__ probs,
+                                                            const float* __restrict__ y_true, float* acc, int M, int ngroups, float ls, float eps) {
+  constexpr int K = 3 * C + 1 + (BD ? 1 : 0);       // (the boundary total is value 3C + 1, behind the CCE sum)
   __shared__ float red[4][OV_STRIDE];
   __shared__ float fin[16][OV_STRIDE + 1];
   __shared__ float tot[OV_STRIDE];
@@ -93,6 +99,17 @@ __global__ __launch_bounds__(256) void overlap_sums_kernel(const OverlapK k, con
       }
       if (CE && 4 * g + j < M) s[3 * C] += ov_cce_pixel<C, false>(p + j * C, y + j * C, ls, eps, nullptr);
     }
+    if constexpr (BD) {
+      float f[4 * C];
+      ov_load_group<C>(bk.phi, g, M, f);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        float t = 0.f;
+#pragma unroll
+        for (int c = 0; c < C; ++c) t += bk.u[c] * (p[j * C + c] * f[j * C + c]);
+        s[3 * C + 1] += t;
+      }
+    }
   }
 #pragma unroll
   for (int i = 0; i < K; ++i) {
@@ -109,7 +126,7 @@ __global__ __launch_bounds__(256) void overlap_sums_kernel(const OverlapK k, con
       const float old = __hip_atomic_exchange(acc + OV_HDR + blockIdx.x * OV_STRIDE + threadIdx.x, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       asm volatile("; ticket after the partials are at the memory side" : "+v"(zero) : "v"(old));
     }
-    for (int msk = 8; msk >= 1; msk >>= 1) zero |= __shfl_xor(zero, msk, 64);     // lane 0 holds a value that depends on all K returns (K <= 13)
+    for (int msk = 8; msk >= 1; msk >>= 1) zero |= __shfl_xor(zero, msk, 64);     // lane 0 holds a value that depends on all K returns (K <= 14)
     if (threadIdx.x == 0) {
       const unsigned tk = __hip_atomic_fetch_add(reinterpret_cast<unsigned*>(acc + 1), 1u + zero, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       s_last = (tk == (unsigned)nb - 1u);
@@ -159,7 +176,13 @@ __global__ __launch_bounds__(256) void overlap_sums_kernel(const OverlapK k, con
     }
     const float ce = CE ? tot[3 * C] : 0.f;
     acc[2] = ce;
-    acc[0] = k.cek * ce + k.ovk * lov;             // OVERWRITES: no zero-fill launch in front of the kernel
+    float loss = k.cek * ce + k.ovk * lov;
+    if constexpr (BD) {
+      const float kb = *bk.wb * bk.bscale, lb = kb * tot[3 * C + 1];
+      acc[12] = lb; acc[13] = kb;
+      loss += lb;                                  // (wb = 0: lb is a zero, the sum the bits of the plain loss)
+    }
+    acc[0] = loss;                                 // OVERWRITES: no zero-fill launch in front of the kernel
     __hip_atomic_store(reinterpret_cast<unsigned*>(acc + 1), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
@@ -167,17 +190,22 @@ __global__ __launch_bounds__(256) void overlap_sums_kernel(const OverlapK k, con
 // ---- pass 2 -------------------------------------------------------------------------------------------------------------------------
 // Row layout: dl[m*8 + c], one 16-byte store per pixel with the pad channels zero.  Quad layout (UssegLossDesc.quad_w): pixel (y, x) in
 // slot 4*((y&1)*2 + (x&1)) of the 16-channel pixel (y/2, x/2), one 8-byte store per pixel - the four pixels of a 2x2 block fill all 16.
-template <int C, bool CE, bool QUAD>
-__global__ __launch_bounds__(256) void overlap_bwd_kernel(const float cek, const float* __restrict__ probs, const float* __restrict__ y_true,
-                                                           const float* __restrict__ acc, bf16_t* __restrict__ dl, int M, int ngroups, int HW,
-                                                           int W, float ls, float eps) {
-  float A[C], B[C];
+template <int C, bool CE, bool QUAD, bool BD>
+__global__ __launch_bounds__(256) void overlap_bwd_kernel(const float cek, const BoundaryK bk, const float* __restrict__ probs,
+                                                           const float* __restrict__ y_true, const float* __restrict__ acc, bf16_t* __restrict__ dl, int M,
+                                                           int ngroups, int HW, int W, float ls, float eps) {
+  float A[C], B[C], U[C];
 #pragma unroll
-  for (int c = 0; c < C; ++c) { A[c] = acc[4 + c]; B[c] = acc[8 + c]; }
+  for (int c = 0; c < C; ++c) { A[c] = acc[4 + c]; B[c] = acc[8 + c]; U[c] = BD ? acc[13] * bk.u[c] : 0.f; }
+  const bool bd = BD && acc[13] != 0.f;
   for (int g = blockIdx.x * 256 + threadIdx.x; g < ngroups; g += gridDim.x * 256) {
     float p[4 * C], y[4 * C];
     ov_load_group<C>(probs, g, M, p);
     ov_load_group<C>(y_true, g, M, y);
+    float f[BD ? 4 * C : 1];
+    if constexpr (BD) {
+      if (bd) ov_load_group<C>(bk.phi, g, M, f);
+    }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int m = 4 * g + j;
@@ -185,6 +213,12 @@ __global__ __launch_bounds__(256) void overlap_bwd_kernel(const float cek, const
       float G[C];
 #pragma unroll
       for (int c = 0; c < C; ++c) G[c] = A[c] * y[j * C + c] + B[c];
+      if constexpr (BD) {
+        if (bd) {
+#pragma unroll
+          for (int c = 0; c < C; ++c) G[c] += U[c] * f[j * C + c];
+        }
+      }
       if (CE) {
         float dce[C];
         ov_cce_pixel<C, true>(p + j * C, y + j * C, ls, eps, dce);
@@ -246,14 +280,33 @@ extern "C" int usseg_overlap_loss_grid(int64_t M) {
   return (int)(g < 1 ? 1 : g > OV_MAX_BLOCKS ? OV_MAX_BLOCKS : g);
 }
 
-extern "C" int usseg_overlap_loss_sums(const UssegLossDesc* d, const UssegOverlapLoss* ol, float ov_scale, const float* probs, const float* y_true,
-                                       float* acc, int64_t acc_floats, usseg_stream_t stream) {
-  int rc = overlap_args("overlap_loss_sums", d, ol, probs, y_true, acc, acc_floats);
+// the boundary term's arguments, checked like the rest (d->C is known to be valid here)
+static int boundary_args(const char* who, const UssegLossDesc* d, const float* phi, const UssegBoundaryLoss* bl, const float* wb) {
+  USSEG_CHECK_ARG(bl, "%s: null boundary-loss struct", who);
+  USSEG_CHECK_ARG(phi && wb, "%s: null pointer (phi, wb)", who);
+  USSEG_CHECK_ARG(((uintptr_t)phi & 15) == 0 && ((uintptr_t)wb & 3) == 0, "%s: phi must be 16-byte, wb 4-byte aligned", who);
+  for (int c = 0; c < d->C; ++c) USSEG_CHECK_ARG(std::isfinite(bl->u[c]) && bl->u[c] >= 0.f, "%s: boundary class weights must be finite and >= 0", who);
+  return USSEG_OK;
+}
+static BoundaryK boundary_k(const UssegLossDesc* d, const float* phi, const UssegBoundaryLoss* bl, const float* wb, float ov_scale) {
+  BoundaryK bk = {};
+  for (int c = 0; c < d->C; ++c) bk.u[c] = bl->u[c];
+  bk.bscale = d->M > 0 ? (float)((double)ov_scale / (double)d->M) : 0.f;
+  bk.phi = phi; bk.wb = wb;
+  return bk;
+}
+
+static int overlap_sums_impl(const char* who, const UssegLossDesc* d, const UssegOverlapLoss* ol, float ov_scale, const float* probs, const float* y_true,
+                             const float* phi, const UssegBoundaryLoss* bl, const float* wb, bool bd, float* acc, int64_t acc_floats,
+                             usseg_stream_t stream) {
+  int rc = overlap_args(who, d, ol, probs, y_true, acc, acc_floats);
   if (rc) return rc;
-  USSEG_CHECK_ARG(std::isfinite(ov_scale) && ov_scale >= 0.f, "overlap_loss_sums: ov_scale must be finite and >= 0");
+  if (bd && (rc = boundary_args(who, d, phi, bl, wb))) return rc;
+  USSEG_CHECK_ARG(std::isfinite(ov_scale) && ov_scale >= 0.f, "%s: ov_scale must be finite and >= 0", who);
   const int grid = usseg_overlap_loss_grid(d->M);
-  USSEG_CHECK_ARG(acc_floats >= OV_HDR + (int64_t)OV_STRIDE * grid, "overlap_loss_sums: a grid of %d workgroups needs %d accumulator floats", grid,
+  USSEG_CHECK_ARG(acc_floats >= OV_HDR + (int64_t)OV_STRIDE * grid, "%s: a grid of %d workgroups needs %d accumulator floats", who, grid,
                   OV_HDR + OV_STRIDE * grid);
+  const BoundaryK bk = bd ? boundary_k(d, phi, bl, wb, ov_scale) : BoundaryK{};
   OverlapK k = {};
   for (int c = 0; c < d->C; ++c) k.w[c] = ol->w[c];
   k.alpha = ol->alpha; k.beta = ol->beta; k.smooth = ol->smooth; k.power = ol->power;
@@ -262,29 +315,44 @@ extern "C" int usseg_overlap_loss_sums(const UssegLossDesc* d, const UssegOverla
   const bool ce = ol->ce_weight != 0.f;
   const int M = (int)d->M, ng = overlap_groups(d);
   hipStream_t s = (hipStream_t)stream;
-#define OV_SUMS(CC)                                                                                                                          \
-  if (ce) hipLaunchKernelGGL((overlap_sums_kernel<CC, true>), dim3(grid), dim3(256), 0, s, k, probs, y_true, acc, M, ng, d->label_smoothing,  \
-                             d->clip_eps);                                                                                                   \
-  else hipLaunchKernelGGL((overlap_sums_kernel<CC, false>), dim3(grid), dim3(256), 0, s, k, probs, y_true, acc, M, ng, 0.f, 0.f)
+#define OV_SUMS2(CC, CEB, BDB)                                                                                                               \
+  hipLaunchKernelGGL((overlap_sums_kernel<CC, CEB, BDB>), dim3(grid), dim3(256), 0, s, k, bk, probs, y_true, acc, M, ng, CEB ? d->label_smoothing : 0.f, \
+                     CEB ? d->clip_eps : 0.f)
+#define OV_SUMS(CC)                                                            \
+  if (ce) { if (bd) OV_SUMS2(CC, true, true); else OV_SUMS2(CC, true, false); } \
+  else { if (bd) OV_SUMS2(CC, false, true); else OV_SUMS2(CC, false, false); }
   switch (d->C) {
-    case 1: OV_SUMS(1); break;
-    case 2: OV_SUMS(2); break;
-    case 3: OV_SUMS(3); break;
-    default: OV_SUMS(4); break;
+    case 1: OV_SUMS(1) break;
+    case 2: OV_SUMS(2) break;
+    case 3: OV_SUMS(3) break;
+    default: OV_SUMS(4) break;
   }
 #undef OV_SUMS
-  return usseg_check_launch("overlap_loss_sums");
+#undef OV_SUMS2
+  return usseg_check_launch(who);
 }
 
-extern "C" int usseg_overlap_loss_bwd(const UssegLossDesc* d, const UssegOverlapLoss* ol, const float* probs, const float* y_true, const float* acc,
-                                      int64_t acc_floats, void* dlogits, usseg_stream_t stream) {
-  int rc = overlap_args("overlap_loss_bwd", d, ol, probs, y_true, acc, acc_floats);
+extern "C" int usseg_overlap_loss_sums(const UssegLossDesc* d, const UssegOverlapLoss* ol, float ov_scale, const float* probs, const float* y_true,
+                                       float* acc, int64_t acc_floats, usseg_stream_t stream) {
+  return overlap_sums_impl("overlap_loss_sums", d, ol, ov_scale, probs, y_true, nullptr, nullptr, nullptr, false, acc, acc_floats, stream);
+}
+
+extern "C" int usseg_overlap_boundary_loss_sums(const UssegLossDesc* d, const UssegOverlapLoss* ol, float ov_scale, const float* probs, const float* y_true,
+                                                const float* phi, const UssegBoundaryLoss* bl, const float* wb, float* acc, int64_t acc_floats,
+                                                usseg_stream_t stream) {
+  return overlap_sums_impl("overlap_boundary_loss_sums", d, ol, ov_scale, probs, y_true, phi, bl, wb, true, acc, acc_floats, stream);
+}
+
+static int overlap_bwd_impl(const char* who, const UssegLossDesc* d, const UssegOverlapLoss* ol, const float* probs, const float* y_true, const float* phi,
+                            const UssegBoundaryLoss* bl, bool bd, const float* acc, int64_t acc_floats, void* dlogits, usseg_stream_t stream) {
+  int rc = overlap_args(who, d, ol, probs, y_true, acc, acc_floats);
   if (rc) return rc;
-  USSEG_CHECK_ARG(dlogits && ((uintptr_t)dlogits & 15) == 0, "overlap_loss_bwd: dlogits must be a 16-byte aligned pointer");
-  USSEG_CHECK_ARG(d->quad_w == 0 || (d->quad_w > 0 && d->quad_w % 2 == 0 && d->HW % (2 * d->quad_w) == 0),
-                  "overlap_loss_bwd: quad layout needs even H and W");
-  USSEG_CHECK_ARG(d->lddl == (d->quad_w ? 16 : 8), "overlap_loss_bwd: dlogits stride must be 8 (16 in the quad layout)");
+  if (bd && (rc = boundary_args(who, d, phi, bl, acc))) return rc;      // (pass 2 reads the coefficient from acc[13], not wb)
+  USSEG_CHECK_ARG(dlogits && ((uintptr_t)dlogits & 15) == 0, "%s: dlogits must be a 16-byte aligned pointer", who);
+  USSEG_CHECK_ARG(d->quad_w == 0 || (d->quad_w > 0 && d->quad_w % 2 == 0 && d->HW % (2 * d->quad_w) == 0), "%s: quad layout needs even H and W", who);
+  USSEG_CHECK_ARG(d->lddl == (d->quad_w ? 16 : 8), "%s: dlogits stride must be 8 (16 in the quad layout)", who);
   if (d->M == 0) return USSEG_OK;
+  const BoundaryK bk = bd ? boundary_k(d, phi, bl, acc, 0.f) : BoundaryK{};
   const float cek = ol->ce_weight * d->inv_global_batch;
   const bool ce = ol->ce_weight != 0.f;
   const int M = (int)d->M, ng = overlap_groups(d);
@@ -293,12 +361,14 @@ extern "C" int usseg_overlap_loss_bwd(const UssegLossDesc* d, const UssegOverlap
   const dim3 grid((unsigned)g);
   bf16_t* dl = (bf16_t*)dlogits;
   hipStream_t s = (hipStream_t)stream;
-#define OV_BWD2(CC, CEB, Q)                                                                                                                  \
-  hipLaunchKernelGGL((overlap_bwd_kernel<CC, CEB, Q>), grid, dim3(256), 0, s, cek, probs, y_true, acc, dl, M, ng, d->HW, d->quad_w ? d->quad_w : 1, \
-                     d->label_smoothing, d->clip_eps)
+#define OV_BWD3(CC, CEB, Q, BDB)                                                                                                             \
+  hipLaunchKernelGGL((overlap_bwd_kernel<CC, CEB, Q, BDB>), grid, dim3(256), 0, s, cek, bk, probs, y_true, acc, dl, M, ng, d->HW,              \
+                     d->quad_w ? d->quad_w : 1, d->label_smoothing, d->clip_eps)
+#define OV_BWD2(CC, CEB, Q) \
+  if (bd) OV_BWD3(CC, CEB, Q, true); else OV_BWD3(CC, CEB, Q, false)
 #define OV_BWD(CC)                                                \
-  if (ce) { if (d->quad_w) OV_BWD2(CC, true, true); else OV_BWD2(CC, true, false); } \
-  else { if (d->quad_w) OV_BWD2(CC, false, true); else OV_BWD2(CC, false, false); }
+  if (ce) { if (d->quad_w) { OV_BWD2(CC, true, true); } else { OV_BWD2(CC, true, false); } } \
+  else { if (d->quad_w) { OV_BWD2(CC, false, true); } else { OV_BWD2(CC, false, false); } }
   switch (d->C) {
     case 1: OV_BWD(1) break;
     case 2: OV_BWD(2) break;
@@ -307,5 +377,16 @@ extern "C" int usseg_overlap_loss_bwd(const UssegLossDesc* d, const UssegOverlap
   }
 #undef OV_BWD
 #undef OV_BWD2
-  return usseg_check_launch("overlap_loss_bwd");
+#undef OV_BWD3
+  return usseg_check_launch(who);
+}
+
+extern "C" int usseg_overlap_loss_bwd(const UssegLossDesc* d, const UssegOverlapLoss* ol, const float* probs, const float* y_true, const float* acc,
+                                      int64_t acc_floats, void* dlogits, usseg_stream_t stream) {
+  return overlap_bwd_impl("overlap_loss_bwd", d, ol, probs, y_true, nullptr, nullptr, false, acc, acc_floats, dlogits, stream);
+}
+
+extern "C" int usseg_overlap_boundary_loss_bwd(const UssegLossDesc* d, const UssegOverlapLoss* ol, const float* probs, const float* y_true, const float* phi,
+                                               const UssegBoundaryLoss* bl, const float* acc, int64_t acc_floats, void* dlogits, usseg_stream_t stream) {
+  return overlap_bwd_impl("overlap_boundary_loss_bwd", d, ol, probs, y_true, phi, bl, true, acc, acc_floats, dlogits, stream);
 }

@@ -16,6 +16,8 @@ from __future__ import annotations
 
 from typing import Dict
 
+import numpy as np
+
 import torch
 
 from ._lib import SEG_COUNTS
@@ -73,6 +75,32 @@ def dice_per_class(counts, num_classes: int = 3):
         raise ValueError(f"{invalid} invalid elements: a class outside [0, {nc}) or a prediction outside [0, 1] (TF raises for both)")
     cm = [c[6 + i * nc:6 + (i + 1) * nc] for i in range(nc)]          # cm[true][pred]
     return [_div_no_nan(2.0 * cm[k][k], sum(cm[k]) + sum(row[k] for row in cm)) for k in range(nc)]
+
+
+def surface_scores_from_counters(counters, sums):
+    """``usseg_surface_dist``'s per-image results -> {"hd", "assd", "n_a", "n_b", "max_ab", "max_ba", "sum_ab", "sum_ba"}, NumPy arrays [N].
+    hd = sqrt(max(max_ab, max_ba)) (the maxima are SQUARED distances); assd = the mean of the two directional means sum_ab / n_a and
+    sum_ba / n_b, as medpy's ``assd``; both NaN for an image where either surface is empty."""
+    c = torch.as_tensor(counters).cpu().numpy().astype(np.int64).reshape(-1, 4)
+    s = torch.as_tensor(sums).cpu().numpy().astype(np.float64).reshape(-1, 2)
+    ok = (c[:, 0] > 0) & (c[:, 1] > 0)
+    na, nb = np.where(ok, c[:, 0], 1), np.where(ok, c[:, 1], 1)
+    hd = np.where(ok, np.sqrt(np.maximum(np.maximum(c[:, 2], c[:, 3]), 0).astype(np.float64)), np.nan)
+    assd = np.where(ok, 0.5 * (s[:, 0] / na + s[:, 1] / nb), np.nan)
+    return {"hd": hd, "assd": assd, "n_a": c[:, 0], "n_b": c[:, 1], "max_ab": c[:, 2], "max_ba": c[:, 3], "sum_ab": s[:, 0], "sum_ba": s[:, 1]}
+
+
+def surface_distances(a, b, device=None):
+    """Hausdorff distance and average symmetric surface distance of two stacks of masks [N,H,W] (anything ``!= 0`` is inside; NumPy or
+    torch), in pixels, on the device: surfaces by the 4-neighbour erosion rule, exact Euclidean distances (usseg.h ``usseg_surface_dist``).
+    -> the dict of ``surface_scores_from_counters``.  HD95 needs a per-image selection and is not provided."""
+    from . import ops
+    dev = torch.device(device if device is not None else "cuda")
+    ta, tb = ((torch.as_tensor(m) != 0).to(device=dev, dtype=torch.uint8).contiguous() for m in (a, b))
+    if ta.dim() != 3 or ta.shape != tb.shape:
+        raise ValueError(f"surface_distances: two [N,H,W] stacks of one shape, got {tuple(ta.shape)} and {tuple(tb.shape)}")
+    counters, sums = ops.surface_dist(ta, tb)
+    return surface_scores_from_counters(counters, sums)
 
 
 def dice_line(neuralnet, seg_metrics):

@@ -1134,6 +1134,80 @@ def overlap_loss_bwd(probs, y_true, acc, dlogits, *, overlap, HW, C_classes, lab
                                             dlogits.data_ptr(), _stream()), "overlap_loss_bwd")
 
 
+# ------------------------------------------------------------------------------------------------ distance maps, the boundary term
+BOUNDARY_KEYS = ("weight", "class_weight", "threshold")
+
+
+def boundary_loss(class_weight) -> L.BoundaryLoss:
+    """A ``UssegBoundaryLoss`` (usseg.h): the per-class weights u[c] of L_B = wb * ov_scale / M * sum_m sum_c u[c] * p_c * phi_c.  ValueError for
+    what the library would refuse."""
+    u = [float(v) for v in class_weight]
+    if not 1 <= len(u) <= 4:
+        raise ValueError(f"boundary loss: 1 to 4 class weights, got {len(u)}")
+    if not all(math.isfinite(v) and v >= 0.0 for v in u):
+        raise ValueError(f"boundary loss: class weights must be finite and >= 0, got {u}")
+    return L.BoundaryLoss((L.c_f32 * 8)(*u))
+
+
+def sdf_ws_bytes(B: int, H: int, W: int, C_classes: int) -> int:
+    """Workspace bytes of ``sdf_labels`` (usseg_sdf_ws_bytes); ValueError for a shape the transform refuses."""
+    n = int(L.load().usseg_sdf_ws_bytes(B, H, W, C_classes))
+    if n < 0:
+        raise ValueError(f"sdf_labels: H and W must lie in [1, 8192] and C in [1, 4], got {B}x{H}x{W}x{C_classes}")
+    return n
+
+
+def sdf_labels(y_true, phi=None, ws=None, *, threshold=0.5):
+    """Kervadec's signed distance map of the labels (usseg.h usseg_sdf_labels): y_true fp32 [B,H,W,C] -> phi fp32 [B,H,W,C], exact.  ``phi`` and
+    ``ws`` (uint8, ``sdf_ws_bytes`` long) are allocated when not given; a captured step passes its own."""
+    assert y_true.dtype == torch.float32 and y_true.is_contiguous() and y_true.dim() == 4
+    B, H, W, Cc = y_true.shape
+    need = sdf_ws_bytes(B, H, W, Cc)
+    if phi is None:
+        phi = torch.empty_like(y_true)
+    if ws is None:
+        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=y_true.device)
+    assert phi.dtype == torch.float32 and phi.is_contiguous() and phi.shape == y_true.shape and ws.dtype == torch.uint8
+    L.check(L.load().usseg_sdf_labels(y_true.data_ptr(), B, H, W, Cc, float(threshold), phi.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "sdf_labels")
+    return phi
+
+
+def surface_dist(a, b, ws=None):
+    """Surface-to-surface distances of two uint8 [N,H,W] masks (usseg.h usseg_surface_dist) -> (counters int64 [N,4], sums fp64 [N,2])."""
+    assert a.dtype == torch.uint8 and b.dtype == torch.uint8 and a.is_contiguous() and b.is_contiguous() and a.dim() == 3 and a.shape == b.shape
+    N, H, W = a.shape
+    need = int(L.load().usseg_surface_ws_bytes(N, H, W))
+    if need < 0:
+        raise ValueError(f"surface_dist: H and W must lie in [1, 8192], got {N}x{H}x{W}")
+    if ws is None:
+        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=a.device)
+    counters = torch.empty((N, 4), dtype=torch.int64, device=a.device)
+    sums = torch.empty((N, 2), dtype=torch.float64, device=a.device)
+    L.check(L.load().usseg_surface_dist(a.data_ptr(), b.data_ptr(), N, H, W, counters.data_ptr(), sums.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+            "surface_dist")
+    return counters, sums
+
+
+def overlap_boundary_loss_sums(probs, y_true, phi, acc, *, overlap, boundary, wb, HW, C_classes, ov_scale=1.0, label_smoothing=0.1, clip_eps=1e-7,
+                               inv_global_batch=1.0):
+    """``overlap_loss_sums`` plus the boundary term: ``phi`` = ``sdf_labels(y_true)``, ``boundary`` a ``boundary_loss(...)``, ``wb`` a DEVICE fp32
+    tensor holding the boundary weight (read when the kernel runs).  acc[0] = overlap loss + L_B, acc[12] = L_B, acc[13] = wb*ov_scale/M."""
+    d = _overlap_desc(probs, y_true, HW, C_classes, 8, label_smoothing, clip_eps, inv_global_batch, 0)
+    assert phi.dtype == torch.float32 and phi.is_contiguous() and phi.shape == probs.shape and wb.dtype == torch.float32 and wb.device == probs.device
+    L.check(L.load().usseg_overlap_boundary_loss_sums(C.byref(d), C.byref(overlap), ov_scale, probs.data_ptr(), y_true.data_ptr(), phi.data_ptr(),
+                                                      C.byref(boundary), wb.data_ptr(), acc.data_ptr(), acc.numel(), _stream()),
+            "overlap_boundary_loss_sums")
+
+
+def overlap_boundary_loss_bwd(probs, y_true, phi, acc, dlogits, *, overlap, boundary, HW, C_classes, label_smoothing=0.1, clip_eps=1e-7,
+                              inv_global_batch=1.0, quad_w=0):
+    """``overlap_loss_bwd`` with the boundary summand acc[13]*u[c]*phi_c(m) in G_c(m): one bf16 rounding."""
+    d = _overlap_desc(probs, y_true, HW, C_classes, 16 if quad_w else 8, label_smoothing, clip_eps, inv_global_batch, quad_w)
+    assert phi.dtype == torch.float32 and phi.is_contiguous() and phi.shape == probs.shape
+    L.check(L.load().usseg_overlap_boundary_loss_bwd(C.byref(d), C.byref(overlap), probs.data_ptr(), y_true.data_ptr(), phi.data_ptr(), C.byref(boundary),
+                                                     acc.data_ptr(), acc.numel(), dlogits.data_ptr(), _stream()), "overlap_boundary_loss_bwd")
+
+
 def quad_bias_expand(bias, C_logical, out):
     L.check(L.load().usseg_quad_bias_expand(bias.data_ptr(), C_logical, out.numel() // 4, out.data_ptr(), _stream()), "quad_bias_expand")
 
