@@ -666,6 +666,38 @@ int usseg_sdf_labels(const float* y_true, int32_t B, int32_t H, int32_t W, int32
 int64_t usseg_surface_ws_bytes(int32_t N, int32_t H, int32_t W);
 int usseg_surface_dist(const uint8_t* a, const uint8_t* b, int32_t N, int32_t H, int32_t W, int64_t* counters, double* sums, void* ws,
                        int64_t ws_bytes, usseg_stream_t stream);
+/* ---- connected components (csrc/components.hip) ----------------------------------------------------------------------------------------
+ * Masks are uint8 [N,H,W], nonzero = inside; components are 4- or 8-connected (any other connectivity is refused) and never cross an image.
+ * H and W each lie in [1, 8192], N in [0, 65535], N*H*W <= 2^29; labels, count, prob and the hit tables are 4-byte, stats 8-byte and the
+ * workspace 16-byte aligned; anything else is USSEG_ERR_BAD_ARG before any launch, like a workspace of fewer than
+ * usseg_components_ws_bytes(N,H,W) bytes (-1 for a refused shape; 12 bytes per pixel plus 4 per image row).  N == 0 returns 0 without a
+ * launch.  Nothing allocates and nothing synchronises with the host: every launch goes to `stream` in order, so a call captures as one
+ * linear chain.  Every result is an integer sum, minimum or maximum: a second call gives the same bits.
+ *
+ * usseg_label_components: labels int32 [N,H,W] = 0 outside the mask and 1..K_n inside, the components of image n numbered in raster order
+ * of their first (smallest linear index) pixel - scipy.ndimage.label's numbering, element for element; count int32 [N] = K_n.
+ *
+ * usseg_component_stats: stats int64 [N,cap,8]; row k-1 of image n describes the component with id k <= cap:
+ *     area, y_min, x_min, y_max, x_max, sum of y, sum of x, peak
+ * peak = the largest prob (fp32 [N,H,W], values in [0, 1]) over the component as its fp32 bit pattern widened to int64; a NaN never wins;
+ * 0 when prob is null.  Rows of ids that do not exist are zero; ids above cap are skipped.  0 <= cap <= H*W.
+ *
+ * usseg_clean_mask: out uint8 [N,H,W] = 1 where the pixel belongs to a component of at least min_area pixels whose peak of prob is at least
+ * min_peak (prob null: the area alone decides), else 0.  Areas and peaks are kept per component root in the workspace, not in a capped table:
+ * right for any number of components.  out may alias mask.  min_area <= 1 with min_peak <= 0 (or no prob) copies the binarised mask.
+ * A NaN min_peak is refused.
+ *
+ * usseg_component_overlap: two label images of one shape; hit_a int32 [N,cap_a], hit_a[n][k-1] = the number of pixels of a's component k
+ * that lie inside any component of b; hit_b [N,cap_b] the other way round.  Ids above the caps are skipped. */
+int64_t usseg_components_ws_bytes(int32_t N, int32_t H, int32_t W);
+int usseg_label_components(const uint8_t* mask, int32_t N, int32_t H, int32_t W, int32_t connectivity, int32_t* labels, int32_t* count, void* ws,
+                           int64_t ws_bytes, usseg_stream_t stream);
+int usseg_component_stats(const int32_t* labels, const float* prob, int32_t N, int32_t H, int32_t W, int32_t cap, int64_t* stats,
+                          usseg_stream_t stream);
+int usseg_clean_mask(const uint8_t* mask, const float* prob, int32_t N, int32_t H, int32_t W, int32_t connectivity, int32_t min_area,
+                     float min_peak, uint8_t* out, void* ws, int64_t ws_bytes, usseg_stream_t stream);
+int usseg_component_overlap(const int32_t* labels_a, const int32_t* labels_b, int32_t N, int32_t H, int32_t W, int32_t cap_a, int32_t cap_b,
+                            int32_t* hit_a, int32_t* hit_b, usseg_stream_t stream);
 /* ---- the boundary term on top of the region-overlap losses (Kervadec et al.; csrc/overlap_loss.hip) ------------------------------------
  *     L_B = wb * ov_scale * (1/M) * sum_m sum_c u[c] * p_c(m) * phi_c(m)          loss = (the overlap loss above) + L_B
  * phi fp32 [M][C] (16-byte aligned) is usseg_sdf_labels' map of the same labels, M the pixels of this call, u[c] per-class weights (finite,

@@ -190,24 +190,65 @@ def Polar_Model(data, cascade: Cascade, names=None, batch_size=16):
 
 
 # ---------------------------------------------------------------------------------------------------------- surface scores
-def surface_scores(result: PolarResult, threshold=0.5, device=None):
+def surface_scores(result: PolarResult, threshold=0.5, device=None, *, pred_mask=None):
     """Hausdorff and average symmetric surface distance of the bleed class, per image: the prediction ``result.bleed_prob > threshold``
     against the label's class 2 (``label > 1.5``: ``label2vec``'s class-2 plane under the 0.5 rule).  -> ``metrics.surface_distances``' dict
-    (``hd`` / ``assd`` NaN for an image without a predicted or without a labelled bleed, ``n_a`` / ``n_b`` the two surface pixel counts)."""
+    (``hd`` / ``assd`` NaN for an image without a predicted or without a labelled bleed, ``n_a`` / ``n_b`` the two surface pixel counts).
+    ``pred_mask`` [N,H,W] (``clean_result``'s, for one) is scored in place of ``bleed_prob > threshold``."""
     from .metrics import surface_distances
-    return surface_distances(np.asarray(result.bleed_prob) > threshold, np.asarray(result.label) > 1.5, device=device)
+    pred = np.asarray(result.bleed_prob) > threshold if pred_mask is None else np.asarray(pred_mask) != 0
+    return surface_distances(pred, np.asarray(result.label) > 1.5, device=device)
 
 
-def write_surface_csv(path, result: PolarResult, threshold=0.5, device=None):
+def write_surface_csv(path, result: PolarResult, threshold=0.5, device=None, *, pred_mask=None):
     """One row per image: name, hd, assd, surface pixels of the prediction, surface pixels of the label.  -> the number of rows."""
     import csv
-    s = surface_scores(result, threshold, device=device)
+    s = surface_scores(result, threshold, device=device, pred_mask=pred_mask)
     names = _names(result)
     with open(path, "w", newline="") as f:
         w = csv.writer(f)
         w.writerow(["name", "hd", "assd", "n_pred", "n_label"])
         for i, n in enumerate(names):
             w.writerow([n, repr(float(s["hd"][i])), repr(float(s["assd"][i])), int(s["n_a"][i]), int(s["n_b"][i])])
+    return len(names)
+
+
+# ---------------------------------------------------------------------------------------------------------- lesions
+def clean_result(result: PolarResult, threshold=0.5, *, min_area, min_peak=0.0, connectivity=8, device=None):
+    """The cleaned bleed mask, uint8 [N,H,W] (NumPy): ``bleed_prob > threshold`` without the connected components of fewer than ``min_area``
+    pixels or whose largest ``bleed_prob`` is below ``min_peak`` (usseg.h ``usseg_clean_mask``, on the device)."""
+    dev = torch.device(device if device is not None else "cuda")
+    prob = torch.from_numpy(np.ascontiguousarray(result.bleed_prob, dtype=np.float32)).to(dev)
+    if prob.dim() != 3:
+        raise ValueError(f"bleed_prob must be [N,H,W], got {tuple(prob.shape)}")
+    mask = (prob > threshold).to(torch.uint8)
+    return ops.clean_mask(mask, prob, connectivity=connectivity, min_area=min_area, min_peak=min_peak, out=mask).cpu().numpy()
+
+
+def lesion_scores(result: PolarResult, threshold=0.5, *, min_area=1, min_peak=0.0, connectivity=8, device=None):
+    """Lesion-wise detection scores of the bleed class (``metrics.lesion_scores``): the cleaned prediction (``clean_result``) against the
+    labelled lesions, the components of ``label > 1.5``."""
+    from .metrics import lesion_scores as scores
+    pred = clean_result(result, threshold, min_area=min_area, min_peak=min_peak, connectivity=connectivity, device=device)
+    return scores(pred, np.asarray(result.label) > 1.5, connectivity=connectivity, device=device)
+
+
+LESION_COLUMNS = ("n_true", "n_pred", "detected", "missed", "false_pos", "largest_true", "largest_pred")
+
+
+def write_lesion_csv(path, result: PolarResult, threshold=0.5, *, min_area=1, min_peak=0.0, connectivity=8, device=None):
+    """One row per image - name and ``LESION_COLUMNS`` - and a final row ``total`` with the column sums (the two ``largest`` columns: the
+    maxima) followed by sensitivity, precision, f1 and false positives per image over the stack.  -> the number of image rows."""
+    import csv
+    s = lesion_scores(result, threshold, min_area=min_area, min_peak=min_peak, connectivity=connectivity, device=device)
+    names = _names(result)
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(["name"] + list(LESION_COLUMNS) + ["sensitivity", "precision", "f1", "fp_per_image"])
+        for i, n in enumerate(names):
+            w.writerow([n] + [int(s[c][i]) for c in LESION_COLUMNS] + [""] * 4)
+        tot = [int(s[c].max(initial=0)) if c.startswith("largest") else int(s[c].sum()) for c in LESION_COLUMNS]
+        w.writerow(["total"] + tot + [repr(float(s[k])) for k in ("sensitivity", "precision", "f1", "fp_per_image")])
     return len(names)
 
 
@@ -385,17 +426,34 @@ def main(argv=None):
     ap.add_argument("--use-vit", action="store_true", help="the checkpoints have the ViT bottleneck")
     ap.add_argument("--surface-csv", default=None, metavar="PATH",
                     help="also write the bleed class's Hausdorff and average symmetric surface distance, one row per image")
+    ap.add_argument("--lesion-csv", default=None, metavar="PATH",
+                    help="also write the bleed class's lesion-wise detection counts, one row per image and a totals row")
+    ap.add_argument("--min-area", type=int, default=None, metavar="N",
+                    help="drop predicted bleed components of fewer than N pixels before --lesion-csv / --surface-csv score them")
+    ap.add_argument("--min-peak", type=float, default=0.0, metavar="P", help="drop predicted bleed components whose largest probability is below P (--lesion-csv; --surface-csv only together with --min-area)")
+    ap.add_argument("--connectivity", type=int, default=8, choices=(4, 8), help="pixel connectivity of a component")
     a = ap.parse_args(argv)
     if a.batch < 1:
         ap.error("--batch must be >= 1")
+    if a.min_area is not None and a.min_area < 1:
+        ap.error("--min-area must be >= 1")
+    if not 0.0 <= a.min_peak <= 1.0:
+        ap.error("--min-peak must lie in [0, 1]")
     data = np.load(a.data)
     names = np.load(a.paths)
     cascade = Cascade.from_checkpoints(a.bleed, a.mask, batch_size=a.batch, use_vit=a.use_vit, transunet=a.transunet)
     geometry = ConeGeometry.from_dir(a.axis_dir, px_per_unit=a.px_per_unit, device=cascade.device)
     result = Polar_Model(data, cascade, names=names, batch_size=a.batch)
     if a.surface_csv is not None:
-        rows = write_surface_csv(a.surface_csv, result, device=cascade.device)
+        cleaned = None
+        if a.min_area is not None:
+            cleaned = clean_result(result, min_area=a.min_area, min_peak=a.min_peak, connectivity=a.connectivity, device=cascade.device)
+        rows = write_surface_csv(a.surface_csv, result, device=cascade.device, pred_mask=cleaned)
         print(f"wrote {rows} surface-score rows to {a.surface_csv}")
+    if a.lesion_csv is not None:
+        rows = write_lesion_csv(a.lesion_csv, result, min_area=a.min_area if a.min_area is not None else 1, min_peak=a.min_peak,
+                                connectivity=a.connectivity, device=cascade.device)
+        print(f"wrote {rows} lesion rows to {a.lesion_csv}")
     paths = Display(result, geometry, a.out, stamp=not a.no_stamp, batch_size=a.batch)
     print(f"wrote {len(paths)} figures under {a.out}")
 

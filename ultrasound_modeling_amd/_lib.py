@@ -223,6 +223,11 @@ _PROTOS = {
     "usseg_sdf_labels": (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp, c_i64, c_vp]),
     "usseg_surface_ws_bytes": (c_i64, [c_i32, c_i32, c_i32]),
     "usseg_surface_dist": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "usseg_components_ws_bytes": (c_i64, [c_i32, c_i32, c_i32]),
+    "usseg_label_components": (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "usseg_component_stats": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
+    "usseg_clean_mask": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp, c_i64, c_vp]),
+    "usseg_component_overlap": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "usseg_overlap_boundary_loss_sums": (C.c_int, [P(LossDesc), P(OverlapLoss), c_f32, c_vp, c_vp, c_vp, P(BoundaryLoss), c_vp, c_vp, c_i64, c_vp]),
     "usseg_overlap_boundary_loss_bwd": (C.c_int, [P(LossDesc), P(OverlapLoss), c_vp, c_vp, c_vp, P(BoundaryLoss), c_vp, c_i64, c_vp, c_vp]),
     "usseg_quad_bias_expand": (C.c_int, [c_vp, c_i32, c_i32, c_vp, c_vp]),

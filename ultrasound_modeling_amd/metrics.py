@@ -23,7 +23,8 @@ import torch
 from ._lib import SEG_COUNTS
 from .ops import seg_counts  # noqa: F401  (the kernel wrapper; re-exported here)
 
-__all__ = ["SEG_COUNTS", "SegMetrics", "counts_to_metrics", "dice_per_class", "dice_line", "seg_counts"]
+__all__ = ["SEG_COUNTS", "SegMetrics", "components", "counts_to_metrics", "dice_per_class", "dice_line", "lesion_scores", "lesion_scores_from_tables",
+           "seg_counts"]
 
 
 def _div_no_nan(a: float, b: float) -> float:
@@ -101,6 +102,87 @@ def surface_distances(a, b, device=None):
         raise ValueError(f"surface_distances: two [N,H,W] stacks of one shape, got {tuple(ta.shape)} and {tuple(tb.shape)}")
     counters, sums = ops.surface_dist(ta, tb)
     return surface_scores_from_counters(counters, sums)
+
+
+def _mask_stack(m, dev, what):
+    t = (torch.as_tensor(m) != 0).to(device=dev, dtype=torch.uint8).contiguous()
+    if t.dim() != 3:
+        raise ValueError(f"{what}: an [N,H,W] stack of masks, got {tuple(t.shape)}")
+    return t
+
+
+def components(mask, connectivity=8, prob=None, device=None):
+    """Connected components of a stack of masks [N,H,W] (anything ``!= 0`` is inside; NumPy or torch) on the device (usseg.h
+    ``usseg_label_components`` / ``usseg_component_stats``): -> {"labels" int32 [N,H,W], "count" [N], "area" [N,cap], "bbox" [N,cap,4]
+    (y_min, x_min, y_max, x_max), "centroid" fp64 [N,cap,2] (y, x; exact integer sums divided once), "peak" fp32 [N,cap]}, NumPy arrays with
+    cap = max(count): the counts are read back once, then the table is sized.  Rows past an image's count are zero (centroid NaN).
+    ``prob`` [N,H,W] gives each component's peak probability (0 without it)."""
+    from . import ops
+    dev = torch.device(device if device is not None else "cuda")
+    tm = _mask_stack(mask, dev, "components")
+    tp = None
+    if prob is not None:
+        tp = torch.as_tensor(prob).to(device=dev, dtype=torch.float32).contiguous()
+        if tp.shape != tm.shape:
+            raise ValueError(f"components: prob {tuple(tp.shape)} and mask {tuple(tm.shape)} differ in shape")
+    labels, count = ops.label_components(tm, connectivity)
+    count = count.cpu().numpy().astype(np.int64)
+    cap = int(count.max()) if count.size else 0
+    st = ops.component_stats(labels, cap, tp).cpu().numpy()
+    area = st[..., 0]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        centroid = st[..., 5:7].astype(np.float64) / area[..., None]
+    peak = st[..., 7].astype(np.uint32).view(np.float32) if st.size else np.zeros(st.shape[:2], np.float32)
+    return {"labels": labels.cpu().numpy(), "count": count, "area": area, "bbox": st[..., 1:5], "centroid": centroid, "peak": peak}
+
+
+def lesion_scores_from_tables(count_true, count_pred, hit_true, hit_pred, area_true, area_pred, min_overlap=1):
+    """The lesion-wise scores from the integer tables of one stack: ``count_*`` [N] component counts, ``hit_true`` [N,cap_t] the pixels of each
+    labelled lesion inside the prediction, ``hit_pred`` [N,cap_p] the pixels of each predicted component inside the label, ``area_*`` the
+    component areas (columns past an image's count are ignored).  A lesion is detected with at least ``min_overlap`` of its pixels inside the
+    prediction; a predicted component without a pixel inside the label is a false positive.  -> per image (int64 [N]) ``n_true, n_pred,
+    detected, missed, false_pos, largest_true, largest_pred`` and over the stack ``sensitivity`` = detected / n_true, ``precision`` =
+    (n_pred - false_pos) / n_pred, their ``f1`` and ``fp_per_image`` = false_pos / N (every division div_no_nan)."""
+    if int(min_overlap) < 1:
+        raise ValueError(f"min_overlap must be >= 1, got {min_overlap}")
+    nt, npd = np.asarray(count_true, np.int64).reshape(-1), np.asarray(count_pred, np.int64).reshape(-1)
+    N = nt.shape[0]
+    table = lambda t: (lambda a: a.reshape(N, a.size // N if N else 0))(np.asarray(t, np.int64))
+    ht, hp, at, apd = table(hit_true), table(hit_pred), table(area_true), table(area_pred)
+    if npd.shape[0] != N or (N and (ht.shape[1] < nt.max() or hp.shape[1] < npd.max() or at.shape[1] < nt.max() or apd.shape[1] < npd.max())):
+        raise ValueError("lesion_scores_from_tables: a table is narrower than the largest count")
+    vt = np.arange(ht.shape[1])[None, :] < nt[:, None]
+    vp = np.arange(hp.shape[1])[None, :] < npd[:, None]
+    detected = ((ht >= int(min_overlap)) & vt).sum(1)
+    false_pos = ((hp == 0) & vp).sum(1)
+    largest_t = np.where(np.arange(at.shape[1])[None, :] < nt[:, None], at, 0).max(1, initial=0)
+    largest_p = np.where(np.arange(apd.shape[1])[None, :] < npd[:, None], apd, 0).max(1, initial=0)
+    sens = _div_no_nan(float(detected.sum()), float(nt.sum()))
+    prec = _div_no_nan(float(npd.sum() - false_pos.sum()), float(npd.sum()))
+    return {"n_true": nt, "n_pred": npd, "detected": detected, "missed": nt - detected, "false_pos": false_pos, "largest_true": largest_t,
+            "largest_pred": largest_p, "sensitivity": sens, "precision": prec, "f1": _div_no_nan(2.0 * prec * sens, prec + sens),
+            "fp_per_image": _div_no_nan(float(false_pos.sum()), float(N))}
+
+
+def lesion_scores(pred, true, *, connectivity=8, min_overlap=1, device=None):
+    """Lesion-wise detection scores of two stacks of masks [N,H,W] on the device: both are labelled (``usseg_label_components``), the
+    overlap and area tables are built there (``usseg_component_overlap`` / ``usseg_component_stats``), and ``lesion_scores_from_tables`` turns
+    them into numbers.  One read-back of the counts sizes the tables."""
+    from . import ops
+    dev = torch.device(device if device is not None else "cuda")
+    tp, tt = _mask_stack(pred, dev, "lesion_scores"), _mask_stack(true, dev, "lesion_scores")
+    if tp.shape != tt.shape:
+        raise ValueError(f"lesion_scores: two [N,H,W] stacks of one shape, got {tuple(tp.shape)} and {tuple(tt.shape)}")
+    N, H, W = tp.shape
+    ws = torch.empty(max(ops.components_ws_bytes(N, H, W), 16), dtype=torch.uint8, device=dev)
+    lp, cp = ops.label_components(tp, connectivity, ws=ws)
+    lt, ct = ops.label_components(tt, connectivity, ws=ws)
+    counts = torch.stack([ct, cp]).cpu().numpy().astype(np.int64)
+    cap_t, cap_p = (int(counts[0].max()), int(counts[1].max())) if N else (0, 0)
+    hit_t, hit_p = ops.component_overlap(lt, lp, cap_t, cap_p)
+    area_t, area_p = ops.component_stats(lt, cap_t)[..., 0], ops.component_stats(lp, cap_p)[..., 0]
+    return lesion_scores_from_tables(counts[0], counts[1], hit_t.cpu().numpy(), hit_p.cpu().numpy(), area_t.cpu().numpy(), area_p.cpu().numpy(),
+                                     min_overlap)
 
 
 def dice_line(neuralnet, seg_metrics):

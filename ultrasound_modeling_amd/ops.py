@@ -1188,6 +1188,98 @@ def surface_dist(a, b, ws=None):
     return counters, sums
 
 
+# ---- connected components (csrc/components.hip) -------------------------------------------------------------------------------------------
+COMPONENT_STAT_FIELDS = ("area", "y_min", "x_min", "y_max", "x_max", "sum_y", "sum_x", "peak_bits")
+
+
+def components_ws_bytes(N: int, H: int, W: int) -> int:
+    """Workspace bytes of ``label_components`` and ``clean_mask`` (usseg_components_ws_bytes); ValueError for a refused shape."""
+    n = int(L.load().usseg_components_ws_bytes(N, H, W))
+    if n < 0:
+        raise ValueError(f"components: H and W must lie in [1, 8192], N in [0, 65535] and N*H*W <= 2^29, got {N}x{H}x{W}")
+    return n
+
+
+def _component_mask(mask, what):
+    assert mask.dtype == torch.uint8 and mask.is_contiguous() and mask.dim() == 3, f"{what}: a contiguous uint8 [N,H,W] mask"
+    return mask.shape
+
+
+def _component_ws(ws, need, device):
+    if ws is None:
+        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=device)
+    assert ws.dtype == torch.uint8 and ws.is_contiguous()
+    return ws
+
+
+def label_components(mask, connectivity=8, labels=None, count=None, ws=None):
+    """Connected components of a uint8 [N,H,W] mask (usseg.h usseg_label_components) -> (labels int32 [N,H,W], count int32 [N]): 0 outside,
+    1..K_n inside in ``scipy.ndimage.label``'s numbering.  ``labels``, ``count`` and ``ws`` (uint8, ``components_ws_bytes`` long) are
+    allocated when not given."""
+    N, H, W = _component_mask(mask, "label_components")
+    ws = _component_ws(ws, components_ws_bytes(N, H, W), mask.device)
+    if labels is None:
+        labels = torch.empty((N, H, W), dtype=torch.int32, device=mask.device)
+    if count is None:
+        count = torch.empty((max(N, 1),), dtype=torch.int32, device=mask.device)[:N]
+    assert labels.dtype == torch.int32 and labels.is_contiguous() and labels.shape == mask.shape
+    assert count.dtype == torch.int32 and count.is_contiguous() and count.numel() == N
+    if N == 0:
+        return labels, count
+    L.check(L.load().usseg_label_components(mask.data_ptr(), N, H, W, int(connectivity), labels.data_ptr(), count.data_ptr(), ws.data_ptr(), ws.numel(),
+                                            _stream()), "label_components")
+    return labels, count
+
+
+def component_stats(labels, cap, prob=None):
+    """Per-component table of a label image (usseg.h usseg_component_stats) -> int64 [N,cap,8], the fields of ``COMPONENT_STAT_FIELDS``."""
+    assert labels.dtype == torch.int32 and labels.is_contiguous() and labels.dim() == 3
+    N, H, W = labels.shape
+    cap = int(cap)
+    if cap < 0:
+        raise ValueError(f"component_stats: cap must be >= 0, got {cap}")
+    if prob is not None:
+        assert prob.dtype == torch.float32 and prob.is_contiguous() and prob.shape == labels.shape
+    stats = torch.empty((N, cap, 8), dtype=torch.int64, device=labels.device)
+    if N * cap:
+        L.check(L.load().usseg_component_stats(labels.data_ptr(), prob.data_ptr() if prob is not None else None, N, H, W, cap, stats.data_ptr(), _stream()),
+                "component_stats")
+    return stats
+
+
+def clean_mask(mask, prob=None, *, connectivity=8, min_area=1, min_peak=0.0, out=None, ws=None):
+    """uint8 [N,H,W]: 1 on the components of ``mask`` with at least ``min_area`` pixels and (with ``prob``) a peak of at least ``min_peak``
+    (usseg.h usseg_clean_mask).  ``out`` may be ``mask``; no host synchronisation, so the call can be captured in a graph."""
+    N, H, W = _component_mask(mask, "clean_mask")
+    ws = _component_ws(ws, components_ws_bytes(N, H, W), mask.device)
+    if out is None:
+        out = torch.empty_like(mask)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and out.shape == mask.shape
+    if prob is not None:
+        assert prob.dtype == torch.float32 and prob.is_contiguous() and prob.shape == mask.shape
+    if N == 0:
+        return out
+    L.check(L.load().usseg_clean_mask(mask.data_ptr(), prob.data_ptr() if prob is not None else None, N, H, W, int(connectivity), int(min_area),
+                                      float(min_peak), out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "clean_mask")
+    return out
+
+
+def component_overlap(la, lb, cap_a, cap_b):
+    """Pixels of each component of ``la`` inside any component of ``lb`` and the reverse (usseg.h usseg_component_overlap)
+    -> (hit_a int32 [N,cap_a], hit_b int32 [N,cap_b])."""
+    assert la.dtype == torch.int32 and lb.dtype == torch.int32 and la.is_contiguous() and lb.is_contiguous() and la.dim() == 3 and la.shape == lb.shape
+    N, H, W = la.shape
+    cap_a, cap_b = int(cap_a), int(cap_b)
+    if cap_a < 0 or cap_b < 0:
+        raise ValueError(f"component_overlap: caps must be >= 0, got {cap_a} and {cap_b}")
+    hit_a = torch.empty((N, cap_a), dtype=torch.int32, device=la.device)
+    hit_b = torch.empty((N, cap_b), dtype=torch.int32, device=la.device)
+    if N and (cap_a or cap_b):
+        L.check(L.load().usseg_component_overlap(la.data_ptr(), lb.data_ptr(), N, H, W, cap_a, cap_b, hit_a.data_ptr() if cap_a else None,
+                                                 hit_b.data_ptr() if cap_b else None, _stream()), "component_overlap")
+    return hit_a, hit_b
+
+
 def overlap_boundary_loss_sums(probs, y_true, phi, acc, *, overlap, boundary, wb, HW, C_classes, ov_scale=1.0, label_smoothing=0.1, clip_eps=1e-7,
                                inv_global_batch=1.0):
     """``overlap_loss_sums`` plus the boundary term: ``phi`` = ``sdf_labels(y_true)``, ``boundary`` a ``boundary_loss(...)``, ``wb`` a DEVICE fp32
