@@ -718,6 +718,71 @@ int usseg_overlap_boundary_loss_sums(const UssegLossDesc* d, const UssegOverlapL
                                      usseg_stream_t stream);
 int usseg_overlap_boundary_loss_bwd(const UssegLossDesc* d, const UssegOverlapLoss* ol, const float* probs, const float* y_true, const float* phi,
                                     const UssegBoundaryLoss* bl, const float* acc, int64_t acc_floats, void* dlogits, usseg_stream_t stream);
+/* ---- a stable segmented radix sort of (key, value) pairs (csrc/lovasz.hip) --------------------------------------------------------------
+ * usseg_sort_pairs_u32: S segments of n (key, value) uint32 pairs, segment s at [s*n, (s+1)*n) of every array.  The order is ascending on the
+ * low key_bits bits of the key and STABLE: pairs whose low bits agree keep their input order.  Bits above key_bits are ignored for the order
+ * and kept in the output.  An LSD radix sort with digits of USSEG_SORT_DIGIT_BITS = 8 bits over tiles of USSEG_SORT_TILE = 2048 pairs (256
+ * threads x 8), segments in grid.y; a digit pass is tile histograms, their offsets, and a scatter that is stable inside a tile (a wave ranks
+ * 64 pairs at a time with one 64-lane ballot per digit bit and keeps its running digit counts in LDS).  The number of launches is fixed by
+ * (S, n, key_bits) - 3 * ceil(key_bits / 8) - and never by the data, so a captured graph holds the call.  No host synchronisation, no
+ * allocation: the workspace (16-byte aligned, usseg_sort_ws_bytes(S, n) bytes; -1 for a refused shape) comes from the caller.  No workgroup
+ * waits for another: a pass boundary is a launch boundary.  Only integer atomics are used, so the result is a function of the inputs alone.
+ * 0 <= S <= 65535, 0 <= n <= 2^29, 1 <= key_bits <= 32; the outputs must not alias the inputs or each other; S == 0 or n == 0 returns 0
+ * without a launch.  Every argument is checked before any launch (USSEG_ERR_BAD_ARG with usseg_last_error text), a workspace that is too
+ * small included. */
+#define USSEG_SORT_TILE 2048
+#define USSEG_SORT_DIGIT_BITS 8
+int64_t usseg_sort_ws_bytes(int32_t S, int64_t n);
+int usseg_sort_pairs_u32(const uint32_t* keys_in, const uint32_t* vals_in, int32_t S, int64_t n, int32_t key_bits, uint32_t* keys_out,
+                         uint32_t* vals_out, void* ws, int64_t ws_bytes, usseg_stream_t stream);
+/* ---- the Lovasz-softmax loss (Berman, Triki, Blaschko, CVPR 2018; csrc/lovasz.hip) -------------------------------------------------------
+ * Not in the reference: the surrogate of the intersection over union the drivers report.  Batch-level (the paper's per_image = False), on the
+ * head's fp32 probabilities p[m][c] and the labels y[m][c] exactly as passed, m over the M pixels of THIS call, C <= 4, M <= 2^29.  Per class c:
+ *     fg(m) = y_c(m) > threshold          (a NaN is not foreground: usseg_sdf_labels' rule)
+ *     e(m)  = fg ? 1 - p_c(m) : p_c(m)    (one fp32 operation)
+ *     key   = the uint32 bit pattern of |e|, clamped to 0x3F800000: every input, NaN or out of range, has a defined place
+ *     order = key descending, ties by ascending pixel index m - a strict order, so the result is a function of the inputs alone
+ * With r(m) the 0-based rank, F(m) the number of foreground pixels of rank <= r(m), Y = sum fg, I = Y - F, U = Y + r + 1 - F, the Lovasz
+ * gradient of the Jaccard loss is built from the exact integers in closed form (never as a difference of two Jaccard values):
+ *     g(m) = 1 / U  at a foreground pixel,   I / (U * (U - 1))  at a background pixel (the product in int64);
+ *     Y = 0:  g = 1 at rank 0 and 0 elsewhere.
+ *     L_c = sum_m e(m) * g(m)                 L_lv = (1/|S|) * sum_{c in S} w[c] * L_c
+ *     loss = ce_weight * CCE + lv_weight * ov_scale * L_lv
+ * S is the set of classes with Y_c > 0 (all_classes = 0: "present", the paper's default) or every class (all_classes = 1); |S| is counted on
+ * the device; an empty S gives L_lv = 0 and a zero gradient.  CCE is loss_kind 0 exactly as the overlap losses carry it, ov_scale their
+ * data-parallel factor.
+ *     G_c(m) = k_c * (fg ? -1 : +1) * g_c(m) (+ the CCE term),   k_c = lv_weight * ov_scale * w[c] / |S| in S, 0 outside;
+ *     dlogit_j = p_j*(G_j - sum_c p_c*G_c), fp32, ONE bf16 rounding.
+ * Three calls behind a probabilities-only forward:
+ *   usseg_lovasz_coeffs      writes g fp32 [M][C] (the layout of probs) and counts int32 [C] = Y_c: keys and payloads, usseg_sort_pairs_u32's
+ *                            passes with S = C, n = M on the key 0x3F800000 - clamped bits (30 key bits; ascending and stable on it is
+ *                            "descending, ties by index"), a scan of fg along the sorted order, the scatter back to pixel order.  16 launches.
+ *                            ws: 16-byte aligned, usseg_lovasz_ws_bytes(M, C) bytes (-1 for a refused shape).
+ *   usseg_lovasz_loss_sums   acc[0] = the scalar loss (OVERWRITTEN); acc[2] = the CCE pixel sum; acc[4+c] = k_c; acc[16+c] = L_c.  The ordered,
+ *                            ticketed grid reduction of usseg_overlap_loss_sums under the same grid rule usseg_overlap_loss_grid(M) and the
+ *                            same accumulator geometry ([1] the ticket, zero between calls; [32 + 16*b + k] workgroup b's partial): the
+ *                            totals are bitwise reproducible and the same depth bound applies.  USSEG_OVERLAP_ACC_FLOATS holds every grid.
+ *   usseg_lovasz_loss_bwd    reads probs, y_true, g and acc[4..8); writes dlogits bf16 [M][8] (lddl 8) or the quad layout (lddl 16) of
+ *                            UssegLossDesc; pad channels are exactly zero.
+ * M = 0 gives loss 0, counts 0 and no further launch.  With lv_weight = 0 and ce_weight = 1 the loss and dlogits equal the loss_kind 0
+ * launch as the overlap pair does in that limit.  w[c], lv_weight, ce_weight finite and >= 0 (only w[0..C) is read); threshold finite;
+ * probs, y_true and g 16-byte aligned.  Of the descriptor the fields the overlap entry points read.  The struct travels BY VALUE, into the
+ * calls and with the launches, so a captured graph holds its numbers.  Nothing allocates and nothing synchronises with the host.  Every
+ * argument is checked before any launch (USSEG_ERR_BAD_ARG with usseg_last_error text), a workspace or accumulator that is too small included. */
+typedef struct UssegLovaszLoss {
+  float w[8];          /* per-class weight */
+  float lv_weight;     /* weight of the Lovasz term */
+  float ce_weight;     /* weight of the CCE term; 0: not evaluated */
+  float threshold;     /* foreground is y > threshold */
+  int32_t all_classes; /* 0: average over the classes present in this call; 1: over all classes */
+} UssegLovaszLoss;
+int64_t usseg_lovasz_ws_bytes(int64_t M, int32_t C);
+int usseg_lovasz_coeffs(const UssegLossDesc* d, UssegLovaszLoss ll, const float* probs, const float* y_true, float* g, int32_t* counts, void* ws,
+                        int64_t ws_bytes, usseg_stream_t stream);
+int usseg_lovasz_loss_sums(const UssegLossDesc* d, UssegLovaszLoss ll, float ov_scale, const float* probs, const float* y_true, const float* g,
+                           const int32_t* counts, float* acc, int64_t acc_floats, usseg_stream_t stream);
+int usseg_lovasz_loss_bwd(const UssegLossDesc* d, UssegLovaszLoss ll, const float* probs, const float* y_true, const float* g, const float* acc,
+                          int64_t acc_floats, void* dlogits, usseg_stream_t stream);
 /* The <= 4-class head Conv2DTranspose(k x k, stride 2, 'same') (Decoder.py:120 k=3; TBI_ResNest.py:124 k=4) in "quad" form: a
  * stride-1 convolution at the INPUT resolution whose 16 output channels are (output parity class)*4 + n, run by
  * usseg_conv2d_fwd/dgrad/wgrad as a 3x3 conv (each parity uses <= 2x2 of the stencil taps, the rest are zero).  With

@@ -102,16 +102,17 @@ class Process(object):
         return m["f1"]
 
 
-def main(train_path, val_path, save_path=None, epochs=50, batch_size=32, num_classes=3, *, loss="cce", overlap=None, boundary=None):
+def main(train_path, val_path, save_path=None, epochs=50, batch_size=32, num_classes=3, *, loss="cce", overlap=None, boundary=None, lovasz=None):
     """MainNumpy.py:150-177 with the paths as arguments: ``VisionTransformer(32, img_size=(256, 80))`` over a ``Dataset_2.Dataset``,
     50 epochs, then a save if ``save_path`` is given.  ``loss``: the model's ``loss=`` ("cce", "my_loss_cat", "focal", "dice", "tversky",
     "dice_ce"); ``overlap``: the settings of the last three (``VisionTransformer(overlap=...)``), which also add a per-class Dice line to the test report;
-    ``boundary``: the boundary term on top of one of those three (``VisionTransformer(boundary=...)``)."""
+    ``boundary``: the boundary term on top of one of those three (``VisionTransformer(boundary=...)``); "lovasz" / "lovasz_ce" with their settings in
+    ``lovasz`` (``VisionTransformer(lovasz=...)``: the Lovasz-softmax loss; the Dice line too)."""
     from .Dataset_2 import Dataset
     from .VisionTransformer import VisionTransformer, overlap_settings
     dataset = Dataset(train_path, val_path, num_classes)
     neuralnet = VisionTransformer(batch_size, img_size=input_size, num_classes=num_classes, loss=loss, overlap=overlap_settings(loss, overlap),
-                                  boundary=boundary)
+                                  boundary=boundary, lovasz=lovasz)
     print(len(neuralnet.visionModel.layers))
     process = Process(batch_size=batch_size, num_classes=num_classes)
     process.training(neuralnet=neuralnet, dataset=dataset, epochs=epochs)

@@ -285,13 +285,15 @@ class Process(object):
 
 
 def main(train_path, val_path, save_path=None, epochs=51, batch_size=64, use_vit=True, *, seed=0, schedule=False, capture_graph=True,
-         loss="cce", overlap=None, boundary=None):
+         loss="cce", overlap=None, boundary=None, lovasz=None):
     """MainParallel.py:201-216 with the paths as arguments: ``VisionTransformer(batch_size=64)`` with the ViT bottleneck, 51 epochs,
     then rank 0 saves if ``save_path`` is given.  Every rank seeds ``random`` with ``seed``, so all draw the same augmentations.
     ``loss``: the model's ``loss=`` ("cce", "my_loss_cat", "focal"); every replica divides it by the global batch all the same.  The
     region-overlap losses ("dice", "tversky", "dice_ce", settings in ``overlap``) are computed per replica on its own images and weighted by
     local batch / global batch: the SUM of the replicas is their batch-weighted mean; they add a per-class Dice line to the test report.
     ``boundary`` (``VisionTransformer(boundary=...)``) adds the boundary term to one of those three, weighted per replica the same way.
+    The Lovasz-softmax loss ("lovasz", "lovasz_ce", settings in ``lovasz``) ranks the pixels of the images a replica holds and is weighted like the
+    overlap term; it adds the Dice line too.
     Under ``nccl`` the model lives on ``cuda:LOCAL_RANK``; the ``USSEG_DIST_BACKEND=gloo`` rehearsal keeps every rank on device 0."""
     from .Dataset import Dataset
     from .VisionTransformer import VisionTransformer, overlap_settings
@@ -302,7 +304,7 @@ def main(train_path, val_path, save_path=None, epochs=51, batch_size=64, use_vit
     random.seed(seed)
     dataset = Dataset(train_path, val_path, batch_size, device=device)
     neuralnet = VisionTransformer(batch_size, img_size=(dataset.height, dataset.width), in_channels=dataset.channel, use_vit=use_vit,
-                                  device=str(device), loss=loss, overlap=overlap_settings(loss, overlap), boundary=boundary)
+                                  device=str(device), loss=loss, overlap=overlap_settings(loss, overlap), boundary=boundary, lovasz=lovasz)
     if rank == 0:
         print(len(neuralnet.visionModel.layers))
     process = Process(batch_size, schedule=schedule, capture_graph=capture_graph)
@@ -325,9 +327,9 @@ def _cli(argv=None):
     ap.add_argument("--seed", type=int, default=0, help="augmentation draws (the same on every rank)")
     ap.add_argument("--schedule", action="store_true", help="install the MainParallel.py:74-79 rate schedule once")
     ap.add_argument("--no-graph", action="store_true", help="run every step eagerly")
-    ap.add_argument("--loss", choices=("cce", "my_loss_cat", "focal", "dice", "tversky", "dice_ce"), default="cce",
+    ap.add_argument("--loss", choices=("cce", "my_loss_cat", "focal", "dice", "tversky", "dice_ce") + ("lovasz", "lovasz_ce"), default="cce",
                     help="the model's loss: CategoricalCrossentropy (the reference's), its class-weighted my_loss_cat, the focal variant, or a "
-                         "region-overlap loss (soft Dice, Tversky 0.3 / 0.7, Dice + CCE)")
+                         "region-overlap loss (soft Dice, Tversky 0.3 / 0.7, Dice + CCE), or the Lovasz-softmax loss (alone, or CCE + it)")
     ap.add_argument("--boundary-weight", type=float, default=None, metavar="W",
                     help="add the boundary term (signed distance map of the labels times the probabilities) with weight W; needs a region-overlap --loss")
     a = ap.parse_args(argv)

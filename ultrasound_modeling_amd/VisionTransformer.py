@@ -308,6 +308,7 @@ class Transformer(nn.Module):
 
 LOSSES = ("cce", "my_loss_cat", "focal")             # the reference's own: per-pixel losses inside the fused head launch
 OVERLAP_LOSSES = ("dice", "tversky", "dice_ce")      # region-overlap losses (not in the reference): two launches behind the probabilities-only head
+LOVASZ_LOSSES = ("lovasz", "lovasz_ce")              # the Lovasz-softmax loss (not in the reference): a device sort of the pixel errors behind that head
 
 
 def overlap_settings(loss, overlap):
@@ -335,6 +336,27 @@ def overlap_config(loss, num_classes, overlap):
     a, b = (0.3, 0.7) if loss == "tversky" else (0.5, 0.5)
     return ops.overlap_loss(w, cfg.get("alpha", a), cfg.get("beta", b), cfg.get("smooth", 1.0), cfg.get("power", 1.0), cfg.get("ov_weight", 1.0),
                             cfg.get("ce_weight", 1.0 if loss == "dice_ce" else 0.0))
+
+
+def lovasz_config(loss, num_classes, lovasz):
+    """``loss`` in LOVASZ_LOSSES and the ``lovasz`` settings (dict or None: every default) -> ``ops.lovasz_loss(...)``; ValueError for a bad or
+    contradictory combination."""
+    if lovasz is not None and not isinstance(lovasz, dict):
+        raise ValueError(f"lovasz: a dict of {ops.LOVASZ_KEYS} (None or {{}} for the defaults), got {type(lovasz).__name__}")
+    cfg = dict(lovasz or {})
+    unknown = [k for k in cfg if k not in ops.LOVASZ_KEYS]
+    if unknown:
+        raise ValueError(f"lovasz: unknown settings {unknown}; known: {ops.LOVASZ_KEYS}")
+    if loss != "lovasz_ce" and cfg.get("ce_weight", 0.0) != 0.0:
+        raise ValueError(f"lovasz: a cross-entropy term needs loss='lovasz_ce', not '{loss}'")
+    if loss == "lovasz_ce" and cfg.get("ce_weight", 1.0) == 0.0:
+        raise ValueError("lovasz: loss='lovasz_ce' with ce_weight = 0 is loss='lovasz'")
+    w = cfg.get("class_weight")
+    w = [1.0] * num_classes if w is None else [float(v) for v in w]
+    if len(w) != num_classes:
+        raise ValueError(f"lovasz: class_weight has {len(w)} entries for {num_classes} classes")
+    return ops.lovasz_loss(w, cfg.get("lv_weight", 1.0), cfg.get("ce_weight", 1.0 if loss == "lovasz_ce" else 0.0), cfg.get("threshold", 0.5),
+                           cfg.get("classes", "present"))
 
 
 def boundary_config(loss, num_classes, boundary):
@@ -370,7 +392,7 @@ class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
                  in_channels: int = 10, use_vit: bool = False, device: Optional[str] = None, seed: Optional[int] = 0,
                  transunet: bool = False, adamw: bool = False, loss: str = "cce", class_factor=None, focal_gamma=None,
                  overlap=None, alpha=None, beta=None, smooth=None, power=None, class_weight=None, ce_weight=None, ov_weight=None,
-                 boundary=None):
+                 boundary=None, lovasz=None):
         """``transunet=True`` builds the older self-contained copy of this model in TBI_TransUNet.py (BASELINE configs[3]):
         BatchNormalization where ResNest.py / Decoder.py use LayerNormalization (:304,426,465,472,503), conv_4 = 256 channels
         (:368), and the loss is CategoricalCrossentropy(label_smoothing=0.1) with the DEFAULT reduction - the mean over all
@@ -403,10 +425,24 @@ class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
         the pixels of sum_c class_weight[c] * p_c * phi_c, phi the exact signed distance map of the labels (``ops.sdf_labels``, computed on the
         device once per step).  Keys: ``weight`` (0.01), ``class_weight`` (0 for class 0, 1 for every other class), ``threshold`` (0.5: the mask
         of a soft label).  ``boundary={}`` takes the defaults.  The weight lives on the device: ``set_boundary_weight`` reaches a captured graph's
-        next replay without a recapture, and a checkpoint keeps it."""
+        next replay without a recapture, and a checkpoint keeps it.
+
+        The Lovasz-softmax loss (Berman et al.; not in the reference; DESIGN.md section 8, usseg.h ``UssegLovaszLoss``), the surrogate of the
+        intersection over union the drivers report, on the images THIS replica holds and batch-level (the paper's ``per_image=False``):
+        ``"lovasz"``, or ``"lovasz_ce"`` = the default CCE plus it.  ``lovasz`` (a dict; None takes every default) sets ``classes`` ("present":
+        average over the classes with a foreground pixel in the batch, the paper's default; "all"), ``class_weight`` (1 per class),
+        ``lv_weight`` (1), ``ce_weight`` (lovasz_ce only, 1), ``threshold`` (0.5: the foreground of a soft label).  Every step sorts the
+        B*H*W errors of each class on the device (``ops.sort_pairs``' kernels); the term is weighted like the overlap term.  ``boundary`` does not
+        combine with it."""
         super().__init__()
-        if loss not in LOSSES + OVERLAP_LOSSES:
-            raise ValueError(f"loss must be one of {LOSSES + OVERLAP_LOSSES}, got {loss!r}")
+        if loss not in LOSSES + OVERLAP_LOSSES + LOVASZ_LOSSES:
+            raise ValueError(f"loss must be one of {LOSSES + OVERLAP_LOSSES + LOVASZ_LOSSES}, got {loss!r}")
+        if lovasz is not None and loss not in LOVASZ_LOSSES:
+            raise ValueError(f"lovasz settings only apply to loss in {LOVASZ_LOSSES}")
+        if loss in LOVASZ_LOSSES and (class_factor is not None or focal_gamma is not None):
+            raise ValueError(f"class_factor / focal_gamma do not apply to loss='{loss}' (its weights are lovasz['class_weight'])")
+        self._lovasz = lovasz_config(loss, num_classes, lovasz) if loss in LOVASZ_LOSSES else None
+        self._lovasz_bufs = {}                  # pixels of a call -> (g, counts, workspace): allocated once per model and batch shape
         given = dict(alpha=alpha, beta=beta, smooth=smooth, power=power, class_weight=class_weight, ce_weight=ce_weight, ov_weight=ov_weight)
         overlap_kw = {k: v for k, v in given.items() if v is not None}      # (the keyword ``alpha`` is Tversky's; ``self.alpha`` below is the focal exponent, :208)
         if overlap is not None and overlap_kw:
@@ -454,7 +490,7 @@ class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
         self.flat = FlatParams(self, self.device)
         self.optimizer = AdamClip(self.flat, lr=learning_rate, clip_norm=1.0,          # :204,:244
                                   weight_decay=weight_decay if adamw else None)
-        self._loss = torch.zeros(ops.ACC_FLOATS if self._overlap is None else ops.OVERLAP_ACC_FLOATS, dtype=torch.float32,
+        self._loss = torch.zeros(ops.ACC_FLOATS if self._overlap is None and self._lovasz is None else ops.OVERLAP_ACC_FLOATS, dtype=torch.float32,
                                  device=self.device)                                         # [0] = the scalar loss
         self._boundary, self._boundary_thr, self._wb = None, 0.5, None
         if bnd is not None:
@@ -483,6 +519,11 @@ class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
     def overlap_loss(self):
         """The ``UssegOverlapLoss`` this model trains with (``loss="dice"`` / ``"tversky"`` / ``"dice_ce"``), or None for a per-pixel loss."""
         return self._overlap
+
+    @property
+    def lovasz_loss(self):
+        """The ``UssegLovaszLoss`` this model trains with (``loss="lovasz"`` / ``"lovasz_ce"``), or None."""
+        return self._lovasz
 
     # ------------------------------------------------------------------ parameters in / out (Keras names)
     @property
@@ -580,6 +621,8 @@ class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
         scale = 1.0 / float(B * H * W) if self.transunet else 1.0 / float(self.batch_size)
         if self._overlap is not None:
             return self._forward_overlap(xh, logits, y, probs, dlogits, scale)
+        if self._lovasz is not None:
+            return self._forward_lovasz(xh, logits, y, probs, dlogits, scale)
         if fused:       # head conv + softmax + loss in one launch (:142, :205, :225-229); falls back to the three launches if it has no kernel
             kw = {} if self._class_loss is None else {"class_loss": self._class_loss}       # (no keyword: today's call of today's symbol)
             if self.decoder._quad.forward_loss(xh, y, probs, self._loss, dlogits, label_smoothing=0.1, clip_eps=1e-7, inv_global_batch=scale, **kw):
@@ -590,15 +633,21 @@ class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
                          label_smoothing=0.1, clip_eps=1e-7, inv_global_batch=scale, quad_w=qw, class_loss=self._class_loss)
         return probs, dlogits
 
-    def _forward_overlap(self, xh, logits, y, probs, dlogits, scale):
-        """The region-overlap losses: today's probabilities-only head launch(es), then the sums pass (scalar loss and backward coefficients into
-        ``self._loss``), then - for a training step - the backward pass that writes ``dlogits``."""
-        B, H, W, C = probs.shape
+    def _head_probs(self, xh, logits, probs):
+        """The probabilities-only head in front of the losses that need every pixel before any gradient: the fused head launch on ``xh`` where it
+        has a kernel, else the head conv, and the softmax of ``logits``."""
+        _, H, W, C = probs.shape
         if xh is not None and not self.decoder._quad.forward_loss(xh, None, probs, None, None):
             logits = self.decoder._head_forward(xh)
             self.decoder._logits = logits
         if logits is not None:
             ops.softmax_loss(logits, None, probs, None, None, HW=H * W, C_classes=C, quad_w=self.decoder.quad_w)
+
+    def _forward_overlap(self, xh, logits, y, probs, dlogits, scale):
+        """The region-overlap losses: today's probabilities-only head launch(es), then the sums pass (scalar loss and backward coefficients into
+        ``self._loss``), then - for a training step - the backward pass that writes ``dlogits``."""
+        B, H, W, C = probs.shape
+        self._head_probs(xh, logits, probs)
         kw = dict(overlap=self._overlap, HW=H * W, C_classes=C, label_smoothing=0.1, clip_eps=1e-7, inv_global_batch=scale)
         ov_scale = 1.0 if self.transunet else float(B) / float(self.batch_size)
         if self._boundary is not None:          # the labels' distance map once per step, then the pair that carries the boundary term
@@ -610,6 +659,34 @@ class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
         ops.overlap_loss_sums(probs, y, self._loss, ov_scale=ov_scale, **kw)
         if dlogits is not None:
             ops.overlap_loss_bwd(probs, y, self._loss, dlogits, quad_w=self.decoder.quad_w, **kw)
+        return probs, dlogits
+
+    def _lovasz_buffers(self, M, C):
+        bufs = self._lovasz_bufs.get((M, C))
+        if bufs is None:
+            bufs = (torch.empty(max(M * C, 4), dtype=torch.float32, device=self.device), torch.zeros(4, dtype=torch.int32, device=self.device),
+                    torch.empty(max(ops.lovasz_ws_bytes(M, C), 16), dtype=torch.uint8, device=self.device))
+            self._lovasz_bufs[(M, C)] = bufs
+        return bufs
+
+    def _lovasz_loss_into(self, acc, probs, y, scale, ov_scale):
+        """The coefficients pass (device sort) and the sums pass on these probabilities and labels: the scalar loss in ``acc[0]``.  -> (g, kw)."""
+        B, H, W, C = probs.shape
+        g, counts, ws = self._lovasz_buffers(B * H * W, C)
+        g = g[:B * H * W * C].view(probs.shape)
+        kw = dict(lovasz=self._lovasz, HW=H * W, C_classes=C)
+        ops.lovasz_coeffs(probs, y, g, counts, ws, **kw)
+        kw.update(label_smoothing=0.1, clip_eps=1e-7, inv_global_batch=scale)
+        ops.lovasz_loss_sums(probs, y, g, counts, acc, ov_scale=ov_scale, **kw)
+        return g, kw
+
+    def _forward_lovasz(self, xh, logits, y, probs, dlogits, scale):
+        """The Lovasz-softmax loss: today's probabilities-only head launch(es), then the coefficients (the sort), the sums pass (scalar loss and
+        k_c into ``self._loss``), then - for a training step - the backward pass that writes ``dlogits``."""
+        self._head_probs(xh, logits, probs)
+        g, kw = self._lovasz_loss_into(self._loss, probs, y, scale, 1.0 if self.transunet else float(probs.shape[0]) / float(self.batch_size))
+        if dlogits is not None:
+            ops.lovasz_loss_bwd(probs, y, g, self._loss, dlogits, quad_w=self.decoder.quad_w, **kw)
         return probs, dlogits
 
     def _predict_body(self, x):
@@ -646,6 +723,11 @@ class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
                 ops.overlap_boundary_loss_sums(y_pred, y_true, phi, acc, boundary=self._boundary, wb=self._wb, **kw)
             else:
                 ops.overlap_loss_sums(y_pred, y_true, acc, **kw)
+            return acc[0].clone()
+        if self._lovasz is not None:        # the Lovasz loss of THESE tensors, weighted as a step weights a batch of their size
+            acc = torch.zeros(ops.OVERLAP_ACC_FLOATS, dtype=torch.float32, device=self.device)
+            self._lovasz_loss_into(acc, y_pred, y_true, 1.0 / float(self.batch_size),
+                                   1.0 if self.transunet else float(y_pred.shape[0]) / float(self.batch_size))
             return acc[0].clone()
         loss = torch.empty(ops.ACC_FLOATS, dtype=torch.float32, device=self.device)
         ops.fill_f32(loss, 0.0)

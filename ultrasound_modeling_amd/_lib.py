@@ -107,6 +107,11 @@ class OverlapLoss(C.Structure):
                 ("ce_weight", c_f32)]
 
 
+class LovaszLoss(C.Structure):
+    """UssegLovaszLoss: the Lovasz-softmax loss, optionally plus CategoricalCrossentropy (usseg.h); passed BY VALUE."""
+    _fields_ = [("w", c_f32 * 8), ("lv_weight", c_f32), ("ce_weight", c_f32), ("threshold", c_f32), ("all_classes", c_i32)]
+
+
 class BoundaryLoss(C.Structure):
     """UssegBoundaryLoss: the per-class weights of the boundary term (usseg.h); passed by reference, copied into the launches."""
     _fields_ = [("u", c_f32 * 8)]
@@ -230,6 +235,12 @@ _PROTOS = {
     "usseg_component_overlap": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "usseg_overlap_boundary_loss_sums": (C.c_int, [P(LossDesc), P(OverlapLoss), c_f32, c_vp, c_vp, c_vp, P(BoundaryLoss), c_vp, c_vp, c_i64, c_vp]),
     "usseg_overlap_boundary_loss_bwd": (C.c_int, [P(LossDesc), P(OverlapLoss), c_vp, c_vp, c_vp, P(BoundaryLoss), c_vp, c_i64, c_vp, c_vp]),
+    "usseg_sort_ws_bytes": (c_i64, [c_i32, c_i64]),
+    "usseg_sort_pairs_u32": (C.c_int, [c_vp, c_vp, c_i32, c_i64, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "usseg_lovasz_ws_bytes": (c_i64, [c_i64, c_i32]),
+    "usseg_lovasz_coeffs": (C.c_int, [P(LossDesc), LovaszLoss, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "usseg_lovasz_loss_sums": (C.c_int, [P(LossDesc), LovaszLoss, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "usseg_lovasz_loss_bwd": (C.c_int, [P(LossDesc), LovaszLoss, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp]),
     "usseg_quad_bias_expand": (C.c_int, [c_vp, c_i32, c_i32, c_vp, c_vp]),
     "usseg_space_to_depth2": (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp]),
     "usseg_tconv_quad_fwd": (C.c_int, [P(ConvDesc), c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),

@@ -1300,6 +1300,92 @@ def overlap_boundary_loss_bwd(probs, y_true, phi, acc, dlogits, *, overlap, boun
                                                      acc.data_ptr(), acc.numel(), dlogits.data_ptr(), _stream()), "overlap_boundary_loss_bwd")
 
 
+# ------------------------------------------------------------------------------------------------ stable radix sort, the Lovasz-softmax loss
+SORT_TILE, SORT_DIGIT_BITS = 2048, 8      # USSEG_SORT_TILE, USSEG_SORT_DIGIT_BITS
+LOVASZ_KEYS = ("classes", "class_weight", "lv_weight", "ce_weight", "threshold")
+_WORDS = (torch.int32, getattr(torch, "uint32", torch.int32))
+
+
+def sort_ws_bytes(S: int, n: int) -> int:
+    need = int(L.load().usseg_sort_ws_bytes(int(S), int(n)))
+    if need < 0:
+        raise ValueError(f"sort_pairs: at most 65535 segments of at most 2^29 pairs, got {S} x {n}")
+    return need
+
+
+def sort_pairs(keys, vals, key_bits=32, ws=None):
+    """A stable ascending sort of 32-bit (key, value) pairs on the low ``key_bits`` bits of the key, read as unsigned (usseg.h
+    usseg_sort_pairs_u32): ``keys`` and ``vals`` [S, n] (or [n]: one segment), int32 or uint32 -> (sorted keys, their values), each row on its own.
+    ``ws`` (uint8, ``sort_ws_bytes(S, n)`` long) is allocated when not given; a captured step passes its own."""
+    assert keys.dtype in _WORDS and vals.dtype in _WORDS and keys.is_contiguous() and vals.is_contiguous() and keys.shape == vals.shape
+    assert keys.dim() in (1, 2)
+    S, n = (1, keys.shape[0]) if keys.dim() == 1 else keys.shape
+    if not 1 <= int(key_bits) <= 32:
+        raise ValueError(f"sort_pairs: key_bits must lie in [1, 32], got {key_bits}")
+    need = sort_ws_bytes(S, n)
+    if ws is None:
+        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=keys.device)
+    assert ws.dtype == torch.uint8
+    ko, vo = torch.empty_like(keys), torch.empty_like(vals)
+    if S and n:
+        L.check(L.load().usseg_sort_pairs_u32(keys.data_ptr(), vals.data_ptr(), S, n, int(key_bits), ko.data_ptr(), vo.data_ptr(), ws.data_ptr(),
+                                              ws.numel(), _stream()), "sort_pairs")
+    return ko, vo
+
+
+def lovasz_loss(class_weight, lv_weight=1.0, ce_weight=0.0, threshold=0.5, classes="present") -> L.LovaszLoss:
+    """A ``UssegLovaszLoss`` (usseg.h): loss = ce_weight * CCE + lv_weight * ov_scale * mean over the classes of ``classes`` ("present": those
+    with a foreground pixel in the call; "all") of w[c] * the Lovasz extension of the Jaccard loss of class c.  ValueError for what the library
+    would refuse: more than 4 weights, a negative or non-finite number, an unknown ``classes`` - and for a loss with both weights zero."""
+    w = [float(v) for v in class_weight]
+    lv_weight, ce_weight, threshold = float(lv_weight), float(ce_weight), float(threshold)
+    if not 1 <= len(w) <= 4:
+        raise ValueError(f"lovasz loss: 1 to 4 class weights, got {len(w)}")
+    if classes not in ("present", "all"):
+        raise ValueError(f"lovasz loss: classes must be 'present' or 'all', got {classes!r}")
+    if not all(math.isfinite(v) and v >= 0.0 for v in w + [lv_weight, ce_weight]):
+        raise ValueError(f"lovasz loss: weights must be finite and >= 0, got {w}, {lv_weight}, {ce_weight}")
+    if not math.isfinite(threshold):
+        raise ValueError(f"lovasz loss: threshold must be finite, got {threshold}")
+    if lv_weight == 0.0 and ce_weight == 0.0:
+        raise ValueError("lovasz loss: lv_weight and ce_weight are both zero")
+    return L.LovaszLoss((L.c_f32 * 8)(*w), lv_weight, ce_weight, threshold, 1 if classes == "all" else 0)
+
+
+def lovasz_ws_bytes(M: int, C_classes: int) -> int:
+    need = int(L.load().usseg_lovasz_ws_bytes(int(M), int(C_classes)))
+    if need < 0:
+        raise ValueError(f"lovasz loss: at most 2^29 pixels of 1 to 4 classes, got {M} x {C_classes}")
+    return need
+
+
+def lovasz_coeffs(probs, y_true, g, counts, ws, *, lovasz, HW, C_classes):
+    """The Lovasz gradient of every pixel and class: ``g`` fp32 (the shape of ``probs``) and ``counts`` int32 [C] = the foreground pixels per class,
+    through the device sort.  ``ws``: uint8, ``lovasz_ws_bytes(M, C)`` long.  Sixteen launches whatever the data."""
+    d = _overlap_desc(probs, y_true, HW, C_classes, 8, 0.1, 1e-7, 1.0, 0)
+    assert g.dtype == torch.float32 and g.is_contiguous() and g.shape == probs.shape and counts.dtype == torch.int32 and counts.numel() >= C_classes
+    assert ws.dtype == torch.uint8
+    L.check(L.load().usseg_lovasz_coeffs(C.byref(d), lovasz, probs.data_ptr(), y_true.data_ptr(), g.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws.numel(),
+                                         _stream()), "lovasz_coeffs")
+
+
+def lovasz_loss_sums(probs, y_true, g, counts, acc, *, lovasz, HW, C_classes, ov_scale=1.0, label_smoothing=0.1, clip_eps=1e-7, inv_global_batch=1.0):
+    """``acc`` (fp32 [OVERLAP_ACC_FLOATS], zeroed once at allocation) receives the scalar loss in [0], the CCE pixel sum in [2], k_c in [4..8) and
+    L_c from [16], all bitwise reproducible (the overlap sums pass's reduction and grid rule)."""
+    d = _overlap_desc(probs, y_true, HW, C_classes, 8, label_smoothing, clip_eps, inv_global_batch, 0)
+    assert g.dtype == torch.float32 and g.is_contiguous() and g.shape == probs.shape and counts.dtype == torch.int32 and counts.numel() >= C_classes
+    L.check(L.load().usseg_lovasz_loss_sums(C.byref(d), lovasz, ov_scale, probs.data_ptr(), y_true.data_ptr(), g.data_ptr(), counts.data_ptr(), acc.data_ptr(),
+                                            acc.numel(), _stream()), "lovasz_loss_sums")
+
+
+def lovasz_loss_bwd(probs, y_true, g, acc, dlogits, *, lovasz, HW, C_classes, label_smoothing=0.1, clip_eps=1e-7, inv_global_batch=1.0, quad_w=0):
+    """d loss / d logits (bf16 [..., 8], or [B,H/2,W/2,16] with ``quad_w``) from the probabilities, the labels, ``g`` and the k_c in ``acc``."""
+    d = _overlap_desc(probs, y_true, HW, C_classes, 16 if quad_w else 8, label_smoothing, clip_eps, inv_global_batch, quad_w)
+    assert g.dtype == torch.float32 and g.is_contiguous() and g.shape == probs.shape
+    L.check(L.load().usseg_lovasz_loss_bwd(C.byref(d), lovasz, probs.data_ptr(), y_true.data_ptr(), g.data_ptr(), acc.data_ptr(), acc.numel(),
+                                           dlogits.data_ptr(), _stream()), "lovasz_loss_bwd")
+
+
 def quad_bias_expand(bias, C_logical, out):
     L.check(L.load().usseg_quad_bias_expand(bias.data_ptr(), C_logical, out.numel() // 4, out.data_ptr(), _stream()), "quad_bias_expand")
 
