@@ -658,14 +658,47 @@ int usseg_overlap_loss_bwd(const UssegLossDesc* d, const UssegOverlapLoss* ol, c
  *     sums     fp64  [N,2] = sum over S(a) of the distance to S(b), sum over S(b) of the distance to S(a)
  * When either surface is empty both maxima are -1 and both sums 0.  The sums are bitwise reproducible: one workgroup per image and
  * direction, a thread adds its pixels in index order, the 256 partial sums are added as a fixed tree; no float atomics.  Hausdorff distance
- * = sqrt(max of the two maxima); average symmetric surface distance (medpy) = mean of sums[0]/|S(a)| and sums[1]/|S(b)|.  HD95 needs a
- * per-image selection and is not provided.  Same limits as above with N for B; workspace usseg_surface_ws_bytes(N,H,W). */
+ * = sqrt(max of the two maxima); average symmetric surface distance (medpy) = mean of sums[0]/|S(a)| and sums[1]/|S(b)|.  HD95 and the
+ * surface Dice need a per-image selection: usseg_surface_stats below.  Same limits as above with N for B; workspace
+ * usseg_surface_ws_bytes(N,H,W).
+ *
+ * usseg_surface_stats: usseg_surface_dist plus order statistics of the distances and counts within a tolerance - what HD95 (the 95th
+ * percentile Hausdorff distance) and the surface Dice at a tolerance (normalised surface Dice, NSD; Nikolov et al., pixel-count form) need.
+ * Per image, with S(a), S(b) as above:
+ *     D_ab   the multiset of SQUARED Euclidean distances from each pixel of S(a) to the nearest pixel of S(b): exact int32, below 2^27
+ *     D_ba   the same from S(b) to S(a);   D_pool  their multiset union;   all three empty if either surface is empty.
+ * Order statistics.  For a set of size n >= 1 and a quantile t in [0, 1]:  pos = t * (double)(n - 1)  (ONE fp64 multiply),  k = floor(pos),
+ * k1 = min(k + 1, n - 1).  The host passes t = q / 100 computed in fp64, so pos is Python's  q / 100 * (n - 1).  The device returns the pair
+ * of squared distances of rank k and rank k1 (rank 0 the smallest), (-1, -1) for an empty set.  The host computes  g = pos - k,
+ * lo = sqrt(d2_k), hi = sqrt(d2_k1)  in fp64 and  value = lo + (hi - lo) * g  - NumPy's linear percentile; q = 100 is the Hausdorff
+ * distance, q = 0 the smallest distance.  Two conventions come from the one call:  pooled = the percentile of D_pool (medpy's hd95:
+ * np.percentile(np.hstack((d_ab, d_ba)), 95));  directed = the larger of the percentiles of D_ab and D_ba (MONAI's).  NaN where either
+ * surface is empty, as hd and assd.
+ * Surface Dice at tolerance tau = (|{D_ab <= t2}| + |{D_ba <= t2}|) / (|S(a)| + |S(b)|) with t2 the largest integer whose square root
+ * (the fp64 value, the distance as it is reported) is <= tau - the host computes it in integer arithmetic and passes it as an int32, which
+ * makes d <= tau exact.  Both surfaces empty: NaN;
+ * exactly one empty: 0.0 (no distance exists and the denominator is positive).
+ *     quant  fp64  [P] HOST array, P in [0, 4], each finite and in [0, 1];   tol2 int32 [T] HOST array, T in [0, 4], each >= 0
+ *            (both are copied by value into the kernel arguments: a captured graph holds them)
+ *     counters int64 [N,4], sums fp64 [N,2]   usseg_surface_dist's, bit for bit (the same per-thread index order and tree)
+ *     sel    int32 [N,3,P,2]   sets D_ab, D_ba, D_pool x quantile x (d2_k, d2_k1)
+ *     within int64 [N,T,2]     |{D_ab <= tol2[t]}|, |{D_ba <= tol2[t]}|
+ * With P == 0 (T == 0) quant and sel (tol2 and within) may be null.  Every output is a function of the inputs: the selection is an integer
+ * radix select (most significant digit first, 8-bit digits, integer atomics in LDS), no sort, no float atomics, no host round trip.  Three
+ * launches whatever the data; nothing allocates.  Limits as usseg_surface_dist; workspace usseg_surface_stats_ws_bytes(N,H,W) =
+ * round16(4*N*H*W) + round16(8*N*H*W) bytes (the row distances, then the int32 [N,2,H,W] plane of squared distances), 16-byte aligned;
+ * counters, sums and within 8-byte, sel 4-byte aligned; anything else is USSEG_ERR_BAD_ARG before any launch.  N == 0 launches nothing.
+ * (A source pixel of an image whose OTHER surface is empty costs one read per image row: the emptiness is known only after the scan.) */
 int64_t usseg_sdf_ws_bytes(int32_t B, int32_t H, int32_t W, int32_t C);
 int usseg_sdf_labels(const float* y_true, int32_t B, int32_t H, int32_t W, int32_t C, float thr, float* phi, void* ws, int64_t ws_bytes,
                      usseg_stream_t stream);
 int64_t usseg_surface_ws_bytes(int32_t N, int32_t H, int32_t W);
 int usseg_surface_dist(const uint8_t* a, const uint8_t* b, int32_t N, int32_t H, int32_t W, int64_t* counters, double* sums, void* ws,
                        int64_t ws_bytes, usseg_stream_t stream);
+int64_t usseg_surface_stats_ws_bytes(int32_t N, int32_t H, int32_t W);
+int usseg_surface_stats(const uint8_t* a, const uint8_t* b, int32_t N, int32_t H, int32_t W, const double* quant, int32_t P, const int32_t* tol2,
+                        int32_t T, int64_t* counters, double* sums, int32_t* sel, int64_t* within, void* ws, int64_t ws_bytes,
+                        usseg_stream_t stream);
 /* ---- connected components (csrc/components.hip) ----------------------------------------------------------------------------------------
  * Masks are uint8 [N,H,W], nonzero = inside; components are 4- or 8-connected (any other connectivity is refused) and never cross an image.
  * H and W each lie in [1, 8192], N in [0, 65535], N*H*W <= 2^29; labels, count, prob and the hit tables are 4-byte, stats 8-byte and the

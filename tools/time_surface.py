@@ -1,0 +1,102 @@
+"""Timing of the surface scores (csrc/sdf.hip; diagnostic): `ops.surface_dist` beside `ops.surface_stats`.
+
+    python tools/time_surface.py [--json PATH] [--tag NAME] [--eager N]
+
+Each call is captured in a HIP graph; a round is three replays between two events, the figure the median (min, max) of five rounds, in
+microseconds per call (tools/time_components.py's method).  Shapes 16 x 256 x 80 and 16 x 256 x 256, two contents (tools/time_loss.py's):
+    blocks    16 x 16 blocks, about 30 % inside, the prediction and the label drawn independently
+    one blob  one small disc per image, the prediction's 150 pixels away from the label's: every source pixel scans long columns
+`surface_stats` is timed at P = 1 (q = 95), T = 1 (t2 = 4) - what HD95 and one surface Dice need - and at P = T = 0, where its third launch
+only reproduces the counters and sums: the difference is the selection.  A tree without `ops.surface_stats` (the parent commit's) gives the
+`surface_dist` rows alone, so that the two trees can be run in alternating processes of one job.  `--eager N` makes N plain calls of each
+instead (for a kernel trace).  One JSON line per (shape, content); `--json` appends them to a file.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import torch  # noqa: E402
+
+from ultrasound_modeling_amd import ops  # noqa: E402
+
+N, REPLAYS, ROUNDS = 16, 3, 5
+
+
+def graph_us(fn):
+    """median, min, max over ROUNDS of the time of one call inside REPLAYS replays of the captured fn, in microseconds"""
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        fn()
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        fn()
+    for _ in range(3):
+        g.replay()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(ROUNDS):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(REPLAYS):
+            g.replay()
+        e1.record()
+        e1.synchronize()
+        out.append(e0.elapsed_time(e1) * 1e3 / REPLAYS)
+    return [round(v, 1) for v in (statistics.median(out), min(out), max(out))]
+
+
+def inputs(H, W):
+    g = torch.Generator().manual_seed(0)
+    blocks = [(torch.rand(N, H // 16, W // 16, generator=g) > 0.70).repeat_interleave(16, 1).repeat_interleave(16, 2) for _ in range(2)]
+    yy, xx = torch.meshgrid(torch.arange(H), torch.arange(W), indexing="ij")
+    blobs = [((yy - cy) ** 2 + (xx - W // 2) ** 2 <= 12 ** 2).expand(N, H, W) for cy in (40, 190)]
+    return (("blocks", blocks), ("one blob", blobs))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--json", default=None)
+    ap.add_argument("--tag", default="this")
+    ap.add_argument("--eager", type=int, default=0)
+    a = ap.parse_args()
+    stats = getattr(ops, "surface_stats", None)
+    for H, W in ((256, 80), (256, 256)):
+        ws = torch.empty(ops.surface_stats_ws_bytes(N, H, W) if stats else int(ops.L.load().usseg_surface_ws_bytes(N, H, W)), dtype=torch.uint8, device="cuda")
+        for name, (pa, pb) in inputs(H, W):
+            ma, mb = pa.to(torch.uint8).contiguous().cuda(), pb.to(torch.uint8).contiguous().cuda()
+            r = {"tree": a.tag, "shape": [N, H, W], "content": name}
+            calls = [("surface_dist_us", lambda: ops.surface_dist(ma, mb, ws=ws))]
+            if stats:
+                o1 = stats(ma, mb, (95,), (4,), ws=ws)
+                o0 = stats(ma, mb, (), (), ws=ws)
+                calls += [("surface_stats_us", lambda: stats(ma, mb, (95,), (4,), ws=ws, out=o1)), ("surface_stats_P0_T0_us", lambda: stats(ma, mb, (), (), ws=ws, out=o0))]
+            if a.eager:
+                for _, fn in calls:
+                    for _ in range(a.eager):
+                        fn()
+                torch.cuda.synchronize()
+                continue
+            # (surface_dist allocates its two small results: inside a capture they come from the graph's pool, once)
+            for key, fn in calls:
+                r[key] = graph_us(fn)
+            c, _ = ops.surface_dist(ma, mb, ws=ws)
+            r["surface_pixels"] = [int(c[:, 0].sum()), int(c[:, 1].sum())]
+            r["max_distance"] = round(float(c[:, 2:].max()) ** 0.5, 1)
+            if stats:
+                r["sel_q95_image0"] = o1[2][0].cpu().tolist()
+            line = json.dumps(r)
+            print(line, flush=True)
+            if a.json:
+                with open(a.json, "a") as f:
+                    f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -28,8 +28,10 @@ input_size = (256, 80)      # :12
 
 
 class Process(object):
-    def __init__(self, batch_size=16, num_classes=3, device=None, schedule=False):
+    def __init__(self, batch_size=16, num_classes=3, device=None, schedule=False, surface=None):
         self.batch_size = batch_size
+        # surface scores of the last class in ``test`` (default off): {"percentiles": [...], "tolerances": [...]} (metrics.surface_distances' arguments)
+        self.surface = None if surface is None else surface_settings(surface)
         self.schedule = schedule            # apply the :83-88 learning-rate / weight-decay schedule (module docstring)
         self.num_classes = num_classes
         self.input_shape = [input_size[0], input_size[1], 10]                                    # :19
@@ -79,11 +81,15 @@ class Process(object):
         """MainNumpy.py:90-147 -> F1 of the epoch's test set; its dict (``phase`` "test") is appended to ``self.history``."""
         print("\nTest...")
         total_loss = None
+        stats = []                                              # per batch: usseg_surface_stats' four tensors, left on the device
         while True:
             x_te, y_te, terminator = dataset.next_test(16)                                       # :97
             loss, class_score = neuralnet.step(x=x_te, y=y_te)                                   # :98
             total_loss = loss.detach().reshape(()).clone() if total_loss is None else total_loss.add_(loss.reshape(()))   # :107, on the device
-            self.metrics.update_state(_labels(y_te, class_score), class_score)                   # :100-106
+            labels = _labels(y_te, class_score)
+            self.metrics.update_state(labels, class_score)                                       # :100-106
+            if self.surface is not None:
+                stats.append(_surface_batch(labels, class_score, self.num_classes, self.surface))
             if terminator:
                 break
             self.test_iter += 1
@@ -97,7 +103,11 @@ class Process(object):
         dice = dice_line(neuralnet, self.metrics)
         if dice is not None:                                    # only with loss="dice" / "tversky" / "dice_ce"
             print("dice per class = {}".format(dice))
-        self.history.append(dict(m, phase="test", epoch=epoch, loss=total_loss))
+        extra = {}
+        if self.surface is not None:
+            extra = surface_summary(stats, self.surface)       # ONE read-back of the epoch's integers
+            print(surface_line(extra, self.surface))
+        self.history.append(dict(m, phase="test", epoch=epoch, loss=total_loss, **extra))
         self.metrics.reset_states()                                                              # :142-146
         return m["f1"]
 
@@ -136,6 +146,56 @@ def install_schedule(neuralnet, schedule=None, lr_scale=1e-2, wd_scale=1e-4):
     if opt.weight_decay is not None:
         neuralnet.weight_decay = wd_scale * schedule
         opt.set_weight_decay(neuralnet.weight_decay)
+
+
+def surface_settings(surface):
+    """``Process(surface=...)`` -> {"percentiles": [...], "tolerances": [...], "tol2": [...]}; ValueError for anything ``metrics.surface_distances`` refuses."""
+    from .metrics import _percentile_list, _tolerance_list
+    if not isinstance(surface, dict) or set(surface) - {"percentiles", "tolerances"}:
+        raise ValueError(f"surface: a dict with 'percentiles' and / or 'tolerances', got {surface!r}")
+    ts, t2 = _tolerance_list(surface.get("tolerances"))
+    return {"percentiles": _percentile_list(surface.get("percentiles")), "tolerances": ts, "tol2": t2}
+
+
+def _surface_batch(labels, probs, num_classes, cfg):
+    """One validation batch's ``usseg_surface_stats`` of the last class: the prediction ``argmax == num_classes - 1`` against the label plane ``> 0.5``.
+    Stream-ordered behind the step; nothing is read back."""
+    from . import ops
+    c = num_classes - 1
+    pred = (probs[..., :num_classes].argmax(-1) == c).to(torch.uint8).contiguous()
+    true = (labels[..., c] > 0.5).to(torch.uint8).contiguous()
+    return ops.surface_stats(pred, true, cfg["percentiles"], cfg["tol2"])
+
+
+def surface_summary(stats, cfg):
+    """The epoch's per-batch device results -> history keys: the means over the scored images of each percentile (pooled and directed) and of the surface
+    Dice at each tolerance, ``surface_scored`` (images where both surfaces exist: their HD is not NaN), ``surface_nsd_scored`` (images with at least one
+    surface) and ``surface_images``."""
+    import numpy as np
+    from .metrics import surface_scores_from_stats
+    parts = [torch.cat([s[i] for s in stats]).cpu() for i in range(4)]
+    s = surface_scores_from_stats(*parts, cfg["percentiles"], cfg["tolerances"])
+    ok, ok_nsd = ~np.isnan(s["hd"]), (s["n_a"] + s["n_b"]) > 0
+
+    def mean(col, keep):
+        v = [float(x) for x in col[keep]]
+        return sum(v) / len(v) if v else float("nan")
+    return {"surface_hd_pct": [mean(s["hd_pct"][:, p], ok) for p in range(len(cfg["percentiles"]))],
+            "surface_hd_pct_directed": [mean(s["hd_pct_directed"][:, p], ok) for p in range(len(cfg["percentiles"]))],
+            "surface_nsd": [mean(s["nsd"][:, t], ok_nsd) for t in range(len(cfg["tolerances"]))],
+            "surface_scored": int(ok.sum()), "surface_nsd_scored": int(ok_nsd.sum()), "surface_images": int(ok.shape[0])}
+
+
+def surface_line(summary, cfg):
+    """The report line after the Dice line."""
+    from .TBIEvaluator import _column_number
+    parts = []
+    for p, q in enumerate(cfg["percentiles"]):
+        parts.append("hd{} = {}, hd{}_directed = {}".format(_column_number(q), summary["surface_hd_pct"][p], _column_number(q), summary["surface_hd_pct_directed"][p]))
+    for t, tau in enumerate(cfg["tolerances"]):
+        parts.append("nsd{} = {}".format(_column_number(tau), summary["surface_nsd"][t]))
+    return "surface (mean over scored images): {} ({} of {} images have both surfaces, {} at least one)".format(
+        ", ".join(parts), summary["surface_scored"], summary["surface_images"], summary["surface_nsd_scored"])
 
 
 def _labels(y, probs):

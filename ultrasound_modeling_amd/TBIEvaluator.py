@@ -190,26 +190,50 @@ def Polar_Model(data, cascade: Cascade, names=None, batch_size=16):
 
 
 # ---------------------------------------------------------------------------------------------------------- surface scores
-def surface_scores(result: PolarResult, threshold=0.5, device=None, *, pred_mask=None):
+def surface_scores(result: PolarResult, threshold=0.5, device=None, *, pred_mask=None, percentiles=None, tolerances=None):
     """Hausdorff and average symmetric surface distance of the bleed class, per image: the prediction ``result.bleed_prob > threshold``
     against the label's class 2 (``label > 1.5``: ``label2vec``'s class-2 plane under the 0.5 rule).  -> ``metrics.surface_distances``' dict
     (``hd`` / ``assd`` NaN for an image without a predicted or without a labelled bleed, ``n_a`` / ``n_b`` the two surface pixel counts).
-    ``pred_mask`` [N,H,W] (``clean_result``'s, for one) is scored in place of ``bleed_prob > threshold``."""
+    ``pred_mask`` [N,H,W] (``clean_result``'s, for one) is scored in place of ``bleed_prob > threshold``.  ``percentiles`` (95 for HD95) and
+    ``tolerances`` (pixels) add ``hd_pct``, ``hd_pct_directed`` and ``nsd`` (``metrics.surface_scores_from_stats``)."""
     from .metrics import surface_distances
     pred = np.asarray(result.bleed_prob) > threshold if pred_mask is None else np.asarray(pred_mask) != 0
-    return surface_distances(pred, np.asarray(result.label) > 1.5, device=device)
+    if percentiles is None and tolerances is None:
+        return surface_distances(pred, np.asarray(result.label) > 1.5, device=device)
+    return surface_distances(pred, np.asarray(result.label) > 1.5, device=device, percentiles=percentiles, tolerances=tolerances)
 
 
-def write_surface_csv(path, result: PolarResult, threshold=0.5, device=None, *, pred_mask=None):
-    """One row per image: name, hd, assd, surface pixels of the prediction, surface pixels of the label.  -> the number of rows."""
+def _column_number(v):
+    """95.0 -> "95", 99.9 -> "99.9": the number as it reads in a column name."""
+    v = float(v)
+    return str(int(v)) if v == int(v) else repr(v)
+
+
+def write_surface_csv(path, result: PolarResult, threshold=0.5, device=None, *, pred_mask=None, percentiles=None, tolerances=None):
+    """One row per image: name, hd, assd, surface pixels of the prediction, surface pixels of the label; with ``percentiles`` / ``tolerances``
+    also hd<q> (pooled, medpy's), hd<q>_directed (MONAI's) per percentile and nsd<tau> per tolerance.  -> the number of rows."""
     import csv
-    s = surface_scores(result, threshold, device=device, pred_mask=pred_mask)
+    extra = percentiles is not None or tolerances is not None
+    if extra:
+        s = surface_scores(result, threshold, device=device, pred_mask=pred_mask, percentiles=percentiles, tolerances=tolerances)
+    else:
+        s = surface_scores(result, threshold, device=device, pred_mask=pred_mask)
     names = _names(result)
+    head = ["name", "hd", "assd", "n_pred", "n_label"]
+    if extra:
+        for q in s["percentiles"]:
+            head += [f"hd{_column_number(q)}", f"hd{_column_number(q)}_directed"]
+        head += [f"nsd{_column_number(t)}" for t in s["tolerances"]]
     with open(path, "w", newline="") as f:
         w = csv.writer(f)
-        w.writerow(["name", "hd", "assd", "n_pred", "n_label"])
+        w.writerow(head)
         for i, n in enumerate(names):
-            w.writerow([n, repr(float(s["hd"][i])), repr(float(s["assd"][i])), int(s["n_a"][i]), int(s["n_b"][i])])
+            row = [n, repr(float(s["hd"][i])), repr(float(s["assd"][i])), int(s["n_a"][i]), int(s["n_b"][i])]
+            if extra:
+                for p in range(len(s["percentiles"])):
+                    row += [repr(float(s["hd_pct"][i][p])), repr(float(s["hd_pct_directed"][i][p]))]
+                row += [repr(float(s["nsd"][i][t])) for t in range(len(s["tolerances"]))]
+            w.writerow(row)
     return len(names)
 
 
@@ -426,6 +450,11 @@ def main(argv=None):
     ap.add_argument("--use-vit", action="store_true", help="the checkpoints have the ViT bottleneck")
     ap.add_argument("--surface-csv", default=None, metavar="PATH",
                     help="also write the bleed class's Hausdorff and average symmetric surface distance, one row per image")
+    ap.add_argument("--surface-percentile", type=float, action="append", default=None, metavar="Q",
+                    help="add hd<Q> (pooled) and hd<Q>_directed columns to --surface-csv: the Q-th percentile of the surface distances, 95 for HD95 "
+                         "(repeatable, up to 4)")
+    ap.add_argument("--surface-tolerance", type=float, action="append", default=None, metavar="T",
+                    help="add an nsd<T> column to --surface-csv: the surface Dice at a tolerance of T pixels (repeatable, up to 4)")
     ap.add_argument("--lesion-csv", default=None, metavar="PATH",
                     help="also write the bleed class's lesion-wise detection counts, one row per image and a totals row")
     ap.add_argument("--min-area", type=int, default=None, metavar="N",
@@ -439,6 +468,14 @@ def main(argv=None):
         ap.error("--min-area must be >= 1")
     if not 0.0 <= a.min_peak <= 1.0:
         ap.error("--min-peak must lie in [0, 1]")
+    if (a.surface_percentile is not None or a.surface_tolerance is not None) and a.surface_csv is None:
+        ap.error("--surface-percentile / --surface-tolerance need --surface-csv")
+    if len(a.surface_percentile or ()) > 4 or len(a.surface_tolerance or ()) > 4:
+        ap.error("at most 4 --surface-percentile and 4 --surface-tolerance")
+    if not all(0.0 <= q <= 100.0 for q in a.surface_percentile or ()):
+        ap.error("--surface-percentile must lie in [0, 100]")
+    if not all(0.0 <= t < float("inf") for t in a.surface_tolerance or ()):
+        ap.error("--surface-tolerance must be finite and >= 0")
     data = np.load(a.data)
     names = np.load(a.paths)
     cascade = Cascade.from_checkpoints(a.bleed, a.mask, batch_size=a.batch, use_vit=a.use_vit, transunet=a.transunet)
@@ -448,7 +485,8 @@ def main(argv=None):
         cleaned = None
         if a.min_area is not None:
             cleaned = clean_result(result, min_area=a.min_area, min_peak=a.min_peak, connectivity=a.connectivity, device=cascade.device)
-        rows = write_surface_csv(a.surface_csv, result, device=cascade.device, pred_mask=cleaned)
+        rows = write_surface_csv(a.surface_csv, result, device=cascade.device, pred_mask=cleaned, percentiles=a.surface_percentile,
+                                 tolerances=a.surface_tolerance)
         print(f"wrote {rows} surface-score rows to {a.surface_csv}")
     if a.lesion_csv is not None:
         rows = write_lesion_csv(a.lesion_csv, result, min_area=a.min_area if a.min_area is not None else 1, min_peak=a.min_peak,

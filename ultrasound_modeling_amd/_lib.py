@@ -228,6 +228,8 @@ _PROTOS = {
     "usseg_sdf_labels": (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp, c_i64, c_vp]),
     "usseg_surface_ws_bytes": (c_i64, [c_i32, c_i32, c_i32]),
     "usseg_surface_dist": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "usseg_surface_stats_ws_bytes": (c_i64, [c_i32, c_i32, c_i32]),
+    "usseg_surface_stats": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "usseg_components_ws_bytes": (c_i64, [c_i32, c_i32, c_i32]),
     "usseg_label_components": (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "usseg_component_stats": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),

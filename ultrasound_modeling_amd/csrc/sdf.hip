@@ -1,5 +1,6 @@
-// Exact Euclidean distance maps on the device (usseg.h: usseg_sdf_labels, usseg_surface_dist): the signed distance map of the labels for the
-// boundary loss, and the surface-to-surface distances behind the Hausdorff / average-symmetric-surface-distance scores.
+// Exact Euclidean distance maps on the device (usseg.h: usseg_sdf_labels, usseg_surface_dist, usseg_surface_stats): the signed distance map of the
+// labels for the boundary loss, and the surface-to-surface distances behind the Hausdorff / average-symmetric-surface-distance scores, their
+// percentiles (HD95) and the surface Dice at a tolerance.
 // One transform, two uses.  A plane is a [H][W] binary image; every pixel wants the squared distance to the nearest pixel of a TARGET set.
 //   row pass     sdf_row_kernel: one wave per image row.  The lanes ballot 64 pixels at a time into a bit row in LDS; a pixel then finds the
 //                nearest set (or clear) bit to its left and right with clz / ffs over at most ceil(W/64) words.  It writes g, the distance
@@ -17,9 +18,14 @@
 //                sdf_surface_kernel   one workgroup per (image, direction): counts both surfaces, then each thread walks its pixels in index
 //                                 order (max of d^2 in int32, sum of sqrt in fp64) and the workgroup adds the 256 partial sums as a fixed
 //                                 tree - bitwise reproducible, no float atomics.
-// phi = the fp64 value - the square root of the exact integer, 1 minus it inside the mask - rounded ONCE to fp32: outside the mask that is the
+//                sdf_plane_kernel     (usseg_surface_stats) one thread per pixel over all images: the squared distance of every surface pixel to the
+//                                 other surface into an int32 [N][2][H][W] plane, for the selection that follows.
+//   selection    sdf_select_kernel    one workgroup per (image, set): sdf_surface_kernel's counters and sums again, from the plane, in the same order
+//                                 (the same bits), the counts within each tolerance, and an integer radix select of the asked-for ranks - most
+//                                 significant digit first, 8-bit digits, a 256-bin histogram in LDS per distinct prefix, four levels.
+// phi =the fp64 value - the square root of the exact integer, 1 minus it inside the mask - rounded ONCE to fp32: outside the mask that is the
 // correctly rounded fp32 root for every integer below 2^31.
-// Nothing here allocates; the intermediate lives in the caller's workspace (usseg_sdf_ws_bytes / usseg_surface_ws_bytes).
+// Nothing here allocates; the intermediate lives in the caller's workspace (usseg_sdf_ws_bytes / usseg_surface_ws_bytes / usseg_surface_stats_ws_bytes).
 #include "common.h"
 #include <cmath>
 
@@ -200,6 +206,183 @@ __global__ __launch_bounds__(256) void sdf_surface_kernel(const uint32_t* __rest
   if (tid == 0) { counters[4 * n + 2 + dir] = mxs[0]; sums[2 * n + dir] = red[0]; }
 }
 
+// ---- surface statistics (usseg.h: usseg_surface_stats): the distances materialised, then an exact integer radix select ------------------
+// plane int32 [N][2][H][W]: [n][0] = squared distance from a pixel of S(a) to S(b), [n][1] = from a pixel of S(b) to S(a); SDF_NOT_SOURCE
+// where the pixel is not on the source surface, -1 (sdf_col_scan's) where it is and the target surface is empty.
+#define SDF_NOT_SOURCE (-2)
+#define SDF_MAX_Q 4
+#define SDF_MAX_RANKS (2 * SDF_MAX_Q)
+#define SDF_SEL_THREADS 1024          // sdf_select_kernel's workgroup: the first 256 threads are sdf_surface_kernel's, all of them fill the histograms
+
+struct SurfStatsArgs {                 // by value in the kernel arguments: a captured graph holds them
+  double quant[SDF_MAX_Q];
+  int32_t tol2[SDF_MAX_Q];
+  int32_t P, T;
+};
+
+// grid (ceil(H*W / 256), N): thread = one pixel, lanes along x
+__global__ __launch_bounds__(256) void sdf_plane_kernel(const uint32_t* __restrict__ g, int32_t* __restrict__ plane, int H, int W) {
+  const int n = blockIdx.y, HW = H * W;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= HW) return;
+  const uint32_t* p = g + (int64_t)n * HW;
+  const uint32_t u = p[i];
+  const int yy = i / W, xx = i - yy * W;
+  int dab = SDF_NOT_SOURCE, dba = SDF_NOT_SOURCE;
+  if ((u & 0xFFFFu) == 0u) dab = sdf_col_scan(p + xx, W, yy, H, 16);
+  if ((u >> 16) == 0u) dba = sdf_col_scan(p + xx, W, yy, H, 0);
+  int32_t* out = plane + (int64_t)n * 2 * HW;
+  out[i] = dab;
+  out[HW + i] = dba;
+}
+
+// one more count in bin `bin` of h for every lane with `match`; the lanes that agree with the first matching lane share one atomic (a surface
+// that lies on the other one is all zeros).  Called by whole waves.
+__device__ __forceinline__ void sdf_hist_add(int* h, int bin, bool match, int lane) {
+  const uint64_t m = __ballot(match);
+  if (!m) return;
+  const int first = __shfl(bin, __ffsll((unsigned long long)m) - 1, 64);
+  const uint64_t same = __ballot(match && bin == first);
+  if (!match) return;
+  if (bin != first) atomicAdd(&h[bin], 1);
+  else if (lane == __ffsll((unsigned long long)same) - 1) atomicAdd(&h[first], __popcll(same));
+}
+
+// grid (P ? 3 : 2, N): set 0 = D_ab, 1 = D_ba, 2 = their union.  Sets 0 and 1 also give usseg_surface_dist's counters and sums of their
+// direction - sdf_surface_kernel's per-thread index order and tree, on the first 256 threads - and the counts within each tolerance.
+__global__ __launch_bounds__(SDF_SEL_THREADS) void sdf_select_kernel(const int32_t* __restrict__ plane, SurfStatsArgs A, int64_t* __restrict__ counters,
+                                                         double* __restrict__ sums, int32_t* __restrict__ sel, int64_t* __restrict__ within, int H, int W) {
+  __shared__ int hist[SDF_MAX_RANKS][256];
+  __shared__ double red[256];
+  __shared__ int mxs[256];
+  __shared__ int s_cnt[2], s_within[SDF_MAX_Q];
+  __shared__ int s_prefix[SDF_MAX_RANKS], s_rem[SDF_MAX_RANKS], s_owner[SDF_MAX_RANKS], s_uniq[SDF_MAX_RANKS], s_nu;
+  const int set = blockIdx.x, n = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int HW = H * W;
+  const int32_t* pl = plane + (int64_t)n * 2 * HW;
+  if (tid < 2) s_cnt[tid] = 0;
+  if (tid < SDF_MAX_Q) s_within[tid] = 0;
+  __syncthreads();
+  {
+    int ca = 0, cb = 0;
+    for (int i = tid; i < HW; i += SDF_SEL_THREADS) {
+      ca += pl[i] != SDF_NOT_SOURCE;
+      cb += pl[HW + i] != SDF_NOT_SOURCE;
+    }
+    for (int msk = 32; msk >= 1; msk >>= 1) { ca += __shfl_xor(ca, msk, 64); cb += __shfl_xor(cb, msk, 64); }
+    if (lane == 0) { atomicAdd(&s_cnt[0], ca); atomicAdd(&s_cnt[1], cb); }
+  }
+  __syncthreads();
+  const int na = s_cnt[0], nb = s_cnt[1];
+  const bool empty = na == 0 || nb == 0;
+  if (set == 0 && tid == 0) { counters[4 * n] = na; counters[4 * n + 1] = nb; }
+  if (set < 2) {
+    const int32_t* e = pl + (int64_t)set * HW;
+    double s = 0.0;
+    int mx = -1, wc[SDF_MAX_Q] = {0, 0, 0, 0};
+    if (!empty && tid < 256) {
+      for (int i = tid; i < HW; i += 256) {
+        const int d2 = e[i];
+        if (d2 < 0) continue;
+        mx = d2 > mx ? d2 : mx;
+        s += sqrt((double)d2);
+#pragma unroll
+        for (int t = 0; t < SDF_MAX_Q; ++t) wc[t] += (t < A.T && d2 <= A.tol2[t]) ? 1 : 0;
+      }
+    }
+    if (tid < 256) { red[tid] = s; mxs[tid] = mx; }
+    __syncthreads();
+    for (int k = 128; k >= 1; k >>= 1) {                        // sdf_surface_kernel's tree
+      if (tid < k) { red[tid] += red[tid + k]; mxs[tid] = mxs[tid] > mxs[tid + k] ? mxs[tid] : mxs[tid + k]; }
+      __syncthreads();
+    }
+#pragma unroll
+    for (int t = 0; t < SDF_MAX_Q; ++t) {
+      int v = wc[t];
+      for (int msk = 32; msk >= 1; msk >>= 1) v += __shfl_xor(v, msk, 64);
+      if (lane == 0 && v) atomicAdd(&s_within[t], v);
+    }
+    __syncthreads();
+    if (tid == 0) { counters[4 * n + 2 + set] = empty ? -1 : mxs[0]; sums[2 * n + set] = empty ? 0.0 : red[0]; }
+    if (tid < A.T) within[((int64_t)n * A.T + tid) * 2 + set] = s_within[tid];
+  }
+  const int P = A.P, R = 2 * P;
+  if (P == 0) return;
+  int32_t* out = sel + ((int64_t)n * 3 + set) * P * 2;
+  if (empty) {
+    if (tid < R) out[tid] = -1;
+    return;
+  }
+  const int32_t* e = pl + (set == 1 ? HW : 0);
+  const int len = set == 2 ? 2 * HW : HW;
+  const int cnt = set == 0 ? na : set == 1 ? nb : na + nb;
+  if (tid < R) {
+    double t = A.quant[0];                                      // (constant indices: the argument struct stays in registers)
+#pragma unroll
+    for (int p = 1; p < SDF_MAX_Q; ++p) t = (tid >> 1) == p ? A.quant[p] : t;
+    const double pos = t * (double)(cnt - 1);
+    int k = (int)floor(pos);
+    if (tid & 1) k = k + 1 < cnt - 1 ? k + 1 : cnt - 1;
+    s_prefix[tid] = 0; s_rem[tid] = k; s_owner[tid] = 0;
+  }
+  if (tid == 0) { s_nu = 1; s_uniq[0] = 0; }
+  __syncthreads();
+  for (int shift = 24; shift >= 0; shift -= 8) {
+    const int nu = s_nu;
+    for (int j = tid; j < nu * 256; j += SDF_SEL_THREADS) (&hist[0][0])[j] = 0;
+    __syncthreads();
+    for (int base = 0; base < len; base += 4 * SDF_SEL_THREADS) {      // four loads in flight; most of the plane is not a source
+      int xs[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int i = base + j * SDF_SEL_THREADS + tid;
+        xs[j] = i < len ? e[i] : -1;
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int x = xs[j];
+        if (!__ballot(x >= 0)) continue;                                // (the whole wave)
+        const int hi = shift == 24 ? 0 : x >> (shift + 8);
+        const int bin = (x >> shift) & 255;
+        for (int u = 0; u < nu; ++u) sdf_hist_add(hist[u], bin, x >= 0 && hi == s_uniq[u], lane);
+      }
+    }
+    __syncthreads();
+    // the bin that holds rank s_rem[r] among the values under s_prefix[r]: a wave per rank, four bins per lane
+    for (int r = wave; r < R; r += SDF_SEL_THREADS / 64) {
+      const int* h = hist[s_owner[r]];
+      const int rem = s_rem[r];
+      const int b0 = h[4 * lane], b1 = h[4 * lane + 1], b2 = h[4 * lane + 2], b3 = h[4 * lane + 3];
+      const int mine = b0 + b1 + b2 + b3;
+      int incl = mine;
+      for (int d = 1; d < 64; d <<= 1) {
+        const int up = __shfl_up(incl, d, 64);
+        if (lane >= d) incl += up;
+      }
+      const int excl = incl - mine;
+      if (excl <= rem && rem < incl) {
+        int q = rem - excl, b = 0;
+        if (q >= b0) { q -= b0; b = 1; if (q >= b1) { q -= b1; b = 2; if (q >= b2) { q -= b2; b = 3; } } }
+        s_prefix[r] = (s_prefix[r] << 8) | (4 * lane + b);
+        s_rem[r] = q;
+      }
+    }
+    __syncthreads();
+    if (tid == 0) {                                             // ranks whose prefixes agree share the next level's histogram
+      int m = 0;
+      for (int r = 0; r < R; ++r) {
+        int o = -1;
+        for (int u = 0; u < m; ++u) if (s_uniq[u] == s_prefix[r]) o = u;
+        if (o < 0) { o = m; s_uniq[m++] = s_prefix[r]; }
+        s_owner[r] = o;
+      }
+      s_nu = m;
+    }
+    __syncthreads();
+  }
+  if (tid < R) out[tid] = s_prefix[tid];
+}
+
 // ---- entry points: every argument is checked before any launch ------------------------------------------------------------------------
 static inline int64_t round16(int64_t v) { return (v + 15) / 16 * 16; }
 
@@ -253,4 +436,46 @@ extern "C" int usseg_surface_dist(const uint8_t* a, const uint8_t* b, int32_t N,
   hipLaunchKernelGGL((sdf_row_kernel<true>), dim3((rows + 3) / 4), dim3(256), 0, s, (const float*)nullptr, a, b, 0.f, g, (uint8_t*)nullptr, rows, H, W, 1);
   hipLaunchKernelGGL(sdf_surface_kernel, dim3(2, N), dim3(256), 0, s, (const uint32_t*)g, counters, sums, H, W);
   return usseg_check_launch("surface_dist");
+}
+
+extern "C" int64_t usseg_surface_stats_ws_bytes(int32_t N, int32_t H, int32_t W) {
+  if (N < 0 || H < 1 || W < 1 || H > SDF_MAX_DIM || W > SDF_MAX_DIM) return -1;
+  return round16((int64_t)4 * N * H * W) + round16((int64_t)8 * N * H * W);      // g, then the plane of squared distances
+}
+
+extern "C" int usseg_surface_stats(const uint8_t* a, const uint8_t* b, int32_t N, int32_t H, int32_t W, const double* quant, int32_t P, const int32_t* tol2,
+                                   int32_t T, int64_t* counters, double* sums, int32_t* sel, int64_t* within, void* ws, int64_t ws_bytes,
+                                   usseg_stream_t stream) {
+  USSEG_CHECK_ARG(H >= 1 && H <= SDF_MAX_DIM && W >= 1 && W <= SDF_MAX_DIM, "surface_stats: H and W must lie in [1, %d], got %d x %d", SDF_MAX_DIM, H, W);
+  USSEG_CHECK_ARG(N >= 0 && N <= 65535, "surface_stats: 0 <= N <= 65535");
+  USSEG_CHECK_ARG((int64_t)N * H * W <= (1 << 29), "surface_stats: more than 2^29 pixels");
+  USSEG_CHECK_ARG(P >= 0 && P <= SDF_MAX_Q, "surface_stats: 0 <= P <= %d quantiles, got %d", SDF_MAX_Q, P);
+  USSEG_CHECK_ARG(T >= 0 && T <= SDF_MAX_Q, "surface_stats: 0 <= T <= %d tolerances, got %d", SDF_MAX_Q, T);
+  USSEG_CHECK_ARG(a && b && counters && sums && ws && (P == 0 || (quant && sel)) && (T == 0 || (tol2 && within)), "surface_stats: null pointer");
+  SurfStatsArgs A = {};
+  for (int p = 0; p < P; ++p) {
+    USSEG_CHECK_ARG(std::isfinite(quant[p]) && quant[p] >= 0.0 && quant[p] <= 1.0, "surface_stats: quantile %d must be finite and lie in [0, 1], got %.17g", p,
+                    quant[p]);
+    A.quant[p] = quant[p];
+  }
+  for (int t = 0; t < T; ++t) {
+    USSEG_CHECK_ARG(tol2[t] >= 0, "surface_stats: squared tolerance %d must be >= 0, got %d", t, tol2[t]);
+    A.tol2[t] = tol2[t];
+  }
+  A.P = P;
+  A.T = T;
+  USSEG_CHECK_ARG(((uintptr_t)counters & 7) == 0 && ((uintptr_t)sums & 7) == 0 && ((uintptr_t)within & 7) == 0 && ((uintptr_t)sel & 3) == 0 &&
+                      ((uintptr_t)ws & 15) == 0,
+                  "surface_stats: counters, sums and within must be 8-byte, sel 4-byte, the workspace 16-byte aligned");
+  USSEG_CHECK_ARG(ws_bytes >= usseg_surface_stats_ws_bytes(N, H, W), "surface_stats: the workspace holds %lld bytes, %lld needed", (long long)ws_bytes,
+                  (long long)usseg_surface_stats_ws_bytes(N, H, W));
+  if (N == 0) return USSEG_OK;
+  uint32_t* g = (uint32_t*)ws;
+  int32_t* plane = (int32_t*)((uint8_t*)ws + round16((int64_t)4 * N * H * W));
+  hipStream_t s = (hipStream_t)stream;
+  const int rows = N * H;
+  hipLaunchKernelGGL((sdf_row_kernel<true>), dim3((rows + 3) / 4), dim3(256), 0, s, (const float*)nullptr, a, b, 0.f, g, (uint8_t*)nullptr, rows, H, W, 1);
+  hipLaunchKernelGGL(sdf_plane_kernel, dim3((H * W + 255) / 256, N), dim3(256), 0, s, (const uint32_t*)g, plane, H, W);
+  hipLaunchKernelGGL(sdf_select_kernel, dim3(P ? 3 : 2, N), dim3(SDF_SEL_THREADS), 0, s, (const int32_t*)plane, A, counters, sums, sel, within, H, W);
+  return usseg_check_launch("surface_stats");
 }

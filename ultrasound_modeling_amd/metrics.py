@@ -14,6 +14,7 @@ Two behaviours of the reference, reproduced on purpose:
 """
 from __future__ import annotations
 
+import math
 from typing import Dict
 
 import numpy as np
@@ -91,17 +92,89 @@ def surface_scores_from_counters(counters, sums):
     return {"hd": hd, "assd": assd, "n_a": c[:, 0], "n_b": c[:, 1], "max_ab": c[:, 2], "max_ba": c[:, 3], "sum_ab": s[:, 0], "sum_ba": s[:, 1]}
 
 
-def surface_distances(a, b, device=None):
+def tolerance_squared(tau) -> int:
+    """The largest integer t2 whose square root - the fp64 value ``math.sqrt(t2)``, the distance as it is reported - is <= ``tau`` (>= 0,
+    finite), so that ``d <= tau`` is exactly ``d2 <= t2`` for a distance d = sqrt(d2).  Integer arithmetic: floor of the square of the exact
+    binary value of ``tau``, as a fraction; one more when the next integer's root ROUNDS to ``tau`` or below (tau = math.sqrt(2.0) lies below
+    the real root of 2 and still admits the pixel at distance math.sqrt(2.0): t2 = 2)."""
+    tau = float(tau)
+    if not (math.isfinite(tau) and tau >= 0.0):
+        raise ValueError(f"a surface tolerance must be finite and >= 0, got {tau}")
+    num, den = tau.as_integer_ratio()                       # tau == num / den exactly
+    t2 = (num * num) // (den * den)                         # floor(tau^2): the real root of m is <= tau  <=>  m <= floor(tau^2)
+    assert t2 * den * den <= num * num < (t2 + 1) * den * den and math.isqrt(t2) <= tau < math.isqrt(t2) + 1
+    if t2 < 2 ** 53 and math.sqrt(t2 + 1) <= tau:          # (the root of t2 + 2 is a whole step further: never again)
+        t2 += 1
+    if t2 >= 2 ** 31:
+        raise ValueError(f"a surface tolerance of {tau} pixels is beyond any image (its square must stay below 2^31)")
+    return t2
+
+
+def _percentile_list(percentiles):
+    qs = [float(q) for q in (percentiles if percentiles is not None else ())]
+    if len(qs) > 4 or not all(math.isfinite(q) and 0.0 <= q <= 100.0 for q in qs):
+        raise ValueError(f"at most 4 surface percentiles, each in [0, 100], got {qs}")
+    return qs
+
+
+def _tolerance_list(tolerances):
+    ts = [float(t) for t in (tolerances if tolerances is not None else ())]
+    if len(ts) > 4:
+        raise ValueError(f"at most 4 surface tolerances, got {ts}")
+    return ts, [tolerance_squared(t) for t in ts]
+
+
+def _order_statistic(q, n, d2_k, d2_k1):
+    """usseg.h's rule for one set of n >= 1 squared distances: pos = q / 100 * (n - 1), g = pos - floor(pos), lerp of the two roots."""
+    pos = q / 100 * (n - 1)
+    g = pos - math.floor(pos)
+    lo, hi = math.sqrt(d2_k), math.sqrt(d2_k1)
+    return lo + (hi - lo) * g
+
+
+def surface_scores_from_stats(counters, sums, sel, within, percentiles=(), tolerances=()):
+    """``usseg_surface_stats``' per-image results -> the dict of ``surface_scores_from_counters`` plus ``hd_pct`` [N,P] (the percentiles of
+    the POOLED distances of both directions: medpy's ``hd95`` at q = 95), ``hd_pct_directed`` [N,P] (the larger of the two directions'
+    percentiles: MONAI's), ``nsd`` [N,T] (surface Dice at each tolerance, pixel-count form), ``percentiles``, ``tolerances``, and the raw
+    integers ``sel`` [N,3,P,2] / ``within`` [N,T,2].  The host arithmetic of usseg.h's definitions, in Python floats: percentiles NaN where
+    either surface is empty; nsd NaN where both are, 0.0 where exactly one is."""
+    qs = _percentile_list(percentiles)
+    ts, _ = _tolerance_list(tolerances)
+    out = surface_scores_from_counters(counters, sums)
+    N, P, T = out["n_a"].shape[0], len(qs), len(ts)
+    sel = torch.as_tensor(sel).cpu().numpy().astype(np.int64).reshape(N, 3, P, 2)
+    within = torch.as_tensor(within).cpu().numpy().astype(np.int64).reshape(N, T, 2)
+    pooled, directed, nsd = np.full((N, P), np.nan), np.full((N, P), np.nan), np.full((N, T), np.nan)
+    for i in range(N):
+        na, nb = int(out["n_a"][i]), int(out["n_b"][i])
+        if na > 0 and nb > 0:
+            for p, q in enumerate(qs):
+                v = [_order_statistic(q, n, int(sel[i, s, p, 0]), int(sel[i, s, p, 1])) for s, n in enumerate((na, nb, na + nb))]
+                pooled[i, p], directed[i, p] = v[2], max(v[0], v[1])
+        if na + nb > 0:
+            for t in range(T):
+                nsd[i, t] = (int(within[i, t, 0]) + int(within[i, t, 1])) / (na + nb)
+    out.update(hd_pct=pooled, hd_pct_directed=directed, nsd=nsd, percentiles=qs, tolerances=ts, sel=sel, within=within)
+    return out
+
+
+def surface_distances(a, b, device=None, *, percentiles=None, tolerances=None):
     """Hausdorff distance and average symmetric surface distance of two stacks of masks [N,H,W] (anything ``!= 0`` is inside; NumPy or
     torch), in pixels, on the device: surfaces by the 4-neighbour erosion rule, exact Euclidean distances (usseg.h ``usseg_surface_dist``).
-    -> the dict of ``surface_scores_from_counters``.  HD95 needs a per-image selection and is not provided."""
+    -> the dict of ``surface_scores_from_counters``.  With ``percentiles`` (up to 4, in [0, 100]: 95 for HD95) and / or ``tolerances`` (up to
+    4, in pixels) one ``usseg_surface_stats`` call instead -> the dict of ``surface_scores_from_stats``."""
     from . import ops
     dev = torch.device(device if device is not None else "cuda")
     ta, tb = ((torch.as_tensor(m) != 0).to(device=dev, dtype=torch.uint8).contiguous() for m in (a, b))
     if ta.dim() != 3 or ta.shape != tb.shape:
         raise ValueError(f"surface_distances: two [N,H,W] stacks of one shape, got {tuple(ta.shape)} and {tuple(tb.shape)}")
-    counters, sums = ops.surface_dist(ta, tb)
-    return surface_scores_from_counters(counters, sums)
+    if percentiles is None and tolerances is None:
+        counters, sums = ops.surface_dist(ta, tb)
+        return surface_scores_from_counters(counters, sums)
+    qs = _percentile_list(percentiles)
+    ts, t2 = _tolerance_list(tolerances)
+    counters, sums, sel, within = ops.surface_stats(ta, tb, qs, t2)
+    return surface_scores_from_stats(counters, sums, sel, within, qs, ts)
 
 
 def _mask_stack(m, dev, what):

@@ -1188,6 +1188,47 @@ def surface_dist(a, b, ws=None):
     return counters, sums
 
 
+def surface_stats_ws_bytes(N: int, H: int, W: int) -> int:
+    """Workspace bytes of ``surface_stats`` (usseg_surface_stats_ws_bytes); ValueError for a shape it refuses."""
+    n = int(L.load().usseg_surface_stats_ws_bytes(N, H, W))
+    if n < 0:
+        raise ValueError(f"surface_stats: H and W must lie in [1, 8192], got {N}x{H}x{W}")
+    return n
+
+
+def surface_stats(a, b, percentiles=(), tol2=(), *, ws=None, out=None):
+    """``surface_dist`` plus the order statistics and tolerance counts behind HD95 and the surface Dice (usseg.h usseg_surface_stats): two
+    uint8 [N,H,W] masks, up to 4 ``percentiles`` q in [0, 100] (passed on as the fp64 quantile q / 100) and up to 4 squared tolerances
+    ``tol2`` (ints >= 0) -> (counters int64 [N,4], sums fp64 [N,2], sel int32 [N,3,P,2], within int64 [N,T,2]).  ``ws`` (uint8,
+    ``surface_stats_ws_bytes`` long) and ``out`` (those four tensors) are allocated when not given; a captured region passes its own."""
+    assert a.dtype == torch.uint8 and b.dtype == torch.uint8 and a.is_contiguous() and b.is_contiguous() and a.dim() == 3 and a.shape == b.shape
+    N, H, W = a.shape
+    quant = [float(q) / 100 for q in percentiles]
+    t2 = [int(t) for t in tol2]
+    P, T = len(quant), len(t2)
+    if P > 4 or T > 4:
+        raise ValueError(f"surface_stats: at most 4 percentiles and 4 tolerances, got {P} and {T}")
+    if not all(math.isfinite(q) and 0.0 <= q <= 1.0 for q in quant):
+        raise ValueError(f"surface_stats: percentiles must lie in [0, 100], got {list(percentiles)}")
+    if not all(0 <= t < 2 ** 31 and t == v for t, v in zip(t2, tol2)):
+        raise ValueError(f"surface_stats: squared tolerances must be integers in [0, 2^31), got {list(tol2)}")
+    need = surface_stats_ws_bytes(N, H, W)
+    if ws is None:
+        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=a.device)
+    if out is None:
+        out = (torch.empty((N, 4), dtype=torch.int64, device=a.device), torch.empty((N, 2), dtype=torch.float64, device=a.device),
+               torch.empty((N, 3, P, 2), dtype=torch.int32, device=a.device), torch.empty((N, T, 2), dtype=torch.int64, device=a.device))
+    counters, sums, sel, within = out
+    for t, dt, shape in ((counters, torch.int64, (N, 4)), (sums, torch.float64, (N, 2)), (sel, torch.int32, (N, 3, P, 2)), (within, torch.int64, (N, T, 2))):
+        assert t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous() and t.device == a.device and ws.dtype == torch.uint8
+    if N == 0:                                          # (empty tensors have no address to pass; the library launches nothing for N == 0 either)
+        return counters, sums, sel, within
+    L.check(L.load().usseg_surface_stats(a.data_ptr(), b.data_ptr(), N, H, W, (C.c_double * max(P, 1))(*quant), P, (C.c_int32 * max(T, 1))(*t2), T,
+                                         counters.data_ptr(), sums.data_ptr(), sel.data_ptr() if P else None, within.data_ptr() if T else None,
+                                         ws.data_ptr(), ws.numel(), _stream()), "surface_stats")
+    return counters, sums, sel, within
+
+
 # ---- connected components (csrc/components.hip) -------------------------------------------------------------------------------------------
 COMPONENT_STAT_FIELDS = ("area", "y_min", "x_min", "y_max", "x_max", "sum_y", "sum_x", "peak_bits")
 
