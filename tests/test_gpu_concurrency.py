@@ -116,9 +116,14 @@ def test_lazy_weight_gradients_equal_inline_order(arch):
     assert ops._LAZY, "lazy weight gradients are the default"
     load = _Load()
     grads = {}
+    # the Swin encoder opens lazy_wgrads() per block behind a switch of its own (SwinTransformer._LAZY_BLOCK): off, with ops._LAZY on,
+    # every weight gradient runs in line where it is queued - the same bits again
+    from ultrasound_modeling_amd import SwinTransformer as ST
+    block0 = ST._LAZY_BLOCK
+    assert block0, "per-block lazy weight gradients are the default"
     try:
-        for lazy in (True, False, True):
-            ops._LAZY = lazy
+        for lazy, block in [(True, True), (False, True), (True, True)] + ([(True, False), (False, False)] if arch == "S" else []):
+            ops._LAZY, ST._LAZY_BLOCK = lazy, block
             for rep in range(3):
                 load.kick(4)
                 step()
@@ -127,6 +132,6 @@ def test_lazy_weight_gradients_equal_inline_order(arch):
                 assert torch.isfinite(g).all() and g.abs().sum().item() > 0
                 if "ref" not in grads:
                     grads["ref"] = g
-                assert torch.equal(g, grads["ref"]), f"lazy={lazy} repeat {rep}: {(g != grads['ref']).sum().item()} gradient entries differ"
+                assert torch.equal(g, grads["ref"]), f"lazy={lazy} block={block} repeat {rep}: {(g != grads['ref']).sum().item()} gradient entries differ"
     finally:
-        ops._LAZY = True
+        ops._LAZY, ST._LAZY_BLOCK = True, block0
