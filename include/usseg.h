@@ -1105,6 +1105,47 @@ int usseg_cone_render(const int32_t* index, int32_t Hp, int32_t Wp, int32_t gap,
                       const double* bmode, int32_t B, int32_t H, int32_t W, const double* ranges, const double* bmode_range, const uint8_t* luts,
                       uint8_t* out, usseg_stream_t stream);
 
+/* ---- ensemble prediction, uncertainty maps and calibration counters (ensemble.hip; not in the reference) -------------------------------
+ * usseg_ensemble_merge merges K member probability tensors in ONE pass: every member is read once, every output written once,
+ * (K*C + C + 2 [+ C]) * 4 bytes per pixel.  Members and outputs are fp32 [B][H][W][C] (entropy, mutual_info: [B][H][W]), 1 <= C <= 4,
+ * 1 <= K <= USSEG_ENSEMBLE_MAX.  members: a HOST array of K device pointers; they and flip_w travel BY VALUE in the kernel arguments, so a
+ * captured graph holds them.  Member k contributes to pixel (b,h,w) its value at (b,h,W-1-w) when bit k of flip_w is set (it was
+ * computed on the mirrored input).  Per pixel, members in ascending k, all fp32 without fused multiply-adds:
+ *     mean_c      = (((p_0c + p_1c) + ...) + p_(K-1)c) / (float)K                 (an IEEE division)
+ *     entropy     = -sum_c t(mean_c),   t(p) = p*logf(p) for p > 0, 0 for p <= 0, NaN for a NaN           (predictive entropy H)
+ *     EH          = -(sum_k sum_c t(p_kc)) / (float)K
+ *     mutual_info = H - EH, 0 where that is negative                               (the BALD term; a NaN stays a NaN)
+ *     variance_c  = sum_k p_kc^2 / (float)K - mean_c^2, 0 where that is negative   (variance may be NULL)
+ * Groups of four pixels as float4 for C = 3 when every base is 16-byte aligned, one pixel per lane otherwise and for the ragged tail.
+ * usseg_ensemble_image_scores: scores fp32 [B][4] = the mean entropy, the mean mutual information, the maximum mutual information (a NaN
+ * wins), and the mean entropy over the pixels whose mean_probs arg-max (first maximum; a NaN is never larger) is class C-1 - 0 when there
+ * is none; counts int32 [B] = the number of those pixels.  One workgroup per image and a fixed summation order: bitwise reproducible.
+ * B, H, W >= 1 and H*W < 2^31 for both.
+ * usseg_calibration_bins: reliability counters of probs against y_true (both fp32 [B][H][W][C], 1 <= C <= 4) in one streaming pass.
+ * cls = -1 (top label): conf = max_c p_c, a hit when the first-maximum index of p equals that of y_true.  cls = k in [0, C): conf = p_k, a
+ * hit when y_true's first-maximum index is k.  A pixel whose conf is NaN or outside [0, 1] is INVALID and only counted as such.  Otherwise
+ * bin = min(bins-1, (int)(conf*(float)bins)) in fp32, 1 <= bins <= USSEG_CALIB_MAX_BINS.  counts: int64 [bins*3 + 2], ADDED INTO (the
+ * caller zeroes it once): per bin the pixel count, the hit count and sum rintf(conf*2^24); then sum rintf(v*2^24) over the valid pixels
+ * with v = sum_c (p_c - onehot_c)^2 (the Brier sum; a v that is NaN or above C counts as C); then the invalid count.  B, H >= 0; W >= 1.
+ * Integer adds only: bitwise reproducible.
+ * All three: every argument is checked before any launch, nothing allocates and nothing synchronises with the host. */
+#define USSEG_ENSEMBLE_MAX 16
+#define USSEG_CALIB_MAX_BINS 64
+typedef struct UssegEnsembleDesc {
+  int32_t B, H, W, C;
+  int32_t K; /* members, 1..USSEG_ENSEMBLE_MAX (image_scores ignores it) */
+} UssegEnsembleDesc;
+int usseg_ensemble_merge(const UssegEnsembleDesc* d, const float* const* members, uint32_t flip_w, float* mean_probs, float* entropy,
+                         float* mutual_info, float* variance, usseg_stream_t stream);
+int usseg_ensemble_image_scores(const UssegEnsembleDesc* d, const float* mean_probs, const float* entropy, const float* mutual_info,
+                                float* scores, int32_t* counts, usseg_stream_t stream);
+typedef struct UssegCalibDesc {
+  int32_t B, H, W, C;
+  int32_t bins; /* 1..USSEG_CALIB_MAX_BINS */
+  int32_t cls;  /* -1: top label; 0..C-1: that class */
+} UssegCalibDesc;
+int usseg_calibration_bins(const UssegCalibDesc* d, const float* probs, const float* y_true, int64_t* counts, usseg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

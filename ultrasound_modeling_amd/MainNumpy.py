@@ -28,8 +28,15 @@ input_size = (256, 80)      # :12
 
 
 class Process(object):
-    def __init__(self, batch_size=16, num_classes=3, device=None, schedule=False, surface=None):
+    def __init__(self, batch_size=16, num_classes=3, device=None, schedule=False, surface=None, calibration=None):
         self.batch_size = batch_size
+        # reliability counters of ``test`` (default off): {"bins": 15, "cls": -1} (metrics.CalibrationBins' arguments)
+        self.calibration = None
+        if calibration is not None:
+            from .metrics import CalibrationBins
+            if not isinstance(calibration, dict) or set(calibration) - {"bins", "cls"}:
+                raise ValueError(f"calibration takes a dict with 'bins' and 'cls', got {calibration!r}")
+            self.calibration = CalibrationBins(calibration.get("bins", 15), calibration.get("cls", -1), device=device if device is not None else "cuda")
         # surface scores of the last class in ``test`` (default off): {"percentiles": [...], "tolerances": [...]} (metrics.surface_distances' arguments)
         self.surface = None if surface is None else surface_settings(surface)
         self.schedule = schedule            # apply the :83-88 learning-rate / weight-decay schedule (module docstring)
@@ -90,6 +97,8 @@ class Process(object):
             self.metrics.update_state(labels, class_score)                                       # :100-106
             if self.surface is not None:
                 stats.append(_surface_batch(labels, class_score, self.num_classes, self.surface))
+            if self.calibration is not None:
+                self.calibration.update(class_score, labels)
             if terminator:
                 break
             self.test_iter += 1
@@ -107,6 +116,12 @@ class Process(object):
         if self.surface is not None:
             extra = surface_summary(stats, self.surface)       # ONE read-back of the epoch's integers
             print(surface_line(extra, self.surface))
+        if self.calibration is not None:
+            from .metrics import calibration_line
+            cal = self.calibration.result()                    # ONE read-back of the epoch's counters
+            print(calibration_line(cal))
+            extra = dict(extra, ece=cal["ece"], mce=cal["mce"], brier=cal["brier"])
+            self.calibration.reset()
         self.history.append(dict(m, phase="test", epoch=epoch, loss=total_loss, **extra))
         self.metrics.reset_states()                                                              # :142-146
         return m["f1"]

@@ -44,6 +44,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .ensemble import Ensemble
 from .ops import roundup
 from .step import PredictDriver
 from .VisionTransformer import VisionTransformer
@@ -56,15 +57,28 @@ class CascadeOutput(NamedTuple):
     bleed_prob: torch.Tensor              # fp32 [B,H,W]: p2 (:239)
 
 
+class EnsembleCascadeOutput(NamedTuple):
+    probs: torch.Tensor                   # the ensemble's mean fp32 [B,H,W,3]
+    mask: Optional[torch.Tensor]          # as CascadeOutput
+    prob_map: torch.Tensor                # as CascadeOutput, of the mean probabilities
+    bleed_prob: torch.Tensor              # as CascadeOutput, of the mean probabilities
+    entropy: torch.Tensor                 # fp32 [B,H,W]: the predictive entropy of the mean (ensemble.EnsembleOutput)
+    mutual_info: torch.Tensor             # fp32 [B,H,W]: what the members disagree about
+    image_scores: torch.Tensor            # fp32 [B,4]: ensemble.EnsembleOutput.image_scores
+
+
 class Cascade(PredictDriver):
     """``Cascade(bleed_model, mask_model=None)``: the bleed model (3 classes) behind an optional brain-mask model (2 classes).
     ``mask_model=None`` is the reference's ``use_brainMask=False``: the bleed model and the maps.  Both models are Arch B segmenters
     (``VisionTransformer``, the ``TBI_TransUNet`` variant included) on one device with one input geometry.  ``predict(x)`` takes
     x [B,H,W,C] (numpy or tensor, fp32 / fp64) and returns a ``CascadeOutput``; after ``capture_predict_graph`` an input of the captured
-    layout replays one graph and the result holds that graph's static buffers (valid until the next call)."""
+    layout replays one graph and the result holds that graph's static buffers (valid until the next call).
+    ``bleed_model`` may be an ``ensemble.Ensemble`` of Arch B models: the mask model still runs once on the un-mirrored input and gates once, the
+    gated input goes through every member, the maps come from the mean probabilities, and ``predict`` returns an ``EnsembleCascadeOutput``."""
 
     def __init__(self, bleed_model, mask_model=None):
-        models = [bleed_model] + ([mask_model] if mask_model is not None else [])
+        self.ensemble = isinstance(bleed_model, Ensemble)
+        models = (list(bleed_model.models) if self.ensemble else [bleed_model]) + ([mask_model] if mask_model is not None else [])
         for m in models:
             if not isinstance(m, VisionTransformer):
                 raise ValueError(f"Cascade takes VisionTransformer models (TBI_TransUNet included), got {type(m).__name__}")
@@ -86,9 +100,10 @@ class Cascade(PredictDriver):
 
     @classmethod
     def from_checkpoints(cls, bleed_path, mask_path=None, *, img_size=(256, 80), in_channels=10, batch_size=16, use_vit=False,
-                         transunet=False):
+                         transunet=False, bleed_extra=(), flip=False):
         """Build the models and load the files ``VisionTransformer.save`` / ``visionModel.save`` wrote (MainNumpy.py:177).
-        ``transunet=True`` builds the ``TBI_TransUNet`` variant (whose ViT bottleneck is always on)."""
+        ``transunet=True`` builds the ``TBI_TransUNet`` variant (whose ViT bottleneck is always on).  ``bleed_extra`` (more bleed checkpoints)
+        or ``flip`` (left-right test-time augmentation) make the bleed model an ``Ensemble``."""
         def build(path, classes):
             if transunet:
                 from .TBI_TransUNet import VisionTransformer as TransUNet
@@ -97,7 +112,10 @@ class Cascade(PredictDriver):
                 m = VisionTransformer(batch_size, img_size, classes, in_channels=in_channels, use_vit=use_vit, seed=None)
             m.load(path)
             return m
-        return cls(build(bleed_path, 3), build(mask_path, 2) if mask_path is not None else None)
+        bleed = build(bleed_path, 3)
+        if bleed_extra or flip:
+            bleed = Ensemble([bleed] + [build(p, 3) for p in bleed_extra], flip=flip)
+        return cls(bleed, build(mask_path, 2) if mask_path is not None else None)
 
     # ------------------------------------------------------------------ PredictDriver hooks
     def _prep_x(self, x):
@@ -119,6 +137,10 @@ class Cascade(PredictDriver):
             B, H, W = pm.shape[:3]
             mask = torch.empty((B, H, W), dtype=torch.uint8, device=self.device)
             ops.cascade_gate(pm, xb, out=xb, mask=mask)                  # the mask model has read xb: it may be overwritten
+        if self.ensemble:
+            e = self.bleed_model._predict_body(xb)
+            prob_map, bleed_prob = ops.cascade_maps(e.probs)
+            return EnsembleCascadeOutput(e.probs, mask, prob_map, bleed_prob, e.entropy, e.mutual_info, e.image_scores)
         probs = self.bleed_model._predict_body(xb)
         prob_map, bleed_prob = ops.cascade_maps(probs)
         return CascadeOutput(probs, mask, prob_map, bleed_prob)
@@ -168,6 +190,90 @@ def Polar_Model(data, cascade: Cascade, names=None, batch_size=16):
     """The batched ``Polar_Model(sAll=True)`` (:163-207 / :210-255 without the plots): every image of ``data`` (``preProcess1``'s layout)
     through ``cascade``, ``batch_size`` images per replay of one captured HIP graph, the last batch padded with zero images whose rows
     are dropped.  -> ``PolarResult`` of NumPy arrays."""
+    return _polar_run(data, cascade, names, batch_size, uncertainty=False)[0]
+
+
+class PolarUncertainty(NamedTuple):
+    result: "PolarResult"
+    entropy: np.ndarray                   # fp32 [N,H,W]
+    mutual_info: np.ndarray               # fp32 [N,H,W]
+    image_scores: np.ndarray              # fp32 [N,4] (ensemble.EnsembleOutput.image_scores)
+
+
+UNCERTAINTY_COLUMNS = ("mean_entropy", "mean_mutual_info", "max_mutual_info", "mean_entropy_bleed")
+
+
+def Polar_Uncertainty(data, cascade: Cascade, names=None, batch_size=16):
+    """``Polar_Model`` for a cascade whose bleed model is an ``Ensemble``: -> ``PolarUncertainty`` = the same ``PolarResult`` (of the mean
+    probabilities) with the NumPy ``entropy``, ``mutual_info`` [N,H,W] and ``image_scores`` [N,4]."""
+    if not getattr(cascade, "ensemble", False):
+        raise ValueError("Polar_Uncertainty needs a Cascade whose bleed model is an ensemble.Ensemble")
+    result, extra, _ = _polar_run(data, cascade, names, batch_size, uncertainty=True)
+    return PolarUncertainty(result, *extra)
+
+
+def write_uncertainty_csv(path, names, image_scores):
+    """One row per image: name and the four image scores (``UNCERTAINTY_COLUMNS``).  -> the number of rows."""
+    import csv
+    image_scores = np.asarray(image_scores)
+    if image_scores.ndim != 2 or image_scores.shape[1] != 4:
+        raise ValueError(f"image_scores must be [N,4], got {image_scores.shape}")
+    names = [str(i) for i in range(len(image_scores))] if names is None else [str(n) for n in names]
+    if len(names) != len(image_scores):
+        raise ValueError(f"{len(names)} names for {len(image_scores)} images")
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(["name"] + list(UNCERTAINTY_COLUMNS))
+        for n, row in zip(names, image_scores):
+            w.writerow([n] + [repr(float(v)) for v in row])
+    return len(names)
+
+
+def calibration_scores(result_probs, labels, bins=15, cls=-1, device=None, batch_size=64):
+    """Reliability table and scores (``metrics.calibration_from_counts``' dict: per-bin ``n`` / ``accuracy`` / ``confidence``, ``ece``, ``mce``,
+    ``brier``, ``n_invalid``) of probabilities [N,H,W,C] against labels - one-hot [N,H,W,C], or a label plane [N,H,W] as ``PolarResult.label`` (class k where
+    k - 0.5 < label <= k + 0.5, clipped to the classes: ``surface_scores``' ``label > 1.5`` for the bleed class).  Counted on the device (``usseg_calibration_bins``), one read-back."""
+    from .metrics import CalibrationBins
+    probs = np.ascontiguousarray(result_probs, dtype=np.float32)
+    if probs.ndim != 4:
+        raise ValueError(f"probabilities must be [N,H,W,C], got {probs.shape}")
+    labels = np.asarray(labels)
+    C = probs.shape[-1]
+    if labels.shape == probs.shape[:3]:
+        with np.errstate(invalid="ignore"):
+            idx = np.clip(np.ceil(np.nan_to_num(labels.astype(np.float64)) - 0.5), 0, C - 1).astype(np.int64)
+        labels = np.eye(C, dtype=np.float32)[idx]
+    if labels.shape != probs.shape:
+        raise ValueError(f"labels {labels.shape} match neither {probs.shape} nor {probs.shape[:3]}")
+    labels = np.ascontiguousarray(labels, dtype=np.float32)
+    dev = torch.device(device if device is not None else "cuda")
+    cal = CalibrationBins(bins, cls, device=dev)
+    if not -1 <= int(cls) < C:
+        raise ValueError(f"cls must be -1 or a class below {C}, got {cls}")
+    for lo in range(0, probs.shape[0], batch_size):
+        cal.update(torch.from_numpy(probs[lo:lo + batch_size]).to(dev), torch.from_numpy(labels[lo:lo + batch_size]).to(dev))
+    return cal.result()
+
+
+def write_calibration_csv(path, scores):
+    """The reliability table - one row per bin: bin, lower edge, upper edge, n, accuracy, confidence - and a final row ``total`` with the
+    number of valid pixels, ECE, MCE, Brier and the invalid count.  -> the number of bin rows."""
+    import csv
+    bins = len(scores["n"])
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(["bin", "lo", "hi", "n", "accuracy", "confidence", "ece", "mce", "brier", "n_invalid"])
+        for b in range(bins):
+            w.writerow([b, repr(b / bins), repr((b + 1) / bins), int(scores["n"][b]), repr(float(scores["accuracy"][b])),
+                        repr(float(scores["confidence"][b]))] + [""] * 4)
+        w.writerow(["total", "", "", int(np.sum(scores["n"])), "", "", repr(float(scores["ece"])), repr(float(scores["mce"])),
+                    repr(float(scores["brier"])), int(scores["n_invalid"])])
+    return bins
+
+
+def _polar_run(data, cascade, names, batch_size, uncertainty, keep_probs=False):
+    """The loop of ``Polar_Model`` -> (``PolarResult``, (entropy, mutual_info, image_scores) with ``uncertainty`` else None, the probabilities
+    [N,H,W,3] with ``keep_probs`` else None)."""
     x, label, bmode = preProcess1(data, cascade.img_size)
     H, W = cascade.img_size
     shape = (batch_size, H, W, x.shape[-1])
@@ -179,6 +285,10 @@ def Polar_Model(data, cascade: Cascade, names=None, batch_size=16):
     prob_map = np.empty((N, H, W), np.float32)
     bleed_prob = np.empty((N, H, W), np.float32)
     mask = np.empty((N, H, W), np.uint8) if cascade.mask_model is not None else None
+    extra = None
+    if uncertainty:
+        extra = (np.empty((N, H, W), np.float32), np.empty((N, H, W), np.float32), np.empty((N, 4), np.float32))
+    probs = np.empty((N, H, W, 3), np.float32) if keep_probs else None
     for lo, n, xb in batches(x, batch_size):
         buf.copy_(torch.from_numpy(xb))
         out = cascade.predict(buf)
@@ -186,7 +296,13 @@ def Polar_Model(data, cascade: Cascade, names=None, batch_size=16):
         bleed_prob[lo:lo + n] = out.bleed_prob[:n].cpu().numpy()
         if mask is not None:
             mask[lo:lo + n] = out.mask[:n].cpu().numpy()
-    return PolarResult(prob_map, bleed_prob, mask, label, bmode, None if names is None else np.asarray(names))
+        if extra is not None:
+            for dst, src in zip(extra, (out.entropy, out.mutual_info, out.image_scores)):
+                dst[lo:lo + n] = src[:n].cpu().numpy()
+        if probs is not None:
+            probs[lo:lo + n] = out.probs[:n].cpu().numpy()
+    result = PolarResult(prob_map, bleed_prob, mask, label, bmode, None if names is None else np.asarray(names))
+    return result, extra, probs
 
 
 # ---------------------------------------------------------------------------------------------------------- surface scores
@@ -461,6 +577,15 @@ def main(argv=None):
                     help="drop predicted bleed components of fewer than N pixels before --lesion-csv / --surface-csv score them")
     ap.add_argument("--min-peak", type=float, default=0.0, metavar="P", help="drop predicted bleed components whose largest probability is below P (--lesion-csv; --surface-csv only together with --min-area)")
     ap.add_argument("--connectivity", type=int, default=8, choices=(4, 8), help="pixel connectivity of a component")
+    ap.add_argument("--tta", default=None, choices=("flip",), help="test-time augmentation of the bleed model: flip = average with the left-right mirror")
+    ap.add_argument("--bleed-extra", action="append", default=None, metavar="CKPT",
+                    help="one more bleed checkpoint to ensemble with --bleed (repeatable; at most 16 members with --tta)")
+    ap.add_argument("--uncertainty-csv", default=None, metavar="PATH",
+                    help="write the ensemble's image scores (mean entropy, mean / max mutual information, mean entropy over the predicted bleed), "
+                         "one row per image; needs --tta or --bleed-extra")
+    ap.add_argument("--calibration-csv", default=None, metavar="PATH",
+                    help="write the reliability table of the bleed model's (or the ensemble's mean) probabilities with ECE, MCE and the Brier score")
+    ap.add_argument("--calibration-bins", type=int, default=15, metavar="N", help="confidence bins of --calibration-csv (1..64)")
     a = ap.parse_args(argv)
     if a.batch < 1:
         ap.error("--batch must be >= 1")
@@ -476,11 +601,28 @@ def main(argv=None):
         ap.error("--surface-percentile must lie in [0, 100]")
     if not all(0.0 <= t < float("inf") for t in a.surface_tolerance or ()):
         ap.error("--surface-tolerance must be finite and >= 0")
+    ensemble = a.tta is not None or bool(a.bleed_extra)
+    if a.uncertainty_csv is not None and not ensemble:
+        ap.error("--uncertainty-csv needs an ensemble: --tta flip and / or --bleed-extra")
+    if not 1 <= a.calibration_bins <= 64:
+        ap.error("--calibration-bins must lie in 1..64")
+    if (1 + len(a.bleed_extra or ())) * (2 if a.tta else 1) > 16:
+        ap.error("at most 16 ensemble members (checkpoints x views)")
     data = np.load(a.data)
     names = np.load(a.paths)
-    cascade = Cascade.from_checkpoints(a.bleed, a.mask, batch_size=a.batch, use_vit=a.use_vit, transunet=a.transunet)
+    cascade = Cascade.from_checkpoints(a.bleed, a.mask, batch_size=a.batch, use_vit=a.use_vit, transunet=a.transunet,
+                                       bleed_extra=tuple(a.bleed_extra or ()), flip=a.tta == "flip")
     geometry = ConeGeometry.from_dir(a.axis_dir, px_per_unit=a.px_per_unit, device=cascade.device)
-    result = Polar_Model(data, cascade, names=names, batch_size=a.batch)
+    if ensemble or a.calibration_csv is not None:
+        result, extra, probs = _polar_run(data, cascade, names, a.batch, uncertainty=ensemble, keep_probs=a.calibration_csv is not None)
+        if a.uncertainty_csv is not None:
+            rows = write_uncertainty_csv(a.uncertainty_csv, _names(result), extra[2])
+            print(f"wrote {rows} uncertainty rows to {a.uncertainty_csv}")
+        if a.calibration_csv is not None:
+            rows = write_calibration_csv(a.calibration_csv, calibration_scores(probs, result.label, bins=a.calibration_bins, device=cascade.device))
+            print(f"wrote {rows} reliability bins to {a.calibration_csv}")
+    else:
+        result = Polar_Model(data, cascade, names=names, batch_size=a.batch)
     if a.surface_csv is not None:
         cleaned = None
         if a.min_area is not None:

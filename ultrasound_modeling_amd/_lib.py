@@ -132,6 +132,18 @@ class SegCountDesc(C.Structure):
 
 SEG_COUNTS = 23     # USSEG_SEG_COUNTS
 
+
+class EnsembleDesc(C.Structure):
+    _fields_ = [("B", c_i32), ("H", c_i32), ("W", c_i32), ("C", c_i32), ("K", c_i32)]
+
+
+class CalibDesc(C.Structure):
+    _fields_ = [("B", c_i32), ("H", c_i32), ("W", c_i32), ("C", c_i32), ("bins", c_i32), ("cls", c_i32)]
+
+
+ENSEMBLE_MAX = 16       # USSEG_ENSEMBLE_MAX
+CALIB_MAX_BINS = 64     # USSEG_CALIB_MAX_BINS
+
 ACT_NONE, ACT_LRELU, ACT_RELU, ACT_ELU, ACT_GELU = 0, 1, 2, 3, 4
 OUT_F32, ACCUMULATE = 1, 2
 
@@ -300,6 +312,9 @@ _PROTOS = {
     "usseg_cone_range": (C.c_int, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "usseg_cone_render": (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, P(C.c_double), c_vp, c_vp, c_vp,
                                     c_vp]),
+    "usseg_ensemble_merge": (C.c_int, [P(EnsembleDesc), P(c_vp), C.c_uint32, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "usseg_ensemble_image_scores": (C.c_int, [P(EnsembleDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "usseg_calibration_bins": (C.c_int, [P(CalibDesc), c_vp, c_vp, c_vp, c_vp]),
 }
 EXPORTED_SYMBOLS = tuple(_PROTOS)
 

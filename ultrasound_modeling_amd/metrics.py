@@ -24,7 +24,7 @@ import torch
 from ._lib import SEG_COUNTS
 from .ops import seg_counts  # noqa: F401  (the kernel wrapper; re-exported here)
 
-__all__ = ["SEG_COUNTS", "SegMetrics", "components", "counts_to_metrics", "dice_per_class", "dice_line", "lesion_scores", "lesion_scores_from_tables",
+__all__ = ["CalibrationBins", "SEG_COUNTS", "SegMetrics", "calibration_from_counts", "calibration_line", "components", "counts_to_metrics", "dice_per_class", "dice_line", "lesion_scores", "lesion_scores_from_tables",
            "seg_counts"]
 
 
@@ -297,3 +297,59 @@ class SegMetrics:
 
     def reset_states(self) -> None:
         self.counts.zero_()
+
+
+# ---------------------------------------------------------------------------------------------------------- calibration
+def calibration_from_counts(counts) -> Dict[str, object]:
+    """Counter block of ``usseg_calibration_bins`` (int64 [bins*3 + 2], CPU or device) -> the reliability table and its scores, in fp64:
+    ``n``, ``accuracy``, ``confidence`` per bin (0 in an empty bin), ``ece`` = sum_b n_b/N * |acc_b - conf_b| (the expected calibration error of
+    Guo et al., ICML 2017), ``mce`` = the largest gap over the non-empty bins, ``brier`` = the mean over the valid pixels of
+    sum_c (p_c - onehot_c)^2, and ``n_invalid``.  The three scores are NaN when no pixel was valid."""
+    c = np.asarray(torch.as_tensor(counts).reshape(-1).cpu().numpy(), np.int64)
+    if c.size < 5 or (c.size - 2) % 3:
+        raise ValueError(f"a calibration counter block holds bins*3 + 2 integers, got {c.size}")
+    bins = (c.size - 2) // 3
+    t = c[:bins * 3].reshape(bins, 3).astype(np.float64)
+    n = t[:, 0]
+    N = float(n.sum())
+    full = n > 0
+    acc = np.divide(t[:, 1], n, out=np.zeros(bins), where=full)
+    conf = np.divide(t[:, 2] / 2.0 ** 24, n, out=np.zeros(bins), where=full)
+    gap = np.abs(acc - conf)
+    out = dict(n=c[:bins * 3].reshape(bins, 3)[:, 0].copy(), accuracy=acc, confidence=conf, n_invalid=int(c[bins * 3 + 1]))
+    if N > 0:
+        out.update(ece=float((n / N * gap).sum()), mce=float(gap[full].max()), brier=float(c[bins * 3]) / 2.0 ** 24 / N)
+    else:
+        out.update(ece=float("nan"), mce=float("nan"), brier=float("nan"))
+    return out
+
+
+class CalibrationBins:
+    """Reliability counters that stay on the device, after ``SegMetrics``: ``update`` is one launch (``ops.calibration_bins``), ``result`` the one
+    copy to the host, ``reset`` one fill.  ``cls`` -1 is top-label calibration, k the class-wise calibration of class k."""
+
+    def __init__(self, bins: int = 15, cls: int = -1, device=None):
+        from ._lib import CALIB_MAX_BINS
+        bins, cls = int(bins), int(cls)
+        if not 1 <= bins <= CALIB_MAX_BINS:
+            raise ValueError(f"bins must be 1..{CALIB_MAX_BINS}, got {bins}")
+        if not -1 <= cls <= 3:
+            raise ValueError(f"cls must be -1 (top label) or a class 0..3, got {cls}")
+        self.bins, self.cls = bins, cls
+        self.counts = torch.zeros(bins * 3 + 2, dtype=torch.int64, device=device if device is not None else "cuda")
+
+    def update(self, probs: torch.Tensor, y: torch.Tensor) -> None:
+        """Add one batch, fp32 [B,H,W,C] on the counters' device; enqueued on the current stream (no host synchronisation)."""
+        from .ops import calibration_bins
+        calibration_bins(probs, y, self.counts, self.bins, self.cls)
+
+    def result(self) -> Dict[str, object]:
+        return calibration_from_counts(self.counts.cpu())
+
+    def reset(self) -> None:
+        self.counts.zero_()
+
+
+def calibration_line(r) -> str:
+    """The drivers' one line per epoch for ``calibration_from_counts``' dict."""
+    return "calibration: ECE = {:.5f}, MCE = {:.5f}, Brier = {:.5f}, invalid = {}".format(r["ece"], r["mce"], r["brier"], r["n_invalid"])

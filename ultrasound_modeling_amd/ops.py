@@ -634,6 +634,87 @@ def cascade_maps(probs, prob_map=None, bleed_prob=None):
     return prob_map, bleed_prob
 
 
+# ------------------------------------------------------------------------------------------------ ensembles and calibration (ensemble.hip)
+def _probs4(t, what):
+    if not (torch.is_tensor(t) and t.dim() == 4 and t.dtype == torch.float32 and t.is_contiguous()):
+        raise ValueError(f"{what}: expected a contiguous fp32 tensor [B,H,W,C], got {getattr(t, 'dtype', type(t).__name__)} "
+                         f"{tuple(getattr(t, 'shape', ()))}")
+    if not t.is_cuda:
+        raise RuntimeError(f"{what}: device tensors only (there is no CPU fallback)")
+    return t
+
+
+def _out_like(t, shape, dtype, ref, what):
+    if t is None:
+        return torch.empty(shape, dtype=dtype, device=ref.device)
+    if not (t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == tuple(shape) and t.device == ref.device):
+        raise ValueError(f"{what}: expected a contiguous {dtype} tensor {tuple(shape)} on {ref.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    return t
+
+
+def ensemble_merge(members, flip_w=0, *, variance=True, mean_probs=None, entropy=None, mutual_info=None, variance_out=None):
+    """Merge K member probability tensors (fp32 [B,H,W,C], one device, 1 <= K <= 16) in one launch (usseg_ensemble_merge; include/usseg.h):
+    the mean, the predictive entropy, the mutual information and - with ``variance`` - the per-class variance.  Bit k of ``flip_w``: member k was
+    computed on the left-right mirrored input and is un-mirrored as it is read.  -> (mean_probs, entropy, mutual_info, variance or None)."""
+    members = list(members)
+    if not 1 <= len(members) <= L.ENSEMBLE_MAX:
+        raise ValueError(f"ensemble_merge: 1..{L.ENSEMBLE_MAX} members, got {len(members)}")
+    first = _probs4(members[0], "ensemble_merge")
+    for m in members[1:]:
+        if _probs4(m, "ensemble_merge").shape != first.shape or m.device != first.device:
+            raise ValueError(f"ensemble_merge: members differ: {tuple(m.shape)} on {m.device}, {tuple(first.shape)} on {first.device}")
+    flip_w = int(flip_w)
+    if flip_w < 0 or flip_w >> len(members):
+        raise ValueError(f"ensemble_merge: flip_w {flip_w:#x} has bits outside the {len(members)} members")
+    B, H, W, C_ = first.shape
+    mean_probs = _out_like(mean_probs, first.shape, torch.float32, first, "ensemble_merge mean_probs")
+    entropy = _out_like(entropy, (B, H, W), torch.float32, first, "ensemble_merge entropy")
+    mutual_info = _out_like(mutual_info, (B, H, W), torch.float32, first, "ensemble_merge mutual_info")
+    var = _out_like(variance_out, first.shape, torch.float32, first, "ensemble_merge variance") if variance or variance_out is not None else None
+    d = L.EnsembleDesc(B, H, W, C_, len(members))
+    ptrs = (C.c_void_p * len(members))(*[m.data_ptr() for m in members])
+    L.check(L.load().usseg_ensemble_merge(C.byref(d), ptrs, flip_w, mean_probs.data_ptr(), entropy.data_ptr(), mutual_info.data_ptr(), _ptr(var),
+                                          _stream()), "ensemble_merge")
+    return mean_probs, entropy, mutual_info, var
+
+
+def ensemble_image_scores(mean_probs, entropy, mutual_info, scores=None, counts=None):
+    """Per image: the mean entropy, the mean and the maximum mutual information, and the mean entropy over the pixels predicted as the last
+    class (usseg_ensemble_image_scores).  -> (scores fp32 [B,4], counts int32 [B]: those pixels).  One launch, bitwise reproducible."""
+    _probs4(mean_probs, "ensemble_image_scores")
+    B, H, W, C_ = mean_probs.shape
+    for t, n in ((entropy, "entropy"), (mutual_info, "mutual_info")):
+        if not (torch.is_tensor(t) and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (B, H, W) and t.device == mean_probs.device):
+            raise ValueError(f"ensemble_image_scores: {n} must be a contiguous fp32 [B,H,W] tensor beside mean_probs {tuple(mean_probs.shape)}")
+    scores = _out_like(scores, (B, 4), torch.float32, mean_probs, "ensemble_image_scores scores")
+    counts = _out_like(counts, (B,), torch.int32, mean_probs, "ensemble_image_scores counts")
+    d = L.EnsembleDesc(B, H, W, C_, 1)
+    L.check(L.load().usseg_ensemble_image_scores(C.byref(d), mean_probs.data_ptr(), entropy.data_ptr(), mutual_info.data_ptr(), scores.data_ptr(),
+                                                 counts.data_ptr(), _stream()), "ensemble_image_scores")
+    return scores, counts
+
+
+def calibration_bins(probs, y_true, counts, bins=15, cls=-1):
+    """counts += the reliability counters of one batch (usseg_calibration_bins): per confidence bin the pixels, the hits and the sum of
+    rint(conf * 2^24), then the Brier sum in the same units and the invalid pixels.  probs, y_true: contiguous fp32 [B,H,W,C] on the device;
+    ``counts``: int64 [bins*3 + 2] there, zeroed by the caller.  ``cls`` -1: top-label calibration, k: class k.  One launch, no host sync."""
+    _probs4(probs, "calibration_bins")
+    if _probs4(y_true, "calibration_bins").shape != probs.shape or y_true.device != probs.device:
+        raise ValueError(f"calibration_bins: probs {tuple(probs.shape)} and y_true {tuple(y_true.shape)} differ")
+    bins, cls = int(bins), int(cls)
+    if not 1 <= bins <= L.CALIB_MAX_BINS:
+        raise ValueError(f"calibration_bins: 1..{L.CALIB_MAX_BINS} bins, got {bins}")
+    B, H, W, C_ = probs.shape
+    if not -1 <= cls < C_:
+        raise ValueError(f"calibration_bins: cls must be -1 or a class below {C_}, got {cls}")
+    if not (torch.is_tensor(counts) and counts.dtype == torch.int64 and counts.is_contiguous() and counts.numel() == bins * 3 + 2
+            and counts.device == probs.device):
+        raise ValueError(f"calibration_bins: counts must be a contiguous int64 tensor of {bins * 3 + 2} elements on {probs.device}")
+    d = L.CalibDesc(B, H, W, C_, bins, cls)
+    L.check(L.load().usseg_calibration_bins(C.byref(d), probs.data_ptr(), y_true.data_ptr(), counts.data_ptr(), _stream()), "calibration_bins")
+    return counts
+
+
 def norm_act_bwd_res(x, dy, C_logical, gamma, beta, dres, dx, dgamma, dbeta, eps, dbias=None):
     """Plain LayerNormalization backward + the residual branch of a pre-norm block: dx = bf16(bf16(LN'(dy)) + dres) in one pass;
     ``dbias`` += the column sums of the stored dx."""
