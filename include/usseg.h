@@ -1146,6 +1146,49 @@ typedef struct UssegCalibDesc {
 } UssegCalibDesc;
 int usseg_calibration_bins(const UssegCalibDesc* d, const float* probs, const float* y_true, int64_t* counts, usseg_stream_t stream);
 
+/* ---- threshold sweeps and temperature scaling (operating_point.hip; not in the reference) ---------------------------------------------
+ * probs, y_true and out are fp32 [B][H][W][C], 1 <= C <= 4, B, H >= 0, W >= 1 and M = B*H*W <= 2^31; M = 0 returns USSEG_OK without a launch.
+ * The label of a pixel is the first-maximum class of y_true (a NaN is never larger), as in usseg_calibration_bins.
+ * usseg_score_sweep: per score bin the negatives and the positives of class cls (0..C-1) in one streaming pass.  The score is
+ * s = probs[p][cls]; a pixel is POSITIVE when its label is cls.  A pixel whose s is NaN or outside [0, 1] is INVALID and only counted as such
+ * (the test comes before any index is formed).  Otherwise bin = min(bins-1, (int)(s*(float)bins)) in fp32, clamped at 0 as well; bins is a
+ * power of two, 2 <= bins <= USSEG_SWEEP_MAX_BINS, so s*bins is exact and "bin >= k" is "s >= k/bins" for k < bins (s = 1 lies in the last bin).  counts: int64 [2*bins + 1], ADDED
+ * INTO (the caller zeroes it once): counts[2b] the negatives of bin b, counts[2b+1] its positives, counts[2*bins] the invalid pixels.  Each
+ * workgroup counts into two histograms of 32-bit LDS counters (32 KB, sized by the constant), a wave whose lanes all hold one (bin,
+ * positive) key adds its population count once, and the workgroup then issues one 64-bit atomic per non-zero counter.  Integer adds only:
+ * bitwise reproducible and independent of the grid.
+ * usseg_temperature_nll: the summed negative log-likelihood of n_beta candidate inverse temperatures, 1 <= n_beta <= USSEG_TEMP_MAX_BETAS,
+ * every pixel read once for all of them.  betas: a HOST array, every entry finite with 0 < beta <= 16; it travels BY VALUE in the kernel
+ * arguments, so a captured graph holds it.  Per pixel, all fp32 without fused multiply-adds, the accurate logf / expf, classes ascending:
+ *     z_c   = logf(p_c + 1e-7f)                                              (the CCE's epsilon)
+ *     m     = max_c beta_j*z_c
+ *     nll_j = (m + logf(sum_c expf(beta_j*z_c - m))) - beta_j*z_y,           y the pixel's label
+ * A pixel with any p_c that is NaN or outside [0, 1] is INVALID and contributes nothing.  counts: int64 [n_beta + 2], ADDED INTO:
+ * counts[j] += (int64)rintf(min(max(nll_j, 0), USSEG_TEMP_NLL_CAP) * 2^20), counts[n_beta] the valid and counts[n_beta+1] the invalid
+ * pixels.  No overflow: 2^10 (the cap) * 2^20 (the unit) * 2^31 (pixels per call) = 2^61 < 2^63; a caller that accumulates calls keeps
+ * their pixel total below 2^33.  64-bit sums per lane, one LDS tree per workgroup, one 64-bit atomic per counter: bitwise reproducible.
+ * usseg_apply_temperature: out_c = expf(beta*z_c - m) / sum_c expf(beta*z_c - m) with z and m as above and an IEEE division (n_beta is
+ * ignored).  beta_dev: a DEVICE float, read by the kernel on every launch - a captured graph follows it; beta == 1 is NOT special-cased.
+ * A pixel with a NaN z_c (a NaN p_c, or one below -1e-7) is NaN in all its classes.  out may alias probs.  Groups of four pixels as float4 for
+ * C = 3 when both bases are 16-byte aligned, one pixel per lane otherwise and for the ragged tail.
+ * All three: every argument is checked before any launch, nothing allocates and nothing synchronises with the host. */
+#define USSEG_SWEEP_MAX_BINS 4096
+#define USSEG_TEMP_MAX_BETAS 16
+#define USSEG_TEMP_NLL_CAP 1024
+typedef struct UssegSweepDesc {
+  int32_t B, H, W, C;
+  int32_t bins; /* a power of two, 2..USSEG_SWEEP_MAX_BINS */
+  int32_t cls;  /* 0..C-1: the class whose score is swept */
+} UssegSweepDesc;
+int usseg_score_sweep(const UssegSweepDesc* d, const float* probs, const float* y_true, int64_t* counts, usseg_stream_t stream);
+typedef struct UssegTempDesc {
+  int32_t B, H, W, C;
+  int32_t n_beta; /* candidates, 1..USSEG_TEMP_MAX_BETAS (apply_temperature ignores it) */
+} UssegTempDesc;
+int usseg_temperature_nll(const UssegTempDesc* d, const float* probs, const float* y_true, const float* betas, int64_t* counts,
+                          usseg_stream_t stream);
+int usseg_apply_temperature(const UssegTempDesc* d, const float* probs, const float* beta_dev, float* out, usseg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,210 @@
+"""Times the operating-point kernels (csrc/operating_point.hip) at the evaluator's shape, everything replayed from HIP graphs as
+tools/time_ensemble.py does: `reps` launches per graph, `rounds` graphs, the median (min - max) beside the bytes each launch must move.
+
+  * ``score_sweep`` at bins = 1024 on uniform scores and on bleed-like scores (at least 95 % of the pixels in bin 0), each WITH the
+    wave-aggregated LDS add (the product's build) and WITHOUT it.  The form without is a second build of the same source with
+    -DUSSEG_SWEEP_AGGREGATE=0 that only this tool makes and loads (tools/build/libusseg_sweep_plain.so; ``--build-only`` makes it where there is
+    a compiler and no GPU); the two forms alternate inside every round, and their counters are compared before anything is timed;
+  * ``temperature_nll`` at 16 candidates, ``apply_temperature`` (out of place and in place);
+  * the yardstick: ``calibration_bins`` at 15 bins, which reads the same bytes with the same structure, in the same job.
+
+``--probe`` measures instead the error of the logf and expf this source is compiled with (the same second build, -DUSSEG_SWEEP_TOOL_PROBE)
+against fp64, over the arguments tests/test_gpu_operating_point.py feeds them: the two constants of its NLL bound.
+
+usage: python tools/time_sweep.py [--rounds N] [--reps R] [--replays P] [--json PATH] [--build-only] [--probe] [B H W]"""
+import argparse
+import ctypes as C
+import json
+import os
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PLAIN = os.path.join(ROOT, "tools", "build", "libusseg_sweep_plain.so")
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--rounds", type=int, default=7)
+ap.add_argument("--reps", type=int, default=50)
+ap.add_argument("--replays", type=int, default=10)
+ap.add_argument("--bins", type=int, default=1024)
+ap.add_argument("--json", default=os.path.join(ROOT, "profiles", "sweep_time.json"))
+ap.add_argument("--build-only", action="store_true", help="compile the tool's second build of operating_point.hip and stop")
+ap.add_argument("--probe", action="store_true", help="measure the device's logf / expf against fp64 and stop")
+ap.add_argument("shape", nargs="*", type=int, default=[16, 256, 80])
+a = ap.parse_args()
+
+
+def build_plain():
+    """hipcc operating_point.hip with the two tool switches -> tools/build/libusseg_sweep_plain.so, the product's flags otherwise.  Its
+    references to the runtime (error text, launch check) resolve against libusseg_hip.so, loaded first with RTLD_GLOBAL."""
+    src = os.path.join(ROOT, "ultrasound_modeling_amd", "csrc", "operating_point.hip")
+    if os.path.exists(PLAIN) and os.path.getmtime(PLAIN) >= os.path.getmtime(src):
+        return
+    os.makedirs(os.path.dirname(PLAIN), exist_ok=True)
+    cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "-O3", "-std=c++17", "-fPIC", "-shared", "--offload-arch=gfx950", "-Wall", "-Wno-unused-function",
+           "-I" + os.path.join(ROOT, "include"), "-fno-slp-vectorize", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops",
+           "-DUSSEG_SWEEP_AGGREGATE=0", "-DUSSEG_SWEEP_TOOL_PROBE", src, "-o", PLAIN]
+    print(" ".join(cmd), flush=True)
+    subprocess.run(cmd, check=True)
+
+
+build_plain()
+if a.build_only:
+    sys.exit(0)
+
+import numpy as np                                                               # noqa: E402
+import torch                                                                     # noqa: E402
+
+sys.path.insert(0, ROOT)
+from ultrasound_modeling_amd import _lib as L, ops                               # noqa: E402
+
+if not torch.cuda.is_available():
+    sys.exit("time_sweep: needs a GPU (a timing on the host says nothing)")
+L.load()
+C.CDLL(L.LIB_PATH, mode=C.RTLD_GLOBAL)
+plain = C.CDLL(PLAIN)
+plain.usseg_score_sweep.restype = C.c_int
+plain.usseg_score_sweep.argtypes = [C.POINTER(L.SweepDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+plain.usseg_tool_logf_expf.restype = C.c_int
+plain.usseg_tool_logf_expf.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+
+
+def ulps(got, ref):
+    """|got - ref| in units of the spacing of fp32 at ref, the largest over the finite, normal references."""
+    got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
+    ok = np.isfinite(ref) & (np.abs(ref) >= 2.0 ** -126)
+    sp = np.spacing(np.abs(ref[ok]).astype(np.float32)).astype(np.float64)
+    return float((np.abs(got[ok] - ref[ok]) / sp).max())
+
+
+def probe():
+    sys.path[:0] = [os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle")]
+    import test_gpu_operating_point as T                                         # its inputs, its betas
+    logs, exps = [], []
+    for (B, H, W, C_, _) in T.SHAPES:
+        p = T._case(B, H, W, C_)[0].reshape(-1, C_)
+        with np.errstate(invalid="ignore"):
+            p = p[((p >= 0) & (p <= 1)).all(-1)]
+        q = (p + np.float32(1e-7)).astype(np.float32)
+        logs.append(q.ravel())
+        z = np.log(q.astype(np.float64)).astype(np.float32)
+        for beta in T.BETAS16 + [16.0, 0.5, 2.5]:
+            t = (np.float32(beta) * z).astype(np.float32)
+            d = (t - t.max(-1, keepdims=True)).astype(np.float32)
+            exps.append(d.ravel())
+            s = np.exp(d.astype(np.float64)).sum(-1).astype(np.float32)
+            logs.append(s)
+    out = {}
+    for name, xs, f in (("logf", np.concatenate(logs), np.log), ("expf", np.concatenate(exps), np.exp)):
+        xs = np.unique(xs)
+        x = torch.from_numpy(xs).cuda()
+        lg, ex = torch.empty_like(x), torch.empty_like(x)
+        L.check(plain.usseg_tool_logf_expf(x.data_ptr(), x.numel(), lg.data_ptr(), ex.data_ptr(), ops._stream()), "tool_logf_expf")
+        torch.cuda.synchronize()
+        got = (lg if name == "logf" else ex).cpu().numpy()
+        with np.errstate(divide="ignore"):
+            out[name] = {"arguments": int(xs.size), "min": float(xs.min()), "max": float(xs.max()), "max_ulp": round(ulps(got, f(xs.astype(np.float64))), 4)}
+        print(f"  {name}: {xs.size} distinct arguments in [{xs.min():.4g}, {xs.max():.4g}]: largest error {out[name]['max_ulp']:.4f} ulp", flush=True)
+    return out
+
+
+if a.probe:
+    res = probe()
+    path = os.path.join(os.path.dirname(a.json), "sweep_ulp.json")
+    json.dump(res, open(path, "w"), indent=1)
+    print("wrote", path)
+    sys.exit(0)
+
+B, H, W = a.shape
+C_ = 3
+M = B * H * W
+bins = a.bins
+g = torch.Generator().manual_seed(0)
+out = {"shape": [B, H, W, C_], "bins": bins, "rounds": a.rounds, "launches_per_round": a.reps * a.replays, "launch_us": {}}
+
+
+def spread(ts):
+    ts = sorted(ts)
+    return {"min": round(ts[0], 4), "median": round(ts[len(ts) // 2], 4), "max": round(ts[-1], 4)}
+
+
+def graph_of(fn):
+    for _ in range(2):
+        fn()
+    torch.cuda.synchronize()
+    gr = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(gr):
+        for _ in range(a.reps):
+            fn()
+    gr.replay()
+    torch.cuda.synchronize()
+    return gr
+
+
+def t(gr):
+    """`replays` replays of one graph of `reps` launches: microseconds per launch."""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(a.replays):
+        gr.replay()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / (a.replays * a.reps) * 1e3
+
+
+def rows(named, nbytes):
+    """Time the named launches alternating inside every round."""
+    graphs = {n: graph_of(fn) for n, fn in named.items()}
+    ts = {n: [] for n in named}
+    for _ in range(a.rounds):
+        for n, gr in graphs.items():
+            ts[n].append(t(gr))
+    for n in named:
+        s = spread(ts[n])
+        out["launch_us"][n] = dict(s, MB=round(nbytes / 1e6, 2), TBps=round(nbytes / s["median"] / 1e6, 3))
+        print(f"  {n:44s} {s['median']:8.2f} us median ({s['min']:.2f} - {s['max']:.2f})   {nbytes / 1e6:6.2f} MB -> {nbytes / s['median'] / 1e6:5.2f} TB/s",
+              flush=True)
+
+
+def sweep_plain(p, y, counts):
+    d = L.SweepDesc(B, H, W, C_, bins, C_ - 1)
+    L.check(plain.usseg_score_sweep(C.byref(d), p.data_ptr(), y.data_ptr(), counts.data_ptr(), ops._stream()), "score_sweep (plain build)")
+
+
+print(f"the launches at {B} x {H} x {W} x {C_} ({M} pixels), {a.rounds} rounds of {a.replays} replays of {a.reps} launches, alternating:")
+uniform = torch.softmax(2 * torch.randn(B, H, W, C_, generator=g), -1).cuda()
+z = 2 * torch.randn(B, H, W, C_, generator=g)
+z[..., 2] -= 14.0                                                                # the bleed class: far below 1/1024 ...
+lesion = torch.rand(B, H, W, generator=g) < 0.03
+z[..., 2][lesion] += 18.0                                                        # ... but for 3 % of the pixels
+bleed = torch.softmax(z, -1).cuda()
+y = torch.nn.functional.one_hot(torch.where(lesion, 2, torch.randint(0, 2, (B, H, W), generator=g)), C_).float().cuda()
+share = float((bleed[..., 2] < 1.0 / bins).float().mean())
+out["bleed_like_share_in_bin_0"] = round(share, 4)
+assert share >= 0.95, share
+print(f"  bleed-like scores: {100 * share:.1f} % of the pixels in bin 0")
+for name, p in (("uniform", uniform), ("bleed-like", bleed)):                    # the two builds count the same integers
+    c0, c1 = (torch.zeros(2 * bins + 1, dtype=torch.int64).cuda() for _ in range(2))
+    ops.score_sweep(p, y, c0, bins, -1)
+    sweep_plain(p, y, c1)
+    torch.cuda.synchronize()
+    assert torch.equal(c0, c1) and int(c0.sum()) == M, name
+cs, cp = (torch.zeros(2 * bins + 1, dtype=torch.int64).cuda() for _ in range(2))
+cal = torch.zeros(15 * 3 + 2, dtype=torch.int64).cuda()
+two = 2 * C_ * 4 * M
+rows({"calibration_bins, 15 bins, top label (yardstick)": lambda: ops.calibration_bins(uniform, y, cal, 15, -1),
+      "score_sweep uniform, wave-aggregated": lambda: ops.score_sweep(uniform, y, cs, bins, -1),
+      "score_sweep uniform, plain": lambda: sweep_plain(uniform, y, cp),
+      "score_sweep bleed-like, wave-aggregated": lambda: ops.score_sweep(bleed, y, cs, bins, -1),
+      "score_sweep bleed-like, plain": lambda: sweep_plain(bleed, y, cp)}, two)
+betas = [float(np.float32(0.125 * 64.0 ** (i / 15))) for i in range(16)]
+nll, nll1 = torch.zeros(18, dtype=torch.int64).cuda(), torch.zeros(3, dtype=torch.int64).cuda()
+beta = torch.full((1,), 0.75).cuda()
+dst, inplace = torch.empty_like(uniform), uniform.clone()
+rows({"temperature_nll, 16 betas": lambda: ops.temperature_nll(uniform, y, betas, nll),
+      "temperature_nll, 1 beta": lambda: ops.temperature_nll(uniform, y, betas[:1], nll1)}, two)
+rows({"apply_temperature": lambda: ops.apply_temperature(uniform, beta, out=dst),
+      "apply_temperature, in place": lambda: ops.apply_temperature(inplace, beta, out=inplace)}, two)
+os.makedirs(os.path.dirname(a.json), exist_ok=True)
+json.dump(out, open(a.json, "w"), indent=1)
+print("wrote", a.json)

@@ -28,8 +28,15 @@ input_size = (256, 80)      # :12
 
 
 class Process(object):
-    def __init__(self, batch_size=16, num_classes=3, device=None, schedule=False, surface=None, calibration=None):
+    def __init__(self, batch_size=16, num_classes=3, device=None, schedule=False, surface=None, calibration=None, sweep=None):
         self.batch_size = batch_size
+        # threshold sweep of ``test`` (default off): {"bins": 1024, "cls": -1} (metrics.SweepCounts' arguments)
+        self.sweep = None
+        if sweep is not None:
+            from .metrics import SweepCounts
+            if not isinstance(sweep, dict) or set(sweep) - {"bins", "cls"}:
+                raise ValueError(f"sweep takes a dict with 'bins' and 'cls', got {sweep!r}")
+            self.sweep = SweepCounts(sweep.get("bins", 1024), sweep.get("cls", -1), device=device if device is not None else "cuda")
         # reliability counters of ``test`` (default off): {"bins": 15, "cls": -1} (metrics.CalibrationBins' arguments)
         self.calibration = None
         if calibration is not None:
@@ -99,6 +106,8 @@ class Process(object):
                 stats.append(_surface_batch(labels, class_score, self.num_classes, self.surface))
             if self.calibration is not None:
                 self.calibration.update(class_score, labels)
+            if self.sweep is not None:
+                self.sweep.update(class_score, labels)
             if terminator:
                 break
             self.test_iter += 1
@@ -122,6 +131,13 @@ class Process(object):
             print(calibration_line(cal))
             extra = dict(extra, ece=cal["ece"], mce=cal["mce"], brier=cal["brier"])
             self.calibration.reset()
+        if self.sweep is not None:
+            from .metrics import sweep_line
+            sw = self.sweep.result()                           # ONE read-back of the epoch's counters
+            print(sweep_line(sw))
+            extra = dict(extra, auc=sw["auc"], average_precision=sw["average_precision"], best_dice=sw["best_dice"][2],
+                         best_dice_threshold=sw["best_dice"][1])
+            self.sweep.reset()
         self.history.append(dict(m, phase="test", epoch=epoch, loss=total_loss, **extra))
         self.metrics.reset_states()                                                              # :142-146
         return m["f1"]

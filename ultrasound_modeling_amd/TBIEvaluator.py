@@ -74,9 +74,14 @@ class Cascade(PredictDriver):
     x [B,H,W,C] (numpy or tensor, fp32 / fp64) and returns a ``CascadeOutput``; after ``capture_predict_graph`` an input of the captured
     layout replays one graph and the result holds that graph's static buffers (valid until the next call).
     ``bleed_model`` may be an ``ensemble.Ensemble`` of Arch B models: the mask model still runs once on the un-mirrored input and gates once, the
-    gated input goes through every member, the maps come from the mean probabilities, and ``predict`` returns an ``EnsembleCascadeOutput``."""
+    gated input goes through every member, the maps come from the mean probabilities, and ``predict`` returns an ``EnsembleCascadeOutput``.
+    ``temperature=T`` (``metrics.fit_temperature``'s, for one) calibrates the bleed model's probabilities in place before the maps:
+    softmax(log(probs + 1e-7) / T), one more launch (``ops.apply_temperature``).  ``probs``, ``prob_map`` and ``bleed_prob`` are then all
+    calibrated; one scalar cannot change the arg-max.  For an ``Ensemble`` it is the temperature of the MEAN probabilities, not one per member,
+    and ``entropy`` / ``mutual_info`` / ``image_scores`` stay those of the members' un-scaled outputs.  1/T lives in a device float the kernel
+    reads, so ``set_temperature`` reaches a captured predict graph without a recapture.  ``temperature=None``: no launch is added."""
 
-    def __init__(self, bleed_model, mask_model=None):
+    def __init__(self, bleed_model, mask_model=None, temperature=None):
         self.ensemble = isinstance(bleed_model, Ensemble)
         models = (list(bleed_model.models) if self.ensemble else [bleed_model]) + ([mask_model] if mask_model is not None else [])
         for m in models:
@@ -97,13 +102,30 @@ class Cascade(PredictDriver):
         self.device = bleed_model.device
         self.img_size = tuple(bleed_model.img_size)
         self.in_channels = bleed_model.input_shape[-1]
+        self._beta = None                   # fp32 [1] on the device: 1 / temperature; None until a temperature is set (no launch is added)
+        if temperature is not None:
+            self.set_temperature(temperature)
+
+    @property
+    def temperature(self):
+        """The temperature the next ``predict`` applies, read from the device (synchronises); None when none was ever set."""
+        return None if self._beta is None else 1.0 / float(self._beta.item())
+
+    def set_temperature(self, T):
+        """From the next ``predict`` on, eager or replayed: the kernel reads the device float, so a captured graph needs no recapture - unless
+        it was captured before the FIRST temperature was set (it holds no temperature launch), which drops the capture."""
+        beta = _beta_of(T)
+        if self._beta is None:
+            self._beta = torch.empty(1, dtype=torch.float32, device=self.device)
+            self._pgraph = None             # a graph captured without the launch cannot follow the value
+        self._beta.fill_(beta)
 
     @classmethod
     def from_checkpoints(cls, bleed_path, mask_path=None, *, img_size=(256, 80), in_channels=10, batch_size=16, use_vit=False,
-                         transunet=False, bleed_extra=(), flip=False):
+                         transunet=False, bleed_extra=(), flip=False, temperature=None):
         """Build the models and load the files ``VisionTransformer.save`` / ``visionModel.save`` wrote (MainNumpy.py:177).
         ``transunet=True`` builds the ``TBI_TransUNet`` variant (whose ViT bottleneck is always on).  ``bleed_extra`` (more bleed checkpoints)
-        or ``flip`` (left-right test-time augmentation) make the bleed model an ``Ensemble``."""
+        or ``flip`` (left-right test-time augmentation) make the bleed model an ``Ensemble``.  ``temperature``: ``Cascade``'s."""
         def build(path, classes):
             if transunet:
                 from .TBI_TransUNet import VisionTransformer as TransUNet
@@ -115,7 +137,7 @@ class Cascade(PredictDriver):
         bleed = build(bleed_path, 3)
         if bleed_extra or flip:
             bleed = Ensemble([bleed] + [build(p, 3) for p in bleed_extra], flip=flip)
-        return cls(bleed, build(mask_path, 2) if mask_path is not None else None)
+        return cls(bleed, build(mask_path, 2) if mask_path is not None else None, temperature=temperature)
 
     # ------------------------------------------------------------------ PredictDriver hooks
     def _prep_x(self, x):
@@ -139,11 +161,23 @@ class Cascade(PredictDriver):
             ops.cascade_gate(pm, xb, out=xb, mask=mask)                  # the mask model has read xb: it may be overwritten
         if self.ensemble:
             e = self.bleed_model._predict_body(xb)
+            if self._beta is not None:
+                ops.apply_temperature(e.probs, self._beta, out=e.probs)     # of the mean; entropy / mutual_info / image_scores are the members'
             prob_map, bleed_prob = ops.cascade_maps(e.probs)
             return EnsembleCascadeOutput(e.probs, mask, prob_map, bleed_prob, e.entropy, e.mutual_info, e.image_scores)
         probs = self.bleed_model._predict_body(xb)
+        if self._beta is not None:
+            ops.apply_temperature(probs, self._beta, out=probs)
         prob_map, bleed_prob = ops.cascade_maps(probs)
         return CascadeOutput(probs, mask, prob_map, bleed_prob)
+
+
+def _beta_of(T):
+    """A temperature -> beta = 1/T as the kernel takes it: finite, with 1/16 <= T (beta <= 16)."""
+    T = float(T)
+    if not (T == T and 1.0 / 16.0 <= T < float("inf")):
+        raise ValueError(f"the temperature must be a finite number >= 1/16, got {T!r}")
+    return 1.0 / T
 
 
 # ---------------------------------------------------------------------------------------------------------- the test-data driver
@@ -229,11 +263,8 @@ def write_uncertainty_csv(path, names, image_scores):
     return len(names)
 
 
-def calibration_scores(result_probs, labels, bins=15, cls=-1, device=None, batch_size=64):
-    """Reliability table and scores (``metrics.calibration_from_counts``' dict: per-bin ``n`` / ``accuracy`` / ``confidence``, ``ece``, ``mce``,
-    ``brier``, ``n_invalid``) of probabilities [N,H,W,C] against labels - one-hot [N,H,W,C], or a label plane [N,H,W] as ``PolarResult.label`` (class k where
-    k - 0.5 < label <= k + 0.5, clipped to the classes: ``surface_scores``' ``label > 1.5`` for the bleed class).  Counted on the device (``usseg_calibration_bins``), one read-back."""
-    from .metrics import CalibrationBins
+def _probs_and_one_hot(result_probs, labels):
+    """-> (probabilities fp32 [N,H,W,C], one-hot labels fp32 [N,H,W,C]), both contiguous NumPy arrays: ``calibration_scores``' label rule."""
     probs = np.ascontiguousarray(result_probs, dtype=np.float32)
     if probs.ndim != 4:
         raise ValueError(f"probabilities must be [N,H,W,C], got {probs.shape}")
@@ -245,7 +276,16 @@ def calibration_scores(result_probs, labels, bins=15, cls=-1, device=None, batch
         labels = np.eye(C, dtype=np.float32)[idx]
     if labels.shape != probs.shape:
         raise ValueError(f"labels {labels.shape} match neither {probs.shape} nor {probs.shape[:3]}")
-    labels = np.ascontiguousarray(labels, dtype=np.float32)
+    return probs, np.ascontiguousarray(labels, dtype=np.float32)
+
+
+def calibration_scores(result_probs, labels, bins=15, cls=-1, device=None, batch_size=64):
+    """Reliability table and scores (``metrics.calibration_from_counts``' dict: per-bin ``n`` / ``accuracy`` / ``confidence``, ``ece``, ``mce``,
+    ``brier``, ``n_invalid``) of probabilities [N,H,W,C] against labels - one-hot [N,H,W,C], or a label plane [N,H,W] as ``PolarResult.label`` (class k where
+    k - 0.5 < label <= k + 0.5, clipped to the classes: ``surface_scores``' ``label > 1.5`` for the bleed class).  Counted on the device (``usseg_calibration_bins``), one read-back."""
+    from .metrics import CalibrationBins
+    probs, labels = _probs_and_one_hot(result_probs, labels)
+    C = probs.shape[-1]
     dev = torch.device(device if device is not None else "cuda")
     cal = CalibrationBins(bins, cls, device=dev)
     if not -1 <= int(cls) < C:
@@ -269,6 +309,56 @@ def write_calibration_csv(path, scores):
         w.writerow(["total", "", "", int(np.sum(scores["n"])), "", "", repr(float(scores["ece"])), repr(float(scores["mce"])),
                     repr(float(scores["brier"])), int(scores["n_invalid"])])
     return bins
+
+
+SWEEP_COLUMNS = ("k", "threshold", "tp", "fp", "fn", "tn", "tpr", "fpr", "precision", "dice")
+
+
+def sweep_scores(result_probs, labels, bins=1024, cls=-1, device=None, batch_size=64):
+    """The operating points of class ``cls`` (default: the last, the bleed class) - ``metrics.sweep_from_counts``' dict: ROC and PR points, Dice
+    against the threshold, ``auc``, ``average_precision``, ``best_dice``, ``best_youden`` - of probabilities [N,H,W,C] against one-hot labels or
+    a label plane, as ``calibration_scores`` takes them.  Counted on the device (``usseg_score_sweep``), one read-back.  A returned threshold
+    can be passed as it is to every ``threshold=`` argument here: "bin >= k" is ``bleed_prob > threshold[k]``."""
+    from .metrics import SweepCounts
+    probs, labels = _probs_and_one_hot(result_probs, labels)
+    C = probs.shape[-1]
+    if not -C <= int(cls) < C:
+        raise ValueError(f"cls must be a class below {C} (or negative, from the last), got {cls}")
+    dev = torch.device(device if device is not None else "cuda")
+    sw = SweepCounts(bins, cls, device=dev)
+    for lo in range(0, probs.shape[0], batch_size):
+        sw.update(torch.from_numpy(probs[lo:lo + batch_size]).to(dev), torch.from_numpy(labels[lo:lo + batch_size]).to(dev))
+    return sw.result()
+
+
+def write_roc_csv(path, scores):
+    """One row per operating point (``SWEEP_COLUMNS``) and a final row ``total``: the valid pixels, AUC, average precision, the best-Dice point
+    (k, threshold, Dice), the Youden point (k, threshold, J) and the invalid count.  -> the number of operating points."""
+    import csv
+    n = len(scores["threshold"])
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(list(SWEEP_COLUMNS) + ["n", "auc", "average_precision", "best_dice_k", "best_dice_threshold", "best_dice", "youden_k", "youden_threshold",
+                                          "youden", "n_invalid"])
+        for k in range(n):
+            w.writerow([k, repr(float(scores["threshold"][k]))] + [int(scores[c][k]) for c in ("tp", "fp", "fn", "tn")] +
+                       [repr(float(scores[c][k])) for c in ("tpr", "fpr", "precision", "dice")] + [""] * 10)
+        bd, by = scores["best_dice"], scores["best_youden"]
+        total = int(scores["tp"][0]) + int(scores["fp"][0])
+        w.writerow(["total"] + [""] * 9 + [total, repr(float(scores["auc"])), repr(float(scores["average_precision"])), int(bd[0]), repr(float(bd[1])),
+                                           repr(float(bd[2])), int(by[0]), repr(float(by[1])), repr(float(by[2])), int(scores["n_invalid"])])
+    return n
+
+
+def fit_cascade_temperature(probs, labels, *, lo=1 / 8, hi=8.0, candidates=16, rounds=4, device=None, batch_size=64):
+    """``metrics.fit_temperature`` of un-scaled probabilities [N,H,W,C] (a run without a temperature, ``keep_probs``) against one-hot labels or
+    a label plane, as ``calibration_scores`` takes them: -> its dict; ``Cascade.set_temperature(d["temperature"])`` applies it."""
+    from .metrics import fit_temperature
+    probs, labels = _probs_and_one_hot(probs, labels)
+    dev = torch.device(device if device is not None else "cuda")
+    parts = [(torch.from_numpy(probs[i:i + batch_size]).to(dev), torch.from_numpy(labels[i:i + batch_size]).to(dev))
+             for i in range(0, probs.shape[0], batch_size)]
+    return fit_temperature(parts, lo=lo, hi=hi, candidates=candidates, rounds=rounds, device=dev)
 
 
 def _polar_run(data, cascade, names, batch_size, uncertainty, keep_probs=False):
@@ -586,7 +676,31 @@ def main(argv=None):
     ap.add_argument("--calibration-csv", default=None, metavar="PATH",
                     help="write the reliability table of the bleed model's (or the ensemble's mean) probabilities with ECE, MCE and the Brier score")
     ap.add_argument("--calibration-bins", type=int, default=15, metavar="N", help="confidence bins of --calibration-csv (1..64)")
+    ap.add_argument("--roc-csv", default=None, metavar="PATH",
+                    help="write the bleed class's threshold sweep: one row per operating point (ROC and PR points, Dice) and a total row with AUC, "
+                         "average precision and the best-Dice and Youden points")
+    ap.add_argument("--sweep-bins", type=int, default=1024, metavar="N", help="score bins of the sweep: a power of two in 2..4096")
+    ap.add_argument("--temperature", type=float, default=None, metavar="T", help="calibrate the bleed probabilities: softmax(log(p + 1e-7) / T)")
+    ap.add_argument("--fit-temperature", action="store_true",
+                    help="fit the temperature on this run's data (it needs the labels), print it with the NLL and the ECE before and after, and predict again with it")
+    ap.add_argument("--threshold", default=None, metavar="T|best-dice|youden",
+                    help="the bleed threshold --surface-csv and --lesion-csv use (default 0.5): a number, or the sweep's best-Dice or Youden point")
     a = ap.parse_args(argv)
+    threshold = None
+    if a.threshold is not None and a.threshold not in ("best-dice", "youden"):
+        try:
+            threshold = float(a.threshold)
+        except ValueError:
+            ap.error("--threshold takes a number, best-dice or youden")
+        if not threshold == threshold:
+            ap.error("--threshold must not be NaN")
+    if a.sweep_bins < 2 or a.sweep_bins > 4096 or a.sweep_bins & (a.sweep_bins - 1):
+        ap.error("--sweep-bins must be a power of two in 2..4096")
+    if a.temperature is not None and a.fit_temperature:
+        ap.error("--temperature and --fit-temperature exclude each other")
+    if a.temperature is not None and not (a.temperature == a.temperature and 1.0 / 16.0 <= a.temperature < float("inf")):
+        ap.error("--temperature must be a finite number >= 1/16")
+    sweep = a.roc_csv is not None or a.threshold in ("best-dice", "youden")
     if a.batch < 1:
         ap.error("--batch must be >= 1")
     if a.min_area is not None and a.min_area < 1:
@@ -613,25 +727,47 @@ def main(argv=None):
     cascade = Cascade.from_checkpoints(a.bleed, a.mask, batch_size=a.batch, use_vit=a.use_vit, transunet=a.transunet,
                                        bleed_extra=tuple(a.bleed_extra or ()), flip=a.tta == "flip")
     geometry = ConeGeometry.from_dir(a.axis_dir, px_per_unit=a.px_per_unit, device=cascade.device)
-    if ensemble or a.calibration_csv is not None:
-        result, extra, probs = _polar_run(data, cascade, names, a.batch, uncertainty=ensemble, keep_probs=a.calibration_csv is not None)
+    if a.temperature is not None:
+        cascade.set_temperature(a.temperature)
+    if a.fit_temperature:
+        result, _, probs = _polar_run(data, cascade, names, a.batch, uncertainty=False, keep_probs=True)
+        fit = fit_cascade_temperature(probs, result.label, device=cascade.device)
+        before = calibration_scores(probs, result.label, bins=a.calibration_bins, device=cascade.device)
+        cascade.set_temperature(fit["temperature"])
+        _, _, probs = _polar_run(data, cascade, names, a.batch, uncertainty=False, keep_probs=True)
+        after = calibration_scores(probs, result.label, bins=a.calibration_bins, device=cascade.device)
+        print("fitted temperature T = {!r} (beta = {!r}): NLL {:.6f} -> {:.6f}, ECE {:.5f} -> {:.5f}".format(
+            fit["temperature"], fit["beta"], fit["nll_at_1"], fit["nll"], before["ece"], after["ece"]))
+    if ensemble or a.calibration_csv is not None or sweep:
+        result, extra, probs = _polar_run(data, cascade, names, a.batch, uncertainty=ensemble, keep_probs=a.calibration_csv is not None or sweep)
         if a.uncertainty_csv is not None:
             rows = write_uncertainty_csv(a.uncertainty_csv, _names(result), extra[2])
             print(f"wrote {rows} uncertainty rows to {a.uncertainty_csv}")
         if a.calibration_csv is not None:
             rows = write_calibration_csv(a.calibration_csv, calibration_scores(probs, result.label, bins=a.calibration_bins, device=cascade.device))
             print(f"wrote {rows} reliability bins to {a.calibration_csv}")
+        if sweep:
+            from .metrics import sweep_line
+            sw = sweep_scores(probs, result.label, bins=a.sweep_bins, device=cascade.device)
+            print(sweep_line(sw))
+            if a.roc_csv is not None:
+                rows = write_roc_csv(a.roc_csv, sw)
+                print(f"wrote {rows} operating points to {a.roc_csv}")
+            if a.threshold in ("best-dice", "youden"):
+                threshold = sw["best_dice" if a.threshold == "best-dice" else "best_youden"][1]
+                print(f"--threshold {a.threshold}: {threshold!r}")
     else:
         result = Polar_Model(data, cascade, names=names, batch_size=a.batch)
+    thr = {} if threshold is None else {"threshold": threshold}          # (absent: every consumer's own default, 0.5)
     if a.surface_csv is not None:
         cleaned = None
         if a.min_area is not None:
-            cleaned = clean_result(result, min_area=a.min_area, min_peak=a.min_peak, connectivity=a.connectivity, device=cascade.device)
-        rows = write_surface_csv(a.surface_csv, result, device=cascade.device, pred_mask=cleaned, percentiles=a.surface_percentile,
+            cleaned = clean_result(result, **thr, min_area=a.min_area, min_peak=a.min_peak, connectivity=a.connectivity, device=cascade.device)
+        rows = write_surface_csv(a.surface_csv, result, **thr, device=cascade.device, pred_mask=cleaned, percentiles=a.surface_percentile,
                                  tolerances=a.surface_tolerance)
         print(f"wrote {rows} surface-score rows to {a.surface_csv}")
     if a.lesion_csv is not None:
-        rows = write_lesion_csv(a.lesion_csv, result, min_area=a.min_area if a.min_area is not None else 1, min_peak=a.min_peak,
+        rows = write_lesion_csv(a.lesion_csv, result, **thr, min_area=a.min_area if a.min_area is not None else 1, min_peak=a.min_peak,
                                 connectivity=a.connectivity, device=cascade.device)
         print(f"wrote {rows} lesion rows to {a.lesion_csv}")
     paths = Display(result, geometry, a.out, stamp=not a.no_stamp, batch_size=a.batch)

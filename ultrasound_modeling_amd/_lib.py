@@ -141,8 +141,20 @@ class CalibDesc(C.Structure):
     _fields_ = [("B", c_i32), ("H", c_i32), ("W", c_i32), ("C", c_i32), ("bins", c_i32), ("cls", c_i32)]
 
 
+class SweepDesc(C.Structure):
+    _fields_ = [("B", c_i32), ("H", c_i32), ("W", c_i32), ("C", c_i32), ("bins", c_i32), ("cls", c_i32)]
+
+
+class TempDesc(C.Structure):
+    _fields_ = [("B", c_i32), ("H", c_i32), ("W", c_i32), ("C", c_i32), ("n_beta", c_i32)]
+
+
 ENSEMBLE_MAX = 16       # USSEG_ENSEMBLE_MAX
 CALIB_MAX_BINS = 64     # USSEG_CALIB_MAX_BINS
+SWEEP_MAX_BINS = 4096   # USSEG_SWEEP_MAX_BINS
+TEMP_MAX_BETAS = 16     # USSEG_TEMP_MAX_BETAS
+TEMP_NLL_CAP = 1024     # USSEG_TEMP_NLL_CAP
+TEMP_NLL_UNIT = 2.0 ** -20    # one count of usseg_temperature_nll's sums
 
 ACT_NONE, ACT_LRELU, ACT_RELU, ACT_ELU, ACT_GELU = 0, 1, 2, 3, 4
 OUT_F32, ACCUMULATE = 1, 2
@@ -315,6 +327,9 @@ _PROTOS = {
     "usseg_ensemble_merge": (C.c_int, [P(EnsembleDesc), P(c_vp), C.c_uint32, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "usseg_ensemble_image_scores": (C.c_int, [P(EnsembleDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "usseg_calibration_bins": (C.c_int, [P(CalibDesc), c_vp, c_vp, c_vp, c_vp]),
+    "usseg_score_sweep": (C.c_int, [P(SweepDesc), c_vp, c_vp, c_vp, c_vp]),
+    "usseg_temperature_nll": (C.c_int, [P(TempDesc), c_vp, c_vp, P(c_f32), c_vp, c_vp]),
+    "usseg_apply_temperature": (C.c_int, [P(TempDesc), c_vp, c_vp, c_vp, c_vp]),
 }
 EXPORTED_SYMBOLS = tuple(_PROTOS)
 

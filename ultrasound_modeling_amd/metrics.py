@@ -25,7 +25,8 @@ from ._lib import SEG_COUNTS
 from .ops import seg_counts  # noqa: F401  (the kernel wrapper; re-exported here)
 
 __all__ = ["CalibrationBins", "SEG_COUNTS", "SegMetrics", "calibration_from_counts", "calibration_line", "components", "counts_to_metrics", "dice_per_class", "dice_line", "lesion_scores", "lesion_scores_from_tables",
-           "seg_counts"]
+           "seg_counts", "SweepCounts", "fit_temperature", "sweep_from_counts", "sweep_line", "sweep_thresholds", "temperature_candidates",
+           "temperature_search"]
 
 
 def _div_no_nan(a: float, b: float) -> float:
@@ -353,3 +354,155 @@ class CalibrationBins:
 def calibration_line(r) -> str:
     """The drivers' one line per epoch for ``calibration_from_counts``' dict."""
     return "calibration: ECE = {:.5f}, MCE = {:.5f}, Brier = {:.5f}, invalid = {}".format(r["ece"], r["mce"], r["brier"], r["n_invalid"])
+
+
+# ---------------------------------------------------------------------------------------------------------- operating points
+def sweep_thresholds(bins: int) -> np.ndarray:
+    """fp32 [bins + 1]: ``threshold[k]`` such that "bin >= k" is ``s > threshold[k]`` for every valid fp32 score s.  ``bins`` is a power of two, so
+    k/bins and s*bins are exact: bin >= k is s >= k/bins, and the largest fp32 below k/bins turns that into a strict comparison, the form every
+    ``threshold=`` argument of the evaluator takes.  k = 0 is -inf (everything is predicted positive); k = bins is 1.0 (nothing is: s = 1 lies
+    in the LAST bin, so the largest fp32 below 1 would wrongly let it through)."""
+    bins = int(bins)
+    t = np.empty(bins + 1, np.float32)
+    t[0] = -np.inf
+    t[1:] = np.nextafter((np.arange(1, bins + 1, dtype=np.float64) / bins).astype(np.float32), np.float32(0))
+    t[bins] = 1.0
+    return t
+
+
+def sweep_from_counts(counts) -> Dict[str, object]:
+    """Counter block of ``usseg_score_sweep`` (int64 [2*bins + 1], CPU or device) -> the operating points of the swept class, from Python
+    integers and fp64 on the host.  Operating point k = 0..bins predicts positive iff bin >= k (``threshold[k]``: ``sweep_thresholds``):
+    ``tp, fp, fn, tn`` (int64 [bins+1]), ``tpr``, ``fpr`` (NaN without positives / negatives), ``precision`` (1 where tp + fp = 0), ``dice`` =
+    2tp/(2tp+fp+fn) (0 where that is 0/0).  ``auc``: the exact Mann-Whitney statistic of the binned score, ties at one half,
+    sum_b pos_b*(2*neg_below_b + neg_b) / (2*P*N), NaN when P or N is 0.  ``average_precision``: sum_k (recall_k - recall_(k+1)) * precision_k,
+    NaN when P is 0.  ``best_dice`` and ``best_youden`` (tpr - fpr): (k, threshold, value), ties to the smallest k.  ``n_invalid``."""
+    c = [int(v) for v in torch.as_tensor(counts).reshape(-1).cpu().tolist()]
+    bins = (len(c) - 1) // 2
+    if len(c) < 5 or len(c) != 2 * bins + 1 or bins & (bins - 1):
+        raise ValueError(f"a sweep counter block holds 2*bins + 1 integers with bins a power of two, got {len(c)}")
+    neg, pos = c[0:2 * bins:2], c[1:2 * bins:2]
+    P, N = sum(pos), sum(neg)
+    tp, fp = [0] * (bins + 1), [0] * (bins + 1)
+    for k in range(bins - 1, -1, -1):
+        tp[k] = tp[k + 1] + pos[k]
+        fp[k] = fp[k + 1] + neg[k]
+    fn, tn = [P - v for v in tp], [N - v for v in fp]
+    nan = float("nan")
+    tpr = [v / P if P else nan for v in tp]
+    fpr = [v / N if N else nan for v in fp]
+    precision = [tp[k] / (tp[k] + fp[k]) if tp[k] + fp[k] else 1.0 for k in range(bins + 1)]
+    dice = [2 * tp[k] / (2 * tp[k] + fp[k] + fn[k]) if 2 * tp[k] + fp[k] + fn[k] else 0.0 for k in range(bins + 1)]
+    below, num = 0, 0
+    for b in range(bins):
+        num += pos[b] * (2 * below + neg[b])
+        below += neg[b]
+    auc = num / (2 * P * N) if P and N else nan
+    ap = sum((tp[k] - tp[k + 1]) * precision[k] for k in range(bins)) / P if P else nan
+    thr = sweep_thresholds(bins)
+
+    def best(v):
+        k = max(range(bins + 1), key=lambda i: (v[i], -i)) if not any(math.isnan(x) for x in v) else 0
+        return k, float(thr[k]), float(v[k])
+    return dict(tp=np.array(tp, np.int64), fp=np.array(fp, np.int64), fn=np.array(fn, np.int64), tn=np.array(tn, np.int64),
+                tpr=np.array(tpr), fpr=np.array(fpr), precision=np.array(precision), dice=np.array(dice), threshold=thr, auc=auc,
+                average_precision=ap, best_dice=best(dice), best_youden=best([a - b for a, b in zip(tpr, fpr)]), n_invalid=c[2 * bins])
+
+
+class SweepCounts:
+    """Sweep counters that stay on the device, after ``CalibrationBins``: ``update`` is one launch (``ops.score_sweep``), ``result`` the one copy
+    to the host (-> ``sweep_from_counts``' dict), ``reset`` one fill.  ``cls``: the swept class; negative counts from the last class."""
+
+    def __init__(self, bins: int = 1024, cls: int = -1, device=None):
+        from ._lib import SWEEP_MAX_BINS
+        bins, cls = int(bins), int(cls)
+        if not 2 <= bins <= SWEEP_MAX_BINS or bins & (bins - 1):
+            raise ValueError(f"bins must be a power of two in 2..{SWEEP_MAX_BINS}, got {bins}")
+        if not -4 <= cls <= 3:
+            raise ValueError(f"cls must be a class 0..3 (or negative, from the last), got {cls}")
+        self.bins, self.cls = bins, cls
+        self.counts = torch.zeros(2 * bins + 1, dtype=torch.int64, device=device if device is not None else "cuda")
+
+    def update(self, probs: torch.Tensor, y: torch.Tensor) -> None:
+        """Add one batch, fp32 [B,H,W,C] on the counters' device; enqueued on the current stream (no host synchronisation)."""
+        from .ops import score_sweep
+        score_sweep(probs, y, self.counts, self.bins, self.cls)
+
+    def result(self) -> Dict[str, object]:
+        return sweep_from_counts(self.counts.cpu())
+
+    def reset(self) -> None:
+        self.counts.zero_()
+
+
+def sweep_line(r) -> str:
+    """The drivers' one line per epoch for ``sweep_from_counts``' dict."""
+    return "sweep: AUC = {:.5f}, AP = {:.5f}, best Dice = {:.5f} at threshold {:.6f}, invalid = {}".format(
+        r["auc"], r["average_precision"], r["best_dice"][2], r["best_dice"][1], r["n_invalid"])
+
+
+def _f32(v) -> float:
+    return float(np.float32(v))
+
+
+def temperature_candidates(lo: float, hi: float, n: int, geometric: bool):
+    """The n candidates of one round of ``fit_temperature`` on [lo, hi], rounded to fp32 (the values the kernel sees), ascending."""
+    if n == 1:
+        return [_f32(lo)]
+    if geometric:
+        return [_f32(lo * (hi / lo) ** (i / (n - 1))) for i in range(n)]
+    return [_f32(lo + (hi - lo) * (i / (n - 1))) for i in range(n)]
+
+
+def temperature_search(evaluate, *, lo=1 / 8, hi=8.0, candidates=16, rounds=4):
+    """The bracket search of ``fit_temperature`` over ``evaluate(betas) -> [sum_0, ..., sum_(n-1), n_valid, n_invalid]`` (integers).  Round 0:
+    ``candidates`` betas geometrically spaced on [lo, hi]; each later round: ``candidates`` betas evenly spaced on [the neighbour below the
+    arg-min, the neighbour above it] (the arg-min itself at an end of the list).  Ties go to the smallest beta.  The NLL is convex in beta
+    (a log-sum-exp of linear functions minus a linear one), so the bracket keeps the minimiser.  Last, beta = 1 is evaluated on its own and wins
+    when its sum is strictly smaller (so the result is never worse than no scaling).  -> (beta, its sum, the sum at 1, (bracket lo, bracket hi),
+    n_valid, n_invalid)."""
+    candidates, rounds = int(candidates), int(rounds)
+    if not (0.0 < lo < hi <= 16.0):
+        raise ValueError(f"fit_temperature: 0 < lo < hi <= 16, got [{lo}, {hi}]")
+    if not 3 <= candidates <= 16 or rounds < 1:
+        raise ValueError(f"fit_temperature: 3..16 candidates and at least one round, got {candidates} and {rounds}")
+    a, b = float(lo), float(hi)
+    for r in range(rounds):
+        betas = temperature_candidates(a, b, candidates, geometric=r == 0)
+        c = [int(v) for v in evaluate(betas)]
+        sums = c[:len(betas)]
+        i = min(range(len(betas)), key=lambda j: (sums[j], betas[j]))
+        if r == 0 and i in (0, len(betas) - 1):
+            edge = "lower" if i == 0 else "upper"
+            raise ValueError(f"fit_temperature: the smallest NLL lies on the {edge} edge of [{lo}, {hi}] (beta = {betas[i]}): widen the interval")
+        a, b = betas[max(i - 1, 0)], betas[min(i + 1, len(betas) - 1)]
+        beta, best, n, n_invalid = betas[i], sums[i], c[len(betas)], c[len(betas) + 1]
+        if not a < b:
+            break                                        # the bracket has closed to neighbouring fp32 values
+    at1 = int(evaluate([1.0])[0])
+    if at1 < best:                                       # the candidates straddle 1 without holding it: "no scaling" is then the better answer
+        beta, best = 1.0, at1
+    return beta, best, at1, (a, b), n, n_invalid
+
+
+def fit_temperature(batches, *, lo=1 / 8, hi=8.0, candidates=16, rounds=4, device=None) -> Dict[str, object]:
+    """Temperature scaling (Guo et al., ICML 2017) fitted on the device: the beta = 1/T that minimises the negative log-likelihood of the labels
+    under softmax(beta * log(probs + 1e-7)), by ``temperature_search``.  ``batches``: a re-iterable of (probs, y_true) pairs [B,H,W,C], device
+    tensors or numpy arrays (uploaded per round).  Each round is one ``ops.temperature_nll`` launch per batch - every candidate in one read -
+    and ONE read-back.  The sums are integers: the fit is bitwise reproducible.  An arg-min on the edge of [lo, hi] after round 0 raises a
+    ``ValueError`` naming the edge.  -> dict(beta, temperature = 1/beta, nll and nll_at_1 (means over the valid pixels), bracket, n, n_invalid)."""
+    from ._lib import TEMP_NLL_UNIT
+    from .ops import temperature_nll
+    dev = torch.device(device if device is not None else "cuda")
+
+    def on_dev(t):
+        return torch.as_tensor(np.ascontiguousarray(t, dtype=np.float32) if isinstance(t, np.ndarray) else t).to(device=dev, dtype=torch.float32).contiguous()
+
+    def evaluate(betas):
+        counts = torch.zeros(len(betas) + 2, dtype=torch.int64, device=dev)
+        for probs, y in batches:
+            temperature_nll(on_dev(probs), on_dev(y), betas, counts)
+        return counts.cpu().tolist()                     # the ONE read-back of the round
+    beta, best, at1, bracket, n, n_invalid = temperature_search(evaluate, lo=lo, hi=hi, candidates=candidates, rounds=rounds)
+    per = TEMP_NLL_UNIT / n if n else float("nan")
+    return dict(beta=beta, temperature=1.0 / beta, nll=best * per, nll_at_1=at1 * per, bracket=bracket, n=n, n_invalid=n_invalid)

@@ -715,6 +715,76 @@ def calibration_bins(probs, y_true, counts, bins=15, cls=-1):
     return counts
 
 
+# ------------------------------------------------------------------------------------------------ operating points (operating_point.hip)
+def _counts_i64(counts, n, ref, what):
+    if not (torch.is_tensor(counts) and counts.dtype == torch.int64 and counts.is_contiguous() and counts.numel() == n and counts.device == ref.device):
+        raise ValueError(f"{what}: counts must be a contiguous int64 tensor of {n} elements on {ref.device}")
+
+
+def score_sweep(probs, y_true, counts, bins=1024, cls=-1):
+    """counts += the sweep counters of one batch (usseg_score_sweep): per score bin of class ``cls`` the negatives and the positives, then the
+    invalid pixels.  probs, y_true: contiguous fp32 [B,H,W,C] on the device; ``counts``: int64 [2*bins + 1] there, zeroed by the caller.
+    ``bins``: a power of two in 2..4096; a negative ``cls`` counts from the last class.  One launch, no host sync."""
+    bins, cls = int(bins), int(cls)
+    if not 2 <= bins <= L.SWEEP_MAX_BINS or bins & (bins - 1):
+        raise ValueError(f"score_sweep: bins must be a power of two in 2..{L.SWEEP_MAX_BINS}, got {bins}")
+    _probs4(probs, "score_sweep")
+    if _probs4(y_true, "score_sweep").shape != probs.shape or y_true.device != probs.device:
+        raise ValueError(f"score_sweep: probs {tuple(probs.shape)} and y_true {tuple(y_true.shape)} differ")
+    B, H, W, C_ = probs.shape
+    if not -C_ <= cls < C_:
+        raise ValueError(f"score_sweep: cls must be a class below {C_} (or negative, from the last), got {cls}")
+    _counts_i64(counts, 2 * bins + 1, probs, "score_sweep")
+    if probs.numel() == 0:                        # an empty batch has no storage to point at: nothing to count, nothing launched
+        return counts
+    d = L.SweepDesc(B, H, W, C_, bins, cls % C_)
+    L.check(L.load().usseg_score_sweep(C.byref(d), probs.data_ptr(), y_true.data_ptr(), counts.data_ptr(), _stream()), "score_sweep")
+    return counts
+
+
+def _beta_list(betas, what):
+    betas = [float(b) for b in (betas.tolist() if hasattr(betas, "tolist") else betas)]
+    if not 1 <= len(betas) <= L.TEMP_MAX_BETAS:
+        raise ValueError(f"{what}: 1..{L.TEMP_MAX_BETAS} betas, got {len(betas)}")
+    for b in betas:
+        if not 0.0 < b <= 16.0:                   # (a NaN compares false)
+            raise ValueError(f"{what}: every beta must be finite with 0 < beta <= 16, got {b!r}")
+    return betas
+
+
+def temperature_nll(probs, y_true, betas, counts):
+    """counts[j] += sum over the valid pixels of rint(nll_j * 2^20), nll_j the negative log-likelihood of the label under
+    softmax(betas[j] * log(probs + 1e-7)); counts[n] += the valid, counts[n+1] += the invalid pixels (usseg_temperature_nll).  ``betas``: 1..16
+    host floats in (0, 16], rounded to fp32; ``counts``: int64 [len(betas) + 2] on the device.  One launch for every candidate, no host sync."""
+    betas = _beta_list(betas, "temperature_nll")
+    _probs4(probs, "temperature_nll")
+    if _probs4(y_true, "temperature_nll").shape != probs.shape or y_true.device != probs.device:
+        raise ValueError(f"temperature_nll: probs {tuple(probs.shape)} and y_true {tuple(y_true.shape)} differ")
+    _counts_i64(counts, len(betas) + 2, probs, "temperature_nll")
+    B, H, W, C_ = probs.shape
+    if probs.numel() == 0:
+        return counts
+    d = L.TempDesc(B, H, W, C_, len(betas))
+    arr = (C.c_float * len(betas))(*betas)
+    L.check(L.load().usseg_temperature_nll(C.byref(d), probs.data_ptr(), y_true.data_ptr(), arr, counts.data_ptr(), _stream()), "temperature_nll")
+    return counts
+
+
+def apply_temperature(probs, beta, out=None):
+    """softmax(beta * log(probs + 1e-7)) per pixel (usseg_apply_temperature).  ``beta``: a one-element fp32 DEVICE tensor (1 / temperature) the
+    kernel reads when it runs, so a captured graph follows it.  ``out`` may be ``probs``.  One launch, no host sync."""
+    _probs4(probs, "apply_temperature")
+    if not (torch.is_tensor(beta) and beta.dtype == torch.float32 and beta.numel() == 1 and beta.device == probs.device):
+        raise ValueError(f"apply_temperature: beta must be a one-element fp32 tensor on {probs.device}")
+    out = _out_like(out, probs.shape, torch.float32, probs, "apply_temperature out")
+    B, H, W, C_ = probs.shape
+    if probs.numel() == 0:
+        return out
+    d = L.TempDesc(B, H, W, C_, 1)
+    L.check(L.load().usseg_apply_temperature(C.byref(d), probs.data_ptr(), beta.data_ptr(), out.data_ptr(), _stream()), "apply_temperature")
+    return out
+
+
 def norm_act_bwd_res(x, dy, C_logical, gamma, beta, dres, dx, dgamma, dbeta, eps, dbias=None):
     """Plain LayerNormalization backward + the residual branch of a pre-norm block: dx = bf16(bf16(LN'(dy)) + dres) in one pass;
     ``dbias`` += the column sums of the stored dx."""
