@@ -958,6 +958,36 @@ int usseg_sumsq_sched_advance(const float* g, int64_t n, float* out, int32_t* st
 int usseg_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, const float* sumsq, float clip_norm, const float* lr_t_dev,
                      const float* wd_t_dev, const uint8_t* decay_mask, float beta1, float beta2, float eps, usseg_stream_t stream);
 
+/* ---- weight averaging inside the optimiser step (tfa.optimizers.MovingAverage / tfa.optimizers.SWA)
+ * The descriptor lives in DEVICE memory and is never a kernel argument, so a captured graph reads whatever it holds when it replays.
+ * Every thread derives the blend coefficient c from t = *step_dev AFTER the step's increment (the t of Adam's bias correction):
+ *   EMA: c = 1 for t <= start (the average tracks the weights), else c = 1 - d_t, d_t = decay, or min(decay, (1+t)/(10+t)) with
+ *        dynamic_decay;
+ *   SWA: c = 1/(k+1) if t >= start and (t-start) % period == 0, k = (t-start)/period (the first snapshot replaces the average), else 0;
+ * and avg[i] = fmaf(c, p[i] - avg[i], avg[i]).  c == 0 writes nothing (no byte of avg moves), c == 1 stores p[i] itself. */
+#define USSEG_AVERAGE_OFF 0
+#define USSEG_AVERAGE_EMA 1
+#define USSEG_AVERAGE_SWA 2
+typedef struct UssegAverage {
+  int32_t mode;                                /* USSEG_AVERAGE_* */
+  float decay;                                 /* EMA: 0 <= decay < 1 */
+  int32_t dynamic_decay;                       /* EMA: nonzero = min(decay, (1+t)/(10+t)) */
+  int32_t start;                               /* EMA: start_step; SWA: the step of the first snapshot */
+  int32_t period;                              /* SWA: steps between snapshots, >= 1 */
+} UssegAverage;
+/* usseg_adamw_step and the average of the UPDATED p in one pass (36 bytes per parameter instead of 28): p, m and v get the bits
+ * usseg_adamw_step gives them.  wd_t_dev may be NULL: no decay, the arithmetic of usseg_adam_clip_step.  p, g, m, v, avg 16-byte aligned,
+ * decay_mask (u8 per element, nullable) 4-byte aligned, any n >= 0. */
+int usseg_adamw_avg_step(float* p, const float* g, float* m, float* v, float* avg, int64_t n, const float* sumsq, float clip_norm,
+                         const float* lr_t_dev, const float* wd_t_dev, const uint8_t* decay_mask, float beta1, float beta2, float eps,
+                         const int32_t* step_dev, const UssegAverage* avg_desc_dev, usseg_stream_t stream);
+/* the average alone, for a p updated elsewhere: the same bits of avg as the fused launch.  avg, p 16-byte aligned, any n >= 0. */
+int usseg_average_update(float* avg, const float* p, int64_t n, const int32_t* step_dev, const UssegAverage* avg_desc_dev,
+                         usseg_stream_t stream);
+/* exchanges two disjoint buffers in place (the averaged weights go where every kernel reads its weights, and back).  a, b 16-byte
+ * aligned, any n >= 0. */
+int usseg_swap_f32(float* a, float* b, int64_t n, usseg_stream_t stream);
+
 /* ---- ViT bottleneck helpers (VisionTransformer.py:9-79,127-174) ------------------------
  * Batched GEMMs on the conv kernels (bf16 operands, fp32 accumulate), 2-level batch (image, head) with element strides:
  *   nt: Y[b1,b2][m][n]  = sum_k X[b1,b2][m][k] * W[b1,b2][n][k]   (M rows, K contiguous in both operands)

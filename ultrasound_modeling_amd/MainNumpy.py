@@ -19,6 +19,8 @@ model with ``train_step(x, y) -> (loss, probs)`` and ``step(x, y) -> (loss, prob
 """
 from __future__ import annotations
 
+import contextlib
+
 import torch
 
 from .metrics import SegMetrics, dice_line
@@ -92,28 +94,35 @@ class Process(object):
             # :83-88 (the learning-rate "schedule"): installed before the first step with schedule=True, see the module docstring
 
     def test(self, neuralnet, dataset, epoch):
-        """MainNumpy.py:90-147 -> F1 of the epoch's test set; its dict (``phase`` "test") is appended to ``self.history``."""
+        """MainNumpy.py:90-147 -> F1 of the epoch's test set; its dict (``phase`` "test") is appended to ``self.history``.  A model built with
+        ``average=`` is validated under ``averaged_weights()`` - loss, counters, Dice line and the optional surface / calibration / sweep
+        scores are the averaged model's - and the report adds the loss of the raw weights (``raw_loss`` in the history)."""
         print("\nTest...")
         total_loss = None
         stats = []                                              # per batch: usseg_surface_stats' four tensors, left on the device
-        while True:
-            x_te, y_te, terminator = dataset.next_test(16)                                       # :97
-            loss, class_score = neuralnet.step(x=x_te, y=y_te)                                   # :98
-            total_loss = loss.detach().reshape(()).clone() if total_loss is None else total_loss.add_(loss.reshape(()))   # :107, on the device
-            labels = _labels(y_te, class_score)
-            self.metrics.update_state(labels, class_score)                                       # :100-106
-            if self.surface is not None:
-                stats.append(_surface_batch(labels, class_score, self.num_classes, self.surface))
-            if self.calibration is not None:
-                self.calibration.update(class_score, labels)
-            if self.sweep is not None:
-                self.sweep.update(class_score, labels)
-            if terminator:
-                break
-            self.test_iter += 1
+        averaged = averaging(neuralnet)
+        raw_loss = _raw_test_loss(neuralnet, dataset) if averaged else None      # the weights as they stand, for comparison
+        with (neuralnet.averaged_weights() if averaged else contextlib.nullcontext()):       # everything scored below: the averaged model
+            while True:
+                x_te, y_te, terminator = dataset.next_test(16)                                       # :97
+                loss, class_score = neuralnet.step(x=x_te, y=y_te)                                   # :98
+                total_loss = loss.detach().reshape(()).clone() if total_loss is None else total_loss.add_(loss.reshape(()))   # :107, on the device
+                labels = _labels(y_te, class_score)
+                self.metrics.update_state(labels, class_score)                                       # :100-106
+                if self.surface is not None:
+                    stats.append(_surface_batch(labels, class_score, self.num_classes, self.surface))
+                if self.calibration is not None:
+                    self.calibration.update(class_score, labels)
+                if self.sweep is not None:
+                    self.sweep.update(class_score, labels)
+                if terminator:
+                    break
+                self.test_iter += 1
         total_loss = float(total_loss)
         m = self.metrics.result()
         print("loss = {}".format(total_loss))
+        if averaged:
+            print("loss (raw weights) = {}".format(raw_loss))
         print("IoU = {}".format(m["mean_iou"]))
         print("f1 = {}".format(m["f1"]))
         print("precision = {}".format(m["precision"]))
@@ -121,9 +130,9 @@ class Process(object):
         dice = dice_line(neuralnet, self.metrics)
         if dice is not None:                                    # only with loss="dice" / "tversky" / "dice_ce"
             print("dice per class = {}".format(dice))
-        extra = {}
+        extra = {"raw_loss": raw_loss} if averaged else {}
         if self.surface is not None:
-            extra = surface_summary(stats, self.surface)       # ONE read-back of the epoch's integers
+            extra = dict(extra, **surface_summary(stats, self.surface))       # ONE read-back of the epoch's integers
             print(surface_line(extra, self.surface))
         if self.calibration is not None:
             from .metrics import calibration_line
@@ -143,23 +152,52 @@ class Process(object):
         return m["f1"]
 
 
-def main(train_path, val_path, save_path=None, epochs=50, batch_size=32, num_classes=3, *, loss="cce", overlap=None, boundary=None, lovasz=None):
+def main(train_path, val_path, save_path=None, epochs=50, batch_size=32, num_classes=3, *, loss="cce", overlap=None, boundary=None, lovasz=None,
+         average=None):
     """MainNumpy.py:150-177 with the paths as arguments: ``VisionTransformer(32, img_size=(256, 80))`` over a ``Dataset_2.Dataset``,
     50 epochs, then a save if ``save_path`` is given.  ``loss``: the model's ``loss=`` ("cce", "my_loss_cat", "focal", "dice", "tversky",
     "dice_ce"); ``overlap``: the settings of the last three (``VisionTransformer(overlap=...)``), which also add a per-class Dice line to the test report;
     ``boundary``: the boundary term on top of one of those three (``VisionTransformer(boundary=...)``); "lovasz" / "lovasz_ce" with their settings in
-    ``lovasz`` (``VisionTransformer(lovasz=...)``: the Lovasz-softmax loss; the Dice line too)."""
+    ``lovasz`` (``VisionTransformer(lovasz=...)``: the Lovasz-softmax loss; the Dice line too).  ``average`` (a dict, or the string
+    ``ema:DECAY[:dynamic]`` / ``swa:START:PERIOD``): EMA / SWA weight averaging - the tests report the averaged model, and the save also writes
+    ``<save_path>.avg``, a plain checkpoint of the averaged weights (``save_averaged``)."""
     from .Dataset_2 import Dataset
     from .VisionTransformer import VisionTransformer, overlap_settings
     dataset = Dataset(train_path, val_path, num_classes)
     neuralnet = VisionTransformer(batch_size, img_size=input_size, num_classes=num_classes, loss=loss, overlap=overlap_settings(loss, overlap),
-                                  boundary=boundary, lovasz=lovasz)
+                                  boundary=boundary, lovasz=lovasz, average=average_setting(average))
     print(len(neuralnet.visionModel.layers))
     process = Process(batch_size=batch_size, num_classes=num_classes)
     process.training(neuralnet=neuralnet, dataset=dataset, epochs=epochs)
     if save_path is not None:
         neuralnet.visionModel.save(save_path)
+        if average is not None:
+            neuralnet.save_averaged(save_path + ".avg")
     return neuralnet, process
+
+
+def averaging(neuralnet) -> bool:
+    """Whether the model's optimiser keeps averaged weights (``flat.AdamClip(average=...)``)."""
+    return getattr(getattr(neuralnet, "optimizer", None), "avg", None) is not None
+
+
+def average_setting(average):
+    """``average`` of the drivers' ``main``: None, the ``AdamClip(average=...)`` dict, or the command-line string."""
+    if isinstance(average, str):
+        from .flat import parse_average
+        return parse_average(average)
+    return average
+
+
+def _raw_test_loss(neuralnet, dataset) -> float:
+    """One more pass over the test set (batches of 16) for the summed loss alone."""
+    total = None
+    while True:
+        x_te, y_te, terminator = dataset.next_test(16)
+        loss, _ = neuralnet.step(x=x_te, y=y_te)
+        total = loss.detach().reshape(()).clone() if total is None else total.add_(loss.reshape(()))
+        if terminator:
+            return float(total)
 
 
 def reference_schedule() -> PiecewiseConstantDecay:

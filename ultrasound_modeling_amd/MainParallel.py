@@ -42,6 +42,7 @@ Deliberate deviations:
 from __future__ import annotations
 
 import argparse
+import contextlib
 import os
 import random
 from typing import Optional, Tuple
@@ -49,6 +50,7 @@ from typing import Optional, Tuple
 import torch
 import torch.distributed as dist
 from . import knobs
+from .MainNumpy import averaging
 from .metrics import dice_line
 
 
@@ -218,12 +220,22 @@ class Process(object):
             self.test(neuralnet, dataset, epoch)                                                 # :72
 
     def test(self, neuralnet, dataset, epoch):
-        """MainParallel.py:81-115 -> F1 of the test set; its dict (``phase`` "test") is appended to ``history``."""
+        """MainParallel.py:81-115 -> F1 of the test set; its dict (``phase`` "test") is appended to ``history``.  A model built with
+        ``average=`` is tested under ``averaged_weights()`` (every rank holds the same average: same weights, same counter); the report adds
+        the loss of the raw weights (``raw_loss`` in the history)."""
         self._mirror(neuralnet)
         self._print("\nTest...")
-        total_loss = self.mirrored_test_step(neuralnet, dataset)                                 # :86, not divided (:89)
+        averaged = averaging(neuralnet)
+        extra = {}
+        if averaged:
+            extra["raw_loss"] = self.mirrored_test_step(neuralnet, dataset)                      # the weights as they stand, for comparison
+            self.metrics.reset_states()
+        with (neuralnet.averaged_weights() if averaged else contextlib.nullcontext()):
+            total_loss = self.mirrored_test_step(neuralnet, dataset)                             # :86, not divided (:89)
         m = self.metrics.result()
         self._print("loss = {}".format(total_loss))
+        if averaged:
+            self._print("loss (raw weights) = {}".format(extra["raw_loss"]))
         self._print("IoU = {}".format(m["mean_iou"]))
         self._print("f1 = {}".format(m["f1"]))
         self._print("precision = {}".format(m["precision"]))
@@ -231,15 +243,18 @@ class Process(object):
         dice = dice_line(neuralnet, self.metrics)
         if dice is not None:                                    # only with loss="dice" / "tversky" / "dice_ce"
             self._print("dice per class = {}".format(dice))
-        self.history.append(dict(m, phase="test", epoch=epoch, loss=total_loss))
+        self.history.append(dict(m, phase="test", epoch=epoch, loss=total_loss, **extra))
         self.metrics.reset_states()                                                              # :110-114
         return m["f1"]
 
     def save(self, neuralnet, path) -> bool:
-        """``visionModel.save(path)`` on rank 0 only (MainParallel.py:216; every rank holds the same weights) -> whether this rank saved."""
+        """``visionModel.save(path)`` on rank 0 only (MainParallel.py:216; every rank holds the same weights) -> whether this rank saved.
+        A model built with ``average=`` also writes ``<path>.avg``, a plain checkpoint of the averaged weights (``save_averaged``)."""
         rank = dist.get_rank(self.group) if dist.is_initialized() else 0
         if rank == 0:
             neuralnet.visionModel.save(path)
+            if averaging(neuralnet):
+                neuralnet.save_averaged(path + ".avg")
         return rank == 0
 
     def mirrored_train_step(self, neuralnet, dataset) -> float:
@@ -285,7 +300,7 @@ class Process(object):
 
 
 def main(train_path, val_path, save_path=None, epochs=51, batch_size=64, use_vit=True, *, seed=0, schedule=False, capture_graph=True,
-         loss="cce", overlap=None, boundary=None, lovasz=None):
+         loss="cce", overlap=None, boundary=None, lovasz=None, average=None):
     """MainParallel.py:201-216 with the paths as arguments: ``VisionTransformer(batch_size=64)`` with the ViT bottleneck, 51 epochs,
     then rank 0 saves if ``save_path`` is given.  Every rank seeds ``random`` with ``seed``, so all draw the same augmentations.
     ``loss``: the model's ``loss=`` ("cce", "my_loss_cat", "focal"); every replica divides it by the global batch all the same.  The
@@ -294,8 +309,11 @@ def main(train_path, val_path, save_path=None, epochs=51, batch_size=64, use_vit
     ``boundary`` (``VisionTransformer(boundary=...)``) adds the boundary term to one of those three, weighted per replica the same way.
     The Lovasz-softmax loss ("lovasz", "lovasz_ce", settings in ``lovasz``) ranks the pixels of the images a replica holds and is weighted like the
     overlap term; it adds the Dice line too.
+    ``average`` (a dict, or the ``--average`` string ``ema:DECAY[:dynamic]`` / ``swa:START:PERIOD``): EMA / SWA weight averaging; the update of
+    every rank keeps the same average (no exchange is added), the tests report the averaged model and rank 0 also saves ``<save_path>.avg``.
     Under ``nccl`` the model lives on ``cuda:LOCAL_RANK``; the ``USSEG_DIST_BACKEND=gloo`` rehearsal keeps every rank on device 0."""
     from .Dataset import Dataset
+    from .MainNumpy import average_setting
     from .VisionTransformer import VisionTransformer, overlap_settings
     rank, world, local = init_distributed()
     nccl = world > 1 and dist.get_backend() == "nccl"
@@ -304,7 +322,8 @@ def main(train_path, val_path, save_path=None, epochs=51, batch_size=64, use_vit
     random.seed(seed)
     dataset = Dataset(train_path, val_path, batch_size, device=device)
     neuralnet = VisionTransformer(batch_size, img_size=(dataset.height, dataset.width), in_channels=dataset.channel, use_vit=use_vit,
-                                  device=str(device), loss=loss, overlap=overlap_settings(loss, overlap), boundary=boundary, lovasz=lovasz)
+                                  device=str(device), loss=loss, overlap=overlap_settings(loss, overlap), boundary=boundary, lovasz=lovasz,
+                                  average=average_setting(average))
     if rank == 0:
         print(len(neuralnet.visionModel.layers))
     process = Process(batch_size, schedule=schedule, capture_graph=capture_graph)
@@ -332,11 +351,21 @@ def _cli(argv=None):
                          "region-overlap loss (soft Dice, Tversky 0.3 / 0.7, Dice + CCE), or the Lovasz-softmax loss (alone, or CCE + it)")
     ap.add_argument("--boundary-weight", type=float, default=None, metavar="W",
                     help="add the boundary term (signed distance map of the labels times the probabilities) with weight W; needs a region-overlap --loss")
+    ap.add_argument("--average", default=None, metavar="ema:DECAY[:dynamic] | swa:START:PERIOD",
+                    help="keep an EMA or SWA average of the weights inside the optimiser step; the tests report the averaged model and "
+                         "--save also writes SAVE.avg with the averaged weights")
     a = ap.parse_args(argv)
+    if a.average is not None:
+        from .flat import parse_average
+        try:
+            parse_average(a.average)
+        except ValueError as e:
+            raise SystemExit(str(e))
     if a.boundary_weight is not None and a.loss not in ("dice", "tversky", "dice_ce"):
         raise SystemExit("--boundary-weight needs --loss dice, tversky or dice_ce")
     main(a.train, a.val, a.save, epochs=a.epochs, batch_size=a.batch_size, use_vit=not a.no_vit, seed=a.seed, schedule=a.schedule,
-         capture_graph=not a.no_graph, loss=a.loss, boundary=None if a.boundary_weight is None else {"weight": a.boundary_weight})
+         capture_graph=not a.no_graph, loss=a.loss, boundary=None if a.boundary_weight is None else {"weight": a.boundary_weight},
+         average=a.average)
     if dist.is_initialized():
         dist.barrier()
         dist.destroy_process_group()

@@ -491,9 +491,10 @@ class ResNest(TrainStepDriver, PredictDriver):
     """TBI_ResNest.py:15-55.  ``step(x, y, train)`` -> (loss map [H,W], accuracy, probabilities)."""
 
     def __init__(self, height, width, channel, num_class, ksize, radix=4, kpaths=4, learning_rate=1e-3, ckpt_dir="./Checkpoint", *,
-                 device: Optional[str] = None, seed: Optional[int] = 0, weight_decay=None):
+                 device: Optional[str] = None, seed: Optional[int] = 0, weight_decay=None, average=None):
         """``learning_rate`` may be a ``schedules.PiecewiseConstantDecay``; ``weight_decay`` (a float or a schedule) turns on the
-        decoupled weight decay of tfa AdamW (None: plain Adam, as the reference)."""
+        decoupled weight decay of tfa AdamW (None: plain Adam, as the reference).  ``average`` (None: off) is ``flat.AdamClip(average=...)``: an EMA or SWA average of the weights kept by the update
+        kernel; ``averaged_weights()`` computes with it, ``save_averaged(path)`` writes it as a plain checkpoint."""
         if seed is not None:
             torch.manual_seed(seed)
         assert height % 64 == 0 and width % 64 == 0, "six 2x2 poolings: H and W must be multiples of 64"
@@ -506,7 +507,7 @@ class ResNest(TrainStepDriver, PredictDriver):
         self.resModel = _ResModel(height, width, channel, num_class, ksize, radix, kpaths)       # :26
         self.flat = FlatParams(self.resModel, self.device)
         self.resModel.repack()
-        self.optimizer = AdamClip(self.flat, lr=learning_rate, clip_norm=None, weight_decay=weight_decay)   # :28 (no clipping, :46)
+        self.optimizer = AdamClip(self.flat, lr=learning_rate, clip_norm=None, weight_decay=weight_decay, average=average)   # :28 (no clipping, :46)
         self.class_factor = [0.06329, 0.027567, 0.90914]                                        # :30 (unused by my_loss_cat)
         self._loss_map = torch.zeros(height * width, dtype=torch.float32, device=self.device)
         self._scale = torch.zeros(height * width * num_class, dtype=torch.float32, device=self.device)
@@ -534,6 +535,7 @@ class ResNest(TrainStepDriver, PredictDriver):
                 bufs[k].copy_(v.to(torch.float32))
             else:
                 raise KeyError(f"unexpected parameter {k}")
+        self.optimizer.params_loaded()          # before the first step an average starts from these weights
         self.resModel.repack()
 
     def export_params(self) -> dict:

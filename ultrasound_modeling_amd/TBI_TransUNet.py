@@ -30,6 +30,7 @@ when ``r % 2`` (:840-842) BEFORE anything else, runs ``imageReduc`` when ``r % 5
 """
 from __future__ import annotations
 
+import contextlib
 import random
 from typing import List, Optional
 
@@ -37,7 +38,7 @@ import torch
 
 from . import DataAugs
 from . import Dataset_2
-from .MainNumpy import _labels, install_schedule
+from .MainNumpy import _labels, _raw_test_loss, average_setting, averaging, install_schedule
 from .metrics import SegMetrics, dice_line
 from .schedules import PiecewiseConstantDecay
 from .VisionTransformer import VisionTransformer as _VisionTransformer, overlap_settings
@@ -52,14 +53,14 @@ class VisionTransformer(_VisionTransformer):
                  in_channels: int = 10, device: Optional[str] = None, seed: Optional[int] = 0, adamw: bool = False,
                  loss: str = "cce", class_factor=None, focal_gamma=None, overlap=None,
                  alpha=None, beta=None, smooth=None, power=None, class_weight=None, ce_weight=None, ov_weight=None, boundary=None,
-                 lovasz=None):
+                 lovasz=None, average=None):
         """``loss`` / ``class_factor`` / ``focal_gamma`` / ``overlap`` / ``boundary`` / ``lovasz``: as in the newer model (``VisionTransformer.VisionTransformer``), with this file's
         reduction - the mean over the B*H*W pixels of the batch (the overlap term of "dice" / "tversky" / "dice_ce" is a ratio of sums and has weight 1, and so
-        has the Lovasz term of "lovasz" / "lovasz_ce")."""
+        has the Lovasz term of "lovasz" / "lovasz_ce").  ``average``: the newer model's (EMA / SWA weight averaging)."""
         super().__init__(batch_size, img_size, num_classes, learning_rate, weight_decay, in_channels=in_channels, use_vit=True,
                          device=device, seed=seed, transunet=True, adamw=adamw, loss=loss, class_factor=class_factor, focal_gamma=focal_gamma,
                          overlap=overlap, alpha=alpha, beta=beta, smooth=smooth, power=power, class_weight=class_weight, ce_weight=ce_weight,
-                         ov_weight=ov_weight, boundary=boundary, lovasz=lovasz)
+                         ov_weight=ov_weight, boundary=boundary, lovasz=lovasz, average=average)
 
     def step(self, x, y, train=False):
         """TBI_TransUNet.py:571-588 -> (loss, probabilities); ``train=True`` also clips and applies the gradients."""
@@ -163,17 +164,22 @@ def test(neuralnet, dataset, epoch):
     (:968).  Its dict (``phase`` "test") is appended to ``history``."""
     print("\nTest...")
     m = SegMetrics(3, round=True, device=neuralnet.device)             # precision / recall / pre_c2 / re_c2 / mio (:749-753)
+    averaged = averaging(neuralnet)   # built with average=: the averaged model is tested, the raw loss reported too
+    extra = {"raw_loss": _raw_test_loss(neuralnet, dataset) / dataset.num_te} if averaged else {}
     total_loss = None
-    while True:
-        x_te, y_te, terminator = dataset.next_test(16)                                               # :946
-        loss, class_score = neuralnet.step(x=x_te, y=y_te, train=False)                              # :947
-        total_loss = loss.detach().reshape(()).clone() if total_loss is None else total_loss.add_(loss.reshape(()))   # :956, on the device
-        m.update_state(_labels(y_te, class_score), class_score)                                      # :949-956
-        if terminator:
-            break
+    with (neuralnet.averaged_weights() if averaged else contextlib.nullcontext()):
+        while True:
+            x_te, y_te, terminator = dataset.next_test(16)                                           # :946
+            loss, class_score = neuralnet.step(x=x_te, y=y_te, train=False)                          # :947
+            total_loss = loss.detach().reshape(()).clone() if total_loss is None else total_loss.add_(loss.reshape(()))   # :956, on the device
+            m.update_state(_labels(y_te, class_score), class_score)                                  # :949-956
+            if terminator:
+                break
     total_loss = float(total_loss) / dataset.num_te                                                  # :968
     r = m.result()
     print("loss = {}".format(total_loss))
+    if averaged:
+        print("loss (raw weights) = {}".format(extra["raw_loss"]))
     print("IoU = {}".format(r["mean_iou"]))
     print("f1 = {}".format(r["f1"]))
     print("precision = {}".format(r["precision"]))
@@ -181,20 +187,23 @@ def test(neuralnet, dataset, epoch):
     dice = dice_line(neuralnet, m)
     if dice is not None:                                        # only with loss="dice" / "tversky" / "dice_ce"
         print("dice per class = {}".format(dice))
-    history.append(dict(r, phase="test", epoch=epoch, loss=total_loss))
+    history.append(dict(r, phase="test", epoch=epoch, loss=total_loss, **extra))
     return r["f1"]
 
 
-def main(train_path, val_path, save_path=None, epochs=51, batch_size=16, *, loss="cce", overlap=None, boundary=None, lovasz=None):
+def main(train_path, val_path, save_path=None, epochs=51, batch_size=16, *, loss="cce", overlap=None, boundary=None, lovasz=None, average=None):
     """:997-1010 with the paths as arguments: 256x80x10 input, batch 16, 51 epochs, then a save if ``save_path`` is given.
     ``loss``: the model's ``loss=`` ("cce", "my_loss_cat", "focal", "dice", "tversky", "dice_ce"); ``overlap``: the settings of the last three,
     which also add a per-class Dice line to the test report; ``boundary``: the boundary term on top of one of those three; "lovasz" / "lovasz_ce" with their
-    settings in ``lovasz`` (the Lovasz-softmax loss; the Dice line too)."""
+    settings in ``lovasz`` (the Lovasz-softmax loss; the Dice line too).  ``average`` (a dict, or ``ema:DECAY[:dynamic]`` / ``swa:START:PERIOD``):
+    EMA / SWA weight averaging - ``test`` reports the averaged model and the save also writes ``<save_path>.avg`` (``save_averaged``)."""
     dataset = Dataset(train_path, val_path)
     neuralnet = VisionTransformer(img_size=input_size, num_classes=3, learning_rate=1e-3, batch_size=batch_size, loss=loss, overlap=overlap_settings(loss, overlap),
-                                  boundary=boundary, lovasz=lovasz)
+                                  boundary=boundary, lovasz=lovasz, average=average_setting(average))
     print(len(neuralnet.visionModel.layers))
     training(neuralnet=neuralnet, dataset=dataset, epochs=epochs, batch_size=batch_size)
     if save_path is not None:
         neuralnet.visionModel.save(save_path)
+        if average is not None:
+            neuralnet.save_averaged(save_path + ".avg")
     return neuralnet

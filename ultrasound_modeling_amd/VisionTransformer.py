@@ -392,7 +392,7 @@ class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
                  in_channels: int = 10, use_vit: bool = False, device: Optional[str] = None, seed: Optional[int] = 0,
                  transunet: bool = False, adamw: bool = False, loss: str = "cce", class_factor=None, focal_gamma=None,
                  overlap=None, alpha=None, beta=None, smooth=None, power=None, class_weight=None, ce_weight=None, ov_weight=None,
-                 boundary=None, lovasz=None):
+                 boundary=None, lovasz=None, average=None):
         """``transunet=True`` builds the older self-contained copy of this model in TBI_TransUNet.py (BASELINE configs[3]):
         BatchNormalization where ResNest.py / Decoder.py use LayerNormalization (:304,426,465,472,503), conv_4 = 256 channels
         (:368), and the loss is CategoricalCrossentropy(label_smoothing=0.1) with the DEFAULT reduction - the mean over all
@@ -433,7 +433,10 @@ class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
         average over the classes with a foreground pixel in the batch, the paper's default; "all"), ``class_weight`` (1 per class),
         ``lv_weight`` (1), ``ce_weight`` (lovasz_ce only, 1), ``threshold`` (0.5: the foreground of a soft label).  Every step sorts the
         B*H*W errors of each class on the device (``ops.sort_pairs``' kernels); the term is weighted like the overlap term.  ``boundary`` does not
-        combine with it."""
+        combine with it.
+
+        ``average`` (None: off) is ``flat.AdamClip(average=...)``: an EMA or SWA average of the weights kept by the update
+        kernel; ``averaged_weights()`` computes with it, ``save_averaged(path)`` writes it as a plain checkpoint."""
         super().__init__()
         if loss not in LOSSES + OVERLAP_LOSSES + LOVASZ_LOSSES:
             raise ValueError(f"loss must be one of {LOSSES + OVERLAP_LOSSES + LOVASZ_LOSSES}, got {loss!r}")
@@ -489,7 +492,7 @@ class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
         self.device = torch.device(dev)
         self.flat = FlatParams(self, self.device)
         self.optimizer = AdamClip(self.flat, lr=learning_rate, clip_norm=1.0,          # :204,:244
-                                  weight_decay=weight_decay if adamw else None)
+                                  weight_decay=weight_decay if adamw else None, average=average)
         self._loss = torch.zeros(ops.ACC_FLOATS if self._overlap is None and self._lovasz is None else ops.OVERLAP_ACC_FLOATS, dtype=torch.float32,
                                  device=self.device)                                         # [0] = the scalar loss
         self._boundary, self._boundary_thr, self._wb = None, 0.5, None
@@ -572,6 +575,7 @@ class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
                 bufs[k].copy_(v.to(torch.float32))
             else:
                 raise KeyError(f"unexpected parameter {k}")
+        self.optimizer.params_loaded()          # before the first step an average starts from these weights
         repack_all(self)
 
     def repack(self):

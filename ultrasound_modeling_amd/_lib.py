@@ -330,6 +330,9 @@ _PROTOS = {
     "usseg_score_sweep": (C.c_int, [P(SweepDesc), c_vp, c_vp, c_vp, c_vp]),
     "usseg_temperature_nll": (C.c_int, [P(TempDesc), c_vp, c_vp, P(c_f32), c_vp, c_vp]),
     "usseg_apply_temperature": (C.c_int, [P(TempDesc), c_vp, c_vp, c_vp, c_vp]),
+    "usseg_adamw_avg_step": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_f32, c_vp, c_vp, c_vp, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp]),
+    "usseg_average_update": (C.c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "usseg_swap_f32": (C.c_int, [c_vp, c_vp, c_i64, c_vp]),
 }
 EXPORTED_SYMBOLS = tuple(_PROTOS)
 

@@ -2,6 +2,7 @@
 // and the optimiser (global-norm clip + Adam) for gfx950.  The big tensors are streamed 16 bytes per lane; the
 // MLP is a few hundred FLOPs per workgroup and runs in fp32 out of LDS.
 #include "common.h"
+#include "optim_elem.h"
 #include <cmath>
 
 static inline int lanes_per_pixel(int chunks) {
@@ -1410,25 +1411,7 @@ extern "C" int usseg_sumsq_sched_advance(const float* g, int64_t n, float* out, 
   return usseg_check_launch("sumsq_sched_advance");
 }
 
-// tfa DecoupledWeightDecayExtension: p - wd_t*p, two roundings (a fused multiply-add would round once)
-__device__ __forceinline__ float decoupled_decay(float p, float wd_t) {
-#pragma clang fp contract(off)
-  return p - wd_t * p;
-}
-// one element of the update: the decay (if on), then adam_kernel's arithmetic on the decayed p.  adam_kernel's two moment statements
-// compile to fma(b1, m, (1-b1)*g') and fma(b2, v, ((1-b2)*g')*g'); left to contraction, the scalar tail here fused the OTHER product
-// (fma((1-b1), g', b1*m)), which differs in the last bit now and then, so the contraction is written out
-__device__ __forceinline__ void adamw_elem(float& p, float g, float& m, float& v, bool decay, float scale, float lr_t, float wd_t, float b1, float b2,
-                                           float eps) {
-  float pi = decay ? decoupled_decay(p, wd_t) : p;
-  float gi = g * scale;
-  float mi = fmaf(b1, m, (1.f - b1) * gi);
-  float vi = fmaf(b2, v, (1.f - b2) * gi * gi);
-  m = mi;
-  v = vi;
-  pi -= lr_t * mi / (sqrtf(vi) + eps);
-  p = pi;
-}
+// decoupled_decay and adamw_elem, one element of the update: optim_elem.h (shared with the averaging update of average.hip)
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                                                      int64_t n, const float* sumsq, float clip_norm, const float* lr_t_dev, const float* wd_t_dev,
                                                      const uint8_t* __restrict__ mask, float b1, float b2, float eps) {

@@ -96,11 +96,21 @@ class AdamClip:
     decay the rates come from a device table (``UssegLrSchedule``) read at the device step counter by the step kernels, so
     ``set_learning_rate`` / ``set_weight_decay`` reach a captured graph's next replay without a recapture.  A float ``lr`` with no
     decay launches exactly the fixed-rate kernels it always did.  
+
+    ``average`` (None: off - nothing is allocated, nothing new is launched, ``state_dict()`` keeps its keys) keeps an average of the weights
+    along the trajectory in one more flat fp32 buffer ``avg``, initialised to the weights as tfa initialises its slot to the variable:
+      * ``{"mode": "ema", "decay": 0.999, "dynamic_decay": False, "start_step": 0}``: tfa.optimizers.MovingAverage;
+      * ``{"mode": "swa", "start": S, "period": P}``: tfa.optimizers.SWA - the arithmetic mean of the weights after steps S, S+P, S+2P, ...
+    The update kernel of ``apply_range`` becomes the one that also blends ``avg`` (``ops.adamw_avg_step``: one more read and one more
+    write per parameter, no further launch), on the table path and on the fixed-rate path alike; ``flat``, ``m`` and ``v`` get the bits they
+    get without averaging.  The settings live in a device descriptor (``UssegAverage``), so ``set_average_decay`` reaches a captured
+    graph's next replay.  BatchNorm moving statistics are not variables and are not averaged.
     """
 
     def __init__(self, flat: FlatParams, lr=1e-3, clip_norm: Optional[float] = 1.0, beta1=0.9, beta2=0.999, eps=1e-7, weight_decay=None,
-                 decay_exclude: Optional[Sequence[str]] = None):
+                 decay_exclude: Optional[Sequence[str]] = None, average: Optional[dict] = None):
         self.flat, self.clip_norm = flat, clip_norm
+        self.average = None if average is None else average_config(average)
         self.lr = _rate(lr, "lr")
         self.weight_decay = None if weight_decay is None else _rate(weight_decay, "weight_decay")
         self.b1, self.b2, self.eps = beta1, beta2, eps
@@ -116,6 +126,46 @@ class AdamClip:
         self._captured = False
         if isinstance(self.lr, PiecewiseConstantDecay) or self.weight_decay is not None:
             self._enable_table()
+        self.avg = self.avg_desc = None
+        self._avg_from_weights = False       # set by a checkpoint without an average: the next ``params_loaded`` starts it from the weights
+        if self.average is not None:
+            self.avg = flat.flat.detach().clone()
+            self.avg_desc = torch.zeros(ops.AVERAGE_WORDS, dtype=torch.int32, device=dev)
+            self._write_average()
+
+    # ---- the weight average -----------------------------------------------------------------------------------------
+    def _write_average(self):
+        """Stream-ordered copy of the host descriptor: a step (or graph replay) enqueued after it blends with the new settings."""
+        self.avg_desc.copy_(torch.from_numpy(_average_words(self.average)))
+
+    def set_average_decay(self, decay):
+        """EMA decay from the next step on (eager or replayed)."""
+        if self.average is None or self.average["mode"] != "ema":
+            raise ValueError("set_average_decay: the optimiser was built without average={'mode': 'ema', ...}")
+        self.average = average_config(dict(self.average, decay=decay))
+        self._write_average()
+
+    def average_state(self):
+        """(mode, t, snapshots taken so far) from the device step counter and descriptor.  Synchronises: for logging."""
+        if self.average is None:
+            return None
+        w = self.avg_desc.cpu().numpy()
+        t = int(self.step_dev.item())
+        mode, start, period = int(w[0]), int(w[3]), max(int(w[4]), 1)
+        if mode == ops.AVERAGE_MODES["swa"]:
+            return "swa", t, 0 if t < start else (t - start) // period + 1
+        return "ema", t, max(t - start, 0)
+
+    def swap_average(self):
+        """Exchanges ``flat.flat`` and ``avg`` in place (one launch, no pointer changes): ``TrainStepDriver.averaged_weights`` calls it twice."""
+        ops.swap_f32(self.flat.flat, self.avg)
+
+    def params_loaded(self):
+        """The model calls this after weights were written into ``flat`` from outside (``load_params``): before the first step, or after a
+        checkpoint that carried no average, the average starts from those weights.  Synchronises (reads the step counter)."""
+        if self.avg is not None and (self._avg_from_weights or int(self.step_dev.item()) == 0):
+            self.avg.copy_(self.flat.flat)
+        self._avg_from_weights = False
 
     # ---- the device table -------------------------------------------------------------------------------------------
     @property
@@ -182,6 +232,11 @@ class AdamClip:
     def apply_range(self, lo: int, hi: int, clip: float = 0.0):
         """Adam update of flat[lo:hi] (elementwise, so any partition of the buffer gives the same result as one launch)."""
         f = self.flat
+        if self.avg is not None:             # the update and the average in one launch; wd_t_dev None = the fixed-rate arithmetic
+            mask = None if self.decay_mask is None or self.sched_dev is None else self.decay_mask[lo:hi]
+            ops.adamw_avg_step(f.flat[lo:hi], f.grad[lo:hi], self.m[lo:hi], self.v[lo:hi], self.avg[lo:hi], self.sumsq, clip, self.lr_t_dev,
+                               self.wd_t_dev, mask, self.b1, self.b2, self.eps, self.step_dev, self.avg_desc)
+            return
         if self.sched_dev is not None:
             mask = None if self.decay_mask is None else self.decay_mask[lo:hi]
             ops.adamw_step(f.flat[lo:hi], f.grad[lo:hi], self.m[lo:hi], self.v[lo:hi], self.sumsq, clip, self.lr_t_dev, self.wd_t_dev, mask,
@@ -205,17 +260,22 @@ class AdamClip:
 
     def state_tensors(self):
         t = [self.m, self.v, self.step_dev, self.lr_t_dev]
-        return t if self.sched_dev is None else t + [self.sched_dev, self.wd_t_dev]
+        t = t if self.sched_dev is None else t + [self.sched_dev, self.wd_t_dev]
+        return t if self.avg is None else t + [self.avg, self.avg_desc]
 
     def state_dict(self):
         """Adam moments in the flat layout + the step counter (what Keras saves with a compiled model); + the rate table if one is used."""
         d = {"__adam_m__": self.m.detach().clone(), "__adam_v__": self.v.detach().clone(), "__adam_step__": self.step_dev.detach().clone()}
         if self.sched_dev is not None:
             d["__adam_sched__"] = self.sched_dev.detach().clone()
+        if self.avg is not None:
+            d["__adam_avg__"] = self.avg.detach().clone()
+            d["__adam_avg_desc__"] = self.avg_desc.detach().clone()
         return d
 
     def load_state_dict(self, d):
         if not d:
+            self._avg_from_weights = self.avg is not None        # a plain checkpoint: the average starts from its weights (params_loaded)
             return
         self.m.copy_(d["__adam_m__"].to(self.m.device))
         self.v.copy_(d["__adam_v__"].to(self.v.device))
@@ -223,6 +283,14 @@ class AdamClip:
         if "__adam_sched__" in d:           # the saved schedule / decay replace the constructor's; the step counter selects the piece
             self.lr, self.weight_decay = _from_table(d["__adam_sched__"].cpu().numpy().astype(np.int32))
             self._enable_table()
+        if self.avg is not None:            # (a checkpoint's average is ignored by an optimiser built without one)
+            if "__adam_avg__" in d:         # the saved settings replace the constructor's, like the rate table
+                self.avg.copy_(d["__adam_avg__"].to(self.avg.device))
+                self.average = _average_from_words(d["__adam_avg_desc__"].cpu().numpy().astype(np.int32))
+                self._write_average()
+            else:                           # no average in the checkpoint: it starts from the weights the caller loads next
+                self._avg_from_weights = True
+                self.avg.copy_(self.flat.flat)
 
 
 # ---------------------------------------------------------------------------------------------------- table helpers
@@ -282,3 +350,66 @@ def _decay_mask(flat: FlatParams, exclude) -> Optional[torch.Tensor]:
     for o, n in hit:
         mask[o:o + n] = 0
     return mask.to(flat.device)
+
+
+# ---------------------------------------------------------------------------------------------------- weight averaging
+_EMA_KEYS = {"mode", "decay", "dynamic_decay", "start_step"}
+_SWA_KEYS = {"mode", "start", "period"}
+
+
+def average_config(average: dict) -> dict:
+    """Validated copy of ``AdamClip(average=...)`` with every default filled in; ValueError on a bad mode, key or number."""
+    if not isinstance(average, dict) or "mode" not in average:
+        raise ValueError(f"average must be a dict with a 'mode' ('ema' or 'swa'), got {average!r}")
+    mode = average["mode"]
+    if mode not in ops.AVERAGE_MODES:
+        raise ValueError(f"average: mode must be one of {tuple(ops.AVERAGE_MODES)}, got {mode!r}")
+    keys = _EMA_KEYS if mode == "ema" else _SWA_KEYS
+    if set(average) - keys:
+        raise ValueError(f"average: unknown keys {sorted(set(average) - keys)} for mode {mode!r} (it takes {sorted(keys)})")
+
+    def integer(name, default, lo):
+        v = average.get(name, default)
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v < 2 ** 31:
+            raise ValueError(f"average: {name} must be an integer >= {lo}, got {v!r}")
+        return int(v)
+    if mode == "ema":
+        decay = float(average.get("decay", 0.999))
+        if not (0.0 <= decay and np.float32(decay) < 1.0):          # as the device reads it, in fp32 (NaN fails both comparisons)
+            raise ValueError(f"average: decay must be in [0, 1), got {decay}")
+        return {"mode": "ema", "decay": decay, "dynamic_decay": bool(average.get("dynamic_decay", False)),
+                "start_step": integer("start_step", 0, 0)}
+    return {"mode": "swa", "start": integer("start", 0, 0), "period": integer("period", 1, 1)}
+
+
+def parse_average(text: str) -> dict:
+    """The drivers' ``--average`` string: ``ema:DECAY[:dynamic]`` or ``swa:START:PERIOD`` -> the validated ``average=`` dict."""
+    parts = str(text).split(":")
+    try:
+        if parts[0] == "ema" and len(parts) in (2, 3) and (len(parts) == 2 or parts[2] == "dynamic"):
+            return average_config({"mode": "ema", "decay": float(parts[1]), "dynamic_decay": len(parts) == 3})
+        if parts[0] == "swa" and len(parts) == 3:
+            return average_config({"mode": "swa", "start": int(parts[1]), "period": int(parts[2])})
+    except ValueError as e:
+        raise ValueError(f"--average {text!r}: {e}") from None
+    raise ValueError(f"--average {text!r}: expected ema:DECAY[:dynamic] or swa:START:PERIOD")
+
+
+def _average_words(cfg: dict) -> np.ndarray:
+    """UssegAverage as int32[5]."""
+    w = np.zeros(ops.AVERAGE_WORDS, dtype=np.int32)
+    w[0] = ops.AVERAGE_MODES[cfg["mode"]]
+    if cfg["mode"] == "ema":
+        w[1] = np.array([cfg["decay"]], dtype=np.float32).view(np.int32)[0]
+        w[2], w[3], w[4] = int(cfg["dynamic_decay"]), cfg["start_step"], 1
+    else:
+        w[3], w[4] = cfg["start"], cfg["period"]
+    return w
+
+
+def _average_from_words(w: np.ndarray) -> dict:
+    if int(w[0]) == ops.AVERAGE_MODES["ema"]:
+        return average_config({"mode": "ema", "decay": float(w[1:2].view(np.float32)[0]), "dynamic_decay": bool(w[2]), "start_step": int(w[3])})
+    if int(w[0]) == ops.AVERAGE_MODES["swa"]:
+        return average_config({"mode": "swa", "start": int(w[3]), "period": int(w[4])})
+    raise ValueError(f"AdamClip: a saved average descriptor with mode {int(w[0])}")

@@ -1000,6 +1000,33 @@ def adamw_step(p, g, m, v, sumsq_t, clip_norm, lr_t_dev, wd_t_dev, decay_mask, b
                                       lr_t_dev.data_ptr(), wd_t_dev.data_ptr(), _ptr(decay_mask), b1, b2, eps, _stream()), "adamw_step")
 
 
+# UssegAverage as int32[5]: mode, decay bits, dynamic_decay, start, period (usseg.h; flat.AdamClip keeps it on the device)
+AVERAGE_MODES = {"ema": 1, "swa": 2}
+AVERAGE_WORDS = 5
+
+
+def adamw_avg_step(p, g, m, v, avg, sumsq_t, clip_norm, lr_t_dev, wd_t_dev, decay_mask, b1, b2, eps, step_dev, avg_desc):
+    """``adamw_step`` (``wd_t_dev`` None: no decay, the fixed-rate arithmetic) and the EMA / SWA average of the updated ``p`` in one launch;
+    the blend coefficient comes from the device descriptor ``avg_desc`` at the device step counter."""
+    assert avg.dtype == torch.float32 and avg.numel() == p.numel() and avg_desc.numel() >= AVERAGE_WORDS
+    L.check(L.load().usseg_adamw_avg_step(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), avg.data_ptr(), p.numel(), _ptr(sumsq_t),
+                                          clip_norm, lr_t_dev.data_ptr(), _ptr(wd_t_dev), _ptr(decay_mask), b1, b2, eps, step_dev.data_ptr(),
+                                          avg_desc.data_ptr(), _stream()), "adamw_avg_step")
+
+
+def average_update(avg, p, step_dev, avg_desc):
+    """The average alone (``p`` updated elsewhere): the same bits of ``avg`` as ``adamw_avg_step``."""
+    assert avg.dtype == torch.float32 and p.dtype == torch.float32 and avg.numel() == p.numel() and avg_desc.numel() >= AVERAGE_WORDS
+    L.check(L.load().usseg_average_update(avg.data_ptr(), p.data_ptr(), p.numel(), step_dev.data_ptr(), avg_desc.data_ptr(), _stream()),
+            "average_update")
+
+
+def swap_f32(a: torch.Tensor, b: torch.Tensor):
+    """Exchanges two disjoint contiguous fp32 buffers in place."""
+    assert a.dtype == torch.float32 and b.dtype == torch.float32 and a.is_contiguous() and b.is_contiguous() and a.numel() == b.numel()
+    L.check(L.load().usseg_swap_f32(a.data_ptr(), b.data_ptr(), a.numel(), _stream()), "swap_f32")
+
+
 # ------------------------------------------------------------------------------------------------ fused stem
 def stem_fwd(x, w1, b1, w2, b2, w3, b3, gamma, beta, mean, var, eps, alpha):
     """ResNest.py:39-47 in one launch -> (y1 [B,H,W,16], t1 [B,H,W,32], c2 [B,H,W,32] pre-norm, pooled [B,H/2,W/2,32])."""

@@ -71,6 +71,7 @@ class TrainStepDriver:
         self._repack()
 
     def _train_body(self, x, y):
+        self._not_averaged()
         probs = self._grad_body(x, y)
         if self.grad_sync is not None:
             self._sync_and_update()
@@ -84,6 +85,7 @@ class TrainStepDriver:
         joined, so no rank waits on it, and the weights stay identical.  The per-replica clip of a zero gradient is a no-op
         (scale = clip / max(0, clip) = 1), so the replica adds exactly nothing to the sum.  With a captured step the update replays
         the captured update graph; a single replica (no ``grad_sync``) takes one Adam step on the zero gradient."""
+        self._not_averaged()
         self._zero_grad()
         if self.grad_sync is None:
             self._update_body()
@@ -95,6 +97,44 @@ class TrainStepDriver:
             g2.replay()
         else:
             self._sync_and_update()
+
+    # ------------------------------------------------------------------ the averaged weights (flat.AdamClip(average=...))
+    _averaged = False
+
+    def _not_averaged(self):
+        if self._averaged:
+            raise RuntimeError("a training step inside averaged_weights(): the weight buffer holds the averages; leave the block first")
+
+    @contextlib.contextmanager
+    def averaged_weights(self, repack: bool = True):
+        """Inside the block the model computes with the optimiser's averaged weights (EMA / SWA): ``flat.flat`` and ``optimizer.avg`` are
+        exchanged IN PLACE (``AdamClip.swap_average``) and the bf16 GEMM operands rebuilt, and exchanged back on the way out.  No pointer changes, so
+        captured training and predict graphs stay valid, and a predict graph replayed inside the block reads the averaged operands.
+        BatchNorm moving statistics are NOT averaged (tfa averages trainable variables only): inside the block they are the raw model's.
+        A training step inside the block raises.  ``repack=False`` skips both operand rebuilds (for reading the fp32 weights only)."""
+        opt = self.optimizer
+        if getattr(opt, "avg", None) is None:
+            raise ValueError("averaged_weights: the model was built without average=")
+        if self._averaged:
+            raise RuntimeError("averaged_weights: already inside the block")
+        opt.swap_average()
+        if repack:
+            self._repack()
+        self._averaged = True
+        try:
+            yield self
+        finally:
+            self._averaged = False
+            opt.swap_average()
+            if repack:
+                self._repack()
+
+    def save_averaged(self, path):
+        """A plain checkpoint whose variables are the averaged weights (BatchNorm statistics as they are, no optimiser state): every loader
+        of a model file reads it with no new knowledge - ``load``, the evaluator's ``--bleed`` / ``--bleed-extra``, ``Cascade``, ``Ensemble``."""
+        with self.averaged_weights(repack=False):
+            d = self.export_params()
+        torch.save(d, path)
 
     # ------------------------------------------------------------------ HIP-graph replay of the whole step
     def capture_graph(self, x, y, warmup: int = 2):
@@ -153,6 +193,7 @@ class TrainStepDriver:
         """-> the STATIC probability buffer of the captured step (overwritten by the next replay)."""
         # a producer that writes the batch straight into the captured step's input buffers (``graph_inputs()``: the device input
         # pipeline, a data loader with pinned staging) skips these two copies
+        self._not_averaged()
         if x.data_ptr() != self._gx.data_ptr():
             self._gx.copy_(x)
         if y.data_ptr() != self._gy.data_ptr():
