@@ -1117,7 +1117,7 @@ int usseg_prep_aug(const UssegPrepAugDesc* d, const UssegPrepAugSample* samples_
 
 /* ---- the evaluator's cone figures (cone.hip; TBIEvaluator.Display, TBIEvaluator.py:276-355 of the reference) ---------------------------
  * pcolormesh(X, Y, C[:-1, :-1], shading='flat') scan-converted at px_per_unit pixels per axis unit, then colour-mapped; DESIGN.md
- * section 4i.  All arithmetic fp64 without fused multiply-adds; every result is order-independent: bitwise reproducible.
+ * section 4h-2.  All arithmetic fp64 without fused multiply-adds; every result is order-independent: bitwise reproducible.
  * usseg_cone_index: X, Y fp64 [H][W] (H, W >= 2); quad q = i*(W-1) + j has the vertices (i,j), (i,j+1), (i+1,j+1), (i+1,j).  Pixel
  * (r, c) of index int32 [Hp][Wp] samples (xmin + (c+0.5)/ppu, ymin + (r+0.5)/ppu) and holds the largest q whose nonzero winding number
  * there is not 0 (half-open crossing rule), or -1.  Hp*Wp*4 bytes must fit int32.  Non-finite quads cover nothing. */
@@ -1218,6 +1218,44 @@ typedef struct UssegTempDesc {
 int usseg_temperature_nll(const UssegTempDesc* d, const float* probs, const float* y_true, const float* betas, int64_t* counts,
                           usseg_stream_t stream);
 int usseg_apply_temperature(const UssegTempDesc* d, const float* probs, const float* beta_dev, float* out, usseg_stream_t stream);
+
+/* ---- elastic and affine warp of a training batch (not in the reference; csrc/warp.hip) --------------
+ * x [B,H,W,C] fp32 or fp64 and y [B,H,W] fp32 -> x_out, y_out of the same shapes and dtypes, every output pixel (i, j) sampled at a source
+ * coordinate that an affine map and a smoothed random displacement give.  Two launches whatever B, the sizes and the draws are; nothing
+ * allocates or synchronises with the host; the sample table and the weights are read from the device on every launch, so a captured graph
+ * follows them.  All coordinate and interpolation arithmetic is fp64 without fused multiply-adds, every sum in the stated order:
+ *   field     u[b][k][i][j], k = 0 rows / 1 columns: `field` as it is if given, else h * 2^-31 - 1 with h the low 32 bits of the 64-bit
+ *             finaliser of usseg_augment's noise applied to seed * 0x9e3779b97f4a7c15 + ((k*H + i)*W + j) (wrapping): uniform on [-1, 1).
+ *   smoothing a separable Gaussian with zero padding, along H and then along W: s[p] = sum over k = -radius..radius ascending of
+ *             w[|k|] * u[p + k], starting from +0.0, taps outside the image skipped; radius == 0 passes u through unchanged.
+ *   source    src0 = ((A00*i + A01*j) + o0) + alpha[0]*s0, src1 = ((A10*i + A11*j) + o1) + alpha[1]*s1, each operation rounded.
+ *   image     bilinear: i0 = floor(src0), f0 = src0 - i0 (likewise src1); out = ((w00*v00 + w01*v01) + w10*v10) + w11*v11 with
+ *             w00 = (1-f0)*(1-f1), w01 = (1-f0)*f1, w10 = f0*(1-f1), w11 = f0*f1; a tap outside the image is 0 and is not read; a coordinate
+ *             that is not finite or not inside (-1, H) x (-1, W) gives 0 (tested in fp64 before any integer is formed); rounded ONCE to x's dtype.
+ *   label     nearest: y[floor(src0 + 0.5)][floor(src1 + 0.5)], 0 outside; never interpolated.
+ *   inactive  active == 0: x_out and y_out are copies of that sample's x and y, bit for bit; its disp_out and field_out are 0.
+ * disp_out (alpha[k]*s_k) and field_out (the field that was used) are optional [B][2][H][W] fp64 outputs.  x_out / y_out must not
+ * overlap x / y.  Every argument is checked before any launch (USSEG_ERR_BAD_ARG with usseg_last_error text): a null pointer, B, H, W or C
+ * below 1, B*H*W*C >= 2^31, a radius outside [0, USSEG_WARP_MAX_RADIUS], a workspace below usseg_warp_ws_bytes, overlapping buffers. */
+#define USSEG_WARP_MAX_RADIUS 64
+typedef struct UssegWarpSample {
+  int32_t active, reserved;
+  uint64_t seed;
+  double alpha[2];   /* rows, cols */
+  double aff[6];     /* A00, A01, A10, A11, o0, o1 */
+} UssegWarpSample;
+typedef struct UssegWarpDesc { int32_t B, H, W, C, x_is_f64, radius; } UssegWarpDesc;
+
+int64_t usseg_warp_ws_bytes(int32_t B, int32_t H, int32_t W);   /* 0 for a B, H or W below 1 */
+int usseg_elastic_warp(const UssegWarpDesc* d, const UssegWarpSample* samples_dev,
+                       const double* weights_dev /* [radius+1], w[0] the centre tap */,
+                       const double* field /* nullable, [B][2][H][W] */,
+                       const void* x, const float* y,
+                       void* ws, int64_t ws_bytes,
+                       void* x_out, float* y_out,
+                       double* disp_out /* nullable, [B][2][H][W] */,
+                       double* field_out /* nullable, [B][2][H][W] */,
+                       usseg_stream_t stream);
 
 #ifdef __cplusplus
 }

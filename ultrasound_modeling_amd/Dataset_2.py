@@ -34,9 +34,11 @@ def label2vec(label: torch.Tensor, num_classes: int) -> torch.Tensor:
 class Dataset(object):
     draw = staticmethod(draw)       # one sample's augmentation draws (DataAugs.draw); TBI_TransUNet.Dataset draws its script's
 
-    def __init__(self, train_path=None, val_path=None, num_classes=3, device="cuda", train_data=None, val_data=None):
+    def __init__(self, train_path=None, val_path=None, num_classes=3, device="cuda", train_data=None, val_data=None, warp=None, warp_seed=0):
         """``train_data`` / ``val_data``: arrays of the on-disk layout [N,1,H,W,12] (label, 10 displacement channels, bMode;
-        Dataset_2.py:33-43) may be passed instead of paths."""
+        Dataset_2.py:33-43) may be passed instead of paths.  ``warp`` (default None: off; a ``warp.warp_config`` dict or ``parse_warp``
+        string): every TRAINING batch is warped elastically and affinely on the device before ``dataAug_batch`` sees it; the warp's draws come
+        from ``random.Random(warp_seed)``, never from the generator of ``draw``."""
         train_data = np.load(train_path, allow_pickle=False) if train_data is None else np.asarray(train_data)
         val_data = np.load(val_path, allow_pickle=False) if val_data is None else np.asarray(val_data)
         self.device = torch.device(device)
@@ -51,12 +53,32 @@ class Dataset(object):
         self.height, self.width, self.channel = (int(v) for v in self.x_te.shape[1:])
         self.min_val, self.max_val = float(self.x_te[0].min()), float(self.x_te[0].max())
         self.num_classes = num_classes
+        self.warp = None
+        if warp is not None:
+            import random
+            from .warp import warp_config
+            self.warp, self.warp_rng = warp_config(warp), random.Random(warp_seed)
+
+    def draw_warps(self, n):
+        """The warp draws of ``n`` samples, in sample order, from the warp's own generator (None without ``warp``)."""
+        if self.warp is None:
+            return None
+        from .warp import draw_warp
+        return [draw_warp(self.warp_rng, self.warp, self.height, self.width) for _ in range(n)]
+
+    def warped(self, x, y, warp_params):
+        """(x, y) of a training batch warped by ``warp_params`` (as they are without ``warp``)."""
+        if self.warp is None:
+            return x, y
+        from .warp import warp_batch
+        return warp_batch(x, y, warp_params, self.warp)
 
     def reset_idx(self):
         self.idx_tr, self.idx_te = 0, 0
 
     def next_train(self, batch_size=1, fix=False, params=None):
-        """Dataset_2.py:88-114 -> (x bf16 [B,H,W,roundup(C,8)], y fp32 [B,H,W,num_classes], terminator), all on the device."""
+        """Dataset_2.py:88-114 -> (x bf16 [B,H,W,roundup(C,8)], y fp32 [B,H,W,num_classes], terminator), all on the device.  With ``warp`` the
+        batch is warped first (its draws: ``draw_warps``), so ``imageReduc`` zeroes the image where the WARPED label is 0."""
         start, end = self.idx_tr, self.idx_tr + batch_size
         x_tr, y_tr = self.x_tr[start:end], self.y_tr[start:end]
         terminator = False
@@ -71,6 +93,8 @@ class Dataset(object):
             x_tr, y_tr = self.x_tr[-1 - batch_size:-1], self.y_tr[-1 - batch_size:-1]
         if params is None:
             params = [self.draw() for _ in range(x_tr.shape[0])]
+        if self.warp is not None:
+            x_tr, y_tr = self.warped(x_tr, y_tr, self.draw_warps(x_tr.shape[0]))
         x, y = dataAug_batch(x_tr, y_tr, params=params, num_classes=self.num_classes)      # :106-112
         return x, y, terminator
 

@@ -153,17 +153,18 @@ class Process(object):
 
 
 def main(train_path, val_path, save_path=None, epochs=50, batch_size=32, num_classes=3, *, loss="cce", overlap=None, boundary=None, lovasz=None,
-         average=None):
+         average=None, warp=None, warp_seed=0):
     """MainNumpy.py:150-177 with the paths as arguments: ``VisionTransformer(32, img_size=(256, 80))`` over a ``Dataset_2.Dataset``,
     50 epochs, then a save if ``save_path`` is given.  ``loss``: the model's ``loss=`` ("cce", "my_loss_cat", "focal", "dice", "tversky",
     "dice_ce"); ``overlap``: the settings of the last three (``VisionTransformer(overlap=...)``), which also add a per-class Dice line to the test report;
     ``boundary``: the boundary term on top of one of those three (``VisionTransformer(boundary=...)``); "lovasz" / "lovasz_ce" with their settings in
     ``lovasz`` (``VisionTransformer(lovasz=...)``: the Lovasz-softmax loss; the Dice line too).  ``average`` (a dict, or the string
     ``ema:DECAY[:dynamic]`` / ``swa:START:PERIOD``): EMA / SWA weight averaging - the tests report the averaged model, and the save also writes
-    ``<save_path>.avg``, a plain checkpoint of the averaged weights (``save_averaged``)."""
+    ``<save_path>.avg``, a plain checkpoint of the averaged weights (``save_averaged``).  ``warp`` (a ``warp.warp_config`` dict or ``parse_warp``
+    string; default off): elastic / affine warp of every training batch ahead of ``dataAug``, its draws from ``random.Random(warp_seed)``."""
     from .Dataset_2 import Dataset
     from .VisionTransformer import VisionTransformer, overlap_settings
-    dataset = Dataset(train_path, val_path, num_classes)
+    dataset = Dataset(train_path, val_path, num_classes, warp=warp, warp_seed=warp_seed)
     neuralnet = VisionTransformer(batch_size, img_size=input_size, num_classes=num_classes, loss=loss, overlap=overlap_settings(loss, overlap),
                                   boundary=boundary, lovasz=lovasz, average=average_setting(average))
     print(len(neuralnet.visionModel.layers))

@@ -300,7 +300,7 @@ class Process(object):
 
 
 def main(train_path, val_path, save_path=None, epochs=51, batch_size=64, use_vit=True, *, seed=0, schedule=False, capture_graph=True,
-         loss="cce", overlap=None, boundary=None, lovasz=None, average=None):
+         loss="cce", overlap=None, boundary=None, lovasz=None, average=None, warp=None):
     """MainParallel.py:201-216 with the paths as arguments: ``VisionTransformer(batch_size=64)`` with the ViT bottleneck, 51 epochs,
     then rank 0 saves if ``save_path`` is given.  Every rank seeds ``random`` with ``seed``, so all draw the same augmentations.
     ``loss``: the model's ``loss=`` ("cce", "my_loss_cat", "focal"); every replica divides it by the global batch all the same.  The
@@ -311,6 +311,8 @@ def main(train_path, val_path, save_path=None, epochs=51, batch_size=64, use_vit
     overlap term; it adds the Dice line too.
     ``average`` (a dict, or the ``--average`` string ``ema:DECAY[:dynamic]`` / ``swa:START:PERIOD``): EMA / SWA weight averaging; the update of
     every rank keeps the same average (no exchange is added), the tests report the averaged model and rank 0 also saves ``<save_path>.avg``.
+    ``warp`` (a ``warp.warp_config`` dict or the ``--warp`` string; default off): elastic / affine warp of every training batch ahead of ``dataAug``;
+    its draws come from ``random.Random(seed)`` on every rank, each rank draws the whole global batch and keeps its slice.
     Under ``nccl`` the model lives on ``cuda:LOCAL_RANK``; the ``USSEG_DIST_BACKEND=gloo`` rehearsal keeps every rank on device 0."""
     from .Dataset import Dataset
     from .MainNumpy import average_setting
@@ -320,7 +322,7 @@ def main(train_path, val_path, save_path=None, epochs=51, batch_size=64, use_vit
     device = torch.device("cuda", local if nccl else 0)
     torch.cuda.set_device(device)
     random.seed(seed)
-    dataset = Dataset(train_path, val_path, batch_size, device=device)
+    dataset = Dataset(train_path, val_path, batch_size, device=device, warp=warp, warp_seed=seed)
     neuralnet = VisionTransformer(batch_size, img_size=(dataset.height, dataset.width), in_channels=dataset.channel, use_vit=use_vit,
                                   device=str(device), loss=loss, overlap=overlap_settings(loss, overlap), boundary=boundary, lovasz=lovasz,
                                   average=average_setting(average))
@@ -354,7 +356,16 @@ def _cli(argv=None):
     ap.add_argument("--average", default=None, metavar="ema:DECAY[:dynamic] | swa:START:PERIOD",
                     help="keep an EMA or SWA average of the weights inside the optimiser step; the tests report the averaged model and "
                          "--save also writes SAVE.avg with the averaged weights")
+    ap.add_argument("--warp", default=None, metavar="SPEC",
+                    help="warp every training batch elastically and affinely on the device before dataAug, e.g. "
+                         "sigma=8,magnitude=2:1,p=0.5,rotate=5,scale=0.05,shift=0:0 (any subset; these are the defaults)")
     a = ap.parse_args(argv)
+    if a.warp is not None:
+        from .warp import parse_warp
+        try:
+            parse_warp(a.warp)
+        except ValueError as e:
+            raise SystemExit(str(e))
     if a.average is not None:
         from .flat import parse_average
         try:
@@ -365,7 +376,7 @@ def _cli(argv=None):
         raise SystemExit("--boundary-weight needs --loss dice, tversky or dice_ce")
     main(a.train, a.val, a.save, epochs=a.epochs, batch_size=a.batch_size, use_vit=not a.no_vit, seed=a.seed, schedule=a.schedule,
          capture_graph=not a.no_graph, loss=a.loss, boundary=None if a.boundary_weight is None else {"weight": a.boundary_weight},
-         average=a.average)
+         average=a.average, warp=a.warp)
     if dist.is_initialized():
         dist.barrier()
         dist.destroy_process_group()

@@ -108,8 +108,8 @@ class Dataset(Dataset_2.Dataset):
     ``dataAug`` in ``next_train``; ``next_test`` does not augment."""
     draw = staticmethod(draw)
 
-    def __init__(self, train_path=None, val_path=None, device="cuda", train_data=None, val_data=None):
-        super().__init__(train_path, val_path, num_classes=3, device=device, train_data=train_data, val_data=val_data)
+    def __init__(self, train_path=None, val_path=None, device="cuda", train_data=None, val_data=None, warp=None, warp_seed=0):
+        super().__init__(train_path, val_path, num_classes=3, device=device, train_data=train_data, val_data=val_data, warp=warp, warp_seed=warp_seed)
         self.num_class = 3                                                                         # :682
 
 
@@ -191,13 +191,15 @@ def test(neuralnet, dataset, epoch):
     return r["f1"]
 
 
-def main(train_path, val_path, save_path=None, epochs=51, batch_size=16, *, loss="cce", overlap=None, boundary=None, lovasz=None, average=None):
+def main(train_path, val_path, save_path=None, epochs=51, batch_size=16, *, loss="cce", overlap=None, boundary=None, lovasz=None, average=None,
+         warp=None, warp_seed=0):
     """:997-1010 with the paths as arguments: 256x80x10 input, batch 16, 51 epochs, then a save if ``save_path`` is given.
     ``loss``: the model's ``loss=`` ("cce", "my_loss_cat", "focal", "dice", "tversky", "dice_ce"); ``overlap``: the settings of the last three,
     which also add a per-class Dice line to the test report; ``boundary``: the boundary term on top of one of those three; "lovasz" / "lovasz_ce" with their
     settings in ``lovasz`` (the Lovasz-softmax loss; the Dice line too).  ``average`` (a dict, or ``ema:DECAY[:dynamic]`` / ``swa:START:PERIOD``):
-    EMA / SWA weight averaging - ``test`` reports the averaged model and the save also writes ``<save_path>.avg`` (``save_averaged``)."""
-    dataset = Dataset(train_path, val_path)
+    EMA / SWA weight averaging - ``test`` reports the averaged model and the save also writes ``<save_path>.avg`` (``save_averaged``).
+    ``warp`` (a ``warp.warp_config`` dict or ``parse_warp`` string; default off): elastic / affine warp of every training batch ahead of ``dataAug``."""
+    dataset = Dataset(train_path, val_path, warp=warp, warp_seed=warp_seed)
     neuralnet = VisionTransformer(img_size=input_size, num_classes=3, learning_rate=1e-3, batch_size=batch_size, loss=loss, overlap=overlap_settings(loss, overlap),
                                   boundary=boundary, lovasz=lovasz, average=average_setting(average))
     print(len(neuralnet.visionModel.layers))

@@ -149,12 +149,22 @@ class TempDesc(C.Structure):
     _fields_ = [("B", c_i32), ("H", c_i32), ("W", c_i32), ("C", c_i32), ("n_beta", c_i32)]
 
 
+class WarpSample(C.Structure):
+    """UssegWarpSample: one sample's draws of the elastic / affine warp (usseg.h); a device table of them is read on every launch."""
+    _fields_ = [("active", c_i32), ("reserved", c_i32), ("seed", C.c_uint64), ("alpha", C.c_double * 2), ("aff", C.c_double * 6)]
+
+
+class WarpDesc(C.Structure):
+    _fields_ = [("B", c_i32), ("H", c_i32), ("W", c_i32), ("C", c_i32), ("x_is_f64", c_i32), ("radius", c_i32)]
+
+
 ENSEMBLE_MAX = 16       # USSEG_ENSEMBLE_MAX
 CALIB_MAX_BINS = 64     # USSEG_CALIB_MAX_BINS
 SWEEP_MAX_BINS = 4096   # USSEG_SWEEP_MAX_BINS
 TEMP_MAX_BETAS = 16     # USSEG_TEMP_MAX_BETAS
 TEMP_NLL_CAP = 1024     # USSEG_TEMP_NLL_CAP
 TEMP_NLL_UNIT = 2.0 ** -20    # one count of usseg_temperature_nll's sums
+WARP_MAX_RADIUS = 64    # USSEG_WARP_MAX_RADIUS
 
 ACT_NONE, ACT_LRELU, ACT_RELU, ACT_ELU, ACT_GELU = 0, 1, 2, 3, 4
 OUT_F32, ACCUMULATE = 1, 2
@@ -333,6 +343,8 @@ _PROTOS = {
     "usseg_adamw_avg_step": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_f32, c_vp, c_vp, c_vp, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp]),
     "usseg_average_update": (C.c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
     "usseg_swap_f32": (C.c_int, [c_vp, c_vp, c_i64, c_vp]),
+    "usseg_warp_ws_bytes": (c_i64, [c_i32, c_i32, c_i32]),
+    "usseg_elastic_warp": (C.c_int, [P(WarpDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
 }
 EXPORTED_SYMBOLS = tuple(_PROTOS)
 

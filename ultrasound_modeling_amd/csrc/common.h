@@ -63,6 +63,12 @@ __device__ __forceinline__ uint4 pack8(const float* f) {
   return v;
 }
 
+// low 32 bits of a 64-bit finaliser: the counter-based generator of usseg_augment's noise (input_pipeline.hip) and of the warp field (warp.hip)
+__device__ __forceinline__ uint32_t aug_hash(uint64_t v) {
+  v ^= v >> 33; v *= 0xff51afd7ed558ccdULL; v ^= v >> 33; v *= 0xc4ceb9fe1a85ec53ULL; v ^= v >> 33;
+  return (uint32_t)v;
+}
+
 __device__ __forceinline__ float apply_act(float v, int act, float alpha) {
   switch (act) {
     case USSEG_ACT_LRELU: return v >= 0.f ? v : alpha * v;

@@ -36,11 +36,6 @@ extern "C" int usseg_label2vec(const float* label, int64_t M, int32_t num_classe
   return usseg_check_launch("label2vec");
 }
 
-__device__ __forceinline__ uint32_t aug_hash(uint64_t v) {
-  v ^= v >> 33; v *= 0xff51afd7ed558ccdULL; v ^= v >> 33; v *= 0xc4ceb9fe1a85ec53ULL; v ^= v >> 33;
-  return (uint32_t)v;
-}
-
 // dataAug (DataAugs.py:82-102) for a whole batch + label2vec + the cast to the model's bf16 NHWC input.  TBI_TransUNet.py:835-875 is the
 // same chain behind a left-right flip (do_flip): (si, sj) are computed in the frame of the flipped image, as the reference's later steps
 // see it, and only the column that is finally read is mirrored.  Its imageReduc(., r % 5) needs no iteration count: the dilation never
