@@ -63,6 +63,9 @@ __device__ __forceinline__ uint4 pack8(const float* f) {
   return v;
 }
 
+// p mod W; `small`: every pixel index fits 31 bits (a uniform branch to the cheaper 32-bit division)
+__device__ __forceinline__ int mod_w(int64_t p, int W, bool small) { return small ? (int)((uint32_t)p % (uint32_t)W) : (int)(p % W); }
+
 // low 32 bits of a 64-bit finaliser: the counter-based generator of usseg_augment's noise (input_pipeline.hip) and of the warp field (warp.hip)
 __device__ __forceinline__ uint32_t aug_hash(uint64_t v) {
   v ^= v >> 33; v *= 0xff51afd7ed558ccdULL; v ^= v >> 33; v *= 0xc4ceb9fe1a85ec53ULL; v ^= v >> 33;
@@ -128,6 +131,70 @@ __device__ __forceinline__ bool grid_ordered_sum(float block_total /* thread 0 *
   return true;
 }
 // (returns true in the workgroup that performed the final addition: for work that must follow the sum)
+
+// The same construction for K <= 16 totals at once (the region losses' sums passes, region_loss.h): acc[1] is the ticket, acc[HDR + STRIDE*b + k]
+// workgroup b's total of value k.  s[] holds the calling thread's K partial sums.  Within a workgroup (256 threads) a wave adds its lanes by a
+// butterfly and thread k < K the four waves as (0+1)+(2+3).  Across workgroups: lanes 0..K-1 of wave 0 publish the K totals with ONE returning
+// agent-scope exchange instruction, all K return values are folded into the operand of the ticket add (so the add cannot issue before every
+// partial is at the memory side), and the LAST workgroup to arrive adds the rows in a fixed order - thread (j, k) the workgroups j, j+16,
+// j+32, ... of value k, then thread k the sixteen j as a balanced tree.  No workgroup waits for another; no float atomics.
+// Returns true in that last workgroup alone, behind a barrier, with the K grid totals in tot[] and the ticket still at gridDim.x: the caller's
+// thread 0 writes its results and puts acc[1] back to zero (relaxed agent-scope store, as above), so the ticket is zero when the kernel ends.
+// The LDS arrays are the calling kernel's own __shared__ declarations (that keeps the LDS layout the sums kernels had when each carried this
+// code itself).  tools/check_ordered_sum.py checks the ISA of this sequence too.
+template <int K, int HDR, int STRIDE>
+__device__ __forceinline__ bool grid_ordered_sums(const float (&s)[K], float* acc, float (&red)[4][STRIDE], float (&fin)[16][STRIDE + 1],
+                                                  float (&tot)[STRIDE], int& s_last) {
+  static_assert(K >= 1 && K <= 16 && STRIDE >= 16, "thread (j, k) = (tid >> 4, tid & 15) owns value k; the return values are folded over 16 lanes");
+#pragma unroll
+  for (int i = 0; i < K; ++i) {
+    float v = s[i];
+    for (int msk = 32; msk >= 1; msk >>= 1) v += __shfl_xor(v, msk, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][i] = v;
+  }
+  __syncthreads();
+  const int nb = gridDim.x;
+  if (threadIdx.x < 64) {
+    unsigned zero = 0u;
+    if (threadIdx.x < K) {
+      const float t = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+      const float old = __hip_atomic_exchange(acc + HDR + blockIdx.x * STRIDE + threadIdx.x, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      asm volatile("; ticket after the partials are at the memory side" : "+v"(zero) : "v"(old));
+    }
+    for (int msk = 8; msk >= 1; msk >>= 1) zero |= __shfl_xor(zero, msk, 64);     // lane 0 holds a value that depends on all K returns
+    if (threadIdx.x == 0) {
+      const unsigned tk = __hip_atomic_fetch_add(reinterpret_cast<unsigned*>(acc + 1), 1u + zero, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      s_last = (tk == (unsigned)nb - 1u);
+    }
+  }
+  __syncthreads();
+  if (!s_last) return false;
+  {
+    const int kk = threadIdx.x & 15, j = threadIdx.x >> 4;
+    float v = 0.f;
+    for (int b0 = j; b0 < nb; b0 += 16 * 8) {     // eight independent loads in flight, added in workgroup order
+      float t[8];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const int b = b0 + 16 * i;
+        t[i] = (b < nb && kk < K) ? __hip_atomic_load(acc + HDR + b * STRIDE + kk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.f;
+      }
+#pragma unroll
+      for (int i = 0; i < 8; ++i) v += t[i];
+    }
+    fin[j][kk] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < K) {
+    const int c = threadIdx.x;
+    float a[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) a[i] = fin[2 * i][c] + fin[2 * i + 1][c];
+    tot[c] = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
+  }
+  __syncthreads();
+  return true;
+}
 
 // ---- shared epilogue of the conv kernels (16x16 MFMA layout: a lane holds Y[pixel = lane&15][n = nbase + 16*bt + j]) ----------------
 // vmcnt retires in issue order and counts stores, so a load issued after a store waits for that store's write latency

@@ -32,8 +32,6 @@ __device__ __forceinline__ float plogp(float p) { return p > 0.f ? p * logf(p) :
 // max(d, 0) that keeps a NaN (fmaxf would drop it)
 __device__ __forceinline__ float clamp0(float d) { return d < 0.f ? 0.f : d; }
 
-__device__ __forceinline__ int mod_w(int64_t p, int W, bool small) { return small ? (int)((uint32_t)p % (uint32_t)W) : (int)(p % W); }
-
 // One pixel's accumulators over the members: the class sums (member 0 starts them: no 0 + p_0), the sums of squares and sum t(p).
 template <int NC>
 struct PixAcc {

@@ -15,10 +15,9 @@
 // Loss.  Per class the pixels are ordered by error, descending, ties by pixel index; the Lovasz gradient of the Jaccard loss at rank r is a
 // closed form in exact integers (usseg.h), so the launches are: keys and payloads (1), the sort (12 at 30 key bits), foreground counts per
 // tile of the sorted order (1), their exclusive scan and Y_c (1), the coefficients scattered back to pixel order (1).  The sums pass and the
-// backward pass restate overlap_loss.hip's two kernels (its ordered, ticketed grid reduction under the same grid rule; its CCE arithmetic;
-// its dlogits layouts) rather than sharing them through a header: that file's kernels stay instruction for instruction what they were.
-#include "common.h"
-#include <cmath>
+// backward pass are the two passes of a region loss as overlap_loss.hip has them, under the same grid rule: the ordered, ticketed grid
+// reduction is grid_ordered_sums (common.h); the group loader, the CCE arithmetic, the dlogits store and the shared checks are region_loss.h's.
+#include "region_loss.h"
 
 #define SORT_TILE USSEG_SORT_TILE
 #define SORT_RADIX (1 << USSEG_SORT_DIGIT_BITS)
@@ -214,9 +213,8 @@ extern "C" int usseg_sort_pairs_u32(const uint32_t* keys_in, const uint32_t* val
 // ---- the Lovasz-softmax loss ---------------------------------------------------------------------------------------------------------
 #define LV_ONE_BITS 0x3F800000u     // fp32 1.0: the clamp of the sort key; keys take 30 bits
 #define LV_KEY_BITS 30
-#define LV_HDR 32        // acc[0] loss, [1] ticket, [2] CCE pixel sum, [4..8) k_c, [16..20) L_c
-#define LV_STRIDE 16     // floats per workgroup row of partials (C + 1 <= 5 used): acc[LV_HDR + 16*b + k], the overlap accumulator's geometry
-#define LV_MAX_BLOCKS ((USSEG_OVERLAP_ACC_FLOATS - LV_HDR) / LV_STRIDE)
+// the accumulator header (region_loss.h has its geometry): acc[0] loss, [1] ticket, [2] CCE pixel sum, [4..8) k_c, [16..20) L_c; C + 1 <= 5
+// floats of a workgroup's row of partials are used
 
 __device__ __forceinline__ bool lv_fg(float y, float thr) { return y > thr; }      // (a NaN is not foreground)
 
@@ -317,67 +315,25 @@ __global__ __launch_bounds__(256) void lovasz_coeffs_kernel(const unsigned* __re
 // the parameters as the kernels take them, by value: lvk = lv_weight * ov_scale and cek = ce_weight * inv_global_batch folded on the host
 struct LovaszK { float w[4]; float lvk, cek, thr; int all; };
 
-template <int C>
-__device__ __forceinline__ void lv_load_group(const float* __restrict__ base, int g, int M, float (&v)[4 * C]) {
-  if (4 * g + 4 <= M) {
-    const float4* q = reinterpret_cast<const float4*>(base) + (int64_t)g * C;
-#pragma unroll
-    for (int i = 0; i < C; ++i) {
-      const float4 t = q[i];
-      v[4 * i] = t.x; v[4 * i + 1] = t.y; v[4 * i + 2] = t.z; v[4 * i + 3] = t.w;
-    }
-  } else {
-    const int n = (M - 4 * g) * C;      // floats that exist in the last, partial group
-#pragma unroll
-    for (int i = 0; i < 4 * C; ++i) v[i] = i < n ? base[(int64_t)g * (4 * C) + i] : 0.f;
-  }
-}
-
-// CategoricalCrossentropy(label_smoothing) on probabilities, one pixel: overlap_loss.hip's ov_cce_pixel, the arithmetic of loss_kind 0
-template <int C, bool GRAD>
-__device__ __forceinline__ float lv_cce_pixel(const float* p, const float* y, float ls, float eps, float* dLdp) {
-  float S = 0.f;
-#pragma unroll
-  for (int c = 0; c < C; ++c) S += p[c];
-  float l = 0.f, u[C], ubar = 0.f;
-#pragma unroll
-  for (int c = 0; c < C; ++c) {
-    const float ys = y[c] * (1.f - ls) + ls / (float)C;
-    const float q = p[c] / S;
-    const float qc = fminf(fmaxf(q, eps), 1.f - eps);
-    l -= ys * __logf(qc);
-    if (GRAD) {
-      u[c] = (q > eps && q < 1.f - eps) ? -ys / qc : 0.f;
-      ubar += u[c] * q;
-    }
-  }
-  if (GRAD) {
-#pragma unroll
-    for (int c = 0; c < C; ++c) dLdp[c] = (u[c] - ubar) / S;
-  }
-  return l;
-}
-
-// K = C + 1 totals (L_c, the CCE pixel sum) by overlap_sums_kernel's ordered reduction: per thread in index order, a wave by a butterfly, the
-// four waves as (0+1)+(2+3), the workgroups' rows published by ONE returning agent-scope exchange each and folded into the operand of the
-// ticket add, the LAST workgroup to arrive adding them in a fixed order.  tools/check_ordered_sum.py checks the ISA of this sequence.
+// K = C + 1 totals (L_c, the CCE pixel sum): a thread adds its pixels in index order, grid_ordered_sums (common.h) the threads, waves and
+// workgroups in a fixed order; thread 0 of the last workgroup to arrive finishes and puts the ticket back to zero.
 template <int C, bool CE>
 __global__ __launch_bounds__(256) void lovasz_sums_kernel(const LovaszK k, const float* __restrict__ probs, const float* __restrict__ y_true,
                                                            const float* __restrict__ gco, const int* __restrict__ counts, float* acc, int M, int ngroups,
                                                            float ls, float eps) {
   constexpr int K = C + 1;
-  __shared__ float red[4][LV_STRIDE];
-  __shared__ float fin[16][LV_STRIDE + 1];
-  __shared__ float tot[LV_STRIDE];
+  __shared__ float red[4][REGION_STRIDE];
+  __shared__ float fin[16][REGION_STRIDE + 1];
+  __shared__ float tot[REGION_STRIDE];
   __shared__ int s_last;
   float s[K];
 #pragma unroll
   for (int i = 0; i < K; ++i) s[i] = 0.f;
   for (int g = blockIdx.x * 256 + threadIdx.x; g < ngroups; g += gridDim.x * 256) {
     float p[4 * C], y[4 * C], gc[4 * C];
-    lv_load_group<C>(probs, g, M, p);
-    lv_load_group<C>(y_true, g, M, y);
-    lv_load_group<C>(gco, g, M, gc);
+    region_load_group<C>(probs, g, M, p);
+    region_load_group<C>(y_true, g, M, y);
+    region_load_group<C>(gco, g, M, gc);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       if (4 * g + j >= M) break;
@@ -386,56 +342,10 @@ __global__ __launch_bounds__(256) void lovasz_sums_kernel(const LovaszK k, const
         const float e = lv_fg(y[j * C + c], k.thr) ? 1.f - p[j * C + c] : p[j * C + c];
         s[c] += e * gc[j * C + c];
       }
-      if (CE) s[C] += lv_cce_pixel<C, false>(p + j * C, y + j * C, ls, eps, nullptr);
+      if (CE) s[C] += region_cce_pixel<C, false>(p + j * C, y + j * C, ls, eps, nullptr);
     }
   }
-#pragma unroll
-  for (int i = 0; i < K; ++i) {
-    float v = s[i];
-    for (int msk = 32; msk >= 1; msk >>= 1) v += __shfl_xor(v, msk, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][i] = v;
-  }
-  __syncthreads();
-  const int nb = gridDim.x;
-  if (threadIdx.x < 64) {
-    unsigned zero = 0u;
-    if (threadIdx.x < K) {
-      const float t = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
-      const float old = __hip_atomic_exchange(acc + LV_HDR + blockIdx.x * LV_STRIDE + threadIdx.x, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      asm volatile("; ticket after the partials are at the memory side" : "+v"(zero) : "v"(old));
-    }
-    for (int msk = 8; msk >= 1; msk >>= 1) zero |= __shfl_xor(zero, msk, 64);     // lane 0 holds a value that depends on all K returns (K <= 5)
-    if (threadIdx.x == 0) {
-      const unsigned tk = __hip_atomic_fetch_add(reinterpret_cast<unsigned*>(acc + 1), 1u + zero, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      s_last = (tk == (unsigned)nb - 1u);
-    }
-  }
-  __syncthreads();
-  if (!s_last) return;
-  {
-    const int kk = threadIdx.x & 15, j = threadIdx.x >> 4;
-    float v = 0.f;
-    for (int b0 = j; b0 < nb; b0 += 16 * 8) {     // eight independent loads in flight, added in workgroup order
-      float t[8];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const int b = b0 + 16 * i;
-        t[i] = (b < nb && kk < K) ? __hip_atomic_load(acc + LV_HDR + b * LV_STRIDE + kk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.f;
-      }
-#pragma unroll
-      for (int i = 0; i < 8; ++i) v += t[i];
-    }
-    fin[j][kk] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < K) {
-    const int c = threadIdx.x;
-    float a[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) a[i] = fin[2 * i][c] + fin[2 * i + 1][c];
-    tot[c] = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
-  }
-  __syncthreads();
+  if (!grid_ordered_sums<K, REGION_HDR, REGION_STRIDE>(s, acc, red, fin, tot, s_last)) return;
   if (threadIdx.x == 0) {
     int ns = 0;
     bool in[C];
@@ -456,7 +366,7 @@ __global__ __launch_bounds__(256) void lovasz_sums_kernel(const LovaszK k, const
   }
 }
 
-// dlogit_j = p_j*(G_j - sum_c p_c*G_c), G_c = k_c*(fg ? -g : +g) (+ the CCE term): overlap_bwd_kernel's layouts, one bf16 rounding
+// dlogit_j = p_j*(G_j - sum_c p_c*G_c), G_c = k_c*(fg ? -g : +g) (+ the CCE term), one bf16 rounding (region_store_dlogits)
 template <int C, bool CE, bool QUAD>
 __global__ __launch_bounds__(256) void lovasz_bwd_kernel(const float cek, const float thr, const float* __restrict__ probs, const float* __restrict__ y_true,
                                                           const float* __restrict__ gco, const float* __restrict__ acc, bf16_t* __restrict__ dl, int M,
@@ -466,9 +376,9 @@ __global__ __launch_bounds__(256) void lovasz_bwd_kernel(const float cek, const 
   for (int c = 0; c < C; ++c) kc[c] = acc[4 + c];
   for (int g = blockIdx.x * 256 + threadIdx.x; g < ngroups; g += gridDim.x * 256) {
     float p[4 * C], y[4 * C], gc[4 * C];
-    lv_load_group<C>(probs, g, M, p);
-    lv_load_group<C>(y_true, g, M, y);
-    lv_load_group<C>(gco, g, M, gc);
+    region_load_group<C>(probs, g, M, p);
+    region_load_group<C>(y_true, g, M, y);
+    region_load_group<C>(gco, g, M, gc);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int m = 4 * g + j;
@@ -481,28 +391,11 @@ __global__ __launch_bounds__(256) void lovasz_bwd_kernel(const float cek, const 
       }
       if (CE) {
         float dce[C];
-        lv_cce_pixel<C, true>(p + j * C, y + j * C, ls, eps, dce);
+        region_cce_pixel<C, true>(p + j * C, y + j * C, ls, eps, dce);
 #pragma unroll
         for (int c = 0; c < C; ++c) G[c] += dce[c] * cek;
       }
-      float dot = 0.f;
-#pragma unroll
-      for (int c = 0; c < C; ++c) dot += G[c] * p[j * C + c];
-      float o[4];
-#pragma unroll
-      for (int c = 0; c < 4; ++c) o[c] = c < C ? p[j * C + (c < C ? c : 0)] * (G[c < C ? c : 0] - dot) : 0.f;
-      if (QUAD) {
-        const unsigned b = (unsigned)m / (unsigned)HW, hw = (unsigned)m - b * (unsigned)HW;
-        const unsigned yy = hw / (unsigned)W, xx = hw - yy * (unsigned)W;
-        const int64_t q = ((int64_t)b * (HW / W / 2) + (yy >> 1)) * (W / 2) + (xx >> 1);
-        uint2 v;
-        v.x = pack2bf(o[0], o[1]); v.y = pack2bf(o[2], o[3]);
-        *reinterpret_cast<uint2*>(dl + q * 16 + 4 * ((yy & 1) * 2 + (xx & 1))) = v;
-      } else {
-        uint4 v;
-        v.x = pack2bf(o[0], o[1]); v.y = pack2bf(o[2], o[3]); v.z = 0u; v.w = 0u;
-        *reinterpret_cast<uint4*>(dl + (int64_t)m * 8) = v;
-      }
+      region_store_dlogits<C, QUAD>(G, p + j * C, dl, m, HW, W);
     }
   }
 }
@@ -516,23 +409,16 @@ extern "C" int64_t usseg_lovasz_ws_bytes(int64_t M, int32_t C) {
 static int lovasz_args(const char* who, const UssegLossDesc* d, const UssegLovaszLoss* ll, const float* probs, const float* y_true, const float* g) {
   USSEG_CHECK_ARG(d, "%s: null descriptor", who);
   USSEG_CHECK_ARG(probs && y_true && g, "%s: null pointer", who);
-  USSEG_CHECK_ARG(d->C >= 1 && d->C <= 4, "%s: 1 <= C <= 4", who);
-  USSEG_CHECK_ARG(d->HW > 0 && d->M >= 0 && d->M % d->HW == 0, "%s: M must be a non-negative multiple of HW", who);
-  USSEG_CHECK_ARG(d->M <= (1 << 29), "%s: more than 2^29 pixels", who);
+  const int rc = region_shape_args(who, d);
+  if (rc) return rc;
   USSEG_CHECK_ARG((((uintptr_t)probs | (uintptr_t)y_true | (uintptr_t)g) & 15) == 0, "%s: probs, y_true and g must be 16-byte aligned", who);
   USSEG_CHECK_ARG(std::isfinite(ll->threshold), "%s: threshold must be finite", who);
   USSEG_CHECK_ARG(ll->all_classes == 0 || ll->all_classes == 1, "%s: all_classes must be 0 or 1", who);
   USSEG_CHECK_ARG(std::isfinite(ll->lv_weight) && ll->lv_weight >= 0.f && std::isfinite(ll->ce_weight) && ll->ce_weight >= 0.f,
                   "%s: lv_weight and ce_weight must be finite and >= 0", who);
   for (int c = 0; c < d->C; ++c) USSEG_CHECK_ARG(std::isfinite(ll->w[c]) && ll->w[c] >= 0.f, "%s: class weights must be finite and >= 0", who);
-  USSEG_CHECK_ARG(std::isfinite(d->inv_global_batch) && d->inv_global_batch >= 0.f, "%s: inv_global_batch must be finite and >= 0", who);
-  if (ll->ce_weight != 0.f) {
-    USSEG_CHECK_ARG(d->label_smoothing >= 0.f && d->label_smoothing < 1.f, "%s: label_smoothing must lie in [0, 1)", who);
-    USSEG_CHECK_ARG(d->clip_eps > 0.f && 1.f - d->clip_eps < 1.f && d->clip_eps < 0.5f, "%s: clip_eps must be > 0 and representable below 1 in fp32", who);
-  }
-  return USSEG_OK;
+  return region_scale_args(who, d, ll->ce_weight);
 }
-static inline int lovasz_groups(const UssegLossDesc* d) { return (int)((d->M + 3) / 4); }
 
 extern "C" int usseg_lovasz_coeffs(const UssegLossDesc* d, UssegLovaszLoss ll, const float* probs, const float* y_true, float* g, int32_t* counts,
                                    void* ws, int64_t ws_bytes, usseg_stream_t stream) {
@@ -585,8 +471,8 @@ extern "C" int usseg_lovasz_loss_sums(const UssegLossDesc* d, UssegLovaszLoss ll
   USSEG_CHECK_ARG(acc && ((uintptr_t)acc & 3) == 0, "%s: acc must be a 4-byte aligned pointer", who);
   USSEG_CHECK_ARG(std::isfinite(ov_scale) && ov_scale >= 0.f, "%s: ov_scale must be finite and >= 0", who);
   const int grid = usseg_overlap_loss_grid(d->M);
-  USSEG_CHECK_ARG(grid <= LV_MAX_BLOCKS && acc_floats >= LV_HDR + (int64_t)LV_STRIDE * grid, "%s: a grid of %d workgroups needs %d accumulator floats",
-                  who, grid, LV_HDR + LV_STRIDE * grid);
+  USSEG_CHECK_ARG(grid <= REGION_MAX_BLOCKS && acc_floats >= REGION_HDR + (int64_t)REGION_STRIDE * grid,
+                  "%s: a grid of %d workgroups needs %d accumulator floats", who, grid, REGION_HDR + REGION_STRIDE * grid);
   LovaszK k = {};
   for (int c = 0; c < d->C; ++c) k.w[c] = ll.w[c];
   k.lvk = ll.lv_weight * ov_scale;
@@ -594,7 +480,7 @@ extern "C" int usseg_lovasz_loss_sums(const UssegLossDesc* d, UssegLovaszLoss ll
   k.thr = ll.threshold;
   k.all = ll.all_classes;
   const bool ce = ll.ce_weight != 0.f;
-  const int M = (int)d->M, ng = lovasz_groups(d);
+  const int M = (int)d->M, ng = region_groups(d);
   hipStream_t s = (hipStream_t)stream;
 #define LV_SUMS2(CC, CEB)                                                                                                                  \
   hipLaunchKernelGGL((lovasz_sums_kernel<CC, CEB>), dim3(grid), dim3(256), 0, s, k, probs, y_true, g, counts, acc, M, ng, CEB ? d->label_smoothing : 0.f, \
@@ -615,19 +501,15 @@ extern "C" int usseg_lovasz_loss_sums(const UssegLossDesc* d, UssegLovaszLoss ll
 extern "C" int usseg_lovasz_loss_bwd(const UssegLossDesc* d, UssegLovaszLoss ll, const float* probs, const float* y_true, const float* g, const float* acc,
                                      int64_t acc_floats, void* dlogits, usseg_stream_t stream) {
   const char* who = "lovasz_loss_bwd";
-  const int rc = lovasz_args(who, d, &ll, probs, y_true, g);
+  int rc = lovasz_args(who, d, &ll, probs, y_true, g);
   if (rc) return rc;
-  USSEG_CHECK_ARG(acc && ((uintptr_t)acc & 3) == 0 && acc_floats >= LV_HDR, "%s: acc must hold its %d header floats", who, LV_HDR);
-  USSEG_CHECK_ARG(dlogits && ((uintptr_t)dlogits & 15) == 0, "%s: dlogits must be a 16-byte aligned pointer", who);
-  USSEG_CHECK_ARG(d->quad_w == 0 || (d->quad_w > 0 && d->quad_w % 2 == 0 && d->HW % (2 * d->quad_w) == 0), "%s: quad layout needs even H and W", who);
-  USSEG_CHECK_ARG(d->lddl == (d->quad_w ? 16 : 8), "%s: dlogits stride must be 8 (16 in the quad layout)", who);
+  USSEG_CHECK_ARG(acc && ((uintptr_t)acc & 3) == 0 && acc_floats >= REGION_HDR, "%s: acc must hold its %d header floats", who, REGION_HDR);
+  if ((rc = region_bwd_args(who, d, dlogits))) return rc;
   if (d->M == 0) return USSEG_OK;
   const float cek = ll.ce_weight * d->inv_global_batch;
   const bool ce = ll.ce_weight != 0.f;
-  const int M = (int)d->M, ng = lovasz_groups(d);
-  int64_t gb = cdiv64(ng, 256);
-  if (gb > 2048) gb = 2048;
-  const dim3 grid((unsigned)gb);
+  const int M = (int)d->M, ng = region_groups(d);
+  const dim3 grid = region_bwd_grid(ng);
   bf16_t* dl = (bf16_t*)dlogits;
   hipStream_t s = (hipStream_t)stream;
 #define LV_BWD2(CC, CEB, Q)                                                                                                              \

@@ -40,9 +40,6 @@ __device__ __forceinline__ void seg_elem(float t, float p, bool last, bool rnd, 
   k.v[6 + NC * NC] += !ok;
 }
 
-// p mod W; `small`: every pixel index fits 31 bits (a uniform branch to the cheaper 32-bit division)
-__device__ __forceinline__ int mod_w(int64_t p, int W, bool small) { return small ? (int)((uint32_t)p % (uint32_t)W) : (int)(p % W); }
-
 // The generic path: one pixel per thread and trip, scalar loads (any C, any alignment; the ragged tail of the fast path).
 template <int NC>
 __device__ __forceinline__ void seg_pixels(const float* __restrict__ yt, const float* __restrict__ yp, int64_t p_begin, int64_t M, int W, int C,
