@@ -816,6 +816,66 @@ int usseg_lovasz_loss_sums(const UssegLossDesc* d, UssegLovaszLoss ll, float ov_
                            const int32_t* counts, float* acc, int64_t acc_floats, usseg_stream_t stream);
 int usseg_lovasz_loss_bwd(const UssegLossDesc* d, UssegLovaszLoss ll, const float* probs, const float* y_true, const float* g, const float* acc,
                           int64_t acc_floats, void* dlogits, usseg_stream_t stream);
+/* ---- an exact grid-wide selection, and the top-k (hard-pixel) cross-entropy on it (csrc/topk_loss.hip) ----------------------------------
+ * usseg_topk_select: S segments of n uint32 keys, segment s at [s*n, (s+1)*n).  With k the count below, per segment
+ *     t = the k-th largest key,   ngt = |{key > t}|,   neq = |{key == t}|       sel int32 [S][4] = {t, ngt, neq, k} (t: the key's bits)
+ * as exact integers.  The count: k = max(1, min(n, floor((double)f * n))) with f the fp32 fraction widened to double (the product is exact),
+ * f read from DEVICE memory when the kernels run - or, with fraction == NULL, the explicit k (1 <= k <= n).  Give one of the two (k = 0 with
+ * a fraction).  On the device the clamp is the whole rule: a fraction that does not compare (NaN) gives k = 1.  An MSD radix select with 8-bit
+ * digits over a table int32 [S][4][256] in the workspace (16-byte aligned, usseg_topk_select_ws_bytes(S) bytes; -1 for a refused S): the table
+ * is zeroed inside the call (a memset node under capture), one launch per digit adds the histogram of the keys that carry the prefix chosen
+ * so far - every workgroup re-derives that prefix and the remaining rank from the tables of the digits before (a 256-entry scan in LDS) -
+ * and a fifth launch writes sel.  Five kernels and one memset, fixed by (S, n) and never by the data, so a captured graph holds the call and
+ * follows the fraction.  No host synchronisation, no allocation.  No workgroup waits for another: a digit boundary is a launch boundary.
+ * Only integer atomics are used, so the result is a function of the inputs alone.  0 <= S <= 2^29, 1 <= n <= 2^29; S == 0 returns 0 without
+ * a launch.  Every argument is checked before any launch (USSEG_ERR_BAD_ARG with usseg_last_error text), a workspace that is too small included.
+ *
+ * The top-k cross-entropy (nnU-Net's TopKLoss; online hard example mining), not in the reference: the mean of the k largest per-pixel losses.
+ * On the head's fp32 probabilities and the labels, probs / y_true fp32 [M][C], C <= 4, 16-byte aligned, M <= 2^29:
+ *     l(m)  = the CategoricalCrossentropy of pixel m, loss_kind 0's arithmetic exactly (divide by the class sum, clip, log, label smoothing),
+ *             stored as fp32;   key(m) = the uint32 bits of l(m) with the sign bit cleared (l >= 0, so bit order is value order; a NaN sorts
+ *             above every finite value, is therefore selected, and makes the loss NaN as CCE's would)
+ *     scope = 0 ("batch"): one segment of n = M pixels;   scope = 1 ("image"): M/HW segments of n = HW
+ *     t_s, ngt_s, neq_s, k as above per segment s,   r_s = k - ngt_s  (1 <= r_s <= neq_s)
+ *     a(m)  = 1 if key > t_s,   r_s / neq_s (one fp32 division) if key == t_s,   0 otherwise
+ * Ties are shared, not broken by index: the loss is the mean of exactly k values (what torch.topk(...).mean() returns), the gradient is the
+ * average of all valid subgradients, nothing depends on pixel order.
+ *     L_tk   = tk_weight * inv_global_batch * (n/k) * sum_m a(m) * l(m)
+ *     G_c(m) = (tk_weight * inv_global_batch * (n/k) * a(m)) * dLdp_c(m),   dLdp the gradient of l (zero where the quotient was clipped);
+ *     dlogit_j = p_j*(G_j - sum_c p_c*G_c), fp32, ONE bf16 rounding.  A pixel with a(m) = 0 stores exact zeros in all its slots.
+ * With fraction 1 every pixel is selected and L_tk is loss_kind 0's loss.  Data-parallel reading: with scope 0 a replica selects among ITS
+ * pixels (the replica reading of the overlap term), with scope 1 the selection is per image and independent of how the batch is split;
+ * inv_global_batch gives the SUM all-reduce the right weight.
+ * Dice + top-k (nnU-Net's DC_and_topk_loss): usseg_overlap_loss_sums runs unchanged with ce_weight = 0 into an accumulator of its own, which
+ * the two calls below take as overlap_acc (NULL: plain top-k): the sums pass adds its [0] to the scalar, the backward pass adds
+ * A_c*y_c(m) + B_c from its [4..12) to G_c(m) before the one rounding.
+ * Three calls behind a probabilities-only forward, the workspace (16-byte aligned, usseg_topk_ws_bytes(M, HW, scope) bytes; -1 for a refused
+ * shape) carrying l fp32 [M] at offset 0, the select table at the next multiple of 256 bytes, sel behind it (again on a multiple of 256):
+ *   usseg_topk_pixel_loss   l, the top digit's histogram in the same launch, the three further digits, sel: five kernels and one memset.
+ *   usseg_topk_loss_sums    reads l and sel: acc[0] = L_tk (+ overlap_acc[0]) (OVERWRITTEN); acc[2] = the plain CCE pixel sum sum_m l(m);
+ *                           acc[4] = the coefficient tk_weight * inv_global_batch * n / k; acc[5] = sum_m a(m)*l(m).  The ordered, ticketed
+ *                           grid reduction of usseg_overlap_loss_sums under the same grid rule usseg_overlap_loss_grid(M) and accumulator
+ *                           geometry ([1] the ticket, zero between calls): bitwise reproducible.  USSEG_OVERLAP_ACC_FLOATS holds every grid.
+ *   usseg_topk_loss_bwd     reads probs, y_true, l, sel, acc[4] (and overlap_acc[4..12)); writes dlogits bf16 [M][8] (lddl 8) or the quad
+ *                           layout (lddl 16) of UssegLossDesc; pad channels are exactly zero.
+ * Seven kernels and one memset for a training step, whatever the data.  M = 0 gives loss 0: the sums pass alone runs (as the other region
+ * losses' does) and nothing else launches.  tk_weight finite and >= 0; of the descriptor the fields the overlap entry points read.  The
+ * struct travels BY VALUE; the fraction is a device pointer, so a captured graph follows it without a recapture.  Every argument is checked
+ * before any launch (USSEG_ERR_BAD_ARG with usseg_last_error text), a workspace one byte short and M > 2^29 included. */
+typedef struct UssegTopkLoss {
+  float tk_weight; /* weight of the top-k term */
+  int32_t scope;   /* 0: one selection over the call's pixels ("batch"); 1: one per image ("image") */
+} UssegTopkLoss;
+int64_t usseg_topk_select_ws_bytes(int64_t S);
+int usseg_topk_select(const uint32_t* keys, int32_t S, int64_t n, const float* fraction, int32_t k, int32_t* sel, void* ws, int64_t ws_bytes,
+                      usseg_stream_t stream);
+int64_t usseg_topk_ws_bytes(int64_t M, int32_t HW, int32_t scope);
+int usseg_topk_pixel_loss(const UssegLossDesc* d, UssegTopkLoss tk, const float* fraction, const float* probs, const float* y_true, void* ws,
+                          int64_t ws_bytes, usseg_stream_t stream);
+int usseg_topk_loss_sums(const UssegLossDesc* d, UssegTopkLoss tk, const void* ws, int64_t ws_bytes, const float* overlap_acc, float* acc,
+                         int64_t acc_floats, usseg_stream_t stream);
+int usseg_topk_loss_bwd(const UssegLossDesc* d, UssegTopkLoss tk, const float* probs, const float* y_true, const void* ws, int64_t ws_bytes,
+                        const float* acc, int64_t acc_floats, const float* overlap_acc, void* dlogits, usseg_stream_t stream);
 /* The <= 4-class head Conv2DTranspose(k x k, stride 2, 'same') (Decoder.py:120 k=3; TBI_ResNest.py:124 k=4) in "quad" form: a
  * stride-1 convolution at the INPUT resolution whose 16 output channels are (output parity class)*4 + n, run by
  * usseg_conv2d_fwd/dgrad/wgrad as a 3x3 conv (each parity uses <= 2x2 of the stencil taps, the rest are zero).  With

@@ -1,0 +1,552 @@
+"""The exact device selection and the top-k (hard-pixel) cross-entropy (usseg.h usseg_topk_select / UssegTopkLoss, csrc/topk_loss.hip) on the GPU:
+
+  * ``ops.topk_select``: (t, ngt, neq, k) exactly against ``topk_restatement.select`` over sizes around the wave, the refinement tile and many
+    workgroups, one and three segments, six key patterns, four counts; three calls bit for bit; a workspace one byte short is refused;
+  * ``ops.topk_pixel_loss``: l per element against the fp64 restatement; sel against ``select`` applied to the GPU's OWN l bits - exactly;
+  * ``ops.topk_loss_sums``: the scalar, the plain CCE sum, the ticket, three calls bit for bit, M = 0;
+  * ``ops.topk_loss_bwd``: ``dlogits`` per element, row and quad layouts, pad channels and every slot of an unselected pixel exactly zero, planted
+    ties at the cut, the Dice term of "dice_topk", fraction 1 against the loss_kind 0 launch;
+  * Arch B at 64x64 and the TransUNet variant with ``loss="topk"`` / ``"dice_topk"``, both scopes: finite steps, the loss falls on a fixed batch,
+    graph replay equals eager bit for bit and follows ``set_topk_fraction`` without a recapture, ``loss="cce"`` does not move, save / load keep the
+    fraction, two gloo ranks equal the two-instance simulation bit for bit (an empty replica included), image scope does not depend on the split.
+
+Bounds.  The selection is integer work on the bits of l: exact.  Every comparison that involves the selection takes it from the GPU's own l
+(never from the fp64 l), so no pixel near the cut can flip between the two sides of a comparison.
+l: region_cce_pixel rounds, per class, the smoothed label (3), the quotient (1), the product with the log (1) and the running sum (1), plus C - 1
+additions of the class sum that every quotient inherits - at most 6 + (C - 1) <= 9 roundings of 2^-24 on terms that all have one sign - and
+``__logf``, whose error is not documented.  MEASURED on these inputs (C in 2, 3, 4; the four shapes): the worst relative error of l against the
+fp64 restatement is 4.3e-7 = 7.2 * 2^-24 (C = 2 at 2x256x80; 6.8 and 6.1 units at C = 3 and 4; 4.5 units on the 63 pixels of 1x9x7), inside the
+nine counted roundings.  The test asserts four times that, 1.72e-6, the margin covering other inputs.  The Lovasz / overlap tests bound the
+same arithmetic through its SUM at 1e-5 relative; this per-element bound is six times tighter and consistent with it.
+Scalar: 1e-5 relative of the restatement evaluated on the GPU's l and weights (the project's bar for a scalar loss).  acc[2], the plain sum
+of non-negative l: ``overlap_restatement.sum_bound(M)`` relative (the grid rule's depth; no product, so one rounding spare).
+dlogits: |dl - ref| <= 4 * 2^-8 * mag + tiny, tests/test_gpu_overlap_loss.py's construction, with mag from the sizes of the terms of
+G_c = coef * a * dLdp_c (+ |A_c|*|y_c| + |B_c| of the Dice term), ref from the weights derived from the GPU's l, and tiny = 2^-20 * coef
+(+ the overlap test's tiny for the Dice term).  The gauss inputs have no pixel within 2^-20 relative of a clip constant
+(tests/test_cpu_topk.py), so no pixel is left out; the check that at most 1e-3 of the pixels are skipped stays for other inputs.
+"""
+import math
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+import overlap_restatement as R
+import topk_restatement as T
+from route_probe import assert_elementwise
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+DEV = "cuda"
+U_BF16 = 2.0 ** -8
+L_REL_MEASURED = 4.3e-7            # see the module docstring
+SHAPES = [(2, 256, 80), (1, 64, 47), (1, 9, 7), (1, 1, 1)]        # many workgroups; a partial last group of four; a partial wave; one pixel
+NAMES = ["topk", "dice_topk"]
+
+
+def _probs(logits):
+    return torch.softmax(logits.float(), -1).contiguous()
+
+
+def _tk(cfg):
+    from ultrasound_modeling_amd import ops
+    return ops.topk_loss(cfg["tk_weight"], cfg["scope"])
+
+
+# ------------------------------------------------------------------------------------------------ the select
+PATTERNS = ("uniform", "all_equal", "two_values", "top_digit", "bottom_digit", "ascending")
+
+
+def _keys(pattern, S, n, rng):
+    if pattern == "uniform":
+        k = rng.integers(0, 1 << 32, (S, n), dtype=np.uint64)
+    elif pattern == "all_equal":
+        k = np.full((S, n), 0x3F123456, dtype=np.uint64)
+    elif pattern == "two_values":
+        k = np.where(rng.random((S, n)) < 0.3, 0xC0000001, 0x3FFFFFFF).astype(np.uint64)
+    elif pattern == "top_digit":
+        k = (rng.integers(0, 256, (S, n), dtype=np.uint64) << 24) | 0x00ABCDEF
+    elif pattern == "bottom_digit":
+        k = rng.integers(0, 256, (S, n), dtype=np.uint64) | 0x7F00FF00
+    else:
+        k = (np.arange(n, dtype=np.uint64) * 3 + 7)[None, :].repeat(S, 0) + np.arange(S, dtype=np.uint64)[:, None]
+    return k.astype(np.uint32)
+
+
+def _want_sel(keys, k):
+    return np.array([list(T.select(row, k)) + [k] for row in keys], dtype=np.int64)
+
+
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 2047, 2048, 2049, 6161, 40960])
+def test_select_is_exact(n):
+    from ultrasound_modeling_amd import ops
+    rng = np.random.default_rng(n)
+    frac = torch.tensor([0.1], dtype=torch.float32, device=DEV)
+    for S in (1, 3):
+        ws = torch.empty(max(ops.topk_select_ws_bytes(S), 16), dtype=torch.uint8, device=DEV)
+        for pattern in PATTERNS:
+            keys = _keys(pattern, S, n, rng)
+            kd = torch.from_numpy(keys.view(np.int32).copy()).to(DEV)
+            k10 = max(1, n // 10)
+            t10, ngt10, neq10 = T.select(keys[0], k10)
+            for k in sorted({1, n, k10, ngt10 + neq10}):          # the last one lands exactly on the last element of segment 0's run of ties
+                runs = [ops.topk_select(kd, k=k, ws=ws).cpu().numpy() for _ in range(3)]
+                assert np.array_equal(runs[0], runs[1]) and np.array_equal(runs[0], runs[2])
+                got = runs[0].astype(np.int64)
+                got[:, 0] &= 0xFFFFFFFF                           # t: the key's bits
+                assert np.array_equal(got, _want_sel(keys, k)), (S, pattern, k)
+            got = ops.topk_select(kd, fraction=frac, ws=ws).cpu().numpy().astype(np.int64)      # the count from the device fraction
+            got[:, 0] &= 0xFFFFFFFF
+            assert T.k_of(0.1, n) == k10 and np.array_equal(got, _want_sel(keys, k10)), (S, pattern, "fraction")
+
+
+def test_select_refuses_a_workspace_one_byte_short():
+    from ultrasound_modeling_amd import _lib as L
+    from ultrasound_modeling_amd import ops
+    keys = torch.arange(3 * 100, dtype=torch.int32, device=DEV).view(3, 100)
+    need = ops.topk_select_ws_bytes(3)
+    with pytest.raises(L.UssegError, match=f"the workspace holds {need - 1} bytes, {need} needed"):
+        ops.topk_select(keys, k=5, ws=torch.empty(need - 1, dtype=torch.uint8, device=DEV))
+    sel = ops.topk_select(keys, k=5, ws=torch.empty(need, dtype=torch.uint8, device=DEV)).cpu().tolist()
+    assert sel == [[95, 4, 1, 5], [195, 4, 1, 5], [295, 4, 1, 5]]
+
+
+# ------------------------------------------------------------------------------------------------ l, the selection inside the loss, the sums
+def _pixel_pass(C, B, H, W, cfg, plant=None):
+    """-> (pd, yd, ws, l fp32 numpy [M], sel numpy [S, 4]) after ``ops.topk_pixel_loss``; ``plant(p32, y)`` may edit the inputs first."""
+    from ultrasound_modeling_amd import ops
+    logits, y = R.inputs(C, B, H, W)
+    p32 = _probs(logits)
+    if plant is not None:
+        plant(p32, y)
+    pd, yd = p32.to(DEV), y.float().to(DEV)
+    M = B * H * W
+    ws = torch.full((max(ops.topk_ws_bytes(M, H * W, cfg["scope"]), 16),), 0xFF, dtype=torch.uint8, device=DEV)      # l = NaN bits: every element must be written
+    frac = torch.tensor([cfg["fraction"]], dtype=torch.float32, device=DEV)
+    ops.topk_pixel_loss(pd, yd, frac, ws, topk=_tk(cfg), HW=H * W, C_classes=C)
+    torch.cuda.synchronize()
+    l, sel = ops.topk_ws_views(ws, M, H * W, cfg["scope"])
+    return p32, y, pd, yd, ws, l.cpu().numpy().copy(), sel.cpu().numpy().astype(np.int64)
+
+
+@pytest.mark.parametrize("scope", T.SCOPES)
+@pytest.mark.parametrize("C", [3, 2, 4])
+@pytest.mark.parametrize("B,H,W", SHAPES)
+def test_pixel_loss_per_element_and_the_selection_on_its_own_bits(B, H, W, C, scope):
+    cfg = T.config(fraction=0.1, scope=scope)
+    p32, y, _, _, _, l, sel = _pixel_pass(C, B, H, W, cfg)
+    want = T.pixel_loss(p32.double().numpy(), y.numpy())
+    rel = np.abs(l.astype(np.float64) - want) / want
+    print(f"\n  l C={C} {B}x{H}x{W}: worst relative error {rel.max():.3e} ({rel.max() / 2.0 ** -24:.2f} * 2^-24)", end="")
+    assert rel.max() <= 4 * L_REL_MEASURED
+    S, n = T.segments(B * H * W, H * W, scope)
+    k = T.k_of(0.1, n)
+    keys = T.keys_of(l).reshape(S, n)
+    assert np.array_equal(sel, _want_sel(keys, k)), "sel must equal select() applied to the GPU's own l bits"
+
+
+@pytest.mark.parametrize("loss", NAMES)
+@pytest.mark.parametrize("scope", T.SCOPES)
+@pytest.mark.parametrize("C", [3, 2, 4])
+@pytest.mark.parametrize("B,H,W", SHAPES)
+def test_sums_against_the_restatement_and_bit_for_bit_over_three_calls(B, H, W, C, scope, loss):
+    from ultrasound_modeling_amd import ops
+    import test_gpu_overlap_loss as OL
+    cfg = T.config(loss, fraction=0.25, scope=scope, tk_weight=0.7)
+    inv, ov_scale, M = 1.0 / 7.0, 0.5, B * H * W
+    p32, y, pd, yd, ws, l, sel = _pixel_pass(C, B, H, W, cfg)
+    acc = torch.zeros(ops.OVERLAP_ACC_FLOATS, device=DEV)
+    ov_acc, dice = None, 0.0
+    if cfg["dice"]:
+        ocfg = OL._cfg("dice", C)
+        ov_acc = torch.zeros(ops.OVERLAP_ACC_FLOATS, device=DEV)
+        ops.overlap_loss_sums(pd, yd, ov_acc, overlap=OL._ol(ocfg), HW=H * W, C_classes=C, ov_scale=ov_scale, inv_global_batch=inv)
+        dice = R.loss(p32.double(), y, ocfg, inv, ov_scale).item()
+    runs = []
+    for _ in range(3):
+        ops.topk_loss_sums(pd, ws, acc, topk=_tk(cfg), HW=H * W, C_classes=C, overlap_acc=ov_acc, inv_global_batch=inv)
+        torch.cuda.synchronize()
+        runs.append(acc[:32].cpu().clone())
+        assert acc[1].item() == 0                              # the ticket counter is back at zero: no per-call zeroing
+    assert torch.equal(runs[0], runs[1]) and torch.equal(runs[0], runs[2])
+    got = runs[0].double()
+    a, k, n = T.all_weights(l, H * W, cfg)
+    assert sel[0, 3] == k
+    want_tk = T.loss(l.astype(np.float64), H * W, cfg, inv, l32=l)
+    assert abs(got[4].item() - cfg["tk_weight"] * inv * n / k) <= 4 * 2.0 ** -24 * got[4].item()
+    print(f"\n  {loss} {scope} C={C} {B}x{H}x{W}: loss {got[0].item():.7f} vs {want_tk + dice:.7f}", end="")
+    assert abs(got[0].item() - (want_tk + dice)) <= 1e-5 * abs(want_tk + dice)
+    plain = float(l.astype(np.float64).sum())
+    assert abs(got[2].item() - plain) <= R.sum_bound(M) * plain
+
+
+def test_sums_of_no_pixels_give_a_zero_loss():
+    """M = 0 through the C ABI (an empty tensor has no data pointer to pass): loss 0, the ticket at zero, no other launch."""
+    import ctypes as C
+    from ultrasound_modeling_amd import _lib as L
+    from ultrasound_modeling_amd import ops
+    acc = torch.zeros(ops.OVERLAP_ACC_FLOATS, device=DEV)
+    acc[0] = 7.0
+    buf = torch.zeros(16, device=DEV)
+    d = L.LossDesc(0, 16, 3, 3, 8, 0, 0.1, 1e-7, 0.25, 0)
+    s = torch.cuda.current_stream().cuda_stream
+    for scope in (0, 1):
+        tk = L.TopkLoss(1.0, scope)
+        L.check(L.load().usseg_topk_pixel_loss(C.byref(d), tk, buf.data_ptr(), buf.data_ptr(), buf.data_ptr(), None, 0, s), "pixel_loss")
+        L.check(L.load().usseg_topk_loss_sums(C.byref(d), tk, None, 0, None, acc.data_ptr(), acc.numel(), s), "sums")
+        L.check(L.load().usseg_topk_loss_bwd(C.byref(d), tk, buf.data_ptr(), buf.data_ptr(), None, 0, acc.data_ptr(), acc.numel(), None, buf.data_ptr(), s), "bwd")
+        torch.cuda.synchronize()
+        assert acc[0].item() == 0.0 and acc[1].item() == 0.0
+        acc[0] = 7.0
+
+
+# ------------------------------------------------------------------------------------------------ dlogits
+def _bwd(loss, C, B, H, W, quad, scope="batch", fraction=0.25, inv=0.25, ov_scale=0.5, plant=None):
+    """-> everything ``_check_dlogits`` needs after the three calls (and ``overlap_loss_sums`` for "dice_topk")."""
+    from ultrasound_modeling_amd import ops
+    import test_gpu_overlap_loss as OL
+    cfg = T.config(loss, fraction=fraction, scope=scope, tk_weight=0.7)
+    p32, y, pd, yd, ws, l, sel = _pixel_pass(C, B, H, W, cfg, plant)
+    acc = torch.zeros(ops.OVERLAP_ACC_FLOATS, device=DEV)
+    ov_acc, ocfg = None, None
+    kw = dict(topk=_tk(cfg), HW=H * W, C_classes=C, inv_global_batch=inv)
+    if cfg["dice"]:
+        ocfg = OL._cfg("dice", C)
+        ov_acc = torch.zeros(ops.OVERLAP_ACC_FLOATS, device=DEV)
+        ops.overlap_loss_sums(pd, yd, ov_acc, overlap=OL._ol(ocfg), HW=H * W, C_classes=C, ov_scale=ov_scale, inv_global_batch=inv)
+    ops.topk_loss_sums(pd, ws, acc, overlap_acc=ov_acc, **kw)
+    dl = torch.full(OL._to_quad_shape(B, H, W) if quad else (B, H, W, 8), float("nan"), dtype=torch.bfloat16, device=DEV)   # every element must be written
+    ops.topk_loss_bwd(pd, yd, ws, acc, dl, overlap_acc=ov_acc, quad_w=W if quad else 0, **kw)
+    torch.cuda.synchronize()
+    return dict(cfg=cfg, ocfg=ocfg, p32=p32, y=y, l=l, sel=sel, dl=dl, inv=inv, ov_scale=ov_scale, HW=H * W)
+
+
+def _check_dlogits(what, d, r):
+    """d [B,H,W,C] against the restatement at the same fp32 probabilities, with the weights derived from the GPU's l.  -> a [M]."""
+    import test_gpu_overlap_loss as OL
+    cfg, p32, y, inv = r["cfg"], r["p32"], r["y"], r["inv"]
+    C = p32.shape[-1]
+    p = p32.double().numpy().reshape(-1, C)
+    a, k, n = T.all_weights(r["l"], r["HW"], cfg)
+    coef = cfg["tk_weight"] * inv * n / k
+    G, _, _ = T.dlogits_terms(p, y.numpy(), a, k, n, cfg, inv)
+    S = np.abs(G)
+    tiny = 2.0 ** -20 * coef
+    if r["ocfg"] is not None:
+        want = OL._restate_at(p32, y, r["ocfg"], inv, r["ov_scale"])
+        G = G + want["G"].numpy().reshape(-1, C)
+        S = S + (want["A"].abs() * y.abs() + want["B"].abs()).numpy().reshape(-1, C)
+        tiny += 2.0 ** -20 * r["ov_scale"] * max(r["ocfg"]["w"]) / want["D"].min().item()
+    ref = p * (G - (G * p).sum(-1, keepdims=True))
+    mag = p * (S + (S * p).sum(-1, keepdims=True))
+    q = p / p.sum(-1, keepdims=True)
+    rel = 2.0 ** -20
+    skip = ((np.abs(q - R.LO) <= rel * R.LO) | (np.abs(q - R.HI) <= rel * R.HI)).any(-1)
+    assert skip.sum() <= 1e-3 * skip.size
+    keep = torch.from_numpy(~skip)
+    assert_elementwise(d.double().cpu().reshape(-1, C)[keep], torch.from_numpy(ref)[keep], torch.from_numpy(mag)[keep], U_BF16, 4.0, tiny=tiny, what=what)
+    return a
+
+
+@pytest.mark.parametrize("loss,scope", [("topk", "batch"), ("topk", "image"), ("dice_topk", "batch")])
+@pytest.mark.parametrize("C", [3, 2, 4])
+@pytest.mark.parametrize("B,H,W", SHAPES)
+def test_dlogits_row_layout_per_element(B, H, W, C, loss, scope):
+    r = _bwd(loss, C, B, H, W, quad=False, scope=scope)
+    dl = r["dl"]
+    assert dl[..., C:].float().abs().max().item() == 0                # pad channels exactly zero (and written: the buffer started as NaN)
+    a = _check_dlogits(f"row {loss} {scope} C={C} {B}x{H}x{W}", dl[..., :C].float(), r)
+    if loss == "topk":                                                 # every slot of every unselected pixel is exactly zero
+        un = torch.from_numpy(a == 0.0)
+        assert (a == 0.0).sum() == a.size - r["sel"][:, 1].sum() - r["sel"][:, 2].sum()
+        assert dl.float().cpu().reshape(-1, 8)[un].abs().max().item() == 0 if un.any() else True
+
+
+@pytest.mark.parametrize("loss,scope", [("topk", "image"), ("dice_topk", "batch")])
+@pytest.mark.parametrize("C", [3, 2, 4])
+@pytest.mark.parametrize("B,H,W", [(2, 256, 80), (1, 64, 46), (3, 10, 6)])      # (the quad layout needs even H and W: 64x46 stands in for 64x47)
+def test_dlogits_quad_layout_per_element(B, H, W, C, loss, scope):
+    import test_gpu_overlap_loss as OL
+    r = _bwd(loss, C, B, H, W, quad=True, scope=scope)
+    d4 = OL._from_quad(r["dl"].float())
+    assert not torch.isnan(d4).any()                                  # all 16 channels of every quad pixel were written
+    if C < 4:
+        assert d4[..., C:].abs().max().item() == 0                    # the pad classes of every parity slot
+    a = _check_dlogits(f"quad {loss} {scope} C={C} {B}x{H}x{W}", d4[..., :C], r)
+    if loss == "topk":
+        un = torch.from_numpy(a == 0.0)
+        assert d4.cpu().reshape(-1, 4)[un].abs().max().item() == 0
+
+
+def test_planted_ties_at_the_cut_share_the_remaining_weight():
+    """Seven pixels get the probabilities and labels of the pixel that sits at the cut: neq = 8 > r, and each tied pixel carries r / neq."""
+    C, B, H, W, f = 3, 1, 64, 47, 0.25
+    logits, y0 = R.inputs(C, B, H, W)
+    l0 = T.pixel_loss(_probs(logits).double().numpy(), y0.numpy())
+    k = T.k_of(f, H * W)
+    at = int(np.argsort(-l0, kind="stable")[k - 3])                  # the pixel of rank k - 3: with its seven copies the run straddles rank k
+    others = [m for m in range(0, H * W, 97) if m != at][:7]
+
+    def plant(p32, y):
+        pf, yf = p32.view(-1, C), y.view(-1, C)
+        for m in others:
+            pf[m], yf[m] = pf[at], yf[at]
+    r = _bwd("topk", C, B, H, W, quad=False, fraction=f, plant=plant)
+    t, ngt, neq, kk = r["sel"][0]
+    assert kk == k and neq >= 8 and 1 <= k - ngt < neq, (ngt, neq, k)
+    a = _check_dlogits("planted ties", r["dl"][..., :C].float(), r)
+    tied = np.nonzero(T.keys_of(r["l"]) == t)[0]
+    assert set(others + [at]) <= set(tied.tolist()) and np.allclose(a[tied], (k - ngt) / neq, rtol=0, atol=1e-15)
+    d = r["dl"].float().cpu().reshape(-1, 8)
+    assert all(torch.equal(d[m], d[at]) for m in others) and d[at].abs().max().item() > 0
+
+
+@pytest.mark.parametrize("quad", [False, True])
+def test_fraction_one_equals_the_existing_cce_launch(quad):
+    """Every pixel selected: the loss and dlogits of the existing loss_kind 0 launch on the same logits, at the bound of the Lovasz CCE-limit test."""
+    from ultrasound_modeling_amd import ops
+    import test_gpu_overlap_loss as OL
+    C, B, H, W, inv = 3, 2, 64, 46, 0.25
+    logits, y = R.inputs(C, B, H, W)
+    yd = y.float().to(DEV)
+    probs = torch.empty(B, H, W, C, device=DEV)
+    loss0 = torch.zeros(ops.ACC_FLOATS, device=DEV)
+    if quad:
+        lq = torch.zeros(B, H // 2, W // 2, 16)
+        for a in range(2):
+            for b in range(2):
+                lq[..., 4 * (a * 2 + b):4 * (a * 2 + b) + C] = logits.float()[:, a::2, b::2, :]
+        lg, dl0 = lq.to(DEV), ops.new_act(B, H // 2, W // 2, 16, DEV)
+    else:
+        lg = torch.zeros(B, H, W, 4)
+        lg[..., :C] = logits.float()
+        lg, dl0 = lg.to(DEV), ops.new_act(B, H, W, 8, DEV)
+    ops.softmax_loss(lg, yd, probs, loss0, dl0, HW=H * W, C_classes=C, inv_global_batch=inv, quad_w=W if quad else 0)
+    for scope in T.SCOPES:
+        cfg = T.config(fraction=1.0, scope=scope)
+        ws = torch.empty(ops.topk_ws_bytes(B * H * W, H * W, scope), dtype=torch.uint8, device=DEV)
+        acc = torch.zeros(ops.OVERLAP_ACC_FLOATS, device=DEV)
+        kw = dict(topk=_tk(cfg), HW=H * W, C_classes=C)
+        ops.topk_pixel_loss(probs, yd, torch.ones(1, device=DEV), ws, **kw)
+        ops.topk_loss_sums(probs, ws, acc, inv_global_batch=inv, **kw)
+        dl1 = torch.full_like(dl0, float("nan"))
+        ops.topk_loss_bwd(probs, yd, ws, acc, dl1, inv_global_batch=inv, quad_w=W if quad else 0, **kw)
+        torch.cuda.synchronize()
+        print(f"\n  fraction 1 ({scope}): {acc[0].item():.7f} vs the CCE launch {loss0[0].item():.7f}", end="")
+        assert abs(acc[0].item() - loss0[0].item()) <= 1e-5 * abs(loss0[0].item())
+        assert abs(acc[2].item() * inv - loss0[0].item()) <= 1e-5 * abs(loss0[0].item())
+        d0, d1 = (OL._from_quad(dl0.float())[..., :C], OL._from_quad(dl1.float())[..., :C]) if quad else (dl0.float()[..., :C], dl1.float()[..., :C])
+        p = probs.double().cpu()
+        pc = p.clone().requires_grad_(True)
+        (inv * R.cce_per_pixel(pc, y).sum()).backward()
+        S = pc.grad.abs()
+        mag = p * (S + (S * p).sum(-1, keepdim=True))
+        assert_elementwise(d1.double().cpu(), d0.double().cpu(), mag, U_BF16, 4.0, tiny=2.0 ** -20 * inv, what=f"fraction 1 ({scope})")
+
+
+# ------------------------------------------------------------------------------------------------ the model
+def _builders():
+    import test_gpu_overlap_loss as OL
+    return {"archB": OL._arch_b, "transunet": OL._transunet}, OL._batches
+
+
+def _want_loss(net, probs, y, inv):
+    """The restatement on the model's own probabilities (selection on fp32(l): a flip at the cut moves the sum by less than the bound)."""
+    tk = net.topk_loss
+    cfg = T.config(net.loss_name, fraction=net.topk_fraction, scope=T.SCOPES[tk.scope], tk_weight=tk.tk_weight)
+    B, H, W, _ = probs.shape
+    want = T.loss(T.pixel_loss(probs.double().cpu().numpy(), y.double().numpy()), H * W, cfg, inv)
+    if cfg["dice"]:
+        ol = net._topk_overlap
+        ocfg = dict(w=list(ol.w)[:net.num_classes], alpha=ol.alpha, beta=ol.beta, smooth=ol.smooth, power=ol.power, ov_weight=ol.ov_weight, ce_weight=0.0)
+        want += R.loss(probs.double().cpu(), y.double(), ocfg, inv, 1.0).item()
+    return want
+
+
+@pytest.mark.parametrize("scope", T.SCOPES)
+@pytest.mark.parametrize("loss", NAMES)
+@pytest.mark.parametrize("make", ["archB", "transunet"])
+def test_the_model_steps_with_the_topk_loss_and_the_loss_falls(make, loss, scope):
+    """Eight steps on one fixed batch, the count tests/test_gpu_overlap_loss.py uses."""
+    builders, batches = _builders()
+    net = builders[make](loss=loss, topk=dict(scope=scope, fraction=0.2))
+    x, y = batches(1, 2, 64, 64)[0]
+    l, probs = net.step(x, y.float())
+    torch.cuda.synchronize()
+    inv = 1.0 / (2 * 64 * 64) if net.transunet else 0.5
+    want = _want_loss(net, probs, y, inv)
+    print(f"\n  {loss} {scope}: step loss {l.item():.6f}, restatement on its probabilities {want:.6f}", end="")
+    assert math.isfinite(l.item()) and abs(l.item() - want) <= 2e-5 * abs(want)
+    got = net.compute_loss(y.float(), probs)
+    if not net.transunet:                                            # compute_loss divides by the global batch, as it does for every loss
+        assert got.shape == () and abs(got.item() - want) <= 2e-5 * abs(want)
+    losses = []
+    for _ in range(8):
+        l, _p = net.train_step(x, y.float())
+        losses.append(l.item())
+    print(f"; {losses[0]:.4f} -> {losses[-1]:.4f}", end="")
+    assert all(math.isfinite(v) for v in losses) and losses[-1] < losses[0]
+    assert net._loss[1].item() == 0 and len(net._topk_bufs) == 1
+
+
+@pytest.mark.parametrize("make,loss,scope", [("archB", "topk", "batch"), ("archB", "dice_topk", "image"), ("transunet", "topk", "image"),
+                                             ("transunet", "dice_topk", "batch")])
+def test_graph_replay_equals_eager_and_follows_the_fraction(make, loss, scope):
+    from test_gpu_step import _assert_same_state, _state
+    builders, batches = _builders()
+    eager, graph = builders[make](loss=loss, topk=dict(scope=scope)), builders[make](loss=loss, topk=dict(scope=scope, fraction=0.1))
+    bs = batches(4, 2, 64, 64)
+    graph.capture_graph(bs[0][0], bs[0][1].float())
+    _assert_same_state(_state(eager), _state(graph), "capture must not change the training state")
+    for i, (x, y) in enumerate(bs[:2]):
+        l0, p0 = eager.train_step(x, y.float())
+        l1, p1 = graph.train_step(x, y.float())
+        torch.cuda.synchronize()
+        assert l0.item() == l1.item(), (i, l0.item(), l1.item())
+        assert torch.equal(p0, p1), i
+        _assert_same_state(_state(eager), _state(graph), f"{loss} step {i}")
+    # the SAME captured graph after set_topk_fraction(0.5) against an eager model BUILT with 0.5 and brought to the same state
+    half = builders[make](loss=loss, topk=dict(scope=scope, fraction=0.5))
+    for x, y in bs[:2]:
+        half.set_topk_fraction(0.1)
+        half.train_step(x, y.float())
+    half.set_topk_fraction(0.5)
+    _assert_same_state(_state(half), _state(graph), "the third model reached the same state")
+    captured = graph._graph
+    graph.set_topk_fraction(0.5)
+    assert graph.topk_fraction == 0.5 and half.topk_fraction == 0.5
+    seen = []
+    for i, (x, y) in enumerate(bs[2:]):
+        l0, p0 = half.train_step(x, y.float())
+        l1, p1 = graph.train_step(x, y.float())
+        torch.cuda.synchronize()
+        assert l0.item() == l1.item() and torch.equal(p0, p1), i
+        _assert_same_state(_state(half), _state(graph), f"{loss} fraction 0.5 step {i}")
+        seen.append(l1.item())
+    assert graph._graph is captured and captured is not None
+    la, _ = eager.train_step(bs[2][0], bs[2][1].float())              # the same weights and batch under the fraction 0.1
+    assert la.item() != seen[0]                                       # (the fraction matters: 0.1 and 0.5 are different losses)
+
+
+def test_the_default_loss_does_not_move_and_save_load_keep_the_fraction(tmp_path):
+    """loss="cce" built before and after a top-k model has been built and stepped: the same bits, and not one top-k buffer."""
+    from ultrasound_modeling_amd import ops
+    builders, batches = _builders()
+    a = builders["archB"](loss="cce")
+    d = builders["archB"](loss="dice_topk", topk=dict(fraction=0.3))
+    bs = batches(2, 2, 64, 64)
+    d.train_step(bs[0][0], bs[0][1].float())
+    b = builders["archB"]()
+    assert a.topk_loss is None and b.topk_loss is None and b.topk_fraction is None and not hasattr(b, "_topk_bufs") and not hasattr(b, "_tkf")
+    assert a._loss.numel() == b._loss.numel() == ops.ACC_FLOATS
+    with pytest.raises(ValueError):
+        b.set_topk_fraction(0.5)
+    for x, y in bs:
+        la, pa = a.train_step(x, y.float())
+        lb, pb = b.train_step(x, y.float())
+        torch.cuda.synchronize()
+        assert la.item() == lb.item() and torch.equal(pa, pb)
+    assert torch.equal(a.flat.flat, b.flat.flat)
+    assert not torch.equal(a.flat.flat, d.flat.flat)
+    # save / load
+    d.set_topk_fraction(0.375)
+    for bad in (0.0, 1.5, float("nan")):
+        with pytest.raises(ValueError):
+            d.set_topk_fraction(bad)
+    d.save(str(tmp_path / "m.pt"))
+    e = builders["archB"](loss="dice_topk")
+    assert e.topk_fraction == pytest.approx(0.1)
+    e.load(str(tmp_path / "m.pt"))
+    assert e.topk_fraction == 0.375 and torch.equal(e.flat.flat, d.flat.flat)
+    b.load(str(tmp_path / "m.pt"))                                    # a model without the loss ignores the entry
+    assert torch.equal(b.flat.flat, d.flat.flat)
+
+
+def test_image_scope_does_not_depend_on_how_the_batch_is_split():
+    """Two replicas with one image each (global batch 2) against one replica with both: with scope="image" the selection is per image, so the
+    summed gradients agree up to the order of the batch sums in the weight gradients - within one bf16 unit of the gradient's norm."""
+    builders, batches = _builders()
+    x, y = batches(1, 2, 64, 64)[0]
+    nets = [builders["archB"](loss="topk", topk=dict(scope="image", fraction=0.2)) for _ in range(3)]
+    for net, sl in zip(nets, (slice(0, 1), slice(1, 2), slice(0, 2))):
+        net.train_step(x[sl], y[sl].float())                           # (the gradient buffer keeps the step's raw gradient: __graft_entry__.smoke reads it so)
+    torch.cuda.synchronize()
+    two, one = (nets[0].flat.grad + nets[1].flat.grad).double(), nets[2].flat.grad.double()
+    assert one.norm().item() > 0 and (two - one).norm().item() <= U_BF16 * one.norm().item()
+    assert abs((nets[0]._loss[0] + nets[1]._loss[0]).item() - nets[2]._loss[0].item()) <= 1e-5 * nets[2]._loss[0].item()
+    # scope="batch" is the replica reading: a replica selects among ITS pixels, and the split matters
+    nets = [builders["archB"](loss="topk", topk=dict(scope="batch", fraction=0.2)) for _ in range(3)]
+    for net, sl in zip(nets, (slice(0, 1), slice(1, 2), slice(0, 2))):
+        net.step(x[sl], y[sl].float())
+    assert abs((nets[0]._loss[0] + nets[1]._loss[0]).item() - nets[2]._loss[0].item()) > 1e-4 * nets[2]._loss[0].item()
+
+
+# ------------------------------------------------------------------------------------------------ two ranks
+def test_two_gloo_ranks_with_dice_topk_equal_the_simulation_bit_for_bit(tmp_path):
+    """tests/test_gpu_overlap_loss.py's two-rank test with ``main(..., loss="dice_topk")``: nine images in batches of four, so the last step
+    leaves rank 1 without an image; ranks and simulation each in a fresh process."""
+    import test_gpu_mainparallel as MP
+    train, val = MP._arrays(MP.N_TRAIN, seed=1), MP._arrays(MP.N_TEST, seed=2)
+    np.save(tmp_path / "train.npy", train)
+    np.save(tmp_path / "val.npy", val)
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "USSEG_DP_CHUNKS")}
+    env.update(USSEG_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", PYTHONPATH=os.pathsep.join([ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle")]))
+    r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes", "1", "--nproc_per_node", "2", "--master_addr", "127.0.0.1",
+                        "--master_port", str(MP._free_port()), os.path.abspath(__file__), str(tmp_path)],
+                       cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, (r.stdout[-3000:], r.stderr[-3000:])
+    assert "dice per class = [" in r.stdout                                           # the drivers' extra report line
+    d = [torch.load(tmp_path / f"rank{k}.pt", weights_only=False) for k in range(2)]
+    assert d[0]["graph"] and d[1]["graph"] and d[0]["loss_name"] == "dice_topk"
+    assert torch.equal(d[0]["state"]["flat"], d[1]["state"]["flat"]), "replicas diverged"
+    r = subprocess.run([sys.executable, os.path.abspath(__file__), str(tmp_path), "simulate"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, (r.stdout[-3000:], r.stderr[-3000:])
+    sim = torch.load(tmp_path / "sim.pt", weights_only=False)
+    want, history = sim["want"], sim["history"]
+    for k in range(2):
+        assert MP._first_difference(d[k]["state"], want[k]) is None, (k, MP._first_difference(d[k]["state"], want[k]))
+    assert want[0]["step"].item() == MP.EPOCHS * 3                                     # three steps an epoch: the last one with an empty rank 1
+    MP._same_history(d[0]["history"], history)
+    MP._same_history(d[1]["history"], history)
+
+
+TWO_RANK_TOPK = dict(fraction=0.2, scope="batch")
+
+
+def _rank(tmp):
+    import torch.distributed as dist
+    import test_gpu_mainparallel as MP
+    from ultrasound_modeling_amd.MainParallel import main
+    net, proc = main(os.path.join(tmp, "train.npy"), os.path.join(tmp, "val.npy"), None, epochs=MP.EPOCHS, batch_size=MP.B, use_vit=False,
+                     seed=MP.SEED, loss="dice_topk", topk=TWO_RANK_TOPK)
+    rank = dist.get_rank()
+    torch.save({"state": MP._state(net), "history": proc.history, "graph": net._graph is not None, "loss_name": net.loss_name},
+               os.path.join(tmp, f"rank{rank}.pt"))
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+def _simulate(tmp):
+    """``test_gpu_mainparallel._simulate`` with both instances built with ``loss="dice_topk"``."""
+    import test_gpu_mainparallel as MP
+    import ultrasound_modeling_amd.VisionTransformer as VT
+    orig, made = VT.VisionTransformer, []
+
+    def make(*a, **kw):
+        made.append(orig(*a, loss="dice_topk", topk=TWO_RANK_TOPK, **kw))
+        return made[-1]
+    VT.VisionTransformer = make
+    want, history = MP._simulate(np.load(os.path.join(tmp, "train.npy")), np.load(os.path.join(tmp, "val.npy")))
+    assert len(made) == 2 and all(n.loss_name == "dice_topk" and n.topk_loss is not None for n in made), "the simulation did not train with dice_topk"
+    torch.save({"want": want, "history": history}, os.path.join(tmp, "sim.pt"))
+
+
+if __name__ == "__main__":
+    sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle")]
+    if sys.argv[2:] == ["simulate"]:
+        _simulate(sys.argv[1])
+    else:
+        _rank(sys.argv[1])

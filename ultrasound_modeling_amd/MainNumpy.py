@@ -153,7 +153,7 @@ class Process(object):
 
 
 def main(train_path, val_path, save_path=None, epochs=50, batch_size=32, num_classes=3, *, loss="cce", overlap=None, boundary=None, lovasz=None,
-         average=None, warp=None, warp_seed=0):
+         average=None, warp=None, warp_seed=0, topk=None):
     """MainNumpy.py:150-177 with the paths as arguments: ``VisionTransformer(32, img_size=(256, 80))`` over a ``Dataset_2.Dataset``,
     50 epochs, then a save if ``save_path`` is given.  ``loss``: the model's ``loss=`` ("cce", "my_loss_cat", "focal", "dice", "tversky",
     "dice_ce"); ``overlap``: the settings of the last three (``VisionTransformer(overlap=...)``), which also add a per-class Dice line to the test report;
@@ -161,12 +161,13 @@ def main(train_path, val_path, save_path=None, epochs=50, batch_size=32, num_cla
     ``lovasz`` (``VisionTransformer(lovasz=...)``: the Lovasz-softmax loss; the Dice line too).  ``average`` (a dict, or the string
     ``ema:DECAY[:dynamic]`` / ``swa:START:PERIOD``): EMA / SWA weight averaging - the tests report the averaged model, and the save also writes
     ``<save_path>.avg``, a plain checkpoint of the averaged weights (``save_averaged``).  ``warp`` (a ``warp.warp_config`` dict or ``parse_warp``
-    string; default off): elastic / affine warp of every training batch ahead of ``dataAug``, its draws from ``random.Random(warp_seed)``."""
+    string; default off): elastic / affine warp of every training batch ahead of ``dataAug``, its draws from ``random.Random(warp_seed)``.
+    "topk" / "dice_topk" with their settings in ``topk`` (``VisionTransformer(topk=...)``: the top-k cross-entropy; the Dice line too)."""
     from .Dataset_2 import Dataset
     from .VisionTransformer import VisionTransformer, overlap_settings
     dataset = Dataset(train_path, val_path, num_classes, warp=warp, warp_seed=warp_seed)
     neuralnet = VisionTransformer(batch_size, img_size=input_size, num_classes=num_classes, loss=loss, overlap=overlap_settings(loss, overlap),
-                                  boundary=boundary, lovasz=lovasz, average=average_setting(average))
+                                  boundary=boundary, lovasz=lovasz, average=average_setting(average), **({} if topk is None else {"topk": topk}))
     print(len(neuralnet.visionModel.layers))
     process = Process(batch_size=batch_size, num_classes=num_classes)
     process.training(neuralnet=neuralnet, dataset=dataset, epochs=epochs)

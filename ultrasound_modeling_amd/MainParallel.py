@@ -300,7 +300,7 @@ class Process(object):
 
 
 def main(train_path, val_path, save_path=None, epochs=51, batch_size=64, use_vit=True, *, seed=0, schedule=False, capture_graph=True,
-         loss="cce", overlap=None, boundary=None, lovasz=None, average=None, warp=None):
+         loss="cce", overlap=None, boundary=None, lovasz=None, average=None, warp=None, topk=None):
     """MainParallel.py:201-216 with the paths as arguments: ``VisionTransformer(batch_size=64)`` with the ViT bottleneck, 51 epochs,
     then rank 0 saves if ``save_path`` is given.  Every rank seeds ``random`` with ``seed``, so all draw the same augmentations.
     ``loss``: the model's ``loss=`` ("cce", "my_loss_cat", "focal"); every replica divides it by the global batch all the same.  The
@@ -309,6 +309,9 @@ def main(train_path, val_path, save_path=None, epochs=51, batch_size=64, use_vit
     ``boundary`` (``VisionTransformer(boundary=...)``) adds the boundary term to one of those three, weighted per replica the same way.
     The Lovasz-softmax loss ("lovasz", "lovasz_ce", settings in ``lovasz``) ranks the pixels of the images a replica holds and is weighted like the
     overlap term; it adds the Dice line too.
+    The top-k cross-entropy ("topk", "dice_topk", settings in ``topk``): with scope "batch" a replica selects among the pixels of the images it holds,
+    with scope "image" the selection is per image and does not depend on how the batch is split; every replica divides by the global batch all
+    the same, and the Dice term of "dice_topk" is weighted like the overlap term.  The Dice line too.
     ``average`` (a dict, or the ``--average`` string ``ema:DECAY[:dynamic]`` / ``swa:START:PERIOD``): EMA / SWA weight averaging; the update of
     every rank keeps the same average (no exchange is added), the tests report the averaged model and rank 0 also saves ``<save_path>.avg``.
     ``warp`` (a ``warp.warp_config`` dict or the ``--warp`` string; default off): elastic / affine warp of every training batch ahead of ``dataAug``;
@@ -325,7 +328,7 @@ def main(train_path, val_path, save_path=None, epochs=51, batch_size=64, use_vit
     dataset = Dataset(train_path, val_path, batch_size, device=device, warp=warp, warp_seed=seed)
     neuralnet = VisionTransformer(batch_size, img_size=(dataset.height, dataset.width), in_channels=dataset.channel, use_vit=use_vit,
                                   device=str(device), loss=loss, overlap=overlap_settings(loss, overlap), boundary=boundary, lovasz=lovasz,
-                                  average=average_setting(average))
+                                  average=average_setting(average), **({} if topk is None else {"topk": topk}))
     if rank == 0:
         print(len(neuralnet.visionModel.layers))
     process = Process(batch_size, schedule=schedule, capture_graph=capture_graph)
@@ -348,9 +351,14 @@ def _cli(argv=None):
     ap.add_argument("--seed", type=int, default=0, help="augmentation draws (the same on every rank)")
     ap.add_argument("--schedule", action="store_true", help="install the MainParallel.py:74-79 rate schedule once")
     ap.add_argument("--no-graph", action="store_true", help="run every step eagerly")
-    ap.add_argument("--loss", choices=("cce", "my_loss_cat", "focal", "dice", "tversky", "dice_ce") + ("lovasz", "lovasz_ce"), default="cce",
+    ap.add_argument("--loss", choices=("cce", "my_loss_cat", "focal", "dice", "tversky", "dice_ce") + ("lovasz", "lovasz_ce") + ("topk", "dice_topk"), default="cce",
                     help="the model's loss: CategoricalCrossentropy (the reference's), its class-weighted my_loss_cat, the focal variant, or a "
-                         "region-overlap loss (soft Dice, Tversky 0.3 / 0.7, Dice + CCE), or the Lovasz-softmax loss (alone, or CCE + it)")
+                         "region-overlap loss (soft Dice, Tversky 0.3 / 0.7, Dice + CCE), or the Lovasz-softmax loss (alone, or CCE + it), or the "
+                         "top-k cross-entropy (alone, or soft Dice + it)")
+    ap.add_argument("--topk-fraction", type=float, default=None, metavar="F",
+                    help="the fraction of the pixels with the largest loss that --loss topk / dice_topk averages over, in (0, 1] (default 0.1)")
+    ap.add_argument("--topk-scope", choices=("batch", "image"), default=None,
+                    help="select among all the pixels a replica holds (batch, the default) or within each image (image)")
     ap.add_argument("--boundary-weight", type=float, default=None, metavar="W",
                     help="add the boundary term (signed distance map of the labels times the probabilities) with weight W; needs a region-overlap --loss")
     ap.add_argument("--average", default=None, metavar="ema:DECAY[:dynamic] | swa:START:PERIOD",
@@ -374,9 +382,18 @@ def _cli(argv=None):
             raise SystemExit(str(e))
     if a.boundary_weight is not None and a.loss not in ("dice", "tversky", "dice_ce"):
         raise SystemExit("--boundary-weight needs --loss dice, tversky or dice_ce")
+    topk = {k: v for k, v in (("fraction", a.topk_fraction), ("scope", a.topk_scope)) if v is not None}
+    if topk and a.loss not in ("topk", "dice_topk"):
+        raise SystemExit("--topk-fraction / --topk-scope need --loss topk or dice_topk")
+    if "fraction" in topk:
+        from . import ops
+        try:
+            ops.topk_fraction_value(topk["fraction"])
+        except ValueError as e:
+            raise SystemExit(str(e))
     main(a.train, a.val, a.save, epochs=a.epochs, batch_size=a.batch_size, use_vit=not a.no_vit, seed=a.seed, schedule=a.schedule,
          capture_graph=not a.no_graph, loss=a.loss, boundary=None if a.boundary_weight is None else {"weight": a.boundary_weight},
-         average=a.average, warp=a.warp)
+         average=a.average, warp=a.warp, **({"topk": topk} if topk else {}))
     if dist.is_initialized():
         dist.barrier()
         dist.destroy_process_group()

@@ -309,6 +309,7 @@ class Transformer(nn.Module):
 LOSSES = ("cce", "my_loss_cat", "focal")             # the reference's own: per-pixel losses inside the fused head launch
 OVERLAP_LOSSES = ("dice", "tversky", "dice_ce")      # region-overlap losses (not in the reference): two launches behind the probabilities-only head
 LOVASZ_LOSSES = ("lovasz", "lovasz_ce")              # the Lovasz-softmax loss (not in the reference): a device sort of the pixel errors behind that head
+TOPK_LOSSES = ("topk", "dice_topk")                  # the top-k (hard-pixel) cross-entropy (not in the reference): a device radix select behind that head
 
 
 def overlap_settings(loss, overlap):
@@ -359,6 +360,33 @@ def lovasz_config(loss, num_classes, lovasz):
                            cfg.get("classes", "present"))
 
 
+def topk_config(loss, num_classes, topk, *, overlap=None, class_factor=None, focal_gamma=None, boundary=None, lovasz=None):
+    """``loss`` in TOPK_LOSSES and the ``topk`` settings (dict or None: every default) -> (``ops.topk_loss(...)``, the fraction, the Dice term's
+    ``ops.overlap_loss(...)`` for "dice_topk" or None); ValueError for a bad or contradictory combination."""
+    if loss not in TOPK_LOSSES:
+        raise ValueError(f"topk settings only apply to loss in {TOPK_LOSSES}")
+    if topk is not None and not isinstance(topk, dict):
+        raise ValueError(f"topk: a dict of {ops.TOPK_KEYS} (None or {{}} for the defaults), got {type(topk).__name__}")
+    cfg = dict(topk or {})
+    unknown = [k for k in cfg if k not in ops.TOPK_KEYS]
+    if unknown:
+        raise ValueError(f"topk: unknown settings {unknown}; known: {ops.TOPK_KEYS}")
+    if class_factor is not None or focal_gamma is not None:
+        raise ValueError(f"class_factor / focal_gamma do not apply to loss='{loss}'")
+    if boundary is not None or lovasz is not None:
+        raise ValueError(f"boundary / lovasz settings do not combine with loss='{loss}'")
+    ov = None
+    if loss == "topk":
+        if overlap is not None:
+            raise ValueError("overlap settings need loss='dice_topk', not 'topk'")
+    else:
+        if dict(overlap or {}).get("ce_weight", 0.0) != 0.0:
+            raise ValueError("overlap: the cross-entropy of loss='dice_topk' is its top-k term; ce_weight must be 0")
+        ov = overlap_config("dice", num_classes, overlap)
+    fraction = ops.topk_fraction_value(cfg.get("fraction", 0.1))
+    return ops.topk_loss(cfg.get("tk_weight", 1.0), cfg.get("scope", "batch")), fraction, ov
+
+
 def boundary_config(loss, num_classes, boundary):
     """The ``boundary`` settings (dict) of a model with ``loss`` in OVERLAP_LOSSES -> (weight, ``ops.boundary_loss(...)``, threshold); ValueError for
     any other loss, an unknown key, a negative or non-finite weight, a wrong-length ``class_weight`` or a NaN threshold."""
@@ -392,7 +420,7 @@ class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
                  in_channels: int = 10, use_vit: bool = False, device: Optional[str] = None, seed: Optional[int] = 0,
                  transunet: bool = False, adamw: bool = False, loss: str = "cce", class_factor=None, focal_gamma=None,
                  overlap=None, alpha=None, beta=None, smooth=None, power=None, class_weight=None, ce_weight=None, ov_weight=None,
-                 boundary=None, lovasz=None, average=None):
+                 boundary=None, lovasz=None, average=None, topk=None):
         """``transunet=True`` builds the older self-contained copy of this model in TBI_TransUNet.py (BASELINE configs[3]):
         BatchNormalization where ResNest.py / Decoder.py use LayerNormalization (:304,426,465,472,503), conv_4 = 256 channels
         (:368), and the loss is CategoricalCrossentropy(label_smoothing=0.1) with the DEFAULT reduction - the mean over all
@@ -435,11 +463,19 @@ class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
         B*H*W errors of each class on the device (``ops.sort_pairs``' kernels); the term is weighted like the overlap term.  ``boundary`` does not
         combine with it.
 
+        The top-k (hard-pixel) cross-entropy (nnU-Net's ``TopKLoss``; not in the reference; DESIGN.md section 8, usseg.h ``UssegTopkLoss``): the
+        default CCE averaged over the k = max(1, floor(fraction * n)) pixels with the largest loss instead of over all n - ``"topk"``, or
+        ``"dice_topk"`` = soft Dice plus it (nnU-Net's ``DC_and_topk_loss``; ``overlap`` then sets the Dice term, ``ce_weight`` excluded).
+        ``topk`` (a dict; None takes every default) sets ``fraction`` (0.1), ``scope`` ("batch": one selection among the pixels THIS replica
+        holds; "image": one per image, independent of how the batch is split) and ``tk_weight`` (1).  Ties at the cut share the remaining
+        weight.  The fraction lives on the device: ``set_topk_fraction`` reaches a captured graph's next replay without a recapture, and a
+        checkpoint keeps it.  ``class_factor``, ``focal_gamma``, ``boundary`` and ``lovasz`` do not combine with it.
+
         ``average`` (None: off) is ``flat.AdamClip(average=...)``: an EMA or SWA average of the weights kept by the update
         kernel; ``averaged_weights()`` computes with it, ``save_averaged(path)`` writes it as a plain checkpoint."""
         super().__init__()
-        if loss not in LOSSES + OVERLAP_LOSSES + LOVASZ_LOSSES:
-            raise ValueError(f"loss must be one of {LOSSES + OVERLAP_LOSSES + LOVASZ_LOSSES}, got {loss!r}")
+        if loss not in LOSSES + OVERLAP_LOSSES + LOVASZ_LOSSES + TOPK_LOSSES:
+            raise ValueError(f"loss must be one of {LOSSES + OVERLAP_LOSSES + LOVASZ_LOSSES + TOPK_LOSSES}, got {loss!r}")
         if lovasz is not None and loss not in LOVASZ_LOSSES:
             raise ValueError(f"lovasz settings only apply to loss in {LOVASZ_LOSSES}")
         if loss in LOVASZ_LOSSES and (class_factor is not None or focal_gamma is not None):
@@ -451,6 +487,12 @@ class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
         if overlap is not None and overlap_kw:
             raise ValueError("give the overlap settings as overlap={...} or as keywords, not both")
         overlap = overlap if overlap is not None else (overlap_kw or None)
+        self._topk, self._topk_overlap, topk_f = None, None, None
+        if topk is not None or loss in TOPK_LOSSES:
+            self._topk, topk_f, self._topk_overlap = topk_config(loss, num_classes, topk, overlap=overlap, class_factor=class_factor,
+                                                                 focal_gamma=focal_gamma, boundary=boundary, lovasz=lovasz)
+            overlap = None                      # (the Dice term of "dice_topk" is held apart: the overlap pair itself does not run the step)
+            self._topk_bufs = {}                # (pixels of a call, pixels of an image) -> workspace: allocated once per model and batch shape
         if overlap is not None and loss not in OVERLAP_LOSSES:
             raise ValueError(f"overlap settings only apply to loss in {OVERLAP_LOSSES}")
         if loss in OVERLAP_LOSSES and overlap is None:
@@ -493,8 +535,11 @@ class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
         self.flat = FlatParams(self, self.device)
         self.optimizer = AdamClip(self.flat, lr=learning_rate, clip_norm=1.0,          # :204,:244
                                   weight_decay=weight_decay if adamw else None, average=average)
-        self._loss = torch.zeros(ops.ACC_FLOATS if self._overlap is None and self._lovasz is None else ops.OVERLAP_ACC_FLOATS, dtype=torch.float32,
-                                 device=self.device)                                         # [0] = the scalar loss
+        self._loss = torch.zeros(ops.ACC_FLOATS if self._overlap is None and self._lovasz is None and self._topk is None else ops.OVERLAP_ACC_FLOATS,
+                                 dtype=torch.float32, device=self.device)                    # [0] = the scalar loss
+        if self._topk is not None:
+            self._tkf = torch.full((1,), topk_f, dtype=torch.float32, device=self.device)     # read by the select kernels when they run
+            self._ov_acc = None if self._topk_overlap is None else torch.zeros(ops.OVERLAP_ACC_FLOATS, dtype=torch.float32, device=self.device)
         self._boundary, self._boundary_thr, self._wb = None, 0.5, None
         if bnd is not None:
             self._boundary, self._boundary_thr = bnd[1], bnd[2]
@@ -528,6 +573,22 @@ class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
         """The ``UssegLovaszLoss`` this model trains with (``loss="lovasz"`` / ``"lovasz_ce"``), or None."""
         return self._lovasz
 
+    @property
+    def topk_loss(self):
+        """The ``UssegTopkLoss`` this model trains with (``loss="topk"`` / ``"dice_topk"``), or None."""
+        return self._topk
+
+    @property
+    def topk_fraction(self):
+        """The top-k fraction the next step uses, read from the device (synchronises); None without a top-k loss."""
+        return None if self._topk is None else float(self._tkf.item())
+
+    def set_topk_fraction(self, f):
+        """From the next step on, eager or replayed: the kernels read the device float, so a captured graph needs no recapture."""
+        if self._topk is None:
+            raise ValueError(f"set_topk_fraction: the model was built without loss in {TOPK_LOSSES}")
+        self._tkf.fill_(ops.topk_fraction_value(f))
+
     # ------------------------------------------------------------------ parameters in / out (Keras names)
     @property
     def visionModel(self):
@@ -540,6 +601,8 @@ class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
         d.update(self.optimizer.state_dict())
         if self._wb is not None:
             d["__boundary_weight__"] = self._wb.detach().clone()
+        if self._topk is not None:
+            d["__topk_fraction__"] = self._tkf.detach().clone()
         torch.save(d, path)
 
     def load(self, path):
@@ -548,6 +611,9 @@ class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
         wb = d.pop("__boundary_weight__", None)      # (a checkpoint of a model without the term leaves the constructor's weight)
         if wb is not None and self._wb is not None:
             self._wb.copy_(wb.to(self._wb.device))
+        tkf = d.pop("__topk_fraction__", None)       # (likewise: a checkpoint without it leaves the constructor's fraction)
+        if tkf is not None and self._topk is not None:
+            self._tkf.copy_(tkf.to(self._tkf.device))
         self.load_params(d)
 
     @property
@@ -627,6 +693,8 @@ class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
             return self._forward_overlap(xh, logits, y, probs, dlogits, scale)
         if self._lovasz is not None:
             return self._forward_lovasz(xh, logits, y, probs, dlogits, scale)
+        if self._topk is not None:
+            return self._forward_topk(xh, logits, y, probs, dlogits, scale)
         if fused:       # head conv + softmax + loss in one launch (:142, :205, :225-229); falls back to the three launches if it has no kernel
             kw = {} if self._class_loss is None else {"class_loss": self._class_loss}       # (no keyword: today's call of today's symbol)
             if self.decoder._quad.forward_loss(xh, y, probs, self._loss, dlogits, label_smoothing=0.1, clip_eps=1e-7, inv_global_batch=scale, **kw):
@@ -693,6 +761,32 @@ class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
             ops.lovasz_loss_bwd(probs, y, g, self._loss, dlogits, quad_w=self.decoder.quad_w, **kw)
         return probs, dlogits
 
+    def _topk_loss_into(self, acc, ov_acc, probs, y, scale, ov_scale):
+        """The per-pixel losses and their selection, the Dice sums of "dice_topk" into ``ov_acc``, then the sums pass: the scalar loss in
+        ``acc[0]``.  -> (workspace, kw)."""
+        B, H, W, C = probs.shape
+        ws = self._topk_bufs.get((B * H * W, H * W))
+        if ws is None:
+            ws = torch.empty(max(ops.topk_ws_bytes(B * H * W, H * W, ops.TOPK_SCOPES[self._topk.scope]), 16), dtype=torch.uint8, device=self.device)
+            self._topk_bufs[(B * H * W, H * W)] = ws
+        kw = dict(topk=self._topk, HW=H * W, C_classes=C, label_smoothing=0.1, clip_eps=1e-7)
+        ops.topk_pixel_loss(probs, y, self._tkf, ws, **kw)
+        kw.update(inv_global_batch=scale, overlap_acc=ov_acc)
+        if ov_acc is not None:
+            ops.overlap_loss_sums(probs, y, ov_acc, overlap=self._topk_overlap, HW=H * W, C_classes=C, ov_scale=ov_scale, label_smoothing=0.1, clip_eps=1e-7,
+                                  inv_global_batch=scale)
+        ops.topk_loss_sums(probs, ws, acc, **kw)
+        return ws, kw
+
+    def _forward_topk(self, xh, logits, y, probs, dlogits, scale):
+        """The top-k cross-entropy: today's probabilities-only head launch(es), then the per-pixel losses with their exact selection, the sums
+        pass (scalar loss and coefficient into ``self._loss``), then - for a training step - the backward pass that writes ``dlogits``."""
+        self._head_probs(xh, logits, probs)
+        ws, kw = self._topk_loss_into(self._loss, self._ov_acc, probs, y, scale, 1.0 if self.transunet else float(probs.shape[0]) / float(self.batch_size))
+        if dlogits is not None:
+            ops.topk_loss_bwd(probs, y, ws, self._loss, dlogits, quad_w=self.decoder.quad_w, **kw)
+        return probs, dlogits
+
     def _predict_body(self, x):
         """The forward of ``_forward_loss`` without labels: the encoder with ``stash=False``, the fused attention, the decoder, and the head
         softmax with no loss.  No loss buffer, gradient, optimiser state or BatchNorm statistic is read or written."""
@@ -732,6 +826,11 @@ class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
             acc = torch.zeros(ops.OVERLAP_ACC_FLOATS, dtype=torch.float32, device=self.device)
             self._lovasz_loss_into(acc, y_pred, y_true, 1.0 / float(self.batch_size),
                                    1.0 if self.transunet else float(y_pred.shape[0]) / float(self.batch_size))
+            return acc[0].clone()
+        if self._topk is not None:          # the top-k loss of THESE tensors, weighted as a step weights a batch of their size
+            acc = torch.zeros(ops.OVERLAP_ACC_FLOATS, dtype=torch.float32, device=self.device)
+            self._topk_loss_into(acc, None if self._ov_acc is None else torch.zeros_like(acc), y_pred, y_true, 1.0 / float(self.batch_size),
+                                 1.0 if self.transunet else float(y_pred.shape[0]) / float(self.batch_size))
             return acc[0].clone()
         loss = torch.empty(ops.ACC_FLOATS, dtype=torch.float32, device=self.device)
         ops.fill_f32(loss, 0.0)

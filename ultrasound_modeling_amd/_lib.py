@@ -112,6 +112,11 @@ class LovaszLoss(C.Structure):
     _fields_ = [("w", c_f32 * 8), ("lv_weight", c_f32), ("ce_weight", c_f32), ("threshold", c_f32), ("all_classes", c_i32)]
 
 
+class TopkLoss(C.Structure):
+    """UssegTopkLoss: the top-k (hard-pixel) cross-entropy (usseg.h); passed BY VALUE.  The fraction is a device float, not a field."""
+    _fields_ = [("tk_weight", c_f32), ("scope", c_i32)]
+
+
 class BoundaryLoss(C.Structure):
     """UssegBoundaryLoss: the per-class weights of the boundary term (usseg.h); passed by reference, copied into the launches."""
     _fields_ = [("u", c_f32 * 8)]
@@ -277,6 +282,12 @@ _PROTOS = {
     "usseg_lovasz_coeffs": (C.c_int, [P(LossDesc), LovaszLoss, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "usseg_lovasz_loss_sums": (C.c_int, [P(LossDesc), LovaszLoss, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "usseg_lovasz_loss_bwd": (C.c_int, [P(LossDesc), LovaszLoss, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp]),
+    "usseg_topk_select_ws_bytes": (c_i64, [c_i64]),
+    "usseg_topk_select": (C.c_int, [c_vp, c_i32, c_i64, c_vp, c_i32, c_vp, c_vp, c_i64, c_vp]),
+    "usseg_topk_ws_bytes": (c_i64, [c_i64, c_i32, c_i32]),
+    "usseg_topk_pixel_loss": (C.c_int, [P(LossDesc), TopkLoss, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "usseg_topk_loss_sums": (C.c_int, [P(LossDesc), TopkLoss, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp]),
+    "usseg_topk_loss_bwd": (C.c_int, [P(LossDesc), TopkLoss, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp]),
     "usseg_quad_bias_expand": (C.c_int, [c_vp, c_i32, c_i32, c_vp, c_vp]),
     "usseg_space_to_depth2": (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp]),
     "usseg_tconv_quad_fwd": (C.c_int, [P(ConvDesc), c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),

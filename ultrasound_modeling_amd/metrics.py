@@ -260,9 +260,9 @@ def lesion_scores(pred, true, *, connectivity=8, min_overlap=1, device=None):
 
 
 def dice_line(neuralnet, seg_metrics):
-    """The drivers' extra report line: the per-class Dice list when the model trains with a region-overlap or the Lovasz-softmax loss, else None (nothing is
-    printed); the history keeps its keys either way."""
-    if getattr(neuralnet, "overlap_loss", None) is None and getattr(neuralnet, "lovasz_loss", None) is None:      # (Arch A has neither property)
+    """The drivers' extra report line: the per-class Dice list when the model trains with a region-overlap, the Lovasz-softmax or a top-k loss, else None
+    (nothing is printed); the history keeps its keys either way."""
+    if all(getattr(neuralnet, name, None) is None for name in ("overlap_loss", "lovasz_loss", "topk_loss")):      # (Arch A has none of the properties)
         return None
     return seg_metrics.dice()
 

@@ -1605,6 +1605,105 @@ def lovasz_loss_bwd(probs, y_true, g, acc, dlogits, *, lovasz, HW, C_classes, la
                                            dlogits.data_ptr(), _stream()), "lovasz_loss_bwd")
 
 
+# ------------------------------------------------------------------------------------------------ exact selection, the top-k cross-entropy
+TOPK_KEYS = ("fraction", "scope", "tk_weight")
+TOPK_SCOPES = ("batch", "image")
+
+
+def topk_fraction_value(fraction) -> float:
+    """The fraction as the device float holds it; ValueError unless it is finite and lies in (0, 1]."""
+    f = float(fraction)
+    if not (math.isfinite(f) and 0.0 < f <= 1.0):
+        raise ValueError(f"topk: fraction must be finite and lie in (0, 1], got {fraction}")
+    return f
+
+
+def topk_loss(tk_weight=1.0, scope="batch") -> L.TopkLoss:
+    """A ``UssegTopkLoss`` (usseg.h): tk_weight * the mean of the k = max(1, floor(fraction * n)) largest per-pixel cross-entropies of each
+    segment - the call's pixels (``scope="batch"``) or each image (``"image"``).  The fraction is a device float the kernels read when they run.
+    ValueError for what the library would refuse."""
+    tk_weight = float(tk_weight)
+    if scope not in TOPK_SCOPES:
+        raise ValueError(f"topk: scope must be one of {TOPK_SCOPES}, got {scope!r}")
+    if not (math.isfinite(tk_weight) and tk_weight >= 0.0):
+        raise ValueError(f"topk: tk_weight must be finite and >= 0, got {tk_weight}")
+    return L.TopkLoss(tk_weight, TOPK_SCOPES.index(scope))
+
+
+def topk_select_ws_bytes(S: int) -> int:
+    need = int(L.load().usseg_topk_select_ws_bytes(int(S)))
+    if need < 0:
+        raise ValueError(f"topk_select: at most 2^29 segments, got {S}")
+    return need
+
+
+def topk_select(keys, fraction=None, k=None, ws=None, sel=None):
+    """The k-th largest key of every row of ``keys`` ([S, n] or [n]; int32 or uint32, read as unsigned), exactly (usseg.h usseg_topk_select)
+    -> ``sel`` int32 [S, 4] = (t as its bits, keys above t, keys equal to t, k).  ``fraction``: a DEVICE fp32 tensor, read when the kernels run
+    (k = max(1, min(n, floor(fraction * n)))) - or an explicit ``k``.  ``ws`` (uint8, ``topk_select_ws_bytes(S)`` long) and ``sel`` are
+    allocated when not given; a captured region passes its own."""
+    assert keys.dtype in _WORDS and keys.is_contiguous() and keys.dim() in (1, 2)
+    S, n = (1, keys.shape[0]) if keys.dim() == 1 else keys.shape
+    if (fraction is None) == (k is None):
+        raise ValueError("topk_select: give the device fraction or an explicit k")
+    if fraction is not None:
+        assert fraction.dtype == torch.float32 and fraction.device == keys.device and fraction.numel() >= 1
+    elif not 1 <= int(k) <= n:
+        raise ValueError(f"topk_select: 1 <= k <= n = {n}, got {k}")
+    need = topk_select_ws_bytes(S)
+    if ws is None:
+        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=keys.device)
+    if sel is None:
+        sel = torch.empty((S, 4), dtype=torch.int32, device=keys.device)
+    assert ws.dtype == torch.uint8 and sel.dtype == torch.int32 and sel.is_contiguous() and tuple(sel.shape) == (S, 4)
+    if S:
+        L.check(L.load().usseg_topk_select(keys.data_ptr(), S, n, None if fraction is None else fraction.data_ptr(), 0 if k is None else int(k),
+                                           sel.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "topk_select")
+    return sel
+
+
+def topk_ws_bytes(M: int, HW: int, scope="batch") -> int:
+    need = int(L.load().usseg_topk_ws_bytes(int(M), int(HW), TOPK_SCOPES.index(scope)))
+    if need < 0:
+        raise ValueError(f"topk: at most 2^29 pixels, a multiple of HW, got {M} with HW = {HW}")
+    return need
+
+
+def topk_ws_views(ws, M: int, HW: int, scope="batch"):
+    """The two results the top-k calls keep in their workspace -> (l fp32 [M], sel int32 [S, 4]) as views of ``ws`` (usseg.h has the layout)."""
+    S = M // HW if scope == "image" else 1
+    a = lambda b: (b + 255) // 256 * 256
+    off = a(4 * M) + a(topk_select_ws_bytes(S))
+    return ws[:4 * M].view(torch.float32), ws[off:off + 16 * S].view(torch.int32).view(S, 4)
+
+
+def topk_pixel_loss(probs, y_true, fraction, ws, *, topk, HW, C_classes, label_smoothing=0.1, clip_eps=1e-7):
+    """The per-pixel cross-entropy of every pixel and its exact selection into ``ws`` (uint8, ``topk_ws_bytes`` long; ``topk_ws_views`` reads
+    them): five kernels and one memset whatever the data.  ``fraction``: a DEVICE fp32 tensor, read when the kernels run."""
+    d = _overlap_desc(probs, y_true, HW, C_classes, 8, label_smoothing, clip_eps, 1.0, 0)
+    assert fraction.dtype == torch.float32 and fraction.device == probs.device and fraction.numel() >= 1 and ws.dtype == torch.uint8
+    L.check(L.load().usseg_topk_pixel_loss(C.byref(d), topk, fraction.data_ptr(), probs.data_ptr(), y_true.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+            "topk_pixel_loss")
+
+
+def topk_loss_sums(probs, ws, acc, *, topk, HW, C_classes, overlap_acc=None, label_smoothing=0.1, clip_eps=1e-7, inv_global_batch=1.0):
+    """``acc`` (fp32 [OVERLAP_ACC_FLOATS], zeroed once at allocation) receives the scalar loss in [0] (plus ``overlap_acc[0]`` when given), the plain
+    CCE pixel sum in [2], the coefficient tk_weight * inv_global_batch * n / k in [4] and sum a*l in [5], all bitwise reproducible.  ``probs``
+    gives the shape only."""
+    d = LossDesc(probs.numel() // C_classes, HW, C_classes, C_classes, 8, 0, label_smoothing, clip_eps, inv_global_batch, 0)
+    L.check(L.load().usseg_topk_loss_sums(C.byref(d), topk, ws.data_ptr(), ws.numel(), _ptr(overlap_acc), acc.data_ptr(), acc.numel(), _stream()),
+            "topk_loss_sums")
+
+
+def topk_loss_bwd(probs, y_true, ws, acc, dlogits, *, topk, HW, C_classes, overlap_acc=None, label_smoothing=0.1, clip_eps=1e-7, inv_global_batch=1.0,
+                  quad_w=0):
+    """d loss / d logits (bf16 [..., 8], or [B,H/2,W/2,16] with ``quad_w``) from the probabilities, the labels, l and sel in ``ws`` and the
+    coefficient in ``acc`` - plus the Dice term's A_c*y + B_c from ``overlap_acc`` when given."""
+    d = _overlap_desc(probs, y_true, HW, C_classes, 16 if quad_w else 8, label_smoothing, clip_eps, inv_global_batch, quad_w)
+    L.check(L.load().usseg_topk_loss_bwd(C.byref(d), topk, probs.data_ptr(), y_true.data_ptr(), ws.data_ptr(), ws.numel(), acc.data_ptr(), acc.numel(),
+                                         _ptr(overlap_acc), dlogits.data_ptr(), _stream()), "topk_loss_bwd")
+
+
 def quad_bias_expand(bias, C_logical, out):
     L.check(L.load().usseg_quad_bias_expand(bias.data_ptr(), C_logical, out.numel() // 4, out.data_ptr(), _stream()), "quad_bias_expand")
 
