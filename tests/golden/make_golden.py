@@ -7,6 +7,11 @@ archB_64x64x1.npz  - BASELINE config 1 ("single 64x64 1-ch tile, UNet forward ..
                      encoder outputs, probabilities, loss, gradient norms of every variable and a few full gradients.
 layers_2x16x16.npz - one tile per layer type (3x3 conv, dilated conv, 1x1, tconv k=3 / k=4, LN+LeakyReLU, BN-inference,
                      avg-pool, residual_S stage): inputs, weights, forward outputs, input- and weight-gradients.
+adam_fixed_rate_bits.npz - the bits of the fixed-rate Adam step as the scalar adam_kernel gives them, recorded on the GPU (not by the CPU
+                     oracle):  python tests/golden/make_golden.py adam_fixed_rate_bits
+                     The independent witness of the default path's bits for the day that kernel is restated on adamw_elem: it can only
+                     be recorded by a tree that still has ops.adam_clip_step, and every tree replays it
+                     (tests/test_gpu_pointwise_routes.py::test_fixed_rate_step_keeps_the_recorded_bits).
 The weights of the first file are re-created from the seed by usseg_oracle.init_*; `param_checksum` guards against a
 PyTorch RNG change.
 """
@@ -73,9 +78,43 @@ def layers():
     np.savez_compressed(os.path.join(HERE, "layers_2x16x16.npz"), **{k: v.astype(np.float32) for k, v in out.items()})
 
 
+def adam_fixed_rate_bits():
+    """The sequence of test_adam_steps("adam", n), n = 3 (n >> 2 == 0: all tail for a float4 walk) and 4099 (several workgroups and a ragged end):
+    three steps of sumsq + adam_advance + adam_clip_step; p, m, v as int32 views, sumsq[0] and lr_t after each."""
+    sys.path.insert(0, os.path.join(HERE, "..", ".."))
+    sys.path.insert(0, os.path.join(HERE, ".."))
+    import pointwise_restatement as PR
+    from ultrasound_modeling_amd import ops
+    if not hasattr(ops, "adam_clip_step"):
+        sys.exit("adam_fixed_rate_bits.npz records the scalar adam_kernel, which this tree no longer has (ops.adam_clip_step is gone): "
+                 "the committed file is the record; it is not regenerated from the kernel that replaced it")
+    assert torch.cuda.is_available(), "adam_fixed_rate_bits is recorded on the GPU"
+    b1, b2, eps = (float(np.float32(v)) for v in (0.9, 0.999, 1e-7))
+    out = {}
+    for n in (3, 4099):
+        p, g0, m, v, _still = (t.cuda() for t in PR.optim_inputs(n))
+        for k, t in zip("pgmv", (p, g0, m, v)):
+            out[f"n{n}::{k}0"] = t.cpu().numpy()
+        step, lr_t = torch.zeros(1, dtype=torch.int32, device="cuda"), torch.zeros(1, device="cuda")
+        ss = torch.zeros(ops.ACC_FLOATS, device="cuda")
+        for it in range(3):
+            g = g0 * (1.0, 1e-3, 0.5)[it]
+            ops.sumsq(g, ss)
+            ops.adam_advance(step, lr_t, 1e-3, b1, b2)
+            ops.adam_clip_step(p, g, m, v, ss, (1.0, 1e9, 0.0)[it], lr_t, b1, b2, eps)
+            for k, t in zip("pmv", (p, m, v)):
+                out[f"n{n}::step{it + 1}::{k}"] = t.view(torch.int32).cpu().numpy()
+            out[f"n{n}::step{it + 1}::sumsq"] = ss[:1].cpu().numpy()
+            out[f"n{n}::step{it + 1}::lr_t"] = lr_t.cpu().numpy()
+    np.savez_compressed(os.path.join(HERE, "adam_fixed_rate_bits.npz"), **out)
+
+
 if __name__ == "__main__":
-    arch_b()
-    layers()
+    if sys.argv[1:] == ["adam_fixed_rate_bits"]:
+        adam_fixed_rate_bits()
+    else:
+        arch_b()
+        layers()
     for f in sorted(os.listdir(HERE)):
         if f.endswith(".npz"):
             print(f, os.path.getsize(os.path.join(HERE, f)) // 1024, "KiB")

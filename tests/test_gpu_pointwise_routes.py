@@ -53,7 +53,8 @@ Routes, and the case that reaches each:
   * loss_from_probs_kernel (kinds 0 and 1), loss_from_probs_cl_kernel (scalar and map), loss_cat_scale_kernel: one block and past their
     caps (test_loss_from_probs, test_loss_cat_scale).
   * sumsq_kernel, sumsq_sched_kernel (test_sumsq); adam_kernel, adamw_kernel (no decay, decay, masked decay with the scalar tail),
-    scale_kernel (test_adam_steps, test_scale_by_clip).
+    scale_kernel (test_adam_steps, test_scale_by_clip); adam_kernel against the bits recorded from it in tests/golden
+    (test_fixed_rate_step_keeps_the_recorded_bits).
 Routes no shape reaches:
   * softmax_loss_pixel forms the quad pixel index (b*(H/2) + y/2)*(W/2) + x/2 in `int`: it overflows only from B*H*W/4 >= 2^31 quad pixels,
     i.e. more than 137 GB of fp32 logits in one call - not allocated here.
@@ -656,6 +657,30 @@ def test_adam_steps(variant, n):
     fixed = still if wd == 0.0 else (still & (mask == 0) if mask is not None else None)
     if fixed is not None:                         # zero gradient and zero moments: p keeps its bits, -0.0 included
         assert torch.equal(p[fixed].view(torch.int32), p0[fixed].view(torch.int32))
+    free()
+
+
+@pytest.mark.parametrize("n", [3, 4099])
+def test_fixed_rate_step_keeps_the_recorded_bits(n):
+    """tests/golden/adam_fixed_rate_bits.npz holds what the scalar adam_kernel gave on the GPU for the sequence of test_adam_steps("adam", n)
+    (make_golden.py adam_fixed_rate_bits): n = 3 is one partial workgroup with n >> 2 == 0, n = 4099 several workgroups and a ragged end
+    with the planted -0.0, zero-moment elements.  Every recorded array, step by step, bit for bit: the witness any later restatement of the
+    fixed-rate step (one that shares adamw_elem with the table path, say) has to reproduce."""
+    import os
+    from ultrasound_modeling_amd import ops
+    rec = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "adam_fixed_rate_bits.npz"))
+    dev = lambda k: torch.from_numpy(rec[f"n{n}::{k}"]).to(DEV)
+    p, g0, m, v = (dev(k + "0") for k in "pgmv")
+    assert all(same_bits(a, b.to(DEV)) for a, b in zip((p, g0, m, v), PR.optim_inputs(n)[:4])), "the fixture's inputs are optim_inputs(n)"
+    step, lr_t, ss = torch.zeros(1, dtype=torch.int32, device=DEV), torch.zeros(1, device=DEV), torch.zeros(ops.ACC_FLOATS, device=DEV)
+    for it in range(3):
+        g = g0 * (1.0, 1e-3, 0.5)[it]
+        ops.sumsq(g, ss)
+        ops.adam_advance(step, lr_t, 1e-3, B1, B2)
+        routed(lambda: ops.adam_clip_step(p, g, m, v, ss, clip_of(it), lr_t, B1, B2, EPS), "adam_kernel")
+        for k, t in zip("pmv", (p, m, v)):
+            assert torch.equal(t.view(torch.int32), dev(f"step{it + 1}::{k}")), f"{k} differs from the recorded bits at n={n} step {it + 1}"
+        assert same_bits(ss[:1], dev(f"step{it + 1}::sumsq")) and same_bits(lr_t, dev(f"step{it + 1}::lr_t")), f"sumsq / lr_t at n={n} step {it + 1}"
     free()
 
 
