@@ -569,7 +569,7 @@ int usseg_loss_from_probs(const UssegLossDesc* d, const float* probs, const floa
  *     d l / d p[c] = factor*w[c]*ys[c]*(gamma*(1-pc)^(gamma-1)*log(pc) - (1-pc)^gamma/pc) for clip_eps < p[c] < 1 - clip_eps, else 0
  * my_loss_cat as committed (:270): factor 3, w = class_factor, gamma 0.  Its focal line (:272-273,277): factor 1, w = 1, gamma = alpha.
  * gamma is 0 (no pow and no 1 - pc evaluated) or lies in [1, 8] (below 1 the derivative is unbounded at the clip edge); w[c] and factor
- * are finite and >= 0; only w[0..C) is read.  The struct travels BY VALUE with the launch, so a captured graph holds its numbers.
+ * are finite and >= 0; only w[0..C) is read.  The struct is passed by reference and copied into the launch (it travels BY VALUE with it), so a captured graph holds its numbers.
  * The three entry points below are the class-loss forms of the three above; the descriptor must say loss_kind 2 and its
  * label_smoothing, clip_eps, inv_global_batch and geometry mean what they mean there.  The scalar is
  * inv_global_batch * sum over all pixels of l, through the same ordered sum (loss: USSEG_ACC_FLOATS floats, [0] OVERWRITTEN);
@@ -620,7 +620,7 @@ int usseg_loss_from_probs_cl(const UssegLossDesc* d, const UssegClassLoss* cl, c
  * the rounding-error bound of the totals follows from it: usseg_overlap_loss_grid(M) = clamp(ceil(ceil(M/4)/256), 1, 512) workgroups of
  * 256 threads; a thread adds groups of 4 consecutive pixels, group index striding by 256*grid.
  * Of the descriptor only M, HW, C, lddl, quad_w, label_smoothing, clip_eps and inv_global_batch are read (M <= 2^29, a multiple of HW; M = 0
- * gives loss 0 and no backward launch).  The struct travels BY VALUE with the launches, so a captured graph holds its numbers.  Every
+ * gives loss 0 and no backward launch).  The struct is passed by reference and copied into the launches (it travels BY VALUE with them), so a captured graph holds its numbers.  Every
  * argument is checked before any launch (USSEG_ERR_BAD_ARG with usseg_last_error text), an accumulator too small for the grid included. */
 typedef struct UssegOverlapLoss {
   float w[8];      /* per-class weight */
@@ -745,7 +745,7 @@ int usseg_component_overlap(const int32_t* labels_a, const int32_t* labels_b, in
  * With *wb == 0 the loss and every dlogits element equal the plain pair's bit for bit (pass 2 skips the summand when acc[13] is zero). */
 typedef struct UssegBoundaryLoss {
   float u[8]; /* per-class weight of the boundary term */
-} UssegBoundaryLoss;
+} UssegBoundaryLoss; /* passed by reference, copied into the launches */
 int usseg_overlap_boundary_loss_sums(const UssegLossDesc* d, const UssegOverlapLoss* ol, float ov_scale, const float* probs, const float* y_true,
                                      const float* phi, const UssegBoundaryLoss* bl, const float* wb, float* acc, int64_t acc_floats,
                                      usseg_stream_t stream);
@@ -1303,7 +1303,7 @@ typedef struct UssegWarpSample {
   uint64_t seed;
   double alpha[2];   /* rows, cols */
   double aff[6];     /* A00, A01, A10, A11, o0, o1 */
-} UssegWarpSample;
+} UssegWarpSample; /* one sample's draws; a device table of them is read on every launch */
 typedef struct UssegWarpDesc { int32_t B, H, W, C, x_is_f64, radius; } UssegWarpDesc;
 
 int64_t usseg_warp_ws_bytes(int32_t B, int32_t H, int32_t W);   /* 0 for a B, H or W below 1 */

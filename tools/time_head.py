@@ -23,11 +23,10 @@ ap.add_argument("shape", nargs="*", type=int, default=[16, 128, 128, 72, 3])
 a = ap.parse_args()
 B, h, w, Cin, NC = a.shape
 lib = C.CDLL(a.lib)
-vp, i32, f32 = C.c_void_p, C.c_int32, C.c_float
-lib.usseg_head_quad_softmax_loss.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp, f32, f32, f32, vp]
+L.bind(lib, ["usseg_head_quad_softmax_loss"])
 has_cl = hasattr(lib, "usseg_head_quad_softmax_loss_cl")
 if has_cl:
-    lib.usseg_head_quad_softmax_loss_cl.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp, f32, f32, f32, C.POINTER(L.ClassLoss), vp]
+    L.bind(lib, ["usseg_head_quad_softmax_loss_cl"])
 
 g = torch.Generator().manual_seed(0)
 x = torch.randn(B, h, w, Cin, generator=g).to(torch.bfloat16).cuda()
@@ -35,7 +34,7 @@ wq = (torch.randn(16, 9 * Cin, generator=g) / (9 * Cin) ** 0.5).to(torch.bfloat1
 bias = torch.zeros(4).cuda()
 y = torch.softmax(torch.randn(B, 2 * h, 2 * w, NC, generator=g), -1).cuda()
 probs = torch.empty(B, 2 * h, 2 * w, NC).cuda()
-loss = torch.zeros(2050).cuda()
+loss = torch.zeros(L.ACC_FLOATS).cuda()
 dl = torch.empty(B, h, w, 16, dtype=torch.bfloat16).cuda()
 
 
@@ -76,10 +75,7 @@ for name, cl in variants:
     print(f"  {name:24s} {min(ts):7.2f} us min, {sorted(ts)[len(ts) // 2]:7.2f} median, {max(ts):7.2f} max   [{' '.join(f'{v:.2f}' for v in ts)}]")
 
 if hasattr(lib, "usseg_overlap_loss_sums"):
-    i64 = C.c_int64
-    lib.usseg_overlap_loss_sums.argtypes = [C.POINTER(L.LossDesc), C.POINTER(L.OverlapLoss), f32, vp, vp, vp, i64, vp]
-    lib.usseg_overlap_loss_bwd.argtypes = [C.POINTER(L.LossDesc), C.POINTER(L.OverlapLoss), vp, vp, vp, i64, vp, vp]
-    lib.usseg_softmax_loss_fwd_bwd.argtypes = [C.POINTER(L.LossDesc), vp, vp, vp, vp, vp, vp, vp]
+    L.bind(lib, ["usseg_overlap_loss_sums", "usseg_overlap_loss_bwd", "usseg_softmax_loss_fwd_bwd"])
     H, W = 2 * h, 2 * w
     M = B * H * W
     from ultrasound_modeling_amd import ops

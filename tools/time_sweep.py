@@ -63,9 +63,8 @@ if not torch.cuda.is_available():
 L.load()
 C.CDLL(L.LIB_PATH, mode=C.RTLD_GLOBAL)
 plain = C.CDLL(PLAIN)
-plain.usseg_score_sweep.restype = C.c_int
-plain.usseg_score_sweep.argtypes = [C.POINTER(L.SweepDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-plain.usseg_tool_logf_expf.restype = C.c_int
+L.bind(plain, ["usseg_score_sweep"])
+plain.usseg_tool_logf_expf.restype = C.c_int                                     # the probe build's own entry point, not in usseg.h
 plain.usseg_tool_logf_expf.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
 
 

@@ -13,6 +13,7 @@ variables to be laid out back to back ("adjacent groups", used by the grouped sp
 """
 from __future__ import annotations
 
+import ctypes as C
 import math
 import re
 from typing import Dict, List, Optional, Sequence
@@ -21,6 +22,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from . import _lib as L
 from . import ops
 from .schedules import MAX_PIECES, PiecewiseConstantDecay
 
@@ -294,7 +296,7 @@ class AdamClip:
 
 
 # ---------------------------------------------------------------------------------------------------- table helpers
-_TABLE_WORDS = 1 + (MAX_PIECES - 1) + 2 * MAX_PIECES          # sizeof(UssegLrSchedule) / 4
+_TABLE_WORDS = C.sizeof(L.LrSchedule) // 4
 
 
 def _rate(x, what):
@@ -320,20 +322,20 @@ def _table(lr, wd) -> np.ndarray:
     if len(b) + 1 > MAX_PIECES:
         raise ValueError(f"AdamClip: learning rate and weight decay need {len(b) + 1} pieces together, at most {MAX_PIECES} are supported")
     xs = b + [b[-1] + 1] if b else [0]          # a step inside each piece: x = b[0] for x <= b[0], b[i] for b[i-1] < x <= b[i], b[-1] + 1
-    t = np.zeros(_TABLE_WORDS, dtype=np.int32)
-    t[0] = len(xs)
-    t[1:1 + len(b)] = b
-    t[16:16 + len(xs)] = np.array([_at(lr, x) for x in xs], dtype=np.float32).view(np.int32)
-    t[32:32 + len(xs)] = np.array([0.0 if wd is None else _at(wd, x) for x in xs], dtype=np.float32).view(np.int32)
-    return t
+    t = L.LrSchedule(n=len(xs))
+    t.boundary[:len(b)] = b
+    t.lr[:len(xs)] = [_at(lr, x) for x in xs]
+    t.wd[:len(xs)] = [0.0 if wd is None else _at(wd, x) for x in xs]
+    return np.frombuffer(t, dtype=np.int32).copy()
 
 
 def _from_table(t: np.ndarray):
-    n = int(t[0])
+    t = L.LrSchedule.from_buffer_copy(np.ascontiguousarray(t, dtype=np.int32))
+    n = t.n
     if not 1 <= n <= MAX_PIECES:
         raise ValueError(f"AdamClip: a saved rate table with {n} pieces")
-    b = [int(x) for x in t[1:n]]
-    lr, wd = t[16:16 + n].view(np.float32), t[32:32 + n].view(np.float32)
+    b = t.boundary[:n - 1]
+    lr, wd = np.array(t.lr[:n], dtype=np.float32), np.array(t.wd[:n], dtype=np.float32)
     mk = (lambda v: PiecewiseConstantDecay(b, v)) if n > 1 else (lambda v: float(v[0]))
     return mk(lr), mk(wd)
 
@@ -396,20 +398,18 @@ def parse_average(text: str) -> dict:
 
 
 def _average_words(cfg: dict) -> np.ndarray:
-    """UssegAverage as int32[5]."""
-    w = np.zeros(ops.AVERAGE_WORDS, dtype=np.int32)
-    w[0] = ops.AVERAGE_MODES[cfg["mode"]]
+    """UssegAverage as int32 words."""
     if cfg["mode"] == "ema":
-        w[1] = np.array([cfg["decay"]], dtype=np.float32).view(np.int32)[0]
-        w[2], w[3], w[4] = int(cfg["dynamic_decay"]), cfg["start_step"], 1
+        a = L.Average(L.AVERAGE_EMA, cfg["decay"], int(cfg["dynamic_decay"]), cfg["start_step"], 1)
     else:
-        w[3], w[4] = cfg["start"], cfg["period"]
-    return w
+        a = L.Average(L.AVERAGE_SWA, 0.0, 0, cfg["start"], cfg["period"])
+    return np.frombuffer(a, dtype=np.int32).copy()
 
 
 def _average_from_words(w: np.ndarray) -> dict:
-    if int(w[0]) == ops.AVERAGE_MODES["ema"]:
-        return average_config({"mode": "ema", "decay": float(w[1:2].view(np.float32)[0]), "dynamic_decay": bool(w[2]), "start_step": int(w[3])})
-    if int(w[0]) == ops.AVERAGE_MODES["swa"]:
-        return average_config({"mode": "swa", "start": int(w[3]), "period": int(w[4])})
-    raise ValueError(f"AdamClip: a saved average descriptor with mode {int(w[0])}")
+    a = L.Average.from_buffer_copy(np.ascontiguousarray(w, dtype=np.int32))
+    if a.mode == L.AVERAGE_EMA:
+        return average_config({"mode": "ema", "decay": a.decay, "dynamic_decay": bool(a.dynamic_decay), "start_step": a.start})
+    if a.mode == L.AVERAGE_SWA:
+        return average_config({"mode": "swa", "start": a.start, "period": a.period})
+    raise ValueError(f"AdamClip: a saved average descriptor with mode {a.mode}")

@@ -14,6 +14,7 @@ import math
 import os
 from typing import Optional, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -22,7 +23,7 @@ from ._lib import (ACCUMULATE, ACT_ELU, ACT_GELU, ACT_LRELU, ACT_NONE, ACT_RELU,
                    SplitAttnDesc, SplitAttnGrads, SplitAttnParams)
 
 BF16 = torch.bfloat16
-ACC_FLOATS = 2050   # USSEG_ACC_FLOATS: a reproducible scalar accumulator ([0] result, [1] ticket, [2..] per-workgroup partials)
+ACC_FLOATS = L.ACC_FLOATS   # a reproducible scalar accumulator ([0] result, [1] ticket, [2..] per-workgroup partials)
 
 
 def roundup(a: int, b: int) -> int:
@@ -294,7 +295,7 @@ def conv2d_fwd_multi(jobs):
         assert (Bo, Ho, Wo) == (B, H, W) and x.dtype == BF16 and out.dtype == BF16
         arr[j].desc = _conv_desc(B, H, W, Cin, Cout, ldx, ldy, ksize, dilation, act, alpha, 0)
         arr[j].x, arr[j].wp, arr[j].bias, arr[j].residual, arr[j].ldr, arr[j].y = x.data_ptr(), wp.data_ptr(), _ptr(bias), None, 0, out.data_ptr()
-    L.check(L.load().usseg_conv2d_fwd_multi(len(jobs), C.addressof(arr), _stream()), "conv2d_fwd_multi")
+    L.check(L.load().usseg_conv2d_fwd_multi(len(jobs), arr, _stream()), "conv2d_fwd_multi")
 
 
 def conv2d_dgrad_multi(jobs):
@@ -306,7 +307,7 @@ def conv2d_dgrad_multi(jobs):
         arr[j].desc = _conv_desc(B, H, W, Cin, Cout, ldx, ldy, ksize, dilation, flags=ACCUMULATE if accumulate else 0)
         arr[j].x, arr[j].wp, arr[j].bias, arr[j].y = dy.data_ptr(), wp_d.data_ptr(), None, dx.data_ptr()
         arr[j].residual, arr[j].ldr = _ptr(residual), (geom(residual)[4] if residual is not None else 0)
-    L.check(L.load().usseg_conv2d_dgrad_multi(len(jobs), C.addressof(arr), _stream()), "conv2d_dgrad_multi")
+    L.check(L.load().usseg_conv2d_dgrad_multi(len(jobs), arr, _stream()), "conv2d_dgrad_multi")
 
 
 def conv2d_wgrad(x, dy, ksize, dilation, dw: torch.Tensor):
@@ -365,7 +366,7 @@ def conv2d_wgrad_multi(jobs):
         arr[j].x, arr[j].dy, arr[j].dw = x.data_ptr(), dy.data_ptr(), _ptr(dw)
         arr[j].dst = C.pointer(dst_map) if dst_map is not None else None
     ws = wgrad_ws(jobs[0][0].device)
-    L.check(L.load().usseg_conv2d_wgrad_multi(len(jobs), C.addressof(arr), ws.data_ptr(), ws.numel(), _stream()), "conv2d_wgrad_multi")
+    L.check(L.load().usseg_conv2d_wgrad_multi(len(jobs), arr, ws.data_ptr(), ws.numel(), _stream()), "conv2d_wgrad_multi")
 
 
 def tconv2d_wgrad_mapped(x, dy, ksize, dst_map):
@@ -414,8 +415,7 @@ def pack_weight(src: torch.Tensor, sT, sN, sK, T, Nn, Kk, dst: torch.Tensor, Kw,
                                        _stream()), "pack_weight")
 
 
-PACK_JOB_DTYPE = [("src", "<u8"), ("dst", "<u8"), ("sT", "<i8"), ("sN", "<i8"), ("sK", "<i8"), ("T", "<i4"), ("Nn", "<i4"), ("Kk", "<i4"),
-                  ("Kw", "<i4"), ("tap_stride", "<i4"), ("n_off", "<i4"), ("k_off", "<i4"), ("reserved", "<i4"), ("nscale", "<u8")]
+PACK_JOB_DTYPE = np.dtype(L.PackJob)
 
 
 def pack_job(src, sT, sN, sK, T, Nn, Kk, dst, Kw, tap_stride, n_off=0, k_off=0, nscale=None):
@@ -427,13 +427,11 @@ def pack_job(src, sT, sN, sK, T, Nn, Kk, dst, Kw, tap_stride, n_off=0, k_off=0, 
 
 
 def make_pack_table(jobs, device) -> torch.Tensor:
-    import numpy as np
     arr = np.array(jobs, dtype=PACK_JOB_DTYPE)
     return torch.from_numpy(arr.view(np.uint8).copy()).to(device)
 
 
-BN_FOLD_JOB_DTYPE = [("gamma", "<u8"), ("beta", "<u8"), ("mean", "<u8"), ("var", "<u8"), ("bias", "<u8"), ("scale", "<u8"), ("shift", "<u8"),
-                     ("C", "<i4"), ("Cp", "<i4"), ("eps", "<f4"), ("reserved", "<i4")]
+BN_FOLD_JOB_DTYPE = np.dtype(L.BnFoldJob)
 
 
 def bn_fold_job(gamma, beta, mean, var, bias, scale, shift, C_logical, eps):
@@ -443,7 +441,6 @@ def bn_fold_job(gamma, beta, mean, var, bias, scale, shift, C_logical, eps):
 
 
 def make_bn_fold_table(jobs, device) -> torch.Tensor:
-    import numpy as np
     arr = np.array(jobs, dtype=BN_FOLD_JOB_DTYPE)
     return torch.from_numpy(arr.view(np.uint8).copy()).to(device)
 
@@ -454,7 +451,6 @@ def bn_fold_batched(table: torch.Tensor, njobs: int):
 
 def make_pack_tilemap(jobs, device, tiles_per_block: int = 4):
     """(job, first tile, count) triples covering every 32x32 tile of every pack job once -> (int32 device tensor, nblocks)."""
-    import numpy as np
     trip = []
     for ji, job in enumerate(jobs):
         T, Nn, Kk = job[5], job[6], job[7]
@@ -477,8 +473,7 @@ def unpack_wgrad(scratch, Mrows, Ncols, T, Nn, Kk, n_off, k_off, dst, sT, sN, sK
                                         scale, 1 if accumulate else 0, _stream()), "unpack_wgrad")
 
 
-UNPACK_JOB_DTYPE = [("scratch", "<u8"), ("dst", "<u8"), ("sT", "<i8"), ("sN", "<i8"), ("sK", "<i8"), ("Mrows", "<i4"), ("Ncols", "<i4"), ("T", "<i4"),
-                    ("Nn", "<i4"), ("Kk", "<i4"), ("n_off", "<i4"), ("k_off", "<i4"), ("accumulate", "<i4"), ("scale", "<f4"), ("reserved", "<i4")]
+UNPACK_JOB_DTYPE = np.dtype(L.UnpackJob)
 
 
 def unpack_job(scratch, Mrows, Ncols, T, Nn, Kk, n_off, k_off, dst, sT, sN, sK, scale=1.0, accumulate=True):
@@ -486,7 +481,6 @@ def unpack_job(scratch, Mrows, Ncols, T, Nn, Kk, n_off, k_off, dst, sT, sN, sK, 
 
 
 def make_unpack_table(jobs, device):
-    import numpy as np
     arr = np.array(jobs, dtype=UNPACK_JOB_DTYPE)
     return torch.from_numpy(arr.view(np.uint8).copy()).to(device), len(jobs), int(max(j[7] * j[8] * j[9] for j in jobs))
 
@@ -561,7 +555,7 @@ def norm_act_bwd_pair(xa, dya, Ca, gamma_a, beta_a, dxa, dgamma_a, dbeta_a, dbia
                                           dgamma_a.data_ptr(), dbeta_a.data_ptr(), dbias_a.data_ptr(), C.byref(db), xb.data_ptr(), doutb.data_ptr(),
                                           gamma_b.data_ptr(), beta_b.data_ptr(), Bb, sa_s.data_ptr(), sa_dg.data_ptr(), float(sa_mult), dxb.data_ptr(),
                                           dgamma_b.data_ptr(), dbeta_b.data_ptr(), dbias_b.data_ptr(), reduce_ws(xa.device).data_ptr(), _stream())
-    if rc == -2:        # USSEG_ERR_UNSUPPORTED
+    if rc == L.ERR_UNSUPPORTED:
         return False
     L.check(rc, "norm_act_bwd_pair")
     return True
@@ -1000,9 +994,9 @@ def adamw_step(p, g, m, v, sumsq_t, clip_norm, lr_t_dev, wd_t_dev, decay_mask, b
                                       lr_t_dev.data_ptr(), wd_t_dev.data_ptr(), _ptr(decay_mask), b1, b2, eps, _stream()), "adamw_step")
 
 
-# UssegAverage as int32[5]: mode, decay bits, dynamic_decay, start, period (usseg.h; flat.AdamClip keeps it on the device)
-AVERAGE_MODES = {"ema": 1, "swa": 2}
-AVERAGE_WORDS = 5
+# UssegAverage as int32 words: mode, decay bits, dynamic_decay, start, period (usseg.h; flat.AdamClip keeps it on the device)
+AVERAGE_MODES = {"ema": L.AVERAGE_EMA, "swa": L.AVERAGE_SWA}
+AVERAGE_WORDS = C.sizeof(L.Average) // 4
 
 
 def adamw_avg_step(p, g, m, v, avg, sumsq_t, clip_norm, lr_t_dev, wd_t_dev, decay_mask, b1, b2, eps, step_dev, avg_desc):
@@ -1262,7 +1256,7 @@ def loss_from_probs(probs, y_true, loss, *, HW, C_classes, loss_kind=0, label_sm
 
 
 # ------------------------------------------------------------------------------------------------ soft Dice / Tversky (+ CCE)
-OVERLAP_ACC_FLOATS = 8224   # USSEG_OVERLAP_ACC_FLOATS: [0] loss, [1] ticket, [2] CCE sum, [4..12) A_c, B_c, [16..32) I, P, Y, T, [32 + 16*b + k] partials
+OVERLAP_ACC_FLOATS = L.OVERLAP_ACC_FLOATS   # [0] loss, [1] ticket, [2] CCE sum, [4..12) A_c, B_c, [16..32) I, P, Y, T, [32 + 16*b + k] partials
 OVERLAP_KEYS = ("alpha", "beta", "smooth", "power", "class_weight", "ce_weight", "ov_weight")
 
 
@@ -1520,7 +1514,7 @@ def overlap_boundary_loss_bwd(probs, y_true, phi, acc, dlogits, *, overlap, boun
 
 
 # ------------------------------------------------------------------------------------------------ stable radix sort, the Lovasz-softmax loss
-SORT_TILE, SORT_DIGIT_BITS = 2048, 8      # USSEG_SORT_TILE, USSEG_SORT_DIGIT_BITS
+SORT_TILE, SORT_DIGIT_BITS = L.SORT_TILE, L.SORT_DIGIT_BITS
 LOVASZ_KEYS = ("classes", "class_weight", "lv_weight", "ce_weight", "threshold")
 _WORDS = (torch.int32, getattr(torch, "uint32", torch.int32))
 
@@ -1891,7 +1885,7 @@ def token_mean_bwd(dy, like):
 
 
 # ------------------------------------------------------------------------------------------------ offline preprocessing (prep.hip)
-PREP_H, PREP_W = 256, 80     # USSEG_PREP_H, USSEG_PREP_W
+PREP_H, PREP_W = L.PREP_H, L.PREP_W
 
 
 def _prep_check(t, name, dtype, ndim):

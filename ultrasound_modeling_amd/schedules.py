@@ -14,7 +14,8 @@ from typing import Sequence
 
 import numpy as np
 
-MAX_PIECES = 16          # USSEG_SCHED_MAX_PIECES
+from ._lib import SCHED_MAX_PIECES as MAX_PIECES
+
 _I32_MAX = 2 ** 31 - 1
 
 
