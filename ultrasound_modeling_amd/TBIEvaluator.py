@@ -482,6 +482,173 @@ def write_lesion_csv(path, result: PolarResult, threshold=0.5, *, min_area=1, mi
     return len(names)
 
 
+# ---------------------------------------------------------------------------------------------------------- per-image / per-patient scores
+def image_scores(result: PolarResult, geometry=None, threshold=0.5, pred_mask=None, device=None):
+    """The bleed class's overlap table per image (``metrics.image_scores``): the prediction ``result.bleed_prob > threshold`` - or
+    ``pred_mask`` [N,H,W], as ``surface_scores`` takes it - against the label's class 2 (``label > 1.5``).  ``geometry``: a
+    ``metrics.ScanGeometry`` (the axes UNCAST) adds the areas in axis units^2."""
+    from .metrics import image_scores as scores
+    pred = np.asarray(result.bleed_prob) > threshold if pred_mask is None else np.asarray(pred_mask) != 0
+    return scores(pred, np.asarray(result.label) > 1.5, geometry, device=device)
+
+
+SCORE_COLUMNS = ("tp", "fp", "fn", "tn", "dice", "iou", "sensitivity", "precision")
+AREA_COLUMNS = ("area_true", "area_pred", "area_tp", "area_dice", "area_error")
+
+
+def _cell(v):
+    """An integer as it is, a float by ``repr`` (round-trips), nothing for None."""
+    if v is None:
+        return ""
+    return int(v) if isinstance(v, (int, np.integer)) else repr(float(v))
+
+
+def _summary_rows(summary, columns, lead):
+    """The rows under a score table: ``pooled`` (the scores of the summed counts), ``mean`` / ``median`` over the defined entries and
+    ``defined`` (how many those are) in the ratio columns; with areas ``loa_lower`` / ``loa_upper`` (Bland-Altman: bias -+ 1.96 sd; the bias
+    is the ``mean`` row's ``area_error``) in the ``area_error`` column; with a bootstrap ``ci_pooled_lower`` / ``ci_pooled_upper`` (pooled Dice
+    under ``dice``, pooled area Dice under ``area_dice``, TOTAL area error under ``area_error``) and ``ci_mean_lower`` / ``ci_mean_upper``
+    (the mean per-image Dice under ``dice``).  ``lead``: the cells between the row's name and the first score column."""
+    def row(name, values):
+        return [name] + list(lead) + [_cell(values.get(c)) for c in columns]
+    ba = summary.get("bland_altman")
+    mean = dict(summary["mean"], **({"area_error": ba["bias"]} if ba else {}))
+    rows = [row("pooled", summary["pooled"]), row("mean", mean), row("median", summary["median"]), row("defined", summary["defined"])]
+    if ba:
+        rows += [row("loa_lower", {"area_error": ba["lower"]}), row("loa_upper", {"area_error": ba["upper"]})]
+    bs = summary.get("bootstrap")
+    if bs:
+        iv = bs["intervals"]
+        for side, name in enumerate(("lower", "upper")):
+            pooled = {"dice": iv["pooled_dice"][side]}
+            if "area_dice" in iv:
+                pooled.update(area_dice=iv["area_dice"][side], area_error=iv["area_error_total"][side])
+            rows.append(row(f"ci_pooled_{name}", pooled))
+        rows += [row(f"ci_mean_{name}", {"dice": iv["mean_dice"][side]}) for side, name in enumerate(("lower", "upper"))]
+    return rows
+
+
+def write_scores_csv(path, result: PolarResult, geometry=None, threshold=0.5, *, pred_mask=None, bootstrap=0, seed=0, alpha=0.05, device=None):
+    """One row per image - name, ``SCORE_COLUMNS`` and with a geometry ``AREA_COLUMNS`` (an undefined ratio reads ``nan``) - then
+    ``_summary_rows``.  ``bootstrap`` = R adds the percentile intervals of R replicates that resample images (``write_patient_csv``'s
+    resample patients).  -> the number of image rows."""
+    import csv
+    from .metrics import summarize
+    t = image_scores(result, geometry, threshold, pred_mask, device=device)
+    names = _names(result)
+    columns = SCORE_COLUMNS + (AREA_COLUMNS if geometry is not None else ())
+    s = summarize(t, bootstrap=bootstrap, seed=seed, alpha=alpha, device=device)
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(["name"] + list(columns))
+        for i, n in enumerate(names):
+            w.writerow([n] + [_cell(t[c][i]) for c in columns])
+        w.writerows(_summary_rows(s, columns, ()))
+    return len(names)
+
+
+def write_patient_csv(path, result: PolarResult, geometry=None, threshold=0.5, *, pred_mask=None, pattern=r"DoD(\d+)", bootstrap=0, seed=0,
+                      alpha=0.05, device=None):
+    """One row per patient (``metrics.patient_of`` of each image name under ``pattern``) - patient, n_images, and the columns of
+    ``write_scores_csv`` from the patient's summed counts - then ``_summary_rows`` over the PATIENTS' table (mean, median and limits of
+    agreement across patients; pooled = the whole run), its bootstrap a cluster bootstrap that resamples patients.  -> the number of
+    patient rows."""
+    import csv
+    from .metrics import grouped, patient_of, summarize
+    t = image_scores(result, geometry, threshold, pred_mask, device=device)
+    groups = [patient_of(n, pattern) for n in _names(result)]
+    g = grouped(t, groups)
+    columns = SCORE_COLUMNS + (AREA_COLUMNS if geometry is not None else ())
+    s = summarize(g, bootstrap=0)
+    if bootstrap:
+        # the cluster bootstrap keeps the per-IMAGE Dice inside each patient's row (dice_q, dice_n), so it is drawn from the image table
+        s["bootstrap"] = summarize(t, groups=groups, bootstrap=bootstrap, seed=seed, alpha=alpha, device=device)["bootstrap"]
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(["patient", "n_images"] + list(columns))
+        for i, p in enumerate(g["groups"]):
+            w.writerow([p, int(g["n_images"][i])] + [_cell(g[c][i]) for c in columns])
+        w.writerows(_summary_rows(s, columns, (int(g["n_images"].sum()),)))
+    return len(g["groups"])
+
+
+LESION_SIZE_COLUMNS = ("pixels", "area", "diameter", "centroid_x", "centroid_y", "x_min", "x_max", "y_min", "y_max")
+
+
+def write_lesion_size_csv(path, result: PolarResult, geometry, threshold=0.5, *, min_area=1, min_peak=0.0, connectivity=8, device=None):
+    """One row per predicted and per labelled bleed component: name, kind (``pred`` / ``true``), id (``scipy.ndimage.label``'s numbering),
+    ``LESION_SIZE_COLUMNS`` in axis units (``metrics.lesion_sizes_from_measure``) and ``matched`` = 1 when at least one of its pixels lies
+    inside a component of the other kind (``ops.component_overlap``), else 0.  The prediction is the cleaned one (``clean_result``), as in
+    ``write_lesion_csv``.  -> the number of component rows."""
+    import csv
+    from .metrics import _lesion_measure, _mask_stack, lesion_sizes_from_measure
+    dev = torch.device(device if device is not None else "cuda")
+    pred = clean_result(result, threshold, min_area=min_area, min_peak=min_peak, connectivity=connectivity, device=dev)
+    lp, cp, mp = _lesion_measure(_mask_stack(pred, dev, "write_lesion_size_csv"), geometry, connectivity)
+    lt, ct, mt = _lesion_measure(_mask_stack(np.asarray(result.label) > 1.5, dev, "write_lesion_size_csv"), geometry, connectivity)
+    hit_p, hit_t = ops.component_overlap(lp, lt, mp.shape[1], mt.shape[1])
+    tables = (("pred", cp, lesion_sizes_from_measure(cp, mp, geometry), hit_p.cpu().numpy()),
+              ("true", ct, lesion_sizes_from_measure(ct, mt, geometry), hit_t.cpu().numpy()))
+    rows = 0
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(["name", "kind", "id"] + list(LESION_SIZE_COLUMNS) + ["matched"])
+        for i, n in enumerate(_names(result)):
+            for kind, count, s, hit in tables:
+                for k in range(int(count[i])):
+                    w.writerow([n, kind, k + 1] + [_cell(s[c][i, k]) for c in LESION_SIZE_COLUMNS] + [int(hit[i, k] > 0)])
+                    rows += 1
+    return rows
+
+
+def _add_score_arguments(ap):
+    ap.add_argument("--scores-csv", default=None, metavar="PATH",
+                    help="also write the bleed class's overlap table, one row per image (tp, fp, fn, tn, Dice, IoU, sensitivity, precision and the "
+                         "areas in axis units^2 from axis_dir's UNCAST axes) and summary rows")
+    ap.add_argument("--patient-csv", default=None, metavar="PATH", help="the same table per patient (--patient-regex), from each patient's summed counts")
+    ap.add_argument("--lesion-size-csv", default=None, metavar="PATH",
+                    help="also write one row per predicted and per labelled bleed component: its area, equivalent diameter, centroid and extent in axis units")
+    ap.add_argument("--patient-regex", default=r"DoD(\d+)", metavar="RE", help="what names a patient inside an image name (its first group)")
+    ap.add_argument("--bootstrap", type=int, default=0, metavar="R",
+                    help="add percentile intervals from R bootstrap replicates to --scores-csv (resampling images) and --patient-csv (resampling patients)")
+    ap.add_argument("--bootstrap-seed", type=int, default=0, metavar="S", help="the seed of --bootstrap")
+
+
+def _check_score_arguments(ap, a):
+    import re
+    if not 0 <= a.bootstrap <= 1 << 20:
+        ap.error("--bootstrap must lie in 0..2^20")
+    if not 0 <= a.bootstrap_seed < 1 << 64:
+        ap.error("--bootstrap-seed must lie in 0..2^64-1")
+    if a.bootstrap and a.scores_csv is None and a.patient_csv is None:
+        ap.error("--bootstrap needs --scores-csv or --patient-csv")
+    try:
+        re.compile(a.patient_regex)
+    except re.error as e:
+        ap.error(f"--patient-regex: {e}")
+
+
+def _write_score_outputs(a, result, thr, device):
+    """``main``'s --scores-csv / --patient-csv / --lesion-size-csv; nothing is read, imported or launched without one of them."""
+    if a.scores_csv is None and a.patient_csv is None and a.lesion_size_csv is None:
+        return
+    from .metrics import ScanGeometry
+    scan = ScanGeometry.from_dir(a.axis_dir)
+    clean = dict(min_area=a.min_area if a.min_area is not None else 1, min_peak=a.min_peak, connectivity=a.connectivity)
+    if a.scores_csv is not None or a.patient_csv is not None:
+        cleaned = clean_result(result, **thr, **clean, device=device)
+        if a.scores_csv is not None:
+            rows = write_scores_csv(a.scores_csv, result, scan, pred_mask=cleaned, bootstrap=a.bootstrap, seed=a.bootstrap_seed, device=device)
+            print(f"wrote {rows} image-score rows to {a.scores_csv}")
+        if a.patient_csv is not None:
+            rows = write_patient_csv(a.patient_csv, result, scan, pred_mask=cleaned, pattern=a.patient_regex, bootstrap=a.bootstrap, seed=a.bootstrap_seed,
+                                     device=device)
+            print(f"wrote {rows} patient rows to {a.patient_csv}")
+    if a.lesion_size_csv is not None:
+        rows = write_lesion_size_csv(a.lesion_size_csv, result, scan, **thr, **clean, device=device)
+        print(f"wrote {rows} lesion-size rows to {a.lesion_size_csv}")
+
+
 # ---------------------------------------------------------------------------------------------------------- the figures
 PANEL_RANGES = ((0.0, 2.0), (0.0, 2.0), (0.0, 1.0))     # Prediction, label, Probability Bleed (:297, :304, :333); bMode per image
 GAP = 16                                                # white pixels between the panels
@@ -685,7 +852,9 @@ def main(argv=None):
                     help="fit the temperature on this run's data (it needs the labels), print it with the NLL and the ECE before and after, and predict again with it")
     ap.add_argument("--threshold", default=None, metavar="T|best-dice|youden",
                     help="the bleed threshold --surface-csv and --lesion-csv use (default 0.5): a number, or the sweep's best-Dice or Youden point")
+    _add_score_arguments(ap)
     a = ap.parse_args(argv)
+    _check_score_arguments(ap, a)
     threshold = None
     if a.threshold is not None and a.threshold not in ("best-dice", "youden"):
         try:
@@ -770,6 +939,7 @@ def main(argv=None):
         rows = write_lesion_csv(a.lesion_csv, result, **thr, min_area=a.min_area if a.min_area is not None else 1, min_peak=a.min_peak,
                                 connectivity=a.connectivity, device=cascade.device)
         print(f"wrote {rows} lesion rows to {a.lesion_csv}")
+    _write_score_outputs(a, result, thr, cascade.device)
     paths = Display(result, geometry, a.out, stamp=not a.no_stamp, batch_size=a.batch)
     print(f"wrote {len(paths)} figures under {a.out}")
 

@@ -1,4 +1,5 @@
-"""ctypes binding of libusseg_hip.so, generated at import from the C ABI declared in include/usseg.h (_abi.py reads it).
+"""ctypes binding of libusseg_hip.so, generated at import from the C ABI declared in include/usseg.h and, for the evaluator's score kernels,
+include/usseg_scores.h (_abi.py reads both; ``ABI`` is the first header's, ``SCORES_ABI`` the second's).
 
 There is NO fallback: if the header or the shared library is missing or a call fails, an exception is raised.
 Nothing here imports the oracle.
@@ -14,6 +15,7 @@ from . import _abi, knobs
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = knobs.get("USSEG_LIB") or os.path.join(_HERE, "libusseg_hip.so")   # USSEG_LIB: a diagnostic build of the SAME sources (tools/diag_norm_variants.sh)
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "usseg.h")
+SCORES_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "usseg_scores.h")
 
 c_i32, c_i64, c_f32, c_vp = C.c_int32, C.c_int64, C.c_float, C.c_void_p
 
@@ -40,14 +42,21 @@ TEMP_NLL_UNIT = 2.0 ** -20    # one count of usseg_temperature_nll's sums (the h
 _PROTOS = ABI.protos    # name: (restype, argtypes)
 EXPORTED_SYMBOLS = tuple(_PROTOS)
 
+# the second header (csrc/scores.hip): its own Abi, so that ABI, _PROTOS and EXPORTED_SYMBOLS stay the first header's alone
+SCORES_ABI = read_header(SCORES_HEADER_PATH)
+SCORES_SYMBOLS = tuple(SCORES_ABI.protos)
+SCORES_MEASURE_FIELDS, SCORES_EMPTY_MIN = SCORES_ABI.consts["USSEG_SCORES_MEASURE_FIELDS"], SCORES_ABI.consts["USSEG_SCORES_EMPTY_MIN"]
+SCORES_BOOT_MAX_K, SCORES_BOOT_MAX = SCORES_ABI.consts["USSEG_SCORES_BOOT_MAX_K"], SCORES_ABI.consts["USSEG_SCORES_BOOT_MAX"]
+
 _lib = None
 
 
-def bind(lib: C.CDLL, names=EXPORTED_SYMBOLS) -> C.CDLL:
-    """Give the named entry points of ``lib`` (any build of these sources) the header's prototypes."""
+def bind(lib: C.CDLL, names=EXPORTED_SYMBOLS, protos=None) -> C.CDLL:
+    """Give the named entry points of ``lib`` (any build of these sources) the prototypes of ``protos`` (default: usseg.h's)."""
+    protos = _PROTOS if protos is None else protos
     for name in names:
         fn = getattr(lib, name)  # AttributeError if the symbol is missing: fail loudly
-        fn.restype, fn.argtypes = _PROTOS[name]
+        fn.restype, fn.argtypes = protos[name]
     return lib
 
 
@@ -59,7 +68,7 @@ def load() -> C.CDLL:
     if not os.path.exists(LIB_PATH):
         raise UssegError(f"{LIB_PATH} not found: build the HIP extension first (python -c 'import __graft_entry__ as g; "
                          f"g.build()'). There is no CPU fallback.")
-    _lib = bind(C.CDLL(LIB_PATH))
+    _lib = bind(bind(C.CDLL(LIB_PATH)), SCORES_SYMBOLS, SCORES_ABI.protos)
     return _lib
 
 

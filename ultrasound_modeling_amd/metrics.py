@@ -15,6 +15,8 @@ Two behaviours of the reference, reproduced on purpose:
 from __future__ import annotations
 
 import math
+import os
+import re
 from typing import Dict
 
 import numpy as np
@@ -26,7 +28,8 @@ from .ops import seg_counts  # noqa: F401  (the kernel wrapper; re-exported here
 
 __all__ = ["CalibrationBins", "SEG_COUNTS", "SegMetrics", "calibration_from_counts", "calibration_line", "components", "counts_to_metrics", "dice_per_class", "dice_line", "lesion_scores", "lesion_scores_from_tables",
            "seg_counts", "SweepCounts", "fit_temperature", "sweep_from_counts", "sweep_line", "sweep_thresholds", "temperature_candidates",
-           "temperature_search"]
+           "temperature_search", "ScanGeometry", "image_scores", "scores_from_counts", "patient_of", "grouped", "summarize", "bootstrap_rows",
+           "bootstrap_statistics", "lesion_sizes", "lesion_sizes_from_measure"]
 
 
 def _div_no_nan(a: float, b: float) -> float:
@@ -506,3 +509,327 @@ def fit_temperature(batches, *, lo=1 / 8, hi=8.0, candidates=16, rounds=4, devic
     beta, best, at1, bracket, n, n_invalid = temperature_search(evaluate, lo=lo, hi=hi, candidates=candidates, rounds=rounds)
     per = TEMP_NLL_UNIT / n if n else float("nan")
     return dict(beta=beta, temperature=1.0 / beta, nll=best * per, nll_at_1=at1 * per, bracket=bracket, n=n, n_invalid=n_invalid)
+
+
+# ---- per-image and per-patient scores, bleed sizes in physical units (csrc/scores.hip, include/usseg_scores.h) ----------------------------
+class ScanGeometry:
+    """The physical geometry of the polar grid, for MEASURING (``TBIEvaluator.ConeGeometry`` is the one that draws): ``xAxis``, ``yAxis`` [H,W],
+    finite, H, W >= 2 (``axis/xAxis.npy`` / ``axis/yAxis.npy``, the position of every sample in axis units).  The axes are used as they are:
+    the ``astype(int)`` the reference applies before it draws (TBIEvaluator.py:23-24) is a display quirk - it only snaps the figure's
+    vertices to whole units - and would put the areas below off by up to a whole cell.
+
+    ``area`` fp64 [H,W]: the cell around each sample, |dXi*dYj - dXj*dYi| (the Jacobian of (row, column) -> (x, y)), where d.i is the central
+    difference along rows, (v[i+1,j] - v[i-1,j]) * 0.5, one-sided in the first and last row (v[1] - v[0], v[H-1] - v[H-2]), and d.j the same
+    along columns.  A deep pixel of a sector scan covers many times the area of a shallow one: a pixel count is not the size of a bleed.
+
+    Fixed-point tables for the kernels (include/usseg_scores.h states the overflow argument: 2^20 * 2^16 * 2^26 = 2^62):
+        quantum = area.max() / (2^20 - 1)         wq = rint(area / quantum), uint32, every value < 2^20
+        xstep = (X.max() - X.min()) / (2^16 - 1)  xq = rint((X - X.min()) / xstep), int32 in [0, 65535]; a zero span: xstep = 1, xq = 0
+    and ystep / yq alike.  ``area_of``, ``x_of`` and ``y_of`` convert the kernels' integer sums back to axis units.  Bounds: every cell is
+    rounded to the nearest quantum once, so an area summed over n pixels is off by at most n * quantum / 2; every coordinate is rounded to
+    the nearest step once, so a centroid is within xstep / 2 (ystep / 2) of the centroid of the exact coordinates under the same weights,
+    and an extent within xstep / 2 of the exact one.  A grid whose largest area is 0 or not finite (collapsed, or overflowing) is refused."""
+
+    WQ_MAX, Q_MAX, MAX_DIM = 2 ** 20 - 1, 2 ** 16 - 1, 8192
+
+    def __init__(self, xAxis, yAxis):
+        X, Y = np.asarray(xAxis), np.asarray(yAxis)
+        if X.shape != Y.shape or X.ndim != 2 or min(X.shape) < 2:
+            raise ValueError(f"xAxis {X.shape} and yAxis {Y.shape} must be one [H,W] grid with H, W >= 2")
+        if max(X.shape) > self.MAX_DIM:
+            raise ValueError(f"H and W must not exceed {self.MAX_DIM} (the kernels' limit, on which the int64 budget rests), got {X.shape}")
+        if not (np.issubdtype(X.dtype, np.number) and np.issubdtype(Y.dtype, np.number)) or np.iscomplexobj(X) or np.iscomplexobj(Y):
+            raise ValueError("xAxis and yAxis must hold real numbers")
+        X, Y = np.ascontiguousarray(X, np.float64), np.ascontiguousarray(Y, np.float64)
+        if not (np.isfinite(X).all() and np.isfinite(Y).all()):
+            raise ValueError("xAxis and yAxis must hold finite numbers")
+
+        def d_i(v):
+            d = np.empty_like(v)
+            d[1:-1] = (v[2:] - v[:-2]) * 0.5
+            d[0] = v[1] - v[0]
+            d[-1] = v[-1] - v[-2]
+            return d
+
+        def d_j(v):
+            d = np.empty_like(v)
+            d[:, 1:-1] = (v[:, 2:] - v[:, :-2]) * 0.5
+            d[:, 0] = v[:, 1] - v[:, 0]
+            d[:, -1] = v[:, -1] - v[:, -2]
+            return d
+        with np.errstate(over="ignore", invalid="ignore"):
+            area = np.abs(d_i(X) * d_j(Y) - d_j(X) * d_i(Y))
+        top = float(area.max())
+        if not (np.isfinite(area).all() and top > 0.0):
+            raise ValueError(f"the grid spans no area, or one that is not finite (largest cell {top!r})")
+        self.X, self.Y, self.area, self.grid = X, Y, area, X.shape
+        self.quantum = top / self.WQ_MAX
+        self.wq = np.minimum(np.rint(area / self.quantum), self.WQ_MAX).astype(np.uint32)
+        self.x_min, self.xstep, self.xq = self._quantise(X)
+        self.y_min, self.ystep, self.yq = self._quantise(Y)
+        self._dev = {}
+
+    @classmethod
+    def _quantise(cls, V):
+        lo = float(V.min())
+        span = float(V.max()) - lo
+        if not np.isfinite(span):
+            raise ValueError(f"the axis spans {span!r}: not a finite number")
+        step = span / cls.Q_MAX
+        if not step > 0.0:                                                  # a zero span (or one so small that the step underflows)
+            return lo, 1.0, np.zeros(V.shape, np.int32)
+        return lo, step, np.clip(np.rint((V - lo) / step), 0, cls.Q_MAX).astype(np.int32)
+
+    @classmethod
+    def from_dir(cls, axis_dir):
+        """Read ``xAxis.npy`` and ``yAxis.npy`` (``DataFilePlayGround.FetchPolarAxis``'s output) from ``axis_dir``, uncast."""
+        return cls(np.load(os.path.join(axis_dir, "xAxis.npy")), np.load(os.path.join(axis_dir, "yAxis.npy")))
+
+    def tables(self, device):
+        """(wq, xq, yq) as int32 [H,W] tensors on ``device`` (wq < 2^20 reads the same as uint32), uploaded once per device."""
+        dev = torch.device(device)
+        if dev not in self._dev:
+            self._dev[dev] = tuple(torch.from_numpy(np.ascontiguousarray(t.astype(np.int32))).to(dev) for t in (self.wq, self.xq, self.yq))
+        return self._dev[dev]
+
+    def area_of(self, sum_wq):
+        """A sum of ``wq`` -> area in axis units^2 (off by at most n * quantum / 2 over n pixels)."""
+        return np.asarray(sum_wq, np.float64) * self.quantum
+
+    @staticmethod
+    def _centre(lo, step, sum_wq_q, sum_wq):
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return lo + step * (np.asarray(sum_wq_q, np.float64) / np.asarray(sum_wq, np.float64))
+
+    def x_of(self, sum_wxq, sum_wq):
+        """Sums of ``wq * xq`` and of ``wq`` -> the area-weighted x in axis units (NaN for an empty sum)."""
+        return self._centre(self.x_min, self.xstep, sum_wxq, sum_wq)
+
+    def y_of(self, sum_wyq, sum_wq):
+        return self._centre(self.y_min, self.ystep, sum_wyq, sum_wq)
+
+    def x_at(self, xq):
+        """A quantised coordinate (an extent of ``component_measure``) -> axis units."""
+        return self.x_min + self.xstep * np.asarray(xq, np.float64)
+
+    def y_at(self, yq):
+        return self.y_min + self.ystep * np.asarray(yq, np.float64)
+
+
+SCORE_COUNTS = ("tp", "fp", "fn", "tn")
+SCORE_AREA_COUNTS = ("w_true", "w_pred", "w_tp")          # sums of ScanGeometry.wq: integers, in quanta
+SCORE_RATIOS = ("dice", "iou", "sensitivity", "precision")
+SCORE_AREAS = ("area_true", "area_pred", "area_tp", "area_dice", "area_error")
+DICE_FIXED_ONE = 2 ** 30                                 # a per-image Dice travels through the bootstrap as rint(dice * 2^30)
+
+
+def _ratio(num, den):
+    """num / den element-wise in fp64, NaN where den == 0 (an undefined score is left out of a mean, never counted as 0 or 1)."""
+    num, den = np.asarray(num, np.float64), np.asarray(den, np.float64)
+    out = np.full(np.broadcast(num, den).shape, np.nan)
+    np.divide(num, den, out=out, where=den != 0)
+    return out
+
+
+def scores_from_counts(tp, fp, fn, tn, w_true=None, w_pred=None, w_tp=None, quantum=None):
+    """Integer columns -> the score table: the counts (int64), ``dice`` = 2tp / (2tp + fp + fn), ``iou`` = tp / (tp + fp + fn),
+    ``sensitivity`` = tp / (tp + fn), ``precision`` = tp / (tp + fp), each NaN where its denominator is 0; with the area sums (in quanta
+    of ``quantum`` axis units^2) also ``area_true / area_pred / area_tp``, ``area_dice`` = 2 w_tp / (w_true + w_pred) and ``area_error`` =
+    area_pred - area_true.  Every derived column is one fp64 division (and one product) of exact integers."""
+    t = {k: np.asarray(v, np.int64).reshape(-1) for k, v in zip(SCORE_COUNTS, (tp, fp, fn, tn))}
+    tp_, fp_, fn_ = t["tp"], t["fp"], t["fn"]
+    t["dice"] = _ratio(2 * tp_, 2 * tp_ + fp_ + fn_)
+    t["iou"] = _ratio(tp_, tp_ + fp_ + fn_)
+    t["sensitivity"] = _ratio(tp_, tp_ + fn_)
+    t["precision"] = _ratio(tp_, tp_ + fp_)
+    if w_true is not None:
+        q = float(quantum)
+        wt, wp, wtp = (np.asarray(v, np.int64).reshape(-1) for v in (w_true, w_pred, w_tp))
+        t.update(w_true=wt, w_pred=wp, w_tp=wtp, quantum=q, area_true=wt * q, area_pred=wp * q, area_tp=wtp * q,
+                 area_dice=_ratio(2 * wtp, wt + wp), area_error=(wp - wt) * q)
+    return t
+
+
+def image_scores(pred_mask, true_mask, geometry=None, device=None):
+    """The overlap table per image of two stacks of masks [N,H,W] (anything ``!= 0`` is inside; NumPy or torch), counted on the device by
+    one ``ops.image_confusion`` call and read back once -> ``scores_from_counts``' table, one entry per image.  With a ``ScanGeometry``
+    every pixel also counts with the area of its cell, which gives the ``area_*`` columns in axis units^2."""
+    from . import ops
+    dev = torch.device(device if device is not None else "cuda")
+    tp_, tt = _mask_stack(pred_mask, dev, "image_scores"), _mask_stack(true_mask, dev, "image_scores")
+    if tp_.shape != tt.shape:
+        raise ValueError(f"image_scores: two [N,H,W] stacks of one shape, got {tuple(tp_.shape)} and {tuple(tt.shape)}")
+    weight = None
+    if geometry is not None:
+        if tuple(geometry.grid) != tuple(tp_.shape[1:]):
+            raise ValueError(f"image_scores: the geometry is {tuple(geometry.grid)}, the masks {tuple(tp_.shape[1:])}")
+        weight = geometry.tables(dev)[0]
+    cm, wcm, invalid = ops.image_confusion(tp_, tt, 2, weight)
+    cm = cm.cpu().numpy()                                                   # cm[n][truth][pred]
+    if weight is None:
+        return scores_from_counts(cm[:, 1, 1], cm[:, 0, 1], cm[:, 1, 0], cm[:, 0, 0])
+    w = wcm.cpu().numpy()
+    return scores_from_counts(cm[:, 1, 1], cm[:, 0, 1], cm[:, 1, 0], cm[:, 0, 0], w[:, 1, 0] + w[:, 1, 1], w[:, 0, 1] + w[:, 1, 1], w[:, 1, 1],
+                              geometry.quantum)
+
+
+def patient_of(name, pattern=r"DoD(\d+)"):
+    """The patient of an image name: what ``pattern`` captures in it (its first group, or the whole match of a pattern without one) -
+    ``DataFilePlayGround``'s patient folders are named DoD<number>.  A name that does not match is its own group."""
+    if isinstance(name, bytes):
+        name = name.decode("utf-8", "replace")
+    name = str(name)
+    m = re.search(pattern, name)
+    if not m:
+        return name
+    return m.group(1) if m.re.groups else m.group(0)
+
+
+def _group_index(groups, n):
+    groups = list(groups)
+    if len(groups) != n:
+        raise ValueError(f"{len(groups)} group labels for {n} images")
+    order = {}
+    idx = np.array([order.setdefault(g, len(order)) for g in groups], np.int64).reshape(-1)
+    return list(order), idx
+
+
+def _sum_by(idx, n_groups, col):
+    out = np.zeros(n_groups, np.int64)
+    np.add.at(out, idx, np.asarray(col, np.int64))
+    return out
+
+
+def grouped(table, groups):
+    """Sum the integer columns of a score table per group (``groups``: one label per image, e.g. ``patient_of`` of each name) and re-derive
+    the ratios from the sums -> a table with one entry per group, in order of first appearance, plus ``groups`` (the labels) and
+    ``n_images`` (images per group)."""
+    n = len(table["tp"])
+    labels, idx = _group_index(groups, n)
+    cols = SCORE_COUNTS + (SCORE_AREA_COUNTS if "w_true" in table else ())
+    sums = {c: _sum_by(idx, len(labels), table[c]) for c in cols}
+    out = scores_from_counts(*(sums[c] for c in cols), **({"quantum": table["quantum"]} if "w_true" in table else {}))
+    out["groups"], out["n_images"] = labels, _sum_by(idx, len(labels), np.ones(n, np.int64))
+    return out
+
+
+def _defined_stats(v):
+    v = np.asarray(v, np.float64)
+    d = v[~np.isnan(v)]
+    return (float(d.mean()) if d.size else float("nan"), float(np.median(d)) if d.size else float("nan"), int(d.size))
+
+
+def bootstrap_rows(table, groups=None):
+    """The integer rows the bootstrap resamples, one per unit (a group when ``groups`` is given, else an image), and their column names:
+    tp, fp, fn, dice_q = the sum of rint(dice * 2^30) over the unit's images with a defined Dice, dice_n = their number; with areas also
+    w_tp, w_true, w_pred."""
+    n = len(table["tp"])
+    dice = np.asarray(table["dice"], np.float64)
+    ok = ~np.isnan(dice)
+    cols = {"tp": table["tp"], "fp": table["fp"], "fn": table["fn"],
+            "dice_q": np.where(ok, np.rint(np.where(ok, dice, 0.0) * DICE_FIXED_ONE), 0).astype(np.int64), "dice_n": ok.astype(np.int64)}
+    if "w_true" in table:
+        cols.update(w_tp=table["w_tp"], w_true=table["w_true"], w_pred=table["w_pred"])
+    names = tuple(cols)
+    if groups is None:
+        return names, np.stack([np.asarray(cols[c], np.int64) for c in names], 1).reshape(n, len(names))
+    labels, idx = _group_index(groups, n)
+    return names, np.stack([_sum_by(idx, len(labels), cols[c]) for c in names], 1).reshape(len(labels), len(names))
+
+
+def bootstrap_statistics(names, sums, quantum=None):
+    """Column sums (of ``bootstrap_rows``' columns; any leading shape) -> the four statistics: ``pooled_dice``, ``mean_dice``, and with areas
+    ``area_dice`` and ``area_error_total`` (axis units^2); NaN where a denominator is 0."""
+    s = {c: np.asarray(sums)[..., i].astype(np.int64) for i, c in enumerate(names)}
+    out = {"pooled_dice": _ratio(2 * s["tp"], 2 * s["tp"] + s["fp"] + s["fn"]), "mean_dice": _ratio(s["dice_q"], s["dice_n"]) / DICE_FIXED_ONE}
+    if "w_true" in s:
+        out["area_dice"] = _ratio(2 * s["w_tp"], s["w_true"] + s["w_pred"])
+        out["area_error_total"] = (s["w_pred"] - s["w_true"]) * float(quantum)
+    return out
+
+
+def summarize(table, groups=None, bootstrap=0, seed=0, alpha=0.05, device=None):
+    """A score table -> its summary:
+      ``pooled``        the scores of the summed counts (``scores_from_counts`` of the column sums: the run as one image);
+      ``mean / median`` of every ratio over the images where it is defined, ``defined`` = how many those are (an image empty in both masks
+                        has no Dice: it is left out, not counted as 0 or 1);
+      ``bland_altman``  of ``area_error`` (with areas): bias = its mean, sd (n - 1), limits of agreement bias -+ 1.96 sd, n.
+    ``bootstrap`` = R > 0 adds ``bootstrap``: percentile intervals [alpha/2, 1 - alpha/2] of ``bootstrap_statistics``' four statistics over R
+    replicates drawn on the device (``ops.bootstrap_sums``, reproducible from ``seed``).  The resampling unit is the group when ``groups``
+    is given - a cluster bootstrap over patients, whose frames are correlated - else the image.  Replicates whose statistic is NaN are
+    dropped from that statistic's interval and counted in ``dropped``."""
+    n = len(table["tp"])
+    areas = "w_true" in table
+    cols = SCORE_COUNTS + (SCORE_AREA_COUNTS if areas else ())
+    pooled = scores_from_counts(*([int(np.asarray(table[c], np.int64).sum())] for c in cols), **({"quantum": table["quantum"]} if areas else {}))
+    pooled = {k: (v[0].item() if isinstance(v, np.ndarray) else v) for k, v in pooled.items()}
+    ratios = SCORE_RATIOS + (("area_dice",) if areas else ())
+    stats = {r: _defined_stats(table[r]) for r in ratios}
+    out = {"n_images": n, "pooled": pooled, "mean": {r: stats[r][0] for r in ratios}, "median": {r: stats[r][1] for r in ratios},
+           "defined": {r: stats[r][2] for r in ratios}}
+    if groups is not None:
+        out["n_groups"] = len(_group_index(groups, n)[0])
+    if areas:
+        e = np.asarray(table["area_error"], np.float64)
+        bias = float(e.mean()) if n else float("nan")
+        sd = float(e.std(ddof=1)) if n > 1 else float("nan")
+        out["bland_altman"] = {"bias": bias, "sd": sd, "lower": bias - 1.96 * sd, "upper": bias + 1.96 * sd, "n": n}
+    R = int(bootstrap)
+    if R < 0:
+        raise ValueError(f"bootstrap must be >= 0, got {bootstrap}")
+    if R:
+        if not 0.0 < float(alpha) < 1.0:
+            raise ValueError(f"alpha must lie in (0, 1), got {alpha}")
+        from . import ops
+        names, rows = bootstrap_rows(table, groups)
+        U = rows.shape[0]
+        if U == 0:
+            raise ValueError("bootstrap: nothing to resample")
+        ops.bootstrap_check_rows(int(np.abs(rows).max(initial=0)), U)
+        dev = torch.device(device if device is not None else "cuda")
+        sums = ops.bootstrap_sums(torch.from_numpy(np.ascontiguousarray(rows)).to(dev), R, seed, check=False).cpu().numpy()
+        st = bootstrap_statistics(names, sums, table.get("quantum"))
+        intervals, dropped = {}, {}
+        for k, v in st.items():
+            ok = v[~np.isnan(v)]
+            dropped[k] = int(v.size - ok.size)
+            lo, hi = (np.quantile(ok, [alpha / 2.0, 1.0 - alpha / 2.0]) if ok.size else (float("nan"), float("nan")))
+            intervals[k] = (float(lo), float(hi))
+        out["bootstrap"] = {"replicates": R, "seed": int(seed), "alpha": float(alpha), "unit": "group" if groups is not None else "image", "units": U,
+                            "intervals": intervals, "dropped": dropped}
+    return out
+
+
+def _lesion_measure(tm, geometry, connectivity):
+    """uint8 [N,H,W] device mask -> (labels int32 device, counts int64 NumPy [N], measure int64 NumPy [N,cap,8]); one read-back sizes the table."""
+    from . import ops
+    if tuple(geometry.grid) != tuple(tm.shape[1:]):
+        raise ValueError(f"lesion_sizes: the geometry is {tuple(geometry.grid)}, the masks {tuple(tm.shape[1:])}")
+    labels, count = ops.label_components(tm, connectivity)
+    count = count.cpu().numpy().astype(np.int64)
+    cap = int(count.max()) if count.size else 0
+    wq, xq, yq = geometry.tables(tm.device)
+    return labels, count, ops.component_measure(labels, wq, xq, yq, cap).cpu().numpy()
+
+
+def lesion_sizes_from_measure(count, measure, geometry):
+    """``ops.component_measure``'s table -> per component, [N,cap] NumPy arrays in axis units: ``pixels``, ``area``, ``diameter`` = the
+    equivalent diameter 2 sqrt(area / pi), ``centroid_x / centroid_y`` (area-weighted), ``x_min / x_max / y_min / y_max``; NaN (pixels 0) in
+    the columns past an image's ``count``."""
+    m = np.asarray(measure, np.int64)
+    present = m[..., 0] > 0
+    nan = lambda v: np.where(present, v, np.nan)
+    area = geometry.area_of(m[..., 1])
+    return {"count": np.asarray(count, np.int64), "pixels": m[..., 0], "area": nan(area), "diameter": nan(2.0 * np.sqrt(area / math.pi)),
+            "centroid_x": nan(geometry.x_of(m[..., 2], m[..., 1])), "centroid_y": nan(geometry.y_of(m[..., 3], m[..., 1])),
+            "x_min": nan(geometry.x_at(m[..., 4])), "x_max": nan(geometry.x_at(m[..., 5])),
+            "y_min": nan(geometry.y_at(m[..., 6])), "y_max": nan(geometry.y_at(m[..., 7]))}
+
+
+def lesion_sizes(mask, geometry, connectivity=8, device=None):
+    """The size of every connected component of a stack of masks [N,H,W] in physical units, measured on the device
+    (``ops.label_components`` + ``ops.component_measure``) -> ``lesion_sizes_from_measure``'s dict; component k of image n is column k-1,
+    in ``scipy.ndimage.label``'s numbering."""
+    dev = torch.device(device if device is not None else "cuda")
+    _, count, measure = _lesion_measure(_mask_stack(mask, dev, "lesion_sizes"), geometry, connectivity)
+    return lesion_sizes_from_measure(count, measure, geometry)

@@ -1493,6 +1493,98 @@ def component_overlap(la, lb, cap_a, cap_b):
     return hit_a, hit_b
 
 
+# ---- per-image scores in pixels and physical units (csrc/scores.hip, include/usseg_scores.h) -----------------------------------------------
+COMPONENT_MEASURE_FIELDS = ("pixels", "sum_w", "sum_wx", "sum_wy", "xq_min", "xq_max", "yq_min", "yq_max")
+
+
+def _scores_out(out, shape, device, what):
+    if out is None:
+        return torch.empty(shape, dtype=torch.int64, device=device)
+    assert out.dtype == torch.int64 and out.is_contiguous() and tuple(out.shape) == tuple(shape) and out.device == device, \
+        f"{what}: a contiguous int64 {tuple(shape)} on {device}"
+    return out
+
+
+def _scores_grid(t, shape, dtype, what):
+    assert t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == tuple(shape) and t.is_cuda, f"{what}: a contiguous {dtype} {tuple(shape)} on the GPU"
+    return t
+
+
+def image_confusion(pred, truth, num_classes=2, weight=None, *, out=None):
+    """The confusion table of every image (usseg_scores.h usseg_image_confusion): ``pred``, ``truth`` uint8 [N,H,W] class ids on the GPU,
+    ``weight`` uint32-valued [H,W] (an int32 or uint32 tensor, e.g. ``ScanGeometry.wq``) or None -> (cm int64 [N,C,C] with cm[n][truth][pred],
+    wcm int64 [N,C,C] or None, invalid int64 [N]).  ``out`` = (cm, wcm, invalid) buffers to write into (wcm None without a weight)."""
+    N, H, W = _component_mask(pred, "image_confusion")
+    assert pred.is_cuda, "image_confusion runs on the GPU only"
+    _scores_grid(truth, (N, H, W), torch.uint8, "image_confusion: truth")
+    C_ = int(num_classes)
+    if not 2 <= C_ <= 4:
+        raise ValueError(f"image_confusion: num_classes must lie in [2, 4], got {num_classes}")
+    if weight is not None:
+        assert weight.dtype in (torch.int32, torch.uint32), "image_confusion: weight must be a 32-bit integer tensor"
+        _scores_grid(weight, (H, W), weight.dtype, "image_confusion: weight")
+    cm, wcm, invalid = out if out is not None else (None, None, None)
+    if (wcm is not None) != (weight is not None) and out is not None:
+        raise ValueError("image_confusion: the wcm buffer goes with a weight: both or neither")
+    cm = _scores_out(cm, (N, C_, C_), pred.device, "image_confusion: cm")
+    wcm = _scores_out(wcm, (N, C_, C_), pred.device, "image_confusion: wcm") if weight is not None else None
+    invalid = _scores_out(invalid, (N,), pred.device, "image_confusion: invalid")
+    if N:
+        L.check(L.load().usseg_image_confusion(pred.data_ptr(), truth.data_ptr(), weight.data_ptr() if weight is not None else None, N, H, W, C_,
+                                               cm.data_ptr(), wcm.data_ptr() if wcm is not None else None, invalid.data_ptr(), _stream()), "image_confusion")
+    return cm, wcm, invalid
+
+
+def component_measure(labels, weight, xq, yq, cap, *, out=None):
+    """Size, position and extent of every component in fixed-point physical units (usseg_scores.h usseg_component_measure): ``labels`` the
+    int32 [N,H,W] of ``label_components``, ``weight`` / ``xq`` / ``yq`` the [H,W] tables of ``metrics.ScanGeometry`` on the GPU
+    -> int64 [N,cap,8], the fields of ``COMPONENT_MEASURE_FIELDS``; absent ids: zeros and the extents (SCORES_EMPTY_MIN, -1)."""
+    assert labels.dtype == torch.int32 and labels.is_contiguous() and labels.dim() == 3 and labels.is_cuda, "component_measure: contiguous int32 [N,H,W] labels on the GPU"
+    N, H, W = labels.shape
+    cap = int(cap)
+    if cap < 0:
+        raise ValueError(f"component_measure: cap must be >= 0, got {cap}")
+    assert weight.dtype in (torch.int32, torch.uint32), "component_measure: weight must be a 32-bit integer tensor"
+    _scores_grid(weight, (H, W), weight.dtype, "component_measure: weight")
+    _scores_grid(xq, (H, W), torch.int32, "component_measure: xq")
+    _scores_grid(yq, (H, W), torch.int32, "component_measure: yq")
+    out = _scores_out(out, (N, cap, 8), labels.device, "component_measure: out")
+    if N * cap:
+        L.check(L.load().usseg_component_measure(labels.data_ptr(), weight.data_ptr(), xq.data_ptr(), yq.data_ptr(), N, H, W, cap, out.data_ptr(), _stream()),
+                "component_measure")
+    return out
+
+
+def bootstrap_check_rows(rows_max_abs: int, U: int) -> None:
+    """The overflow rule of ``bootstrap_sums``: U draws of values up to ``rows_max_abs`` must stay inside int64, |v| <= 2^62 / U."""
+    if U > 0 and int(rows_max_abs) > (1 << 62) // int(U):
+        raise ValueError(f"bootstrap_sums: a value of magnitude {int(rows_max_abs)} times {U} draws can overflow int64 (|v| <= 2^62 / U)")
+
+
+def bootstrap_sums(rows, replicates, seed=0, *, out=None, check=True):
+    """Bootstrap replicates of the column sums of ``rows`` int64 [U,K] on the GPU (usseg_scores.h usseg_bootstrap_sums) -> int64 [R,K]; the
+    draws are the header's counter-based generator, so (seed, r, U) fix replicate r.  ``check`` reads the largest magnitude back once to
+    refuse rows with |v| > 2^62 / U; pass ``check=False`` (after ``bootstrap_check_rows`` on the host) inside a graph capture."""
+    assert rows.dtype == torch.int64 and rows.is_contiguous() and rows.dim() == 2 and rows.is_cuda, "bootstrap_sums: contiguous int64 [U,K] rows on the GPU"
+    U, K = rows.shape
+    R, seed = int(replicates), int(seed)
+    if not 1 <= K <= L.SCORES_BOOT_MAX_K:
+        raise ValueError(f"bootstrap_sums: K must lie in [1, {L.SCORES_BOOT_MAX_K}], got {K}")
+    if not 0 <= R <= L.SCORES_BOOT_MAX or U > L.SCORES_BOOT_MAX:
+        raise ValueError(f"bootstrap_sums: R and U must not exceed 2^20, got R = {R}, U = {U}")
+    if R > 0 and U == 0:
+        raise ValueError(f"bootstrap_sums: {R} replicates of an empty table")
+    if not 0 <= seed < 1 << 64:
+        raise ValueError(f"bootstrap_sums: the seed must fit 64 unsigned bits, got {seed}")
+    if check and U:
+        lo, hi = torch.aminmax(rows)
+        bootstrap_check_rows(max(-int(lo), int(hi)), U)
+    out = _scores_out(out, (R, K), rows.device, "bootstrap_sums: out")
+    if R and U:
+        L.check(L.load().usseg_bootstrap_sums(rows.data_ptr(), U, K, seed, R, out.data_ptr(), _stream()), "bootstrap_sums")
+    return out
+
+
 def overlap_boundary_loss_sums(probs, y_true, phi, acc, *, overlap, boundary, wb, HW, C_classes, ov_scale=1.0, label_smoothing=0.1, clip_eps=1e-7,
                                inv_global_batch=1.0):
     """``overlap_loss_sums`` plus the boundary term: ``phi`` = ``sdf_labels(y_true)``, ``boundary`` a ``boundary_loss(...)``, ``wb`` a DEVICE fp32
