@@ -23,6 +23,7 @@ import contextlib
 
 import torch
 
+from .distill import distill_line
 from .metrics import SegMetrics, dice_line
 from .schedules import PiecewiseConstantDecay
 
@@ -130,6 +131,9 @@ class Process(object):
         dice = dice_line(neuralnet, self.metrics)
         if dice is not None:                                    # only with loss="dice" / "tversky" / "dice_ce"
             print("dice per class = {}".format(dice))
+        terms = distill_line(neuralnet)
+        if terms is not None:                                   # only with loss="distill": the last validation batch's two terms
+            print("distill terms: {}".format(terms))
         extra = {"raw_loss": raw_loss} if averaged else {}
         if self.surface is not None:
             extra = dict(extra, **surface_summary(stats, self.surface))       # ONE read-back of the epoch's integers
@@ -153,7 +157,7 @@ class Process(object):
 
 
 def main(train_path, val_path, save_path=None, epochs=50, batch_size=32, num_classes=3, *, loss="cce", overlap=None, boundary=None, lovasz=None,
-         average=None, warp=None, warp_seed=0, topk=None):
+         average=None, warp=None, warp_seed=0, topk=None, teacher=None, distill=None):
     """MainNumpy.py:150-177 with the paths as arguments: ``VisionTransformer(32, img_size=(256, 80))`` over a ``Dataset_2.Dataset``,
     50 epochs, then a save if ``save_path`` is given.  ``loss``: the model's ``loss=`` ("cce", "my_loss_cat", "focal", "dice", "tversky",
     "dice_ce"); ``overlap``: the settings of the last three (``VisionTransformer(overlap=...)``), which also add a per-class Dice line to the test report;
@@ -162,12 +166,21 @@ def main(train_path, val_path, save_path=None, epochs=50, batch_size=32, num_cla
     ``ema:DECAY[:dynamic]`` / ``swa:START:PERIOD``): EMA / SWA weight averaging - the tests report the averaged model, and the save also writes
     ``<save_path>.avg``, a plain checkpoint of the averaged weights (``save_averaged``).  ``warp`` (a ``warp.warp_config`` dict or ``parse_warp``
     string; default off): elastic / affine warp of every training batch ahead of ``dataAug``, its draws from ``random.Random(warp_seed)``.
-    "topk" / "dice_topk" with their settings in ``topk`` (``VisionTransformer(topk=...)``: the top-k cross-entropy; the Dice line too)."""
+    "topk" / "dice_topk" with their settings in ``topk`` (``VisionTransformer(topk=...)``: the top-k cross-entropy; the Dice line too).
+    "distill" with ``teacher`` (a model, an ``Ensemble``, or checkpoint paths - a list or a comma-separated string; several make an ensemble) and
+    its settings in ``distill`` (``VisionTransformer(distill=...)``): knowledge distillation; the test report adds the hard and soft terms of
+    the last validation batch."""
     from .Dataset_2 import Dataset
     from .VisionTransformer import VisionTransformer, overlap_settings
     dataset = Dataset(train_path, val_path, num_classes, warp=warp, warp_seed=warp_seed)
+    kw = {} if topk is None else {"topk": topk}
+    if teacher is not None or distill is not None:
+        if isinstance(teacher, (str, list, tuple)):
+            from .distill import load_teacher
+            teacher = load_teacher(teacher, input_size, 10, "cuda", num_classes=num_classes)
+        kw.update(teacher=teacher, distill=distill)
     neuralnet = VisionTransformer(batch_size, img_size=input_size, num_classes=num_classes, loss=loss, overlap=overlap_settings(loss, overlap),
-                                  boundary=boundary, lovasz=lovasz, average=average_setting(average), **({} if topk is None else {"topk": topk}))
+                                  boundary=boundary, lovasz=lovasz, average=average_setting(average), **kw)
     print(len(neuralnet.visionModel.layers))
     process = Process(batch_size=batch_size, num_classes=num_classes)
     process.training(neuralnet=neuralnet, dataset=dataset, epochs=epochs)

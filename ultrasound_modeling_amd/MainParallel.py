@@ -51,6 +51,7 @@ import torch
 import torch.distributed as dist
 from . import knobs
 from .MainNumpy import averaging
+from .distill import distill_line
 from .metrics import dice_line
 
 
@@ -243,6 +244,9 @@ class Process(object):
         dice = dice_line(neuralnet, self.metrics)
         if dice is not None:                                    # only with loss="dice" / "tversky" / "dice_ce"
             self._print("dice per class = {}".format(dice))
+        terms = distill_line(neuralnet)
+        if terms is not None:                                   # only with loss="distill": this replica's last validation batch, one read-back an epoch
+            self._print("distill terms: {}".format(terms))
         self.history.append(dict(m, phase="test", epoch=epoch, loss=total_loss, **extra))
         self.metrics.reset_states()                                                              # :110-114
         return m["f1"]
@@ -300,7 +304,8 @@ class Process(object):
 
 
 def main(train_path, val_path, save_path=None, epochs=51, batch_size=64, use_vit=True, *, seed=0, schedule=False, capture_graph=True,
-         loss="cce", overlap=None, boundary=None, lovasz=None, average=None, warp=None, topk=None):
+         loss="cce", overlap=None, boundary=None, lovasz=None, average=None, warp=None, topk=None, teacher=None, distill=None,
+         teacher_use_vit=None, teacher_flip=False):
     """MainParallel.py:201-216 with the paths as arguments: ``VisionTransformer(batch_size=64)`` with the ViT bottleneck, 51 epochs,
     then rank 0 saves if ``save_path`` is given.  Every rank seeds ``random`` with ``seed``, so all draw the same augmentations.
     ``loss``: the model's ``loss=`` ("cce", "my_loss_cat", "focal"); every replica divides it by the global batch all the same.  The
@@ -312,6 +317,10 @@ def main(train_path, val_path, save_path=None, epochs=51, batch_size=64, use_vit
     The top-k cross-entropy ("topk", "dice_topk", settings in ``topk``): with scope "batch" a replica selects among the pixels of the images it holds,
     with scope "image" the selection is per image and does not depend on how the batch is split; every replica divides by the global batch all
     the same, and the Dice term of "dice_topk" is weighted like the overlap term.  The Dice line too.
+    Knowledge distillation ("distill", settings in ``distill``): ``teacher`` is a model, an ``Ensemble``, or checkpoint paths (a list or a
+    comma-separated string; several, or ``teacher_flip``, make an ensemble; ``teacher_use_vit`` says whether they have the ViT bottleneck,
+    default: as the student).  Every replica holds its own copy of the teacher, which sees the replica's slice of the batch; the loss is
+    divided by the global batch all the same, so the SUM of the replicas is the batch's loss.  The test report adds the two terms.
     ``average`` (a dict, or the ``--average`` string ``ema:DECAY[:dynamic]`` / ``swa:START:PERIOD``): EMA / SWA weight averaging; the update of
     every rank keeps the same average (no exchange is added), the tests report the averaged model and rank 0 also saves ``<save_path>.avg``.
     ``warp`` (a ``warp.warp_config`` dict or the ``--warp`` string; default off): elastic / affine warp of every training batch ahead of ``dataAug``;
@@ -326,9 +335,16 @@ def main(train_path, val_path, save_path=None, epochs=51, batch_size=64, use_vit
     torch.cuda.set_device(device)
     random.seed(seed)
     dataset = Dataset(train_path, val_path, batch_size, device=device, warp=warp, warp_seed=seed)
+    kw = {} if topk is None else {"topk": topk}
+    if teacher is not None or distill is not None:
+        if isinstance(teacher, (str, list, tuple)):
+            from .distill import load_teacher
+            teacher = load_teacher(teacher, (dataset.height, dataset.width), dataset.channel, device,
+                                   use_vit=use_vit if teacher_use_vit is None else teacher_use_vit, flip=teacher_flip)
+        kw.update(teacher=teacher, distill=distill)
     neuralnet = VisionTransformer(batch_size, img_size=(dataset.height, dataset.width), in_channels=dataset.channel, use_vit=use_vit,
                                   device=str(device), loss=loss, overlap=overlap_settings(loss, overlap), boundary=boundary, lovasz=lovasz,
-                                  average=average_setting(average), **({} if topk is None else {"topk": topk}))
+                                  average=average_setting(average), **kw)
     if rank == 0:
         print(len(neuralnet.visionModel.layers))
     process = Process(batch_size, schedule=schedule, capture_graph=capture_graph)
@@ -351,10 +367,17 @@ def _cli(argv=None):
     ap.add_argument("--seed", type=int, default=0, help="augmentation draws (the same on every rank)")
     ap.add_argument("--schedule", action="store_true", help="install the MainParallel.py:74-79 rate schedule once")
     ap.add_argument("--no-graph", action="store_true", help="run every step eagerly")
-    ap.add_argument("--loss", choices=("cce", "my_loss_cat", "focal", "dice", "tversky", "dice_ce") + ("lovasz", "lovasz_ce") + ("topk", "dice_topk"), default="cce",
+    ap.add_argument("--loss", choices=("cce", "my_loss_cat", "focal", "dice", "tversky", "dice_ce") + ("lovasz", "lovasz_ce") + ("topk", "dice_topk") + ("distill",), default="cce",
                     help="the model's loss: CategoricalCrossentropy (the reference's), its class-weighted my_loss_cat, the focal variant, or a "
                          "region-overlap loss (soft Dice, Tversky 0.3 / 0.7, Dice + CCE), or the Lovasz-softmax loss (alone, or CCE + it), or the "
-                         "top-k cross-entropy (alone, or soft Dice + it)")
+                         "top-k cross-entropy (alone, or soft Dice + it), or knowledge distillation from --teacher")
+    ap.add_argument("--teacher", default=None, metavar="CKPT[,CKPT...]",
+                    help="the teacher checkpoint(s) of --loss distill; more than one, or --teacher-flip, makes an ensemble whose mean is the teacher")
+    ap.add_argument("--teacher-use-vit", action="store_true", help="the teacher checkpoints have the ViT bottleneck (default: as the student)")
+    ap.add_argument("--teacher-flip", action="store_true", help="add the left-right mirrored view of every teacher member")
+    ap.add_argument("--distill-temperature", type=float, default=None, metavar="T", help="the softening temperature in [1/8, 8] (default 2)")
+    ap.add_argument("--distill-soft-weight", type=float, default=None, metavar="A", help="the weight of the soft term (default 0.5)")
+    ap.add_argument("--distill-hard-weight", type=float, default=None, metavar="B", help="the weight of the label term (default 0.5)")
     ap.add_argument("--topk-fraction", type=float, default=None, metavar="F",
                     help="the fraction of the pixels with the largest loss that --loss topk / dice_topk averages over, in (0, 1] (default 0.1)")
     ap.add_argument("--topk-scope", choices=("batch", "image"), default=None,
@@ -391,9 +414,23 @@ def _cli(argv=None):
             ops.topk_fraction_value(topk["fraction"])
         except ValueError as e:
             raise SystemExit(str(e))
+    dst = {k: v for k, v in (("temperature", a.distill_temperature), ("soft_weight", a.distill_soft_weight), ("hard_weight", a.distill_hard_weight))
+           if v is not None}
+    if (dst or a.teacher or a.teacher_use_vit or a.teacher_flip) and a.loss != "distill":
+        raise SystemExit("--teacher / --teacher-use-vit / --teacher-flip / --distill-* need --loss distill")
+    dkw = {}
+    if a.loss == "distill":
+        if not a.teacher:
+            raise SystemExit("--loss distill needs --teacher CKPT[,CKPT...]")
+        from .distill import distill_config
+        try:
+            distill_config(dst)
+        except ValueError as e:
+            raise SystemExit(str(e))
+        dkw = dict(teacher=a.teacher, distill=dst, teacher_use_vit=True if a.teacher_use_vit else None, teacher_flip=a.teacher_flip)
     main(a.train, a.val, a.save, epochs=a.epochs, batch_size=a.batch_size, use_vit=not a.no_vit, seed=a.seed, schedule=a.schedule,
          capture_graph=not a.no_graph, loss=a.loss, boundary=None if a.boundary_weight is None else {"weight": a.boundary_weight},
-         average=a.average, warp=a.warp, **({"topk": topk} if topk else {}))
+         average=a.average, warp=a.warp, **({"topk": topk} if topk else {}), **dkw)
     if dist.is_initialized():
         dist.barrier()
         dist.destroy_process_group()

@@ -21,6 +21,7 @@ import torch
 import torch.nn as nn
 
 from . import knobs
+from . import distill as _distill
 from . import ops
 from . import Decoder as _DEC
 from . import ResNest as _ENC
@@ -310,6 +311,7 @@ LOSSES = ("cce", "my_loss_cat", "focal")             # the reference's own: per-
 OVERLAP_LOSSES = ("dice", "tversky", "dice_ce")      # region-overlap losses (not in the reference): two launches behind the probabilities-only head
 LOVASZ_LOSSES = ("lovasz", "lovasz_ce")              # the Lovasz-softmax loss (not in the reference): a device sort of the pixel errors behind that head
 TOPK_LOSSES = ("topk", "dice_topk")                  # the top-k (hard-pixel) cross-entropy (not in the reference): a device radix select behind that head
+DISTILL_LOSSES = ("distill",)                        # knowledge distillation from a teacher (not in the reference): distill.Distill owns it, one launch behind that head
 
 
 def overlap_settings(loss, overlap):
@@ -420,7 +422,7 @@ class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
                  in_channels: int = 10, use_vit: bool = False, device: Optional[str] = None, seed: Optional[int] = 0,
                  transunet: bool = False, adamw: bool = False, loss: str = "cce", class_factor=None, focal_gamma=None,
                  overlap=None, alpha=None, beta=None, smooth=None, power=None, class_weight=None, ce_weight=None, ov_weight=None,
-                 boundary=None, lovasz=None, average=None, topk=None):
+                 boundary=None, lovasz=None, average=None, topk=None, distill=None, teacher=None):
         """``transunet=True`` builds the older self-contained copy of this model in TBI_TransUNet.py (BASELINE configs[3]):
         BatchNormalization where ResNest.py / Decoder.py use LayerNormalization (:304,426,465,472,503), conv_4 = 256 channels
         (:368), and the loss is CategoricalCrossentropy(label_smoothing=0.1) with the DEFAULT reduction - the mean over all
@@ -471,11 +473,31 @@ class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
         weight.  The fraction lives on the device: ``set_topk_fraction`` reaches a captured graph's next replay without a recapture, and a
         checkpoint keeps it.  ``class_factor``, ``focal_gamma``, ``boundary`` and ``lovasz`` do not combine with it.
 
+        Knowledge distillation (Hinton et al.; not in the reference; DESIGN.md section 8, usseg_distill.h): ``loss="distill"`` with
+        ``teacher=`` a ``VisionTransformer`` (TransUNet variant included) or an ``ensemble.Ensemble`` of them (``flip=True`` allowed) trains against
+        the teacher's softened probabilities as well as the labels: hard_weight * the default CCE + soft_weight * T^2 * KL(teacher_T || student_T).
+        ``distill`` (a dict; None takes every default) sets ``temperature`` (2.0), ``soft_weight`` (0.5) and ``hard_weight`` (0.5): ordinary
+        choices from the literature whose effect on this data nobody has measured.  Every step runs the teacher's label-free forward inside the
+        step (a captured graph holds it); the teacher is never trained.  The settings live on the device: ``set_distill`` reaches a captured
+        graph's next replay without a recapture, and a checkpoint keeps them.  ``class_factor``, ``focal_gamma``, ``overlap``, ``boundary``,
+        ``lovasz`` and ``topk`` do not combine with it.
+
         ``average`` (None: off) is ``flat.AdamClip(average=...)``: an EMA or SWA average of the weights kept by the update
         kernel; ``averaged_weights()`` computes with it, ``save_averaged(path)`` writes it as a plain checkpoint."""
         super().__init__()
-        if loss not in LOSSES + OVERLAP_LOSSES + LOVASZ_LOSSES + TOPK_LOSSES:
-            raise ValueError(f"loss must be one of {LOSSES + OVERLAP_LOSSES + LOVASZ_LOSSES + TOPK_LOSSES}, got {loss!r}")
+        if loss not in LOSSES + OVERLAP_LOSSES + LOVASZ_LOSSES + TOPK_LOSSES + DISTILL_LOSSES:
+            raise ValueError(f"loss must be one of {LOSSES + OVERLAP_LOSSES + LOVASZ_LOSSES + TOPK_LOSSES + DISTILL_LOSSES}, got {loss!r}")
+        if loss in DISTILL_LOSSES:
+            if teacher is None:
+                raise ValueError(f"loss='{loss}' needs teacher=: a VisionTransformer or an Ensemble of them")
+            given_other = dict(class_factor=class_factor, focal_gamma=focal_gamma, overlap=overlap, boundary=boundary, lovasz=lovasz, topk=topk, alpha=alpha,
+                               beta=beta, smooth=smooth, power=power, class_weight=class_weight, ce_weight=ce_weight, ov_weight=ov_weight)
+            other = [k for k, v in given_other.items() if v is not None]
+            if other:
+                raise ValueError(f"{other} do not combine with loss='{loss}' (its settings are distill={{...}})")
+            _distill.distill_config(distill)        # (refused before anything is built)
+        elif distill is not None or teacher is not None:
+            raise ValueError(f"distill= / teacher= only apply to loss in {DISTILL_LOSSES}, not to '{loss}'")
         if lovasz is not None and loss not in LOVASZ_LOSSES:
             raise ValueError(f"lovasz settings only apply to loss in {LOVASZ_LOSSES}")
         if loss in LOVASZ_LOSSES and (class_factor is not None or focal_gamma is not None):
@@ -540,6 +562,10 @@ class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
         if self._topk is not None:
             self._tkf = torch.full((1,), topk_f, dtype=torch.float32, device=self.device)     # read by the select kernels when they run
             self._ov_acc = None if self._topk_overlap is None else torch.zeros(ops.OVERLAP_ACC_FLOATS, dtype=torch.float32, device=self.device)
+        self._distill = None
+        if loss in DISTILL_LOSSES:              # the owner holds the teacher, the device settings and the accumulator: its [0] is this model's loss
+            self._distill = _distill.Distill(teacher, distill, self)
+            self._loss = self._distill.acc
         self._boundary, self._boundary_thr, self._wb = None, 0.5, None
         if bnd is not None:
             self._boundary, self._boundary_thr = bnd[1], bnd[2]
@@ -589,6 +615,21 @@ class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
             raise ValueError(f"set_topk_fraction: the model was built without loss in {TOPK_LOSSES}")
         self._tkf.fill_(ops.topk_fraction_value(f))
 
+    @property
+    def distill_settings(self):
+        """{"temperature", "soft_weight", "hard_weight"} the next step uses, read from the device (synchronises); None without ``loss="distill"``."""
+        return None if self._distill is None else self._distill.get()
+
+    def set_distill(self, temperature=None, soft_weight=None, hard_weight=None):
+        """From the next step on, eager or replayed: the kernel reads the device table, so a captured graph needs no recapture."""
+        if self._distill is None:
+            raise ValueError(f"set_distill: the model was built without loss in {DISTILL_LOSSES}")
+        self._distill.set(temperature=temperature, soft_weight=soft_weight, hard_weight=hard_weight)
+
+    def distill_terms(self):
+        """{"hard", "soft"}: the two weighted terms of the last step's loss (synchronises); None without ``loss="distill"``."""
+        return None if self._distill is None else self._distill.terms()
+
     # ------------------------------------------------------------------ parameters in / out (Keras names)
     @property
     def visionModel(self):
@@ -603,6 +644,8 @@ class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
             d["__boundary_weight__"] = self._wb.detach().clone()
         if self._topk is not None:
             d["__topk_fraction__"] = self._tkf.detach().clone()
+        if self._distill is not None:
+            d["__distill__"] = self._distill.settings.detach().clone()
         torch.save(d, path)
 
     def load(self, path):
@@ -614,6 +657,9 @@ class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
         tkf = d.pop("__topk_fraction__", None)       # (likewise: a checkpoint without it leaves the constructor's fraction)
         if tkf is not None and self._topk is not None:
             self._tkf.copy_(tkf.to(self._tkf.device))
+        dst = d.pop("__distill__", None)             # (likewise: a checkpoint without it leaves the constructor's settings)
+        if dst is not None and self._distill is not None:
+            self._distill.load_table(dst)
         self.load_params(d)
 
     @property
@@ -695,6 +741,8 @@ class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
             return self._forward_lovasz(xh, logits, y, probs, dlogits, scale)
         if self._topk is not None:
             return self._forward_topk(xh, logits, y, probs, dlogits, scale)
+        if self._distill is not None:
+            return self._distill_forward(x, xh, logits, y, probs, dlogits, scale)
         if fused:       # head conv + softmax + loss in one launch (:142, :205, :225-229); falls back to the three launches if it has no kernel
             kw = {} if self._class_loss is None else {"class_loss": self._class_loss}       # (no keyword: today's call of today's symbol)
             if self.decoder._quad.forward_loss(xh, y, probs, self._loss, dlogits, label_smoothing=0.1, clip_eps=1e-7, inv_global_batch=scale, **kw):
@@ -787,6 +835,13 @@ class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
             ops.topk_loss_bwd(probs, y, ws, self._loss, dlogits, quad_w=self.decoder.quad_w, **kw)
         return probs, dlogits
 
+    def _distill_forward(self, x, xh, logits, y, probs, dlogits, scale):
+        """Knowledge distillation: today's probabilities-only head launch(es), then the owner's part - the teacher's label-free forward on this
+        stream and the one launch that writes the scalar loss into ``self._loss`` and, for a training step, ``dlogits``."""
+        self._head_probs(xh, logits, probs)
+        self._distill.forward(x, y, probs, dlogits, scale=scale, quad_w=self.decoder.quad_w)
+        return probs, dlogits
+
     def _predict_body(self, x):
         """The forward of ``_forward_loss`` without labels: the encoder with ``stash=False``, the fused attention, the decoder, and the head
         softmax with no loss.  No loss buffer, gradient, optimiser state or BatchNorm statistic is read or written."""
@@ -809,9 +864,14 @@ class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
     def compute_loss(self, y_true, y_pred):
         """VisionTransformer.py:225-227: ``self.loss`` - CategoricalCrossentropy(label_smoothing=0.1, reduction NONE) by default, the
         class loss under ``loss="my_loss_cat"`` / ``"focal"`` - on PROBABILITIES, summed and divided by the global batch size
-        -> scalar.  (train_step/step use the fused softmax+loss kernel instead.)"""
+        -> scalar.  (train_step/step use the fused softmax+loss kernel instead.)  Under ``loss="distill"`` there is no input here that could show
+        a teacher: the result is the HARD term alone, weighted by ``hard_weight`` (``step(x, y)`` runs the teacher and returns the full loss)."""
         y_true, y_pred = self._prep_y(y_true), self._prep_y(y_pred)
         H, W = y_pred.shape[1], y_pred.shape[2]
+        if self._distill is not None:       # the teacher's place is taken by y_pred itself: q == p, whose soft term is exactly zero
+            acc = torch.zeros(ops.DISTILL_ACC_FLOATS, dtype=torch.float32, device=self.device)
+            self._distill.loss_into(acc, y_pred, y_true, y_pred, None, scale=1.0 / float(self.batch_size))
+            return acc[4].clone()
         if self._overlap is not None:       # the overlap loss of THESE tensors, weighted as a step weights a batch of their size
             acc = torch.zeros(ops.OVERLAP_ACC_FLOATS, dtype=torch.float32, device=self.device)
             kw = dict(overlap=self._overlap, HW=H * W, C_classes=y_pred.shape[-1], label_smoothing=0.1, clip_eps=1e-7,

@@ -1,5 +1,6 @@
 """ctypes binding of libusseg_hip.so, generated at import from the C ABI declared in include/usseg.h and, for the evaluator's score kernels,
-include/usseg_scores.h (_abi.py reads both; ``ABI`` is the first header's, ``SCORES_ABI`` the second's).
+include/usseg_scores.h and, for the distillation loss, include/usseg_distill.h (_abi.py reads all three; ``ABI`` is the first header's,
+``SCORES_ABI`` the second's, ``DISTILL_ABI`` the third's).
 
 There is NO fallback: if the header or the shared library is missing or a call fails, an exception is raised.
 Nothing here imports the oracle.
@@ -16,6 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = knobs.get("USSEG_LIB") or os.path.join(_HERE, "libusseg_hip.so")   # USSEG_LIB: a diagnostic build of the SAME sources (tools/diag_norm_variants.sh)
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "usseg.h")
 SCORES_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "usseg_scores.h")
+DISTILL_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "usseg_distill.h")
 
 c_i32, c_i64, c_f32, c_vp = C.c_int32, C.c_int64, C.c_float, C.c_void_p
 
@@ -48,6 +50,12 @@ SCORES_SYMBOLS = tuple(SCORES_ABI.protos)
 SCORES_MEASURE_FIELDS, SCORES_EMPTY_MIN = SCORES_ABI.consts["USSEG_SCORES_MEASURE_FIELDS"], SCORES_ABI.consts["USSEG_SCORES_EMPTY_MIN"]
 SCORES_BOOT_MAX_K, SCORES_BOOT_MAX = SCORES_ABI.consts["USSEG_SCORES_BOOT_MAX_K"], SCORES_ABI.consts["USSEG_SCORES_BOOT_MAX"]
 
+# the third header (csrc/distill.hip): likewise its own Abi, with its own struct and constants
+DISTILL_ABI = read_header(DISTILL_HEADER_PATH)
+DISTILL_SYMBOLS = tuple(DISTILL_ABI.protos)
+DistillDesc = DISTILL_ABI.structs["UssegDistillDesc"]
+DISTILL_ACC_FLOATS, DISTILL_SETTINGS = DISTILL_ABI.consts["USSEG_DISTILL_ACC_FLOATS"], DISTILL_ABI.consts["USSEG_DISTILL_SETTINGS"]
+
 _lib = None
 
 
@@ -68,7 +76,7 @@ def load() -> C.CDLL:
     if not os.path.exists(LIB_PATH):
         raise UssegError(f"{LIB_PATH} not found: build the HIP extension first (python -c 'import __graft_entry__ as g; "
                          f"g.build()'). There is no CPU fallback.")
-    _lib = bind(bind(C.CDLL(LIB_PATH)), SCORES_SYMBOLS, SCORES_ABI.protos)
+    _lib = bind(bind(bind(C.CDLL(LIB_PATH)), SCORES_SYMBOLS, SCORES_ABI.protos), DISTILL_SYMBOLS, DISTILL_ABI.protos)
     return _lib
 
 

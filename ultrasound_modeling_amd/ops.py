@@ -1790,6 +1790,29 @@ def topk_loss_bwd(probs, y_true, ws, acc, dlogits, *, topk, HW, C_classes, overl
                                          _ptr(overlap_acc), dlogits.data_ptr(), _stream()), "topk_loss_bwd")
 
 
+# ------------------------------------------------------------------------------------------------ knowledge distillation (usseg_distill.h)
+DISTILL_ACC_FLOATS = L.DISTILL_ACC_FLOATS   # [0] loss, [1] ticket, [2] sum hard, [3] sum soft, [4] weighted hard term, [5] weighted soft term, partials
+DISTILL_SETTINGS = L.DISTILL_SETTINGS       # the device table: [0] temperature, [1] soft_weight, [2] hard_weight, [3] reserved
+
+
+def distill_grid(M: int) -> int:
+    """Workgroups of the distillation launch for M pixels (usseg_distill.h: the grid rule the accumulator's size follows from)."""
+    return int(L.load().usseg_distill_grid(int(M)))
+
+
+def distill_loss(probs, y_true, q, settings, acc, dlogits=None, *, HW, C_classes, label_smoothing=0.1, clip_eps=1e-7, inv_global_batch=1.0, quad_w=0):
+    """The distillation loss of usseg_distill.h in ONE launch: ``probs`` (the student's), ``y_true`` and ``q`` (the teacher's probabilities) fp32
+    [..., C]; ``settings`` a DEVICE fp32 tensor [DISTILL_SETTINGS] = (temperature, soft_weight, hard_weight, 0), read when the kernel runs;
+    ``acc`` fp32 [DISTILL_ACC_FLOATS], zeroed once at allocation: the scalar loss in [0], the hard and soft pixel sums in [2], [3], the two
+    weighted terms in [4], [5], all bitwise reproducible.  ``dlogits`` (bf16 [..., 8], or [B,H/2,W/2,16] with ``quad_w`` = the full-resolution
+    width) receives d loss / d logits, or None for the loss alone."""
+    assert all(t.dtype == torch.float32 and t.is_contiguous() for t in (probs, y_true, q)) and probs.shape == y_true.shape == q.shape
+    assert settings.dtype == torch.float32 and settings.numel() >= DISTILL_SETTINGS and settings.device == probs.device and acc.dtype == torch.float32
+    d = L.DistillDesc(probs.numel() // C_classes, HW, C_classes, 16 if quad_w else 8, quad_w, label_smoothing, clip_eps, inv_global_batch)
+    L.check(L.load().usseg_distill_loss(C.byref(d), probs.data_ptr(), y_true.data_ptr(), q.data_ptr(), settings.data_ptr(), acc.data_ptr(), acc.numel(),
+                                        _ptr(dlogits), _stream()), "distill_loss")
+
+
 def quad_bias_expand(bias, C_logical, out):
     L.check(L.load().usseg_quad_bias_expand(bias.data_ptr(), C_logical, out.numel() // 4, out.data_ptr(), _stream()), "quad_bias_expand")
 
