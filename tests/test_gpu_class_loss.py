@@ -254,13 +254,13 @@ def _batches(n, B, H, W):
 
 
 def _model_form(net):
-    cl = net._class_loss
+    cl = net._seg_loss.class_loss
     return list(cl.w)[:net.num_classes], cl.gamma, cl.factor
 
 
 def test_the_default_loss_did_not_move():
     a, b = _arch_b(), _arch_b(loss="cce")
-    assert a._class_loss is None and b._class_loss is None and a.loss_name == b.loss_name == "cce"
+    assert a._seg_loss.class_loss is None and b._seg_loss.class_loss is None and a.loss_name == b.loss_name == "cce"
     assert a.alpha == 2 and a.class_factor == [0.06329, 0.027567, 0.90914]
     for x, y in _batches(2, 2, 64, 64):
         la, pa = a.train_step(x, y.float())

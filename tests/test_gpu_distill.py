@@ -334,13 +334,14 @@ def test_graph_replay_equals_eager_and_follows_the_settings(make):
 
 def test_the_default_loss_does_not_move_and_save_load_keep_the_settings(tmp_path):
     from ultrasound_modeling_amd import ops
+    from ultrasound_modeling_amd.distill import Distill
     import test_gpu_overlap_loss as OL
     a = OL._arch_b(loss="cce")
     d = _student("archB", _teacher("archB", 5))
     bs = _batches(2)
     d.train_step(bs[0][0], bs[0][1].float())
     b = OL._arch_b()
-    assert a._distill is None and b._distill is None and b.distill_settings is None and b.distill_terms() is None
+    assert not isinstance(a._seg_loss, Distill) and not isinstance(b._seg_loss, Distill) and b.distill_settings is None and b.distill_terms() is None
     assert a._loss.numel() == b._loss.numel() == ops.ACC_FLOATS
     with pytest.raises(ValueError):
         b.set_distill(temperature=2.0)
@@ -462,6 +463,7 @@ def _simulate(tmp):
     """``test_gpu_mainparallel._simulate`` with both instances built with ``loss="distill"`` and a teacher of their own."""
     import test_gpu_mainparallel as MP
     import ultrasound_modeling_amd.VisionTransformer as VT
+    from ultrasound_modeling_amd.distill import Distill
     orig, made = VT.VisionTransformer, []
 
     def make(*a, **kw):
@@ -473,7 +475,7 @@ def _simulate(tmp):
         return made[-1]
     VT.VisionTransformer = make
     want, history = MP._simulate(np.load(os.path.join(tmp, "train.npy")), np.load(os.path.join(tmp, "val.npy")))
-    assert len(made) == 2 and all(n.loss_name == "distill" and n._distill is not None for n in made), "the simulation did not train with distill"
+    assert len(made) == 2 and all(n.loss_name == "distill" and isinstance(n._seg_loss, Distill) for n in made), "the simulation did not train with distill"
     torch.save({"want": want, "history": history}, os.path.join(tmp, "sim.pt"))
 
 

@@ -260,7 +260,7 @@ def _batches(n, B, H, W):
 
 
 def _model_cfg(net):
-    ol = net._overlap
+    ol = net.overlap_loss
     return dict(w=list(ol.w)[:net.num_classes], alpha=ol.alpha, beta=ol.beta, smooth=ol.smooth, power=ol.power, ov_weight=ol.ov_weight, ce_weight=ol.ce_weight)
 
 
@@ -319,7 +319,7 @@ def test_the_default_loss_does_not_move_across_the_new_code():
     d.train_step(bs[0][0], bs[0][1].float())
     b = _arch_b()
     from ultrasound_modeling_amd import ops
-    assert a._overlap is None and b._overlap is None and a._loss.numel() == b._loss.numel() == ops.ACC_FLOATS
+    assert a.overlap_loss is None and b.overlap_loss is None and a._loss.numel() == b._loss.numel() == ops.ACC_FLOATS
     for x, y in bs:
         la, pa = a.train_step(x, y.float())
         lb, pb = b.train_step(x, y.float())

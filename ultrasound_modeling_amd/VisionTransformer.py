@@ -14,21 +14,21 @@ actually build; its variables carry the reference's attribute paths (``transform
 from __future__ import annotations
 
 import contextlib
-import math
 from typing import Optional
 
 import torch
 import torch.nn as nn
 
 from . import knobs
-from . import distill as _distill
 from . import ops
+from . import seg_loss
 from . import Decoder as _DEC
 from . import ResNest as _ENC
 from .Decoder import DecoderBlock, DecoderCup
 from .flat import AdamClip, FlatParams
 from .layers import BatchNormalization, Conv2D, LayerNormalization, _Workspace
 from .ResNest import ResNest, cardinal, residual_S
+from .seg_loss import LOSSES, OVERLAP_LOSSES, LOVASZ_LOSSES, TOPK_LOSSES, DISTILL_LOSSES, overlap_settings, overlap_config, lovasz_config, topk_config, boundary_config, _boundary_weight  # noqa: F401  (imported from here by the drivers and the tests)
 
 _FUSED_HEAD = knobs.get("USSEG_FUSED_HEAD")      # quad-form head conv + softmax + loss as one launch (csrc/attn_loss_optim.hip)
 from .ops import BF16, roundup
@@ -307,116 +307,6 @@ class Transformer(nn.Module):
         self.embeddings.backward(d_hidden, d_feats)
 
 
-LOSSES = ("cce", "my_loss_cat", "focal")             # the reference's own: per-pixel losses inside the fused head launch
-OVERLAP_LOSSES = ("dice", "tversky", "dice_ce")      # region-overlap losses (not in the reference): two launches behind the probabilities-only head
-LOVASZ_LOSSES = ("lovasz", "lovasz_ce")              # the Lovasz-softmax loss (not in the reference): a device sort of the pixel errors behind that head
-TOPK_LOSSES = ("topk", "dice_topk")                  # the top-k (hard-pixel) cross-entropy (not in the reference): a device radix select behind that head
-DISTILL_LOSSES = ("distill",)                        # knowledge distillation from a teacher (not in the reference): distill.Distill owns it, one launch behind that head
-
-
-def overlap_settings(loss, overlap):
-    """What the drivers hand the constructor: for a region-overlap loss with no settings given, the empty dict (every default)."""
-    return {} if overlap is None and loss in OVERLAP_LOSSES else overlap
-
-
-def overlap_config(loss, num_classes, overlap):
-    """``loss`` in OVERLAP_LOSSES and the ``overlap`` settings (dict or None) -> ``ops.overlap_loss(...)``; ValueError for a bad or
-    contradictory combination."""
-    cfg = dict(overlap or {})
-    unknown = [k for k in cfg if k not in ops.OVERLAP_KEYS]
-    if unknown:
-        raise ValueError(f"overlap: unknown settings {unknown}; known: {ops.OVERLAP_KEYS}")
-    if loss != "tversky" and ("alpha" in cfg or "beta" in cfg):
-        raise ValueError(f"overlap: alpha / beta belong to loss='tversky'; '{loss}' is alpha = beta = 0.5")
-    if loss != "dice_ce" and cfg.get("ce_weight", 0.0) != 0.0:
-        raise ValueError(f"overlap: a cross-entropy term needs loss='dice_ce', not '{loss}'")
-    if loss == "dice_ce" and cfg.get("ce_weight", 1.0) == 0.0:
-        raise ValueError("overlap: loss='dice_ce' with ce_weight = 0 is loss='dice'")
-    w = cfg.get("class_weight")
-    w = [1.0 / num_classes] * num_classes if w is None else [float(v) for v in w]
-    if len(w) != num_classes:
-        raise ValueError(f"overlap: class_weight has {len(w)} entries for {num_classes} classes")
-    a, b = (0.3, 0.7) if loss == "tversky" else (0.5, 0.5)
-    return ops.overlap_loss(w, cfg.get("alpha", a), cfg.get("beta", b), cfg.get("smooth", 1.0), cfg.get("power", 1.0), cfg.get("ov_weight", 1.0),
-                            cfg.get("ce_weight", 1.0 if loss == "dice_ce" else 0.0))
-
-
-def lovasz_config(loss, num_classes, lovasz):
-    """``loss`` in LOVASZ_LOSSES and the ``lovasz`` settings (dict or None: every default) -> ``ops.lovasz_loss(...)``; ValueError for a bad or
-    contradictory combination."""
-    if lovasz is not None and not isinstance(lovasz, dict):
-        raise ValueError(f"lovasz: a dict of {ops.LOVASZ_KEYS} (None or {{}} for the defaults), got {type(lovasz).__name__}")
-    cfg = dict(lovasz or {})
-    unknown = [k for k in cfg if k not in ops.LOVASZ_KEYS]
-    if unknown:
-        raise ValueError(f"lovasz: unknown settings {unknown}; known: {ops.LOVASZ_KEYS}")
-    if loss != "lovasz_ce" and cfg.get("ce_weight", 0.0) != 0.0:
-        raise ValueError(f"lovasz: a cross-entropy term needs loss='lovasz_ce', not '{loss}'")
-    if loss == "lovasz_ce" and cfg.get("ce_weight", 1.0) == 0.0:
-        raise ValueError("lovasz: loss='lovasz_ce' with ce_weight = 0 is loss='lovasz'")
-    w = cfg.get("class_weight")
-    w = [1.0] * num_classes if w is None else [float(v) for v in w]
-    if len(w) != num_classes:
-        raise ValueError(f"lovasz: class_weight has {len(w)} entries for {num_classes} classes")
-    return ops.lovasz_loss(w, cfg.get("lv_weight", 1.0), cfg.get("ce_weight", 1.0 if loss == "lovasz_ce" else 0.0), cfg.get("threshold", 0.5),
-                           cfg.get("classes", "present"))
-
-
-def topk_config(loss, num_classes, topk, *, overlap=None, class_factor=None, focal_gamma=None, boundary=None, lovasz=None):
-    """``loss`` in TOPK_LOSSES and the ``topk`` settings (dict or None: every default) -> (``ops.topk_loss(...)``, the fraction, the Dice term's
-    ``ops.overlap_loss(...)`` for "dice_topk" or None); ValueError for a bad or contradictory combination."""
-    if loss not in TOPK_LOSSES:
-        raise ValueError(f"topk settings only apply to loss in {TOPK_LOSSES}")
-    if topk is not None and not isinstance(topk, dict):
-        raise ValueError(f"topk: a dict of {ops.TOPK_KEYS} (None or {{}} for the defaults), got {type(topk).__name__}")
-    cfg = dict(topk or {})
-    unknown = [k for k in cfg if k not in ops.TOPK_KEYS]
-    if unknown:
-        raise ValueError(f"topk: unknown settings {unknown}; known: {ops.TOPK_KEYS}")
-    if class_factor is not None or focal_gamma is not None:
-        raise ValueError(f"class_factor / focal_gamma do not apply to loss='{loss}'")
-    if boundary is not None or lovasz is not None:
-        raise ValueError(f"boundary / lovasz settings do not combine with loss='{loss}'")
-    ov = None
-    if loss == "topk":
-        if overlap is not None:
-            raise ValueError("overlap settings need loss='dice_topk', not 'topk'")
-    else:
-        if dict(overlap or {}).get("ce_weight", 0.0) != 0.0:
-            raise ValueError("overlap: the cross-entropy of loss='dice_topk' is its top-k term; ce_weight must be 0")
-        ov = overlap_config("dice", num_classes, overlap)
-    fraction = ops.topk_fraction_value(cfg.get("fraction", 0.1))
-    return ops.topk_loss(cfg.get("tk_weight", 1.0), cfg.get("scope", "batch")), fraction, ov
-
-
-def boundary_config(loss, num_classes, boundary):
-    """The ``boundary`` settings (dict) of a model with ``loss`` in OVERLAP_LOSSES -> (weight, ``ops.boundary_loss(...)``, threshold); ValueError for
-    any other loss, an unknown key, a negative or non-finite weight, a wrong-length ``class_weight`` or a NaN threshold."""
-    if loss not in OVERLAP_LOSSES:
-        raise ValueError(f"boundary: the boundary term is an add-on to loss in {OVERLAP_LOSSES}, not to '{loss}'")
-    if not isinstance(boundary, dict):
-        raise ValueError(f"boundary: a dict of {ops.BOUNDARY_KEYS} ({{}} for the defaults), got {type(boundary).__name__}")
-    unknown = [k for k in boundary if k not in ops.BOUNDARY_KEYS]
-    if unknown:
-        raise ValueError(f"boundary: unknown settings {unknown}; known: {ops.BOUNDARY_KEYS}")
-    weight = _boundary_weight(boundary.get("weight", 0.01))
-    u = boundary.get("class_weight")
-    u = [0.0] + [1.0] * (num_classes - 1) if u is None else [float(v) for v in u]
-    if len(u) != num_classes:
-        raise ValueError(f"boundary: class_weight has {len(u)} entries for {num_classes} classes")
-    thr = float(boundary.get("threshold", 0.5))
-    if math.isnan(thr):
-        raise ValueError("boundary: threshold is NaN")
-    return weight, ops.boundary_loss(u), thr
-
-
-def _boundary_weight(w):
-    w = float(w)
-    if not (math.isfinite(w) and w >= 0.0):
-        raise ValueError(f"boundary: weight must be finite and >= 0, got {w}")
-    return w
-
-
 class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
     def __init__(self, batch_size, img_size=(256, 80), num_classes=3, learning_rate=1e-3, weight_decay=1e-4, *,
                  in_channels: int = 10, use_vit: bool = False, device: Optional[str] = None, seed: Optional[int] = 0,
@@ -432,7 +322,7 @@ class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
         the decoupled weight decay of tfa.optimizers.AdamW, the optimiser the reference has commented out (:203); by default it stays
         unused, as in the reference.
 
-        ``loss`` is the reference's ``self.loss`` (:205-207), fixed at construction (a captured graph holds its numbers):
+        ``loss`` is the reference's ``self.loss`` (:205-207), fixed at construction (a captured graph holds its numbers; seg_loss.py has its owner):
           * ``"cce"`` (default): CategoricalCrossentropy(label_smoothing=0.1), as the reference compiles it;
           * ``"my_loss_cat"``: the method the reference keeps one commented line away (:207, :259-280) as executed - factor 3,
             ``self.class_factor`` per class, clipped probabilities NOT divided by their class sum;
@@ -485,59 +375,9 @@ class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
         ``average`` (None: off) is ``flat.AdamClip(average=...)``: an EMA or SWA average of the weights kept by the update
         kernel; ``averaged_weights()`` computes with it, ``save_averaged(path)`` writes it as a plain checkpoint."""
         super().__init__()
-        if loss not in LOSSES + OVERLAP_LOSSES + LOVASZ_LOSSES + TOPK_LOSSES + DISTILL_LOSSES:
-            raise ValueError(f"loss must be one of {LOSSES + OVERLAP_LOSSES + LOVASZ_LOSSES + TOPK_LOSSES + DISTILL_LOSSES}, got {loss!r}")
-        if loss in DISTILL_LOSSES:
-            if teacher is None:
-                raise ValueError(f"loss='{loss}' needs teacher=: a VisionTransformer or an Ensemble of them")
-            given_other = dict(class_factor=class_factor, focal_gamma=focal_gamma, overlap=overlap, boundary=boundary, lovasz=lovasz, topk=topk, alpha=alpha,
-                               beta=beta, smooth=smooth, power=power, class_weight=class_weight, ce_weight=ce_weight, ov_weight=ov_weight)
-            other = [k for k, v in given_other.items() if v is not None]
-            if other:
-                raise ValueError(f"{other} do not combine with loss='{loss}' (its settings are distill={{...}})")
-            _distill.distill_config(distill)        # (refused before anything is built)
-        elif distill is not None or teacher is not None:
-            raise ValueError(f"distill= / teacher= only apply to loss in {DISTILL_LOSSES}, not to '{loss}'")
-        if lovasz is not None and loss not in LOVASZ_LOSSES:
-            raise ValueError(f"lovasz settings only apply to loss in {LOVASZ_LOSSES}")
-        if loss in LOVASZ_LOSSES and (class_factor is not None or focal_gamma is not None):
-            raise ValueError(f"class_factor / focal_gamma do not apply to loss='{loss}' (its weights are lovasz['class_weight'])")
-        self._lovasz = lovasz_config(loss, num_classes, lovasz) if loss in LOVASZ_LOSSES else None
-        self._lovasz_bufs = {}                  # pixels of a call -> (g, counts, workspace): allocated once per model and batch shape
-        given = dict(alpha=alpha, beta=beta, smooth=smooth, power=power, class_weight=class_weight, ce_weight=ce_weight, ov_weight=ov_weight)
-        overlap_kw = {k: v for k, v in given.items() if v is not None}      # (the keyword ``alpha`` is Tversky's; ``self.alpha`` below is the focal exponent, :208)
-        if overlap is not None and overlap_kw:
-            raise ValueError("give the overlap settings as overlap={...} or as keywords, not both")
-        overlap = overlap if overlap is not None else (overlap_kw or None)
-        self._topk, self._topk_overlap, topk_f = None, None, None
-        if topk is not None or loss in TOPK_LOSSES:
-            self._topk, topk_f, self._topk_overlap = topk_config(loss, num_classes, topk, overlap=overlap, class_factor=class_factor,
-                                                                 focal_gamma=focal_gamma, boundary=boundary, lovasz=lovasz)
-            overlap = None                      # (the Dice term of "dice_topk" is held apart: the overlap pair itself does not run the step)
-            self._topk_bufs = {}                # (pixels of a call, pixels of an image) -> workspace: allocated once per model and batch shape
-        if overlap is not None and loss not in OVERLAP_LOSSES:
-            raise ValueError(f"overlap settings only apply to loss in {OVERLAP_LOSSES}")
-        if loss in OVERLAP_LOSSES and overlap is None:
-            raise ValueError(f"loss={loss!r} needs its settings: overlap={{}} for the defaults, or any of {ops.OVERLAP_KEYS}")
-        if loss in OVERLAP_LOSSES and (class_factor is not None or focal_gamma is not None):
-            raise ValueError(f"class_factor / focal_gamma do not apply to loss='{loss}' (its weights are overlap['class_weight'])")
-        self._overlap = overlap_config(loss, num_classes, overlap) if loss in OVERLAP_LOSSES else None
-        bnd = None if boundary is None else boundary_config(loss, num_classes, boundary)
-        if focal_gamma is not None and loss != "focal":
-            raise ValueError("focal_gamma only applies to loss='focal'")
-        self.alpha = 2                                                                  # :208
-        self.class_factor = [0.06329, 0.027567, 0.90914] if class_factor is None else [float(v) for v in class_factor]   # :209
-        if (loss == "my_loss_cat" or class_factor is not None) and len(self.class_factor) != num_classes:
-            raise ValueError(f"class_factor has {len(self.class_factor)} entries for {num_classes} classes")
-        self.loss_name = loss
-        if loss == "my_loss_cat":
-            self._class_loss = ops.class_loss(self.class_factor, 0.0, 3.0)              # :270
-        elif loss == "focal":
-            gamma = float(self.alpha if focal_gamma is None else focal_gamma)
-            weighted = class_factor is not None
-            self._class_loss = ops.class_loss(self.class_factor if weighted else [1.0] * num_classes, gamma, 3.0 if weighted else 1.0)   # :272-273,277
-        else:
-            self._class_loss = None
+        own = seg_loss.resolve(loss, num_classes, class_factor=class_factor, focal_gamma=focal_gamma, overlap=overlap, alpha=alpha, beta=beta, smooth=smooth, power=power,
+                               class_weight=class_weight, ce_weight=ce_weight, ov_weight=ov_weight, boundary=boundary, lovasz=lovasz, topk=topk, distill=distill, teacher=teacher)
+        self._seg_loss, self.loss_name, self.alpha, self.class_factor = own, loss, own.alpha, own.class_factor      # (every refusal comes first; seg_loss.py has the families)
         if seed is not None:
             torch.manual_seed(seed)
         assert img_size[0] % 16 == 0 and img_size[1] % 16 == 0, "H and W must be multiples of 16 (four 2x2 poolings)"
@@ -557,78 +397,34 @@ class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
         self.flat = FlatParams(self, self.device)
         self.optimizer = AdamClip(self.flat, lr=learning_rate, clip_norm=1.0,          # :204,:244
                                   weight_decay=weight_decay if adamw else None, average=average)
-        self._loss = torch.zeros(ops.ACC_FLOATS if self._overlap is None and self._lovasz is None and self._topk is None else ops.OVERLAP_ACC_FLOATS,
-                                 dtype=torch.float32, device=self.device)                    # [0] = the scalar loss
-        if self._topk is not None:
-            self._tkf = torch.full((1,), topk_f, dtype=torch.float32, device=self.device)     # read by the select kernels when they run
-            self._ov_acc = None if self._topk_overlap is None else torch.zeros(ops.OVERLAP_ACC_FLOATS, dtype=torch.float32, device=self.device)
-        self._distill = None
-        if loss in DISTILL_LOSSES:              # the owner holds the teacher, the device settings and the accumulator: its [0] is this model's loss
-            self._distill = _distill.Distill(teacher, distill, self)
-            self._loss = self._distill.acc
-        self._boundary, self._boundary_thr, self._wb = None, 0.5, None
-        if bnd is not None:
-            self._boundary, self._boundary_thr = bnd[1], bnd[2]
-            self._wb = torch.full((1,), bnd[0], dtype=torch.float32, device=self.device)      # read by the sums kernel when it runs
+        own.place(self)                         # the device settings, the accumulator and, for "distill", the checks of the teacher
+        self._loss = own.acc                    # [0] = the scalar loss; this tensor for the model's life (a captured graph holds it)
         self.grad_sync = None                   # set by the data-parallel wrapper: callable(flat_grad)
         self._graph = None
 
-    @property
-    def boundary_loss(self):
-        """The ``UssegBoundaryLoss`` of a model built with ``boundary=``, or None."""
-        return self._boundary
-
-    @property
-    def boundary_weight(self):
-        """The boundary weight the next step uses, read from the device (synchronises); None without a boundary term."""
-        return None if self._wb is None else float(self._wb.item())
+    overlap_loss = property(lambda self: self._seg_loss.overlap, doc='The ``UssegOverlapLoss`` this model trains with (``loss="dice"`` / ``"tversky"`` / ``"dice_ce"``), or None for a per-pixel loss.')
+    lovasz_loss = property(lambda self: self._seg_loss.lovasz, doc='The ``UssegLovaszLoss`` this model trains with (``loss="lovasz"`` / ``"lovasz_ce"``), or None.')
+    topk_loss = property(lambda self: self._seg_loss.topk, doc='The ``UssegTopkLoss`` this model trains with (``loss="topk"`` / ``"dice_topk"``), or None.')
+    boundary_loss = property(lambda self: self._seg_loss.boundary, doc="The ``UssegBoundaryLoss`` of a model built with ``boundary=``, or None.")
+    boundary_weight = property(lambda self: self._seg_loss.boundary_weight(), doc="The boundary weight the next step uses, read from the device (synchronises); None without a boundary term.")
+    topk_fraction = property(lambda self: self._seg_loss.topk_fraction(), doc="The top-k fraction the next step uses, read from the device (synchronises); None without a top-k loss.")
+    distill_settings = property(lambda self: self._seg_loss.distill_settings(), doc='{"temperature", "soft_weight", "hard_weight"} the next step uses, read from the device (synchronises); None without ``loss="distill"``.')
 
     def set_boundary_weight(self, w):
         """From the next step on, eager or replayed: the kernel reads the device float, so a captured graph needs no recapture."""
-        if self._wb is None:
-            raise ValueError("set_boundary_weight: the model was built without boundary=")
-        self._wb.fill_(_boundary_weight(w))
-
-    @property
-    def overlap_loss(self):
-        """The ``UssegOverlapLoss`` this model trains with (``loss="dice"`` / ``"tversky"`` / ``"dice_ce"``), or None for a per-pixel loss."""
-        return self._overlap
-
-    @property
-    def lovasz_loss(self):
-        """The ``UssegLovaszLoss`` this model trains with (``loss="lovasz"`` / ``"lovasz_ce"``), or None."""
-        return self._lovasz
-
-    @property
-    def topk_loss(self):
-        """The ``UssegTopkLoss`` this model trains with (``loss="topk"`` / ``"dice_topk"``), or None."""
-        return self._topk
-
-    @property
-    def topk_fraction(self):
-        """The top-k fraction the next step uses, read from the device (synchronises); None without a top-k loss."""
-        return None if self._topk is None else float(self._tkf.item())
+        self._seg_loss.set_boundary_weight(w)
 
     def set_topk_fraction(self, f):
         """From the next step on, eager or replayed: the kernels read the device float, so a captured graph needs no recapture."""
-        if self._topk is None:
-            raise ValueError(f"set_topk_fraction: the model was built without loss in {TOPK_LOSSES}")
-        self._tkf.fill_(ops.topk_fraction_value(f))
-
-    @property
-    def distill_settings(self):
-        """{"temperature", "soft_weight", "hard_weight"} the next step uses, read from the device (synchronises); None without ``loss="distill"``."""
-        return None if self._distill is None else self._distill.get()
+        self._seg_loss.set_topk_fraction(f)
 
     def set_distill(self, temperature=None, soft_weight=None, hard_weight=None):
         """From the next step on, eager or replayed: the kernel reads the device table, so a captured graph needs no recapture."""
-        if self._distill is None:
-            raise ValueError(f"set_distill: the model was built without loss in {DISTILL_LOSSES}")
-        self._distill.set(temperature=temperature, soft_weight=soft_weight, hard_weight=hard_weight)
+        self._seg_loss.set_distill(temperature=temperature, soft_weight=soft_weight, hard_weight=hard_weight)
 
     def distill_terms(self):
         """{"hard", "soft"}: the two weighted terms of the last step's loss (synchronises); None without ``loss="distill"``."""
-        return None if self._distill is None else self._distill.terms()
+        return self._seg_loss.distill_terms()
 
     # ------------------------------------------------------------------ parameters in / out (Keras names)
     @property
@@ -640,26 +436,13 @@ class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
         """model.save of a compiled Keras model (MainNumpy.py:177): variables, BN statistics AND the optimiser state."""
         d = self.export_params()
         d.update(self.optimizer.state_dict())
-        if self._wb is not None:
-            d["__boundary_weight__"] = self._wb.detach().clone()
-        if self._topk is not None:
-            d["__topk_fraction__"] = self._tkf.detach().clone()
-        if self._distill is not None:
-            d["__distill__"] = self._distill.settings.detach().clone()
+        d.update(self._seg_loss.state())        # the loss's device settings (the boundary weight, the top-k fraction, the distillation table)
         torch.save(d, path)
 
     def load(self, path):
         d = torch.load(path, map_location="cpu", weights_only=True)
         self.optimizer.load_state_dict({k: d.pop(k) for k in list(d) if k.startswith("__adam_")})
-        wb = d.pop("__boundary_weight__", None)      # (a checkpoint of a model without the term leaves the constructor's weight)
-        if wb is not None and self._wb is not None:
-            self._wb.copy_(wb.to(self._wb.device))
-        tkf = d.pop("__topk_fraction__", None)       # (likewise: a checkpoint without it leaves the constructor's fraction)
-        if tkf is not None and self._topk is not None:
-            self._tkf.copy_(tkf.to(self._tkf.device))
-        dst = d.pop("__distill__", None)             # (likewise: a checkpoint without it leaves the constructor's settings)
-        if dst is not None and self._distill is not None:
-            self._distill.load_table(dst)
+        self._seg_loss.load_state(d)            # (a checkpoint without an entry leaves the constructor's value; another family's entry is ignored)
         self.load_params(d)
 
     @property
@@ -735,23 +518,23 @@ class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
             dlogits = ops.new_act(B, H // 2, W // 2, 16, self.device) if qw else ops.new_act(B, H, W, 8, self.device)
         # :205,:227 sum / GLOBAL batch; TBI_TransUNet.py:546 (default reduction): mean over the B*H*W pixels of the batch
         scale = 1.0 / float(B * H * W) if self.transunet else 1.0 / float(self.batch_size)
-        if self._overlap is not None:
-            return self._forward_overlap(xh, logits, y, probs, dlogits, scale)
-        if self._lovasz is not None:
-            return self._forward_lovasz(xh, logits, y, probs, dlogits, scale)
-        if self._topk is not None:
-            return self._forward_topk(xh, logits, y, probs, dlogits, scale)
-        if self._distill is not None:
-            return self._distill_forward(x, xh, logits, y, probs, dlogits, scale)
+        own = self._seg_loss
+        if not own.fused_head:      # the probabilities of every pixel first, then the family's own launches: the scalar loss (and what its backward reads) into ``_loss``
+            self._head_probs(xh, logits, probs)
+            own.loss_into(self._loss, x, probs, y, dlogits, scale=scale, ov_scale=self._ov_scale(B), quad_w=qw)
+            return probs, dlogits
         if fused:       # head conv + softmax + loss in one launch (:142, :205, :225-229); falls back to the three launches if it has no kernel
-            kw = {} if self._class_loss is None else {"class_loss": self._class_loss}       # (no keyword: today's call of today's symbol)
+            kw = {} if own.class_loss is None else {"class_loss": own.class_loss}           # (no keyword: today's call of today's symbol)
             if self.decoder._quad.forward_loss(xh, y, probs, self._loss, dlogits, label_smoothing=0.1, clip_eps=1e-7, inv_global_batch=scale, **kw):
                 return probs, dlogits
             logits = self.decoder._head_forward(xh)
             self.decoder._logits = logits
         ops.softmax_loss(logits, y, probs, self._loss, dlogits, HW=H * W, C_classes=self.num_classes, loss_kind=0,
-                         label_smoothing=0.1, clip_eps=1e-7, inv_global_batch=scale, quad_w=qw, class_loss=self._class_loss)
+                         label_smoothing=0.1, clip_eps=1e-7, inv_global_batch=scale, quad_w=qw, class_loss=own.class_loss)
         return probs, dlogits
+
+    def _ov_scale(self, B):     # the weight of a region term computed on B images: SUM-reduced replicas train on the batch-weighted mean
+        return 1.0 if self.transunet else float(B) / float(self.batch_size)
 
     def _head_probs(self, xh, logits, probs):
         """The probabilities-only head in front of the losses that need every pixel before any gradient: the fused head launch on ``xh`` where it
@@ -762,85 +545,6 @@ class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
             self.decoder._logits = logits
         if logits is not None:
             ops.softmax_loss(logits, None, probs, None, None, HW=H * W, C_classes=C, quad_w=self.decoder.quad_w)
-
-    def _forward_overlap(self, xh, logits, y, probs, dlogits, scale):
-        """The region-overlap losses: today's probabilities-only head launch(es), then the sums pass (scalar loss and backward coefficients into
-        ``self._loss``), then - for a training step - the backward pass that writes ``dlogits``."""
-        B, H, W, C = probs.shape
-        self._head_probs(xh, logits, probs)
-        kw = dict(overlap=self._overlap, HW=H * W, C_classes=C, label_smoothing=0.1, clip_eps=1e-7, inv_global_batch=scale)
-        ov_scale = 1.0 if self.transunet else float(B) / float(self.batch_size)
-        if self._boundary is not None:          # the labels' distance map once per step, then the pair that carries the boundary term
-            phi = ops.sdf_labels(y, threshold=self._boundary_thr)
-            ops.overlap_boundary_loss_sums(probs, y, phi, self._loss, boundary=self._boundary, wb=self._wb, ov_scale=ov_scale, **kw)
-            if dlogits is not None:
-                ops.overlap_boundary_loss_bwd(probs, y, phi, self._loss, dlogits, boundary=self._boundary, quad_w=self.decoder.quad_w, **kw)
-            return probs, dlogits
-        ops.overlap_loss_sums(probs, y, self._loss, ov_scale=ov_scale, **kw)
-        if dlogits is not None:
-            ops.overlap_loss_bwd(probs, y, self._loss, dlogits, quad_w=self.decoder.quad_w, **kw)
-        return probs, dlogits
-
-    def _lovasz_buffers(self, M, C):
-        bufs = self._lovasz_bufs.get((M, C))
-        if bufs is None:
-            bufs = (torch.empty(max(M * C, 4), dtype=torch.float32, device=self.device), torch.zeros(4, dtype=torch.int32, device=self.device),
-                    torch.empty(max(ops.lovasz_ws_bytes(M, C), 16), dtype=torch.uint8, device=self.device))
-            self._lovasz_bufs[(M, C)] = bufs
-        return bufs
-
-    def _lovasz_loss_into(self, acc, probs, y, scale, ov_scale):
-        """The coefficients pass (device sort) and the sums pass on these probabilities and labels: the scalar loss in ``acc[0]``.  -> (g, kw)."""
-        B, H, W, C = probs.shape
-        g, counts, ws = self._lovasz_buffers(B * H * W, C)
-        g = g[:B * H * W * C].view(probs.shape)
-        kw = dict(lovasz=self._lovasz, HW=H * W, C_classes=C)
-        ops.lovasz_coeffs(probs, y, g, counts, ws, **kw)
-        kw.update(label_smoothing=0.1, clip_eps=1e-7, inv_global_batch=scale)
-        ops.lovasz_loss_sums(probs, y, g, counts, acc, ov_scale=ov_scale, **kw)
-        return g, kw
-
-    def _forward_lovasz(self, xh, logits, y, probs, dlogits, scale):
-        """The Lovasz-softmax loss: today's probabilities-only head launch(es), then the coefficients (the sort), the sums pass (scalar loss and
-        k_c into ``self._loss``), then - for a training step - the backward pass that writes ``dlogits``."""
-        self._head_probs(xh, logits, probs)
-        g, kw = self._lovasz_loss_into(self._loss, probs, y, scale, 1.0 if self.transunet else float(probs.shape[0]) / float(self.batch_size))
-        if dlogits is not None:
-            ops.lovasz_loss_bwd(probs, y, g, self._loss, dlogits, quad_w=self.decoder.quad_w, **kw)
-        return probs, dlogits
-
-    def _topk_loss_into(self, acc, ov_acc, probs, y, scale, ov_scale):
-        """The per-pixel losses and their selection, the Dice sums of "dice_topk" into ``ov_acc``, then the sums pass: the scalar loss in
-        ``acc[0]``.  -> (workspace, kw)."""
-        B, H, W, C = probs.shape
-        ws = self._topk_bufs.get((B * H * W, H * W))
-        if ws is None:
-            ws = torch.empty(max(ops.topk_ws_bytes(B * H * W, H * W, ops.TOPK_SCOPES[self._topk.scope]), 16), dtype=torch.uint8, device=self.device)
-            self._topk_bufs[(B * H * W, H * W)] = ws
-        kw = dict(topk=self._topk, HW=H * W, C_classes=C, label_smoothing=0.1, clip_eps=1e-7)
-        ops.topk_pixel_loss(probs, y, self._tkf, ws, **kw)
-        kw.update(inv_global_batch=scale, overlap_acc=ov_acc)
-        if ov_acc is not None:
-            ops.overlap_loss_sums(probs, y, ov_acc, overlap=self._topk_overlap, HW=H * W, C_classes=C, ov_scale=ov_scale, label_smoothing=0.1, clip_eps=1e-7,
-                                  inv_global_batch=scale)
-        ops.topk_loss_sums(probs, ws, acc, **kw)
-        return ws, kw
-
-    def _forward_topk(self, xh, logits, y, probs, dlogits, scale):
-        """The top-k cross-entropy: today's probabilities-only head launch(es), then the per-pixel losses with their exact selection, the sums
-        pass (scalar loss and coefficient into ``self._loss``), then - for a training step - the backward pass that writes ``dlogits``."""
-        self._head_probs(xh, logits, probs)
-        ws, kw = self._topk_loss_into(self._loss, self._ov_acc, probs, y, scale, 1.0 if self.transunet else float(probs.shape[0]) / float(self.batch_size))
-        if dlogits is not None:
-            ops.topk_loss_bwd(probs, y, ws, self._loss, dlogits, quad_w=self.decoder.quad_w, **kw)
-        return probs, dlogits
-
-    def _distill_forward(self, x, xh, logits, y, probs, dlogits, scale):
-        """Knowledge distillation: today's probabilities-only head launch(es), then the owner's part - the teacher's label-free forward on this
-        stream and the one launch that writes the scalar loss into ``self._loss`` and, for a training step, ``dlogits``."""
-        self._head_probs(xh, logits, probs)
-        self._distill.forward(x, y, probs, dlogits, scale=scale, quad_w=self.decoder.quad_w)
-        return probs, dlogits
 
     def _predict_body(self, x):
         """The forward of ``_forward_loss`` without labels: the encoder with ``stash=False``, the fused attention, the decoder, and the head
@@ -867,36 +571,9 @@ class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
         -> scalar.  (train_step/step use the fused softmax+loss kernel instead.)  Under ``loss="distill"`` there is no input here that could show
         a teacher: the result is the HARD term alone, weighted by ``hard_weight`` (``step(x, y)`` runs the teacher and returns the full loss)."""
         y_true, y_pred = self._prep_y(y_true), self._prep_y(y_pred)
-        H, W = y_pred.shape[1], y_pred.shape[2]
-        if self._distill is not None:       # the teacher's place is taken by y_pred itself: q == p, whose soft term is exactly zero
-            acc = torch.zeros(ops.DISTILL_ACC_FLOATS, dtype=torch.float32, device=self.device)
-            self._distill.loss_into(acc, y_pred, y_true, y_pred, None, scale=1.0 / float(self.batch_size))
-            return acc[4].clone()
-        if self._overlap is not None:       # the overlap loss of THESE tensors, weighted as a step weights a batch of their size
-            acc = torch.zeros(ops.OVERLAP_ACC_FLOATS, dtype=torch.float32, device=self.device)
-            kw = dict(overlap=self._overlap, HW=H * W, C_classes=y_pred.shape[-1], label_smoothing=0.1, clip_eps=1e-7,
-                      ov_scale=1.0 if self.transunet else float(y_pred.shape[0]) / float(self.batch_size), inv_global_batch=1.0 / float(self.batch_size))
-            if self._boundary is not None:
-                phi = ops.sdf_labels(y_true, threshold=self._boundary_thr)
-                ops.overlap_boundary_loss_sums(y_pred, y_true, phi, acc, boundary=self._boundary, wb=self._wb, **kw)
-            else:
-                ops.overlap_loss_sums(y_pred, y_true, acc, **kw)
-            return acc[0].clone()
-        if self._lovasz is not None:        # the Lovasz loss of THESE tensors, weighted as a step weights a batch of their size
-            acc = torch.zeros(ops.OVERLAP_ACC_FLOATS, dtype=torch.float32, device=self.device)
-            self._lovasz_loss_into(acc, y_pred, y_true, 1.0 / float(self.batch_size),
-                                   1.0 if self.transunet else float(y_pred.shape[0]) / float(self.batch_size))
-            return acc[0].clone()
-        if self._topk is not None:          # the top-k loss of THESE tensors, weighted as a step weights a batch of their size
-            acc = torch.zeros(ops.OVERLAP_ACC_FLOATS, dtype=torch.float32, device=self.device)
-            self._topk_loss_into(acc, None if self._ov_acc is None else torch.zeros_like(acc), y_pred, y_true, 1.0 / float(self.batch_size),
-                                 1.0 if self.transunet else float(y_pred.shape[0]) / float(self.batch_size))
-            return acc[0].clone()
-        loss = torch.empty(ops.ACC_FLOATS, dtype=torch.float32, device=self.device)
-        ops.fill_f32(loss, 0.0)
-        ops.loss_from_probs(y_pred, y_true, loss, HW=H * W, C_classes=y_pred.shape[-1], loss_kind=0, label_smoothing=0.1, clip_eps=1e-7,
-                            inv_global_batch=1.0 / float(self.batch_size), class_loss=self._class_loss)
-        return loss[0].clone()
+        own, acc = self._seg_loss, torch.zeros_like(self._loss)      # the loss of THESE tensors, a region term weighted as a step weights a batch of their size
+        own.loss_into(acc, None, y_pred, y_true, None, scale=1.0 / float(self.batch_size), ov_scale=self._ov_scale(y_pred.shape[0]), quad_w=0)
+        return acc[own.reported].clone()
 
     def my_loss_cat(self, y_true, y_pred):
         """VisionTransformer.py:259-280 as committed, whatever ``loss=`` says: on PROBABILITIES [B,H,W,classes] -> the fp32 [H,W] map

@@ -2,9 +2,9 @@
 
 An ``ensemble.Ensemble`` of N members costs N forwards per image; distillation takes what it knows back into ONE model: the student is trained
 against the teacher's softened probabilities as well as the labels (include/usseg_distill.h has the definition, DESIGN.md section 8 the
-gradient).  This module is the loss's owner: ``distill_config`` checks the settings on the host, ``Distill`` holds the teacher, the device
-settings table and the accumulator, runs the teacher's label-free forward on the current stream and then the ONE launch of
-``ops.distill_loss``.  ``VisionTransformer(loss="distill", distill={...}, teacher=...)`` is the hook that calls it.
+gradient).  This module is the loss's owner, with the surface of seg_loss.py's families: ``distill_config`` checks the settings on the host,
+``Distill`` holds the teacher, the device settings table and the accumulator, runs the teacher's label-free forward on the current stream and
+then the ONE launch of ``ops.distill_loss``.  ``VisionTransformer(loss="distill", distill={...}, teacher=...)`` is the model that calls it.
 """
 from __future__ import annotations
 
@@ -13,6 +13,7 @@ import math
 import torch
 
 from . import ops
+from .seg_loss import SegLoss
 
 DISTILL_KEYS = ("temperature", "soft_weight", "hard_weight")
 DISTILL_DEFAULTS = {"temperature": 2.0, "soft_weight": 0.5, "hard_weight": 0.5}
@@ -90,19 +91,29 @@ def load_teacher(checkpoints, img_size, in_channels, device, *, num_classes=3, u
     return Ensemble(models, flip=flip) if len(models) > 1 or flip else models[0]
 
 
-class Distill:
-    """``Distill(teacher, config, student)``: the distillation loss of ``student`` (a ``VisionTransformer``) against ``teacher``.
+class Distill(SegLoss):
+    """``Distill(teacher, config, student)``: the distillation loss of ``student`` (a ``VisionTransformer``) against ``teacher``; without
+    ``student`` only the settings are checked (``seg_loss.resolve``), and ``place(student)`` does the rest once the student has its device.
 
     Owns the teacher, the device settings table (``settings``: temperature, soft_weight, hard_weight - read by the kernel when it runs, so a
-    captured graph follows ``set`` on its next replay) and the accumulator (``acc``: [0] the loss).  The teacher is never trained: only its
+    captured graph follows ``set_distill`` on its next replay) and the accumulator (``acc``: [0] the loss).  The teacher is never trained: only its
     label-free ``_predict_body`` runs, which reads no loss buffer, gradient, optimiser state or BatchNorm statistic and writes none.
 
     Refused with a ValueError: a teacher that is (or contains) the student, a teacher on another device or with another image size, input
     channel or class count, and a teacher whose ``_predict_state()`` is not empty (Arch A members with their always-on dropout: a captured
     training step would have to carry their counters)."""
 
-    def __init__(self, teacher, config, student):
+    acc_floats = ops.DISTILL_ACC_FLOATS
+    reported = 4            # ``compute_loss`` has no input that could show a teacher: the HARD term alone, weighted
+
+    def __init__(self, teacher, config, student=None):
         self.config = distill_config(config)
+        self.teacher = teacher
+        if student is not None:
+            self.place(student)
+
+    def place(self, student):
+        teacher = self.teacher
         dev, hw, cin, ncls, models = teacher_spec(teacher)
         if any(m is student for m in models) or teacher is student:
             raise ValueError("distill: the teacher is the student itself")
@@ -113,30 +124,33 @@ class Distill:
         if teacher._predict_state():
             raise ValueError("distill: a teacher whose predict advances device state (TBI_ResNest.ResNest members with their always-on dropout) "
                              "is out of scope: a captured training step would have to carry its counters")
-        self.teacher = teacher
-        self.device = student.device
+        super().place(student)
         self.settings = torch.tensor(_table(self.config), dtype=torch.float32, device=self.device)
-        self.acc = torch.zeros(ops.DISTILL_ACC_FLOATS, dtype=torch.float32, device=self.device)
 
     # ------------------------------------------------------------------ the settings on the device
-    def get(self) -> dict:
+    def distill_settings(self) -> dict:
         """The settings the next step uses, read from the device (synchronises)."""
         v = self.settings.tolist()
         return {"temperature": v[0], "soft_weight": v[1], "hard_weight": v[2]}
 
-    def set(self, temperature=None, soft_weight=None, hard_weight=None):
+    def set_distill(self, temperature=None, soft_weight=None, hard_weight=None):
         """From the next step on, eager or replayed: the kernel reads the device table, so a captured graph needs no recapture.  A setting left
         None keeps its value; the combination passes ``distill_config``."""
         given = {k: v for k, v in (("temperature", temperature), ("soft_weight", soft_weight), ("hard_weight", hard_weight)) if v is not None}
         self.config = distill_config({**self.config, **given})
         self.settings.copy_(torch.tensor(_table(self.config), dtype=torch.float32))
 
-    def load_table(self, t):
-        """A checkpoint's table (fp32 [DISTILL_SETTINGS]) -> the device, checked like ``set``."""
-        v = [float(a) for a in t.tolist()]
-        self.set(temperature=v[0], soft_weight=v[1], hard_weight=v[2])
+    def state(self):
+        return {"__distill__": self.settings.detach().clone()}
 
-    def terms(self) -> dict:
+    def load_state(self, d):
+        """A checkpoint's table (fp32 [DISTILL_SETTINGS]) -> the device, checked like ``set_distill``."""
+        t = d.get("__distill__")
+        super().load_state(d)                   # (pops every family's entry; this one's is no plain copy)
+        if t is not None:
+            self.set_distill(*(float(a) for a in t.tolist()[:3]))
+
+    def distill_terms(self) -> dict:
         """{"hard", "soft"}: the two weighted terms of the LAST call (their sum is the loss); synchronises."""
         v = self.acc[4:6].tolist()
         return {"hard": v[0], "soft": v[1]}
@@ -148,12 +162,10 @@ class Distill:
         q = getattr(q, "probs", q)
         return q if q.is_contiguous() else q.contiguous()
 
-    def loss_into(self, acc, probs, y, q, dlogits, *, scale, quad_w=0):
-        """The ONE launch on these tensors: the scalar loss in ``acc[0]``, ``dlogits`` written when given."""
+    def loss_into(self, acc, x, probs, y, dlogits, *, scale, ov_scale=1.0, quad_w=0):
+        """``teacher._predict_body(x)`` on the current stream, then the ONE launch: the scalar loss in ``acc[0]``, ``dlogits`` written when given.
+        ``x`` None (``compute_loss``): the teacher's place is taken by ``probs`` itself, q == p, whose soft term is exactly zero."""
         _, H, W, C = probs.shape
+        q = probs if x is None else self.teacher_probs(x)
         ops.distill_loss(probs, y, q, self.settings, acc, dlogits, HW=H * W, C_classes=C, label_smoothing=0.1, clip_eps=1e-7, inv_global_batch=scale,
                          quad_w=quad_w)
-
-    def forward(self, x, y, probs, dlogits, *, scale, quad_w=0):
-        """``teacher._predict_body(x)`` on the current stream, then the one launch: the loss in ``self.acc[0]``."""
-        self.loss_into(self.acc, probs, y, self.teacher_probs(x), dlogits, scale=scale, quad_w=quad_w)
