@@ -1,9 +1,11 @@
 """Per-layer 3x3 conv timing (forward and backward-data) on the Arch B shapes: python tools/bench_conv.py [B]
 Set USSEG_BIG=0 / USSEG_NO_HALO=1 to time the other kernels on the same shapes."""
-import sys, time, torch
+import sys, torch
+import timing
 sys.path.insert(0, ".")
 from ultrasound_modeling_amd import ops
 
+timing.require_gpu("bench_conv")
 dev = torch.device("cuda:0")
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 16
 # name, H, Cin, Cout, dilation
@@ -23,19 +25,8 @@ if os.environ.get("STEM"):
 
 
 def timeit(fn, reps=10):
-    fn(); torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    cs = torch.cuda.Stream()
-    with torch.cuda.stream(cs):
-        with torch.cuda.graph(g, stream=cs):
-            for _ in range(reps):
-                fn()
-    g.replay(); torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(5):
-        g.replay()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) / (5 * reps)
+    """`reps` calls in one HIP graph, one window of five replays between two device events: seconds per call."""
+    return timing.window_us(timing.graph_of(fn, reps), reps, 5) * 1e-6
 
 
 for name, H, Cin, Cout, d in LAYERS:

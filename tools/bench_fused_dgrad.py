@@ -1,7 +1,9 @@
 """Fused four-branch backward-data (Decoder stage) timing in isolation: python tools/bench_fused_dgrad.py [B]"""
-import sys, time, torch
+import sys, torch
+import timing
 sys.path.insert(0, ".")
 from ultrasound_modeling_amd import ops
+timing.require_gpu("bench_fused_dgrad")
 dev = torch.device("cuda:0")
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 16
 # name, H, Cin (dx channels), q (channels per branch)
@@ -10,16 +12,8 @@ CASES = [("b0 s1 dx512 q64 @32", 32, 512, 64), ("b0 s2 dx256 q64 @32", 32, 256, 
 
 
 def timeit(fn, reps=10):
-    fn(); torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph(); cs = torch.cuda.Stream()
-    with torch.cuda.stream(cs):
-        with torch.cuda.graph(g, stream=cs):
-            for _ in range(reps): fn()
-    g.replay(); torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(5): g.replay()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) / (5 * reps)
+    """`reps` calls in one HIP graph, one window of five replays between two device events: seconds per call."""
+    return timing.window_us(timing.graph_of(fn, reps), reps, 5) * 1e-6
 
 
 for name, H, Cin, q in CASES:

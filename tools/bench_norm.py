@@ -1,7 +1,9 @@
 """Norm fwd/bwd bandwidth on the Arch B shapes: python tools/bench_norm.py"""
-import sys, time, torch
+import sys, torch
+import timing
 sys.path.insert(0, ".")
 from ultrasound_modeling_amd import ops
+timing.require_gpu("bench_norm")
 dev = torch.device("cuda:0")
 # name, M, C, Cphys, G, mode
 CASES = [("stem BN 32 @256^2", 16 * 256 * 256, 32, 32, 1, 1), ("s1 LN1 9(3g)", 16 * 128 * 128, 9, 16, 3, 0), ("s1 LN2 30(3g)", 16 * 128 * 128, 30, 32, 3, 0),
@@ -9,16 +11,8 @@ CASES = [("stem BN 32 @256^2", 16 * 256 * 256, 32, 32, 1, 1), ("s1 LN1 9(3g)", 1
          ("s2 sc LN 128", 16 * 64 * 64, 128, 128, 1, 0), ("b1 BN 128 @64^2", 16 * 64 * 64, 128, 128, 1, 1), ("s3 sc LN 256", 16 * 32 * 32, 256, 256, 1, 0),
          ("b0 BN 256 @32^2", 16 * 32 * 32, 256, 256, 1, 1), ("s4 sc LN 512", 16 * 16 * 16, 512, 512, 1, 0)]
 def timeit(fn, reps=10):
-    fn(); torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph(); cs = torch.cuda.Stream()
-    with torch.cuda.stream(cs):
-        with torch.cuda.graph(g, stream=cs):
-            for _ in range(reps): fn()
-    g.replay(); torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(5): g.replay()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) / (5 * reps)
+    """`reps` calls in one HIP graph, one window of five replays between two device events: seconds per call."""
+    return timing.window_us(timing.graph_of(fn, reps), reps, 5) * 1e-6
 for name, M, C, Cp, G, mode in CASES:
     x = torch.randn(1, 1, M, Cp, device=dev).to(torch.bfloat16); dy = torch.randn_like(x.float()).to(torch.bfloat16)
     y = torch.empty_like(x); dx = torch.empty_like(x)

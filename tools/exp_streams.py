@@ -1,8 +1,10 @@
 """Experiment: do independent conv launches captured on forked streams overlap inside one HIP graph?"""
-import sys, time, torch
+import sys, torch
+import timing
 sys.path.insert(0, ".")
 from ultrasound_modeling_amd import ops
 
+timing.require_gpu("exp_streams")
 dev = torch.device("cuda:0")
 B, H, Cin, Cb = 16, int(sys.argv[1]) if len(sys.argv) > 1 else 32, int(sys.argv[2]) if len(sys.argv) > 2 else 512, int(sys.argv[3]) if len(sys.argv) > 3 else 64
 x = torch.randn(B, H, H, Cin, device=dev).to(torch.bfloat16)
@@ -40,20 +42,7 @@ def forked():
 def bench(fn, name):
     fn(); torch.cuda.synchronize()
     ref = out.clone()
-    g = torch.cuda.CUDAGraph()
-    cs = torch.cuda.Stream()
-    with torch.cuda.stream(cs):
-        with torch.cuda.graph(g, stream=cs):
-            for _ in range(10):
-                fn()
-    for _ in range(3):
-        g.replay()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(20):
-        g.replay()
-    torch.cuda.synchronize()
-    dt = (time.perf_counter() - t0) / 200
+    dt = timing.window_us(timing.graph_of(fn, 10), 10, 20) * 1e-6                   # ten groups a graph, one window of twenty replays
     print(f"{name}: {dt * 1e6:.1f} us per 4-branch group; same={torch.equal(ref, out)}")
 
 

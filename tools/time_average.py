@@ -7,12 +7,12 @@ snapshots (c = 0: avg is neither read nor written).  DESIGN.md section 4g-2.
 
 usage: python tools/time_average.py [--reps 20] [--iters 15] [--out profiles/average_step.json]"""
 import argparse
-import json
 import os
-import statistics
 import sys
 
 import torch
+
+import timing
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from ultrasound_modeling_amd import flat, ops  # noqa: E402
@@ -22,36 +22,13 @@ HBM = 6.29e12
 HYPER = (0.9, 0.999, 1e-7)
 
 
-def _time(fn, reps, iters):
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(s):
-        fn()
-    torch.cuda.current_stream().wait_stream(s)
-    torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        for _ in range(reps):
-            fn()
-    graph.replay()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(iters):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        graph.replay()
-        e1.record()
-        torch.cuda.synchronize()
-        ts.append(e0.elapsed_time(e1) * 1e3 / reps)
-    return statistics.median(ts), min(ts)
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--iters", type=int, default=15)
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "average_step.json"))
     a = ap.parse_args()
+    timing.require_gpu("time_average")
     result = {"device": torch.cuda.get_device_name(0), "reps": a.reps, "iters": a.iters, "unit": "us per repetition, median of iters", "sizes": {}}
     for name, n in SIZES.items():
         p, g, m, v = (torch.randn(n, device="cuda") * s for s in (0.1, 1e-3, 1e-4, 0.0))
@@ -74,8 +51,10 @@ def main():
             "fused, no snapshot": (28, lambda: ops.adamw_avg_step(p, g, m, v, avg, sumsq, 0.0, lr_t, wd, None, *HYPER, step, swa)),
         }
         row = {"n": n}
-        for label, (nbytes, fn) in variants.items():
-            med, lo = _time(fn, a.reps, a.iters)
+        ts = timing.time_calls({label: fn for label, (_, fn) in variants.items()}, a.iters, a.reps, replays=1)      # the variants alternate
+        for label, (nbytes, _) in variants.items():
+            sp = timing.spread(ts[label])
+            med, lo = sp["median"], sp["min"]
             bound = n * nbytes / HBM * 1e6
             row[label] = {"median_us": round(med, 2), "min_us": round(lo, 2), "hbm_bound_us": round(bound, 2)}
             print(f"{name} n={n} {label:28s} median {med:7.1f} us  min {lo:7.1f} us  (HBM bound {bound:6.1f} us)", flush=True)
@@ -86,10 +65,7 @@ def main():
         row["fused_not_slower_than_two_launches"] = fused <= pair
         print(f"{name}: fused / adamw_step = {fused / base:.3f} (bound {9 / 7 * 1.10:.3f}); two launches / fused = {pair / fused:.3f}", flush=True)
         result["sizes"][name] = row
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump(result, f, indent=1)
-        f.write("\n")
+    timing.write_json(a.out, result)
 
 
 if __name__ == "__main__":

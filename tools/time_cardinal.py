@@ -15,6 +15,7 @@ if PH:
     subprocess.run(["/opt/rocm/bin/hipcc", "-shared", "-fPIC", "--offload-arch=gfx950", "gpurun_out/card_timing.o"] + objs + ["-o", out], check=True)
     os.environ["USSEG_LIB"] = os.path.abspath(out)
 import torch
+import timing
 sys.path.insert(0, ".")
 from ultrasound_modeling_amd import ops
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 16
@@ -31,16 +32,8 @@ for st, (cin, cv11, cvkk, oc) in enumerate(((32, 3, 10, 64), (64, 7, 21, 128), (
     wsc = (torch.randn(oc, cin, device=dev) * 0.1).to(torch.bfloat16)
     f = lambda n: torch.randn(n, device=dev) * 0.1
     args = (x, w1, f(Up), 1 + f(Up), f(Up), w2, f(Vp), 1 + f(Vp), f(Vp), wsc, f(oc), 1 + f(oc), f(oc), P, cv11, cvkk, Up, Vp, oc, 1e-3, 0.3)
-    for _ in range(3):
-        ops.cardinal_fwd(*args)
-    n = 50
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(n):
-        ops.cardinal_fwd(*args)
-    e1.record()
-    torch.cuda.synchronize()
-    print(f"stage {st + 1}: {h}x{h} cin {cin}: {e0.elapsed_time(e1) * 1e3 / n:.1f} us per launch")
+    us = timing.time_steps(lambda: ops.cardinal_fwd(*args), 1, 50, warm=3)[0] * 1e3
+    print(f"stage {st + 1}: {h}x{h} cin {cin}: {us:.1f} us per launch")
     if PH:
         from ultrasound_modeling_amd import _lib
         buf = (ctypes.c_ulonglong * 32)()
@@ -78,18 +71,7 @@ for st, (cin, cv11, cvkk, oc) in enumerate(((32, 3, 10, 64), (64, 7, 21, 128), (
         ops.conv2d_dgrad(dv, w2d, 3, 1, du)
         ops.norm_act_bwd(u_raw, du, U, g1, be1, dcat[..., :Up], gr[3], gr[4], 0, P, 1e-3, ops.ACT_LRELU, 0.3, dbias=gr[5])
         ops.norm_act_bwd(sc_raw, dsc, oc, gsc, besc, dcat[..., Up:], gr[6], gr[7], 0, 1, 1e-3, ops.ACT_LRELU, 0.3, dbias=gr[8])
-    res = []
-    for fn in (fused, unfused):
-        for _ in range(3):
-            fn()
-        n = 50
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(n):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        res.append(e0.elapsed_time(e1) * 1e3 / n)
+    res = [timing.time_steps(fn, 1, 50, warm=3)[0] * 1e3 for fn in (fused, unfused)]
     print(f"stage {st + 1}: {h}x{h}: fused {res[0]:.1f} us, the four launches + their finishing reductions {res[1]:.1f} us")
     if PH:
         fused()

@@ -12,13 +12,15 @@ One JSON line per (shape, input, connectivity).
 """
 import json
 import os
-import statistics
 import sys
+import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
+
+import timing  # noqa: E402
 
 from ultrasound_modeling_amd import ops  # noqa: E402
 
@@ -26,35 +28,13 @@ N, REPLAYS, ROUNDS = 16, 3, 5
 STRUCTURE = {4: [[0, 1, 0], [1, 1, 1], [0, 1, 0]], 8: [[1, 1, 1], [1, 1, 1], [1, 1, 1]]}
 
 
-def graph_us(fn):
-    """median, min, max over ROUNDS of the time of one call inside REPLAYS replays of the captured fn, in microseconds"""
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        fn()
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        fn()
-    for _ in range(3):
-        g.replay()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(ROUNDS):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(REPLAYS):
-            g.replay()
-        e1.record()
-        e1.synchronize()
-        out.append(e0.elapsed_time(e1) * 1e3 / REPLAYS)
-    return [round(v, 1) for v in (statistics.median(out), min(out), max(out))]
+def triple(ts):
+    sp = timing.spread(ts, 1)
+    return [sp["median"], sp["min"], sp["max"]]
 
 
 def scipy_us(mask, connectivity):
     """the host path: copy the mask to the host, scipy.ndimage.label per image"""
-    import time
     from scipy import ndimage as nd
     out, k = [], 0
     for _ in range(ROUNDS):
@@ -63,7 +43,7 @@ def scipy_us(mask, connectivity):
         m = mask.cpu().numpy()
         k = sum(nd.label(p, structure=STRUCTURE[connectivity])[1] for p in m)
         out.append((time.perf_counter() - t0) * 1e6)
-    return [round(v, 1) for v in (statistics.median(out), min(out), max(out))], k
+    return triple(out), k
 
 
 def inputs(H, W):
@@ -84,6 +64,7 @@ def inputs(H, W):
 
 
 def main():
+    timing.require_gpu("time_components")
     for H, W in ((256, 80), (256, 256)):
         ws = torch.empty(ops.components_ws_bytes(N, H, W), dtype=torch.uint8, device="cuda")
         labels = torch.empty((N, H, W), dtype=torch.int32, device="cuda")
@@ -92,9 +73,11 @@ def main():
             out = torch.empty_like(mask)
             for c in (4, 8):
                 r = {"shape": [N, H, W], "input": name, "connectivity": c, "density": round(float(mask.float().mean()), 4)}
-                r["label_us"] = graph_us(lambda: ops.label_components(mask, c, labels=labels, count=count, ws=ws))
+                ts = timing.time_calls({"label_us": lambda: ops.label_components(mask, c, labels=labels, count=count, ws=ws),
+                                        "clean_us": lambda: ops.clean_mask(mask, prob, connectivity=c, min_area=5, min_peak=0.6, out=out, ws=ws)}, ROUNDS, 1, REPLAYS)
+                r["label_us"] = triple(ts["label_us"])
                 r["components"] = int(count.sum())
-                r["clean_us"] = graph_us(lambda: ops.clean_mask(mask, prob, connectivity=c, min_area=5, min_peak=0.6, out=out, ws=ws))
+                r["clean_us"] = triple(ts["clean_us"])
                 r["kept"] = round(float(out.float().mean()), 4)
                 r["scipy_us"], k = scipy_us(mask, c)
                 assert k == r["components"], (k, r["components"])

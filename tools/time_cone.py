@@ -23,6 +23,8 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
+import timing  # noqa: E402
+
 H, W = 256, 80
 
 
@@ -65,20 +67,9 @@ def table(args):
     def batch():
         rg, _ = ops.cone_range(dev[3])
         return ops.cone_render(geo.index, dev[0], dev[1], dev[2], dev[3], PANEL_RANGES, rg, luts, geo.gap)
-    for _ in range(5):
-        batch()
-    torch.cuda.synchronize()
-    per = []
-    for _ in range(args.repeats):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(args.calls):
-            batch()
-        e1.record()
-        e1.synchronize()
-        per.append(e0.elapsed_time(e1) * 1e3 / args.calls)
-    out["render_us"] = statistics.median(per)
-    out["render_us_min_max"] = [min(per), max(per)]
+    per = timing.spread([ms * 1e3 for ms in timing.time_steps(batch, args.repeats, args.calls, warm=5)], 6)
+    out["render_us"] = per["median"]
+    out["render_us_min_max"] = [per["min"], per["max"]]
     written = B * int(np.prod(geo.figure_shape))
     read = sum(d.numel() * d.element_size() for d in dev) + geo.index.numel() * 4
     out["render_bytes"] = [written, read]

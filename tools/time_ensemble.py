@@ -10,11 +10,12 @@ graphs as tools/time_lovasz.py does:
 
 usage: python tools/time_ensemble.py [--k K ...] [--rounds N] [--replays R] [--reps R] [--no-models] [--json PATH] [B H W]"""
 import argparse
-import json
 import os
 import sys
 
 import torch
+
+import timing
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--k", nargs="*", type=int, default=[2, 4, 8])
@@ -30,43 +31,20 @@ C_ = 3
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from ultrasound_modeling_amd import ops                                         # noqa: E402
 
-if not torch.cuda.is_available():
-    sys.exit("time_ensemble: needs a GPU (a timing on the host says nothing)")
+timing.require_gpu("time_ensemble")
 out = {"shape": [B, H, W, C_], "launch_us": {}, "predict_ms": {}}
 g = torch.Generator().manual_seed(0)
 M = B * H * W
 
 
-def spread(ts):
-    ts = sorted(ts)
-    return {"min": round(ts[0], 4), "median": round(ts[len(ts) // 2], 4), "max": round(ts[-1], 4)}
-
-
-def t(fn):
-    """One graph of `reps` launches, replayed three times: microseconds per launch."""
-    for _ in range(2):
-        fn()
-    torch.cuda.synchronize()
-    gr = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(gr):
-        for _ in range(a.reps):
-            fn()
-    gr.replay()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(3):
-        gr.replay()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / (3 * a.reps) * 1e3
-
-
-def row(name, fn, nbytes):
-    s = spread([t(fn) for _ in range(a.rounds)])
-    out["launch_us"][name] = dict(s, MB=round(nbytes / 1e6, 2), TBps=round(nbytes / s["median"] / 1e6, 3))
-    print(f"  {name:34s} {s['min']:8.2f} us min, {s['median']:8.2f} median, {s['max']:8.2f} max   {nbytes / 1e6:6.2f} MB -> "
-          f"{nbytes / s['median'] / 1e6:5.2f} TB/s", flush=True)
+def rows(named):
+    """Time the named launches (name -> (fn, bytes)), three replays a window, alternating inside every round."""
+    ts = timing.time_calls({n: fn for n, (fn, _) in named.items()}, a.rounds, a.reps, replays=3)
+    for name, (_, nbytes) in named.items():
+        s = timing.spread(ts[name])
+        out["launch_us"][name] = dict(s, MB=round(nbytes / 1e6, 2), TBps=round(nbytes / s["median"] / 1e6, 3))
+        print(f"  {name:34s} {s['min']:8.2f} us min, {s['median']:8.2f} median, {s['max']:8.2f} max   {nbytes / 1e6:6.2f} MB -> "
+              f"{nbytes / s['median'] / 1e6:5.2f} TB/s", flush=True)
 
 
 print(f"the launches at {B} x {H} x {W} x {C_} ({M} pixels), {a.rounds} graphs of {a.reps} launches:")
@@ -74,14 +52,16 @@ members = [torch.softmax(2 * torch.randn(B, H, W, C_, generator=g), -1).cuda() f
 y = torch.nn.functional.one_hot(torch.randint(0, C_, (B, H, W), generator=g), C_).float().cuda()
 bufs = dict(mean_probs=torch.empty_like(members[0]), entropy=torch.empty(B, H, W).cuda(), mutual_info=torch.empty(B, H, W).cuda(),
             variance_out=torch.empty_like(members[0]))
+named = {}
 for K in a.k:
     flip_w = 0xAAAA & ((1 << K) - 1)                                             # every second member mirrored, as Ensemble(flip=True) orders them
-    row(f"ensemble_merge K={K} (mirrored {bin(flip_w).count('1')})", lambda: ops.ensemble_merge(members[:K], flip_w, **bufs), (K * C_ + C_ + 2 + C_) * 4 * M)
-    row(f"ensemble_merge K={K} (none mirrored)", lambda: ops.ensemble_merge(members[:K], 0, **bufs), (K * C_ + C_ + 2 + C_) * 4 * M)
+    named[f"ensemble_merge K={K} (mirrored {bin(flip_w).count('1')})"] = (lambda K=K, flip_w=flip_w: ops.ensemble_merge(members[:K], flip_w, **bufs), (K * C_ + C_ + 2 + C_) * 4 * M)
+    named[f"ensemble_merge K={K} (none mirrored)"] = (lambda K=K: ops.ensemble_merge(members[:K], 0, **bufs), (K * C_ + C_ + 2 + C_) * 4 * M)
 scores, counts = torch.empty(B, 4).cuda(), torch.empty(B, dtype=torch.int32).cuda()
-row("ensemble_image_scores", lambda: ops.ensemble_image_scores(bufs["mean_probs"], bufs["entropy"], bufs["mutual_info"], scores, counts), (C_ + 2) * 4 * M)
+named["ensemble_image_scores"] = (lambda: ops.ensemble_image_scores(bufs["mean_probs"], bufs["entropy"], bufs["mutual_info"], scores, counts), (C_ + 2) * 4 * M)
 cal = torch.zeros(15 * 3 + 2, dtype=torch.int64).cuda()
-row("calibration_bins, 15 bins, top label", lambda: ops.calibration_bins(members[0], y, cal, 15, -1), 2 * C_ * 4 * M)
+named["calibration_bins, 15 bins, top label"] = (lambda: ops.calibration_bins(members[0], y, cal, 15, -1), 2 * C_ * 4 * M)
+rows(named)
 
 if not a.no_models:
     from ultrasound_modeling_amd.ensemble import Ensemble                        # noqa: E402
@@ -91,15 +71,6 @@ if not a.no_models:
     single = models[0]
     single.capture_predict_graph(x)
     sx = single.predict_inputs()
-
-    def timed(fn):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(a.replays):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) / a.replays
 
     print(f"Arch B {B} x {H} x {W} x 10, captured predict, {a.rounds} rounds of {a.replays} replays, the two forms alternating:")
     for K in a.k:
@@ -114,21 +85,15 @@ if not a.no_models:
             for _ in range(K):
                 single.predict(sx)
 
-        for fn in (k_singles, lambda: ens.predict(ex)):
-            for _ in range(3):
-                fn()
-        torch.cuda.synchronize()
-        te, ts = [], []
-        for _ in range(a.rounds):
-            ts.append(timed(k_singles))
-            te.append(timed(lambda: ens.predict(ex)))
-        se, ss = spread(te), spread(ts)
+        forms = {"singles": k_singles, "ensemble": lambda: ens.predict(ex)}
+        ts = {n: [] for n in forms}
+        for r, n in timing.schedule(list(forms), a.rounds):                     # one window of each form per round; the first round warms up
+            ts[n] += timing.time_steps(forms[n], 1, a.replays, warm=0 if r else 3)
+        se, ss = timing.spread(ts["ensemble"]), timing.spread(ts["singles"])
         out["predict_ms"][str(K)] = {"ensemble": se, "k_single_replays": ss, "ratio_of_medians": round(se["median"] / ss["median"], 4)}
         print(f"  K={K}: ensemble graph {se['min']:8.4f} ms min, {se['median']:8.4f} median, {se['max']:8.4f} max | {K} single replays "
               f"{ss['min']:8.4f} min, {ss['median']:8.4f} median, {ss['max']:8.4f} max | ensemble / singles = {se['median'] / ss['median']:.4f}", flush=True)
         del ens
 
 if a.json:
-    os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
-    with open(a.json, "w") as f:
-        json.dump(out, f, indent=1)
+    timing.write_json(a.json, out)

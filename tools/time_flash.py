@@ -5,6 +5,8 @@ import sys
 
 import torch
 
+import timing
+
 sys.path.insert(0, ".")
 from ultrasound_modeling_amd import ops
 
@@ -19,15 +21,8 @@ scale = 1 / math.sqrt(nh)
 
 
 def t(fn, reps=20):
-    for _ in range(3):
-        fn()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / reps * 1e3
+    """Eager: three warm-up calls, then `reps` calls between two events -> microseconds per call."""
+    return timing.time_steps(fn, 1, reps, warm=3)[0] * 1e3
 
 
 fl = 4 * B * nh * N * N * 128

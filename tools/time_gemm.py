@@ -4,6 +4,8 @@ import sys
 
 import torch
 
+import timing
+
 sys.path.insert(0, ".")
 from ultrasound_modeling_amd import ops
 from ultrasound_modeling_amd.flat import FlatParams
@@ -18,16 +20,9 @@ x = torch.randn(1, M, 1, K).to(torch.bfloat16).cuda()
 dy = torch.randn(1, M, 1, N).to(torch.bfloat16).cuda()
 
 
-def t(fn):
-    for _ in range(3):
-        fn()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / reps * 1e3
+def t(fn, reps=reps):
+    """Eager: three warm-up calls, then `reps` calls between two events -> microseconds per call."""
+    return timing.time_steps(fn, 1, reps, warm=3)[0] * 1e3
 
 
 fl = 2.0 * M * K * N

@@ -2,7 +2,7 @@
 shape with tools/time_conv.py's method: `reps` launches captured into one HIP graph, replayed three times between two events.
 usage: python tools/time_head.py [--lib PATH] [--rounds N] [B h w Cin C]
   --lib PATH: time that build of the library instead (e.g. the parent commit's, which has only the CategoricalCrossentropy entry point);
-  each variant is timed `rounds` times, so the run-to-run spread stands beside every number.
+  each variant is timed `rounds` times, the variants alternating inside every round (tools/timing.py), so the spread stands beside every number.
 With a library that has the region-overlap losses (csrc/overlap_loss.hip) it also times, in the same process, the path they take - the
 probabilities-only head launch, the sums pass and the backward pass, together and one by one - and the softmax_loss kernel on the same
 pixels, and prints each kernel's achieved bytes/s against the bytes it must move."""
@@ -11,6 +11,8 @@ import ctypes as C
 import sys
 
 import torch
+
+import timing
 
 sys.path.insert(0, ".")
 from ultrasound_modeling_amd import _lib as L
@@ -46,33 +48,15 @@ def launch(cl):
     assert rc == 0, rc
 
 
-def t(fn, reps):
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    gr = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(gr):
-        for _ in range(reps):
-            fn()
-    gr.replay()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(3):
-        gr.replay()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / (3 * reps) * 1e3
-
-
 variants = [("cce (loss_kind 0)", None)]
 if has_cl:
     cf = (C.c_float * 8)(0.06329, 0.027567, 0.90914)
     variants += [("my_loss_cat (gamma 0)", L.ClassLoss(cf, 0.0, 3.0)), ("focal (gamma 2)", L.ClassLoss((C.c_float * 8)(*([1.0] * 8)), 2.0, 1.0))]
 print(f"{a.lib}: fused head {B}x{h}x{w} {Cin} channels, {NC} classes")
-for name, cl in variants:
-    ts = [t(lambda: launch(cl), a.reps) for _ in range(a.rounds)]
-    print(f"  {name:24s} {min(ts):7.2f} us min, {sorted(ts)[len(ts) // 2]:7.2f} median, {max(ts):7.2f} max   [{' '.join(f'{v:.2f}' for v in ts)}]")
+timing.require_gpu("time_head")
+for name, ts in timing.time_calls({name: lambda cl=cl: launch(cl) for name, cl in variants}, a.rounds, a.reps, replays=3).items():
+    s = timing.spread(ts, 2)
+    print(f"  {name:24s} {s['min']:7.2f} us min, {s['median']:7.2f} median, {s['max']:7.2f} max   [{' '.join(f'{v:.2f}' for v in ts)}]")
 
 if hasattr(lib, "usseg_overlap_loss_sums"):
     L.bind(lib, ["usseg_overlap_loss_sums", "usseg_overlap_loss_bwd", "usseg_softmax_loss_fwd_bwd"])
@@ -98,18 +82,17 @@ if hasattr(lib, "usseg_overlap_loss_sums"):
     def softmax_loss():
         assert lib.usseg_softmax_loss_fwd_bwd(C.byref(dq), logits.data_ptr(), y.data_ptr(), None, probs.data_ptr(), loss.data_ptr(), dl.data_ptr(), stream()) == 0
 
-    def row(name, fn, nbytes=None):
-        ts = [t(fn, a.reps) for _ in range(a.rounds)]
-        med = sorted(ts)[len(ts) // 2]
-        bw = "" if nbytes is None else f"   {nbytes / 1e6:6.1f} MB -> {nbytes / med / 1e6:5.2f} TB/s"
-        print(f"  {name:40s} {min(ts):7.2f} us min, {med:7.2f} median, {max(ts):7.2f} max{bw}")
-
     uw = (C.c_float * 8)(*([1.0 / NC] * NC))
     rd = 2 * M * NC * 4
-    row("head, probabilities only", head_probs_only)
+    named = {"head, probabilities only": (head_probs_only, None)}                 # name -> (fn, bytes it must move)
     for name, ol in (("dice", L.OverlapLoss(uw, 0.5, 0.5, 1.0, 1.0, 1.0, 0.0)), ("dice_ce", L.OverlapLoss(uw, 0.5, 0.5, 1.0, 1.0, 1.0, 1.0))):
-        row(f"{name}: head + sums + bwd", lambda: (head_probs_only(), sums(ol), bwd(ol)))
-        row(f"{name}: sums (pass 1)", lambda: sums(ol), rd)
-        row(f"{name}: bwd (pass 2)", lambda: bwd(ol), rd + M * 8)
+        named[f"{name}: head + sums + bwd"] = (lambda ol=ol: (head_probs_only(), sums(ol), bwd(ol)), None)
+        named[f"{name}: sums (pass 1)"] = (lambda ol=ol: sums(ol), rd)
+        named[f"{name}: bwd (pass 2)"] = (lambda ol=ol: bwd(ol), rd + M * 8)
     # softmax_loss_kernel: quad fp32 logits read (64 B per 2x2 pixels = 16 B a pixel), labels read AND probabilities written (2 * M*NC*4), dlogits written (8 B a pixel)
-    row("softmax_loss (quad logits, cce)", softmax_loss, M * 16 + 2 * M * NC * 4 + M * 8)
+    named["softmax_loss (quad logits, cce)"] = (softmax_loss, M * 16 + 2 * M * NC * 4 + M * 8)
+    ts = timing.time_calls({n: fn for n, (fn, _) in named.items()}, a.rounds, a.reps, replays=3)
+    for name, (_, nbytes) in named.items():
+        s = timing.spread(ts[name], 2)
+        bw = "" if nbytes is None else f"   {nbytes / 1e6:6.1f} MB -> {nbytes / s['median'] / 1e6:5.2f} TB/s"
+        print(f"  {name:40s} {s['min']:7.2f} us min, {s['median']:7.2f} median, {s['max']:7.2f} max{bw}")

@@ -1,4 +1,5 @@
 import sys, torch
+import timing
 sys.path.insert(0, ".")
 from ultrasound_modeling_amd import ops
 B, H, W, C = 16, 256, 256, 3
@@ -9,6 +10,7 @@ loss = torch.zeros(ops.ACC_FLOATS, device="cuda")
 dl = torch.empty(B, H // 2, W // 2, 16, dtype=torch.bfloat16, device="cuda")
 big = torch.empty(256 * 1024 * 1024 // 4, device="cuda")
 def run(): ops.softmax_loss(logits, y, probs, loss, dl, HW=H * W, C_classes=C, loss_kind=0, inv_global_batch=1 / 16, quad_w=W)
+# (one event pair per call with the cache flushed OUTSIDE the pair: the one protocol here that tools/timing.py does not offer)
 for _ in range(3): run()
 for flush in (False, True):
     ts = []
@@ -21,13 +23,8 @@ for flush in (False, True):
 
 # ---- the boundary term: sdf_labels alone, then the two passes of the overlap + boundary pair ---------------------
 def _time(fn, n=10):
-    for _ in range(3): fn()
-    ts = []
-    for _ in range(n):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(); fn(); e1.record(); torch.cuda.synchronize()
-        ts.append(e0.elapsed_time(e1) * 1e3)
-    return sorted(ts)[len(ts) // 2], min(ts), max(ts)
+    sp = timing.spread([ms * 1e3 for ms in timing.time_steps(fn, n, 1, warm=3)])         # eager, one call a window
+    return sp["median"], sp["min"], sp["max"]
 
 g = torch.Generator().manual_seed(0)
 lab = torch.rand(B, H // 16, W // 16, generator=g)                      # bench.py's labels: 16x16 blocks, about 30 % class 1/2

@@ -8,11 +8,12 @@
 
 usage: python tools/time_lovasz.py [--root DIR] [--loss NAME ...] [--rounds N] [--replays K] [--reps R] [--json PATH] [B H W]"""
 import argparse
-import json
 import os
 import sys
 
 import torch
+
+import timing
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -29,39 +30,21 @@ from ultrasound_modeling_amd import _lib as L                                   
 from ultrasound_modeling_amd import ops                                         # noqa: E402
 from ultrasound_modeling_amd.VisionTransformer import VisionTransformer         # noqa: E402
 
+timing.require_gpu("time_lovasz")
 out = {"root": a.root, "shape": [B, H, W], "step_ms": {}, "launch_us": {}}
 g = torch.Generator().manual_seed(0)
-x = torch.randn(B, H, W, 10, generator=g).clamp_(-1, 1).cuda()
-lab = torch.zeros(B, H, W, dtype=torch.long)
-lab[:, H // 3:H // 3 + H // 8, W // 3:W // 3 + W // 8] = 2                       # a bleed class of about 1.5 % of the pixels inside a band of class 1
-lab[:, H // 4:3 * H // 4, :][lab[:, H // 4:3 * H // 4, :] == 0] = 1
-y = torch.nn.functional.one_hot(lab, 3).float().cuda()
-
-
-def spread(ts):
-    ts = sorted(ts)
-    return {"min": round(ts[0], 4), "median": round(ts[len(ts) // 2], 4), "max": round(ts[-1], 4)}
-
+x, y = timing.bleed_batch(B, H, W, 10, g)
 
 print(f"{a.root}: Arch B {B} x {H} x {W} x 10, HIP-graph replay, {a.rounds} rounds of {a.replays} replays")
 for name in a.loss:
     kw = {"overlap": {}} if name in ("dice", "tversky", "dice_ce") else {}
     net = VisionTransformer(batch_size=B, img_size=(H, W), loss=name, **kw)
     net.capture_graph(x, y)
-    for _ in range(5):
-        net.train_step(x, y)
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(a.rounds):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(a.replays):
-            l, _p = net.train_step(x, y)
-        e1.record()
-        torch.cuda.synchronize()
-        ts.append(e0.elapsed_time(e1) / a.replays)
-    out["step_ms"][name] = dict(spread(ts), loss=float(l.item()))
-    print(f"  step, loss={name:10s} {min(ts):8.4f} ms min, {sorted(ts)[len(ts) // 2]:8.4f} median, {max(ts):8.4f} max   (loss {l.item():.5f})", flush=True)
+    last = {}
+    sp = timing.spread(timing.time_steps(lambda: last.update(loss=net.train_step(x, y)[0]), a.rounds, a.replays))
+    l = float(last["loss"].item())
+    out["step_ms"][name] = dict(sp, loss=l)
+    print(f"  step, loss={name:10s} {sp['min']:8.4f} ms min, {sp['median']:8.4f} median, {sp['max']:8.4f} max   (loss {l:.5f})", flush=True)
     del net
 
 if hasattr(L.load(), "usseg_lovasz_coeffs"):
@@ -76,43 +59,21 @@ if hasattr(L.load(), "usseg_lovasz_coeffs"):
     sws = torch.empty(ops.sort_ws_bytes(C_, M), dtype=torch.uint8).cuda()
     ll = ops.lovasz_loss([1.0] * C_, 1.0, 1.0)
     kw = dict(lovasz=ll, HW=H * W, C_classes=C_)
-
-    def t(fn):
-        for _ in range(2):
-            fn()
-        torch.cuda.synchronize()
-        gr = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(gr):
-            for _ in range(a.reps):
-                fn()
-        gr.replay()
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(3):
-            gr.replay()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) / (3 * a.reps) * 1e3
-
-    def row(name, fn, launches, nbytes):
-        ts = [t(fn) for _ in range(a.rounds)]
-        s = spread(ts)
-        out["launch_us"][name] = dict(s, launches=launches, MB=round(nbytes / 1e6, 1))
-        print(f"  {name:34s} {launches:3d} launches {s['min']:8.2f} us min, {s['median']:8.2f} median, {s['max']:8.2f} max   {nbytes / 1e6:6.1f} MB -> "
-              f"{nbytes / s['median'] / 1e6:5.2f} TB/s", flush=True)
-
     n = C_ * M
     hist = C_ * ((M + ops.SORT_TILE - 1) // ops.SORT_TILE) * 256 * 4
     per_pass = 4 * n + 2 * hist + (8 * n + hist) + 8 * n                         # histogram read; offsets read + written; scatter: pairs read, offsets read, pairs written
     sort_b = 4 * per_pass
-    print(f"the loss's launches at M = {M}, C = {C_} ({n} pairs):")
-    row("sort_pairs, 30 key bits", lambda: ops.sort_pairs(keys, vals, 30, sws), 12, sort_b)
-    row("lovasz_coeffs (keys, sort, scan)", lambda: ops.lovasz_coeffs(probs, y, gco, counts, ws, **kw), 16, 8 * n + 8 * n + sort_b + 4 * n + 4 * n + 4 * n)
-    row("lovasz_loss_sums", lambda: ops.lovasz_loss_sums(probs, y, gco, counts, acc, inv_global_batch=1.0 / B, **kw), 1, 12 * n)
-    row("lovasz_loss_bwd (quad)", lambda: ops.lovasz_loss_bwd(probs, y, gco, acc, dl, inv_global_batch=1.0 / B, quad_w=W, **kw), 1, 12 * n + 8 * M)
+    print(f"the loss's launches at M = {M}, C = {C_} ({n} pairs), the calls alternating:")
+    named = {"sort_pairs, 30 key bits": (lambda: ops.sort_pairs(keys, vals, 30, sws), 12, sort_b),
+             "lovasz_coeffs (keys, sort, scan)": (lambda: ops.lovasz_coeffs(probs, y, gco, counts, ws, **kw), 16, 8 * n + 8 * n + sort_b + 4 * n + 4 * n + 4 * n),
+             "lovasz_loss_sums": (lambda: ops.lovasz_loss_sums(probs, y, gco, counts, acc, inv_global_batch=1.0 / B, **kw), 1, 12 * n),
+             "lovasz_loss_bwd (quad)": (lambda: ops.lovasz_loss_bwd(probs, y, gco, acc, dl, inv_global_batch=1.0 / B, quad_w=W, **kw), 1, 12 * n + 8 * M)}
+    ts = timing.time_calls({k: fn for k, (fn, _, _) in named.items()}, a.rounds, a.reps, replays=3)
+    for name, (_, launches, nbytes) in named.items():
+        s = timing.spread(ts[name])
+        out["launch_us"][name] = dict(s, launches=launches, MB=round(nbytes / 1e6, 1))
+        print(f"  {name:34s} {launches:3d} launches {s['min']:8.2f} us min, {s['median']:8.2f} median, {s['max']:8.2f} max   {nbytes / 1e6:6.1f} MB -> "
+              f"{nbytes / s['median'] / 1e6:5.2f} TB/s", flush=True)
 
 if a.json:
-    os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
-    with open(a.json, "w") as f:
-        json.dump(out, f, indent=1)
+    timing.write_json(a.json, out)

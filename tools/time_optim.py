@@ -6,10 +6,11 @@ launch and the HBM bound of 28 B per parameter (29 with the mask) at 6.29 TB/s. 
 usage: python tools/time_optim.py [--reps 20] [--iters 15]"""
 import argparse
 import os
-import statistics
 import sys
 
 import torch
+
+import timing
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from ultrasound_modeling_amd import ops  # noqa: E402
@@ -36,31 +37,10 @@ def main():
             "adamw wd>0": lambda: ops.adamw_step(p, g, m, v, sumsq, 0.0, lr_t, wd, None, 0.9, 0.999, 1e-7),
             "adamw wd>0 mask": lambda: ops.adamw_step(p, g, m, v, sumsq, 0.0, lr_t, wd, mask, 0.9, 0.999, 1e-7),
         }
-        for label, fn in variants.items():
-            s = torch.cuda.Stream()
-            s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):
-                fn()
-            torch.cuda.current_stream().wait_stream(s)
-            torch.cuda.synchronize()
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                for _ in range(a.reps):
-                    fn()
-            graph.replay()
-            torch.cuda.synchronize()
-            ts = []
-            for _ in range(a.iters):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                graph.replay()
-                e1.record()
-                torch.cuda.synchronize()
-                ts.append(e0.elapsed_time(e1) * 1e3 / a.reps)
+        for label, ts in timing.time_calls(variants, a.iters, a.reps, replays=1).items():                           # the variants alternate
+            sp = timing.spread(ts)
             bound = n * (29 if "mask" in label else 28) / HBM * 1e6
-            print(f"{name} n={n} {label:16s} median {statistics.median(ts):7.1f} us  min {min(ts):7.1f} us  (HBM bound {bound:6.1f} us)",
-                  flush=True)
-            del graph
+            print(f"{name} n={n} {label:16s} median {sp['median']:7.1f} us  min {sp['min']:7.1f} us  (HBM bound {bound:6.1f} us)", flush=True)
 
 
 if __name__ == "__main__":

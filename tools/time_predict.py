@@ -10,12 +10,13 @@ B=1 row runs at 256x256x1 as well.  One JSON line per row.
 import argparse
 import json
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch  # noqa: E402
+
+import timing  # noqa: E402
 
 
 def build(arch, B, H, W, C):
@@ -33,19 +34,9 @@ def batch(B, H, W, C):
 
 
 def per_call_ms(fn, calls, repeats):
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(repeats):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(calls):
-            fn()
-        e1.record()
-        e1.synchronize()
-        out.append(e0.elapsed_time(e1) / calls)
-    return statistics.median(out), min(out), max(out)
+    """(median, min, max) over `repeats` windows of `calls` back-to-back calls, after three warm-up calls: ms per call."""
+    sp = timing.spread(timing.time_steps(fn, repeats, calls, warm=3), 6)
+    return sp["median"], sp["min"], sp["max"]
 
 
 def table(args):

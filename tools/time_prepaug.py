@@ -11,7 +11,6 @@ of the same batch through the NumPy / scipy restatement of tests/prepaug_restate
 import argparse
 import json
 import os
-import statistics
 import sys
 import time
 
@@ -20,6 +19,8 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
+
+import timing  # noqa: E402
 
 N, H, W, Cc = 64, 256, 80, 12
 
@@ -44,20 +45,12 @@ def main(a):
     if a.trace:
         print("trace: 3 batches", flush=True)
         return
-    per = []
-    for _ in range(a.repeats):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(a.calls):
-            dataAug_batch(xd, sets)
-        e1.record()
-        e1.synchronize()
-        per.append(e0.elapsed_time(e1) / a.calls)
+    per = timing.time_steps(lambda: dataAug_batch(xd, sets), a.repeats, a.calls, warm=0)
     t0 = time.perf_counter()
     for k in range(a.host_records):
         R.dataAug(x[k], sets[k], field[k])
     host = (time.perf_counter() - t0) * 1e3 * N / a.host_records
-    out = {"batch": [N, H, W, Cc], "device_ms": statistics.median(per), "device_ms_min_max": [min(per), max(per)], "host_ms": host,
+    out = {"batch": [N, H, W, Cc], "device_ms": timing.spread(per, 6)["median"], "device_ms_min_max": [min(per), max(per)], "host_ms": host,
            "host_records_timed": a.host_records, "record_bytes": int(x.nbytes)}
     print(f"device {out['device_ms']:.3f} ms per batch ({min(per):.3f} .. {max(per):.3f}); restatement on the host {host:.0f} ms per batch", flush=True)
     print(json.dumps(out), flush=True)

@@ -10,7 +10,6 @@ wrong kernel is not timed.  Nothing has a predecessor to be compared with: the n
 
 usage: python tools/time_scores.py [--rounds N] [--reps R] [--replays P] [--json PATH] [N H W]"""
 import argparse
-import json
 import os
 import sys
 
@@ -27,12 +26,13 @@ a = ap.parse_args()
 import numpy as np                                                               # noqa: E402
 import torch                                                                     # noqa: E402
 
+import timing                                                                    # noqa: E402
+
 sys.path.insert(0, ROOT)
 from ultrasound_modeling_amd import ops                                          # noqa: E402
 from ultrasound_modeling_amd.metrics import ScanGeometry                         # noqa: E402
 
-if not torch.cuda.is_available():
-    sys.exit("time_scores: needs a GPU (a timing on the host says nothing)")
+timing.require_gpu("time_scores")
 
 N, H, W = a.shape
 M = N * H * W
@@ -40,44 +40,11 @@ g = torch.Generator().manual_seed(0)
 out = {"shape": [N, H, W], "rounds": a.rounds, "launches_per_round": a.reps * a.replays, "call_us": {}}
 
 
-def spread(ts):
-    ts = sorted(ts)
-    return {"min": round(ts[0], 4), "median": round(ts[len(ts) // 2], 4), "max": round(ts[-1], 4)}
-
-
-def graph_of(fn):
-    for _ in range(2):
-        fn()
-    torch.cuda.synchronize()
-    gr = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(gr):
-        for _ in range(a.reps):
-            fn()
-    gr.replay()
-    torch.cuda.synchronize()
-    return gr
-
-
-def t(gr):
-    """`replays` replays of one graph of `reps` calls: microseconds per call."""
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(a.replays):
-        gr.replay()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / (a.replays * a.reps) * 1e3
-
-
 def rows(named):
     """Time the named calls (name -> (fn, bytes)) alternating inside every round."""
-    graphs = {n: graph_of(fn) for n, (fn, _) in named.items()}
-    ts = {n: [] for n in named}
-    for _ in range(a.rounds):
-        for n, gr in graphs.items():
-            ts[n].append(t(gr))
+    ts = timing.time_calls({n: fn for n, (fn, _) in named.items()}, a.rounds, a.reps, a.replays)
     for n, (_, nbytes) in named.items():
-        s = spread(ts[n])
+        s = timing.spread(ts[n])
         out["call_us"][n] = dict(s, MB=round(nbytes / 1e6, 2), TBps=round(nbytes / s["median"] / 1e6, 3))
         print(f"  {n:52s} {s['median']:9.2f} us median ({s['min']:.2f} - {s['max']:.2f})   {nbytes / 1e6:7.2f} MB -> {nbytes / s['median'] / 1e6:5.2f} TB/s",
               flush=True)
@@ -142,6 +109,5 @@ b1, b2 = torch.empty((1000, K), dtype=torch.int64, device="cuda"), torch.empty((
 rows({f"bootstrap_sums U={N} K=8 R=1000": (lambda: ops.bootstrap_sums(units, 1000, 1, out=b1, check=False), 8 * K * (N + 1000)),
       f"bootstrap_sums U={N} K=8 R=10000": (lambda: ops.bootstrap_sums(units, 10000, 1, out=b2, check=False), 8 * K * (N + 10000)),
       "bootstrap_sums U=64 K=8 R=10000": (lambda: ops.bootstrap_sums(patients, 10000, 1, out=b2, check=False), 8 * K * (64 + 10000))})
-os.makedirs(os.path.dirname(a.json), exist_ok=True)
-json.dump(out, open(a.json, "w"), indent=1)
+timing.write_json(a.json, out)
 print("wrote", a.json)

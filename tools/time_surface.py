@@ -14,42 +14,17 @@ instead (for a kernel trace).  One JSON line per (shape, content); `--json` appe
 import argparse
 import json
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
+import timing  # noqa: E402
+
 from ultrasound_modeling_amd import ops  # noqa: E402
 
 N, REPLAYS, ROUNDS = 16, 3, 5
-
-
-def graph_us(fn):
-    """median, min, max over ROUNDS of the time of one call inside REPLAYS replays of the captured fn, in microseconds"""
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        fn()
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        fn()
-    for _ in range(3):
-        g.replay()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(ROUNDS):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(REPLAYS):
-            g.replay()
-        e1.record()
-        e1.synchronize()
-        out.append(e0.elapsed_time(e1) * 1e3 / REPLAYS)
-    return [round(v, 1) for v in (statistics.median(out), min(out), max(out))]
 
 
 def inputs(H, W):
@@ -66,6 +41,7 @@ def main():
     ap.add_argument("--tag", default="this")
     ap.add_argument("--eager", type=int, default=0)
     a = ap.parse_args()
+    timing.require_gpu("time_surface")
     stats = getattr(ops, "surface_stats", None)
     for H, W in ((256, 80), (256, 256)):
         ws = torch.empty(ops.surface_stats_ws_bytes(N, H, W) if stats else int(ops.L.load().usseg_surface_ws_bytes(N, H, W)), dtype=torch.uint8, device="cuda")
@@ -84,8 +60,9 @@ def main():
                 torch.cuda.synchronize()
                 continue
             # (surface_dist allocates its two small results: inside a capture they come from the graph's pool, once)
-            for key, fn in calls:
-                r[key] = graph_us(fn)
+            for key, ts in timing.time_calls(dict(calls), ROUNDS, 1, REPLAYS).items():          # the calls alternate; [median, min, max]
+                sp = timing.spread(ts, 1)
+                r[key] = [sp["median"], sp["min"], sp["max"]]
             c, _ = ops.surface_dist(ma, mb, ws=ws)
             r["surface_pixels"] = [int(c[:, 0].sum()), int(c[:, 1].sum())]
             r["max_distance"] = round(float(c[:, 2:].max()) ** 0.5, 1)

@@ -14,7 +14,6 @@ against fp64, over the arguments tests/test_gpu_operating_point.py feeds them: t
 usage: python tools/time_sweep.py [--rounds N] [--reps R] [--replays P] [--json PATH] [--build-only] [--probe] [B H W]"""
 import argparse
 import ctypes as C
-import json
 import os
 import subprocess
 import sys
@@ -55,11 +54,12 @@ if a.build_only:
 import numpy as np                                                               # noqa: E402
 import torch                                                                     # noqa: E402
 
+import timing                                                                    # noqa: E402
+
 sys.path.insert(0, ROOT)
 from ultrasound_modeling_amd import _lib as L, ops                               # noqa: E402
 
-if not torch.cuda.is_available():
-    sys.exit("time_sweep: needs a GPU (a timing on the host says nothing)")
+timing.require_gpu("time_sweep")
 L.load()
 C.CDLL(L.LIB_PATH, mode=C.RTLD_GLOBAL)
 plain = C.CDLL(PLAIN)
@@ -110,7 +110,7 @@ def probe():
 if a.probe:
     res = probe()
     path = os.path.join(os.path.dirname(a.json), "sweep_ulp.json")
-    json.dump(res, open(path, "w"), indent=1)
+    timing.write_json(path, res)
     print("wrote", path)
     sys.exit(0)
 
@@ -122,44 +122,11 @@ g = torch.Generator().manual_seed(0)
 out = {"shape": [B, H, W, C_], "bins": bins, "rounds": a.rounds, "launches_per_round": a.reps * a.replays, "launch_us": {}}
 
 
-def spread(ts):
-    ts = sorted(ts)
-    return {"min": round(ts[0], 4), "median": round(ts[len(ts) // 2], 4), "max": round(ts[-1], 4)}
-
-
-def graph_of(fn):
-    for _ in range(2):
-        fn()
-    torch.cuda.synchronize()
-    gr = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(gr):
-        for _ in range(a.reps):
-            fn()
-    gr.replay()
-    torch.cuda.synchronize()
-    return gr
-
-
-def t(gr):
-    """`replays` replays of one graph of `reps` launches: microseconds per launch."""
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(a.replays):
-        gr.replay()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / (a.replays * a.reps) * 1e3
-
-
 def rows(named, nbytes):
     """Time the named launches alternating inside every round."""
-    graphs = {n: graph_of(fn) for n, fn in named.items()}
-    ts = {n: [] for n in named}
-    for _ in range(a.rounds):
-        for n, gr in graphs.items():
-            ts[n].append(t(gr))
+    ts = timing.time_calls(named, a.rounds, a.reps, a.replays)
     for n in named:
-        s = spread(ts[n])
+        s = timing.spread(ts[n])
         out["launch_us"][n] = dict(s, MB=round(nbytes / 1e6, 2), TBps=round(nbytes / s["median"] / 1e6, 3))
         print(f"  {n:44s} {s['median']:8.2f} us median ({s['min']:.2f} - {s['max']:.2f})   {nbytes / 1e6:6.2f} MB -> {nbytes / s['median'] / 1e6:5.2f} TB/s",
               flush=True)
@@ -204,6 +171,5 @@ rows({"temperature_nll, 16 betas": lambda: ops.temperature_nll(uniform, y, betas
       "temperature_nll, 1 beta": lambda: ops.temperature_nll(uniform, y, betas[:1], nll1)}, two)
 rows({"apply_temperature": lambda: ops.apply_temperature(uniform, beta, out=dst),
       "apply_temperature, in place": lambda: ops.apply_temperature(inplace, beta, out=inplace)}, two)
-os.makedirs(os.path.dirname(a.json), exist_ok=True)
-json.dump(out, open(a.json, "w"), indent=1)
+timing.write_json(a.json, out)
 print("wrote", a.json)

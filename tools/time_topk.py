@@ -10,10 +10,10 @@
 usage: python tools/time_topk.py [--parent DIR] [--rounds N] [--replays K] [--reps R] [--json PATH] [B H W]
        python tools/time_topk.py --child ROOT --loss NAME ... [--replays K] [B H W]      (one round of one tree: prints a JSON line)"""
 import argparse
-import json
 import os
-import subprocess
 import sys
+
+import timing
 
 HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ap = argparse.ArgumentParser()
@@ -29,38 +29,20 @@ a = ap.parse_args()
 B, H, W = a.shape
 
 
-def median(ts):
-    return sorted(ts)[len(ts) // 2]
-
-
 def child(root, losses):
     """One round of one tree: a captured Arch B step per loss -> {loss: ms per step}."""
     sys.path.insert(0, root)
     import torch
     from ultrasound_modeling_amd.VisionTransformer import VisionTransformer
-    g = torch.Generator().manual_seed(0)
-    x = torch.randn(B, H, W, 1, generator=g).clamp_(-1, 1).cuda()
-    lab = torch.zeros(B, H, W, dtype=torch.long)
-    lab[:, H // 3:H // 3 + H // 8, W // 3:W // 3 + W // 8] = 2                   # a bleed class of about 1.5 % of the pixels inside a band of class 1
-    lab[:, H // 4:3 * H // 4, :][lab[:, H // 4:3 * H // 4, :] == 0] = 1
-    y = torch.nn.functional.one_hot(lab, 3).float().cuda()
+    x, y = timing.bleed_batch(B, H, W, 1, torch.Generator().manual_seed(0))
     res = {}
     for name in losses:
         kw = {"overlap": {}} if name in ("dice", "tversky", "dice_ce") else {}
         net = VisionTransformer(batch_size=B, img_size=(H, W), in_channels=1, loss=name, **kw)
         net.capture_graph(x, y)
-        for _ in range(5):
-            net.train_step(x, y)
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(a.replays):
-            net.train_step(x, y)
-        e1.record()
-        torch.cuda.synchronize()
-        res[name] = e0.elapsed_time(e1) / a.replays
+        res[name] = timing.time_steps(lambda: net.train_step(x, y), 1, a.replays)[0]
         del net
-    print("TIME_TOPK " + json.dumps(res), flush=True)
+    timing.emit("TIME_TOPK", res)
 
 
 if a.child is not None:
@@ -71,6 +53,7 @@ import torch                                                                    
 sys.path.insert(0, HERE)
 from ultrasound_modeling_amd import ops                                           # noqa: E402
 
+timing.require_gpu("time_topk")
 out = {"shape": [B, H, W], "launch_us": {}, "step_ms": {}}
 C_, M = 3, B * H * W
 g = torch.Generator().manual_seed(0)
@@ -81,34 +64,17 @@ acc = torch.zeros(ops.OVERLAP_ACC_FLOATS).cuda()
 dl = torch.empty(B, H // 2, W // 2, 16, dtype=torch.bfloat16).cuda()
 
 
-def t(fn):
-    for _ in range(2):
-        fn()
-    torch.cuda.synchronize()
-    gr = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(gr):
-        for _ in range(a.reps):
-            fn()
-    gr.replay()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(3):
-        gr.replay()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / (3 * a.reps) * 1e3
+def rows(named):
+    """Time the named calls (name -> (fn, launches, bytes)), three replays a window, alternating inside every round."""
+    ts = timing.time_calls({n: fn for n, (fn, _, _) in named.items()}, a.rounds, a.reps, replays=3)
+    for name, (_, launches, nbytes) in named.items():
+        sp = timing.spread(ts[name], 2)
+        out["launch_us"][name] = dict(sp, launches=launches, MB=round(nbytes / 1e6, 1))
+        print(f"  {name:44s} {launches:2d} launches {sp['min']:8.2f} us min, {sp['median']:8.2f} median, {sp['max']:8.2f} max   {nbytes / 1e6:6.1f} MB -> "
+              f"{nbytes / sp['median'] / 1e6:5.2f} TB/s", flush=True)
 
 
-def row(name, fn, launches, nbytes):
-    ts = sorted(t(fn) for _ in range(a.rounds))
-    out["launch_us"][name] = dict(min=round(ts[0], 2), median=round(median(ts), 2), max=round(ts[-1], 2), launches=launches, MB=round(nbytes / 1e6, 1))
-    print(f"  {name:44s} {launches:2d} launches {ts[0]:8.2f} us min, {median(ts):8.2f} median, {ts[-1]:8.2f} max   {nbytes / 1e6:6.1f} MB -> "
-          f"{nbytes / median(ts) / 1e6:5.2f} TB/s", flush=True)
-
-
-print(f"the top-k loss's launches at M = {M}, C = {C_}, fraction 0.1 (HIP-graph replay, {a.rounds} rounds):")
-for scope in ("batch", "image"):
+def scope_rows(scope):
     tk = ops.topk_loss(1.0, scope)
     ws = torch.empty(ops.topk_ws_bytes(M, H * W, scope), dtype=torch.uint8).cuda()
     kw = dict(topk=tk, HW=H * W, C_classes=C_)
@@ -118,32 +84,27 @@ for scope in ("batch", "image"):
     pix()
     keys = ops.topk_ws_views(ws, M, H * W, scope)[0].view(torch.int32).clone().view(-1, M if scope == "batch" else H * W)
     sws = torch.empty(ops.topk_select_ws_bytes(keys.shape[0]), dtype=torch.uint8).cuda()
-    row(f"{scope}: topk_pixel_loss (l, 4 digits, sel)", pix, 5, 24 * M + 4 * M + 3 * 4 * M)
-    row(f"{scope}: topk_select alone on those keys", lambda: ops.topk_select(keys, fraction=frac, ws=sws), 5, 4 * 4 * M)
-    row(f"{scope}: topk_loss_sums", sums, 1, 4 * M)
-    row(f"{scope}: topk_loss_bwd (quad)", bwd, 1, 24 * M + 4 * M + 8 * M)
-    row(f"{scope}: the whole sequence", lambda: (pix(), sums(), bwd()), 7, 24 * M + 4 * M + 3 * 4 * M + 4 * M + 24 * M + 4 * M + 8 * M)
+    rows({f"{scope}: topk_pixel_loss (l, 4 digits, sel)": (pix, 5, 24 * M + 4 * M + 3 * 4 * M),
+          f"{scope}: topk_select alone on those keys": (lambda: ops.topk_select(keys, fraction=frac, ws=sws), 5, 4 * 4 * M),
+          f"{scope}: topk_loss_sums": (sums, 1, 4 * M),
+          f"{scope}: topk_loss_bwd (quad)": (bwd, 1, 24 * M + 4 * M + 8 * M),
+          f"{scope}: the whole sequence": (lambda: (pix(), sums(), bwd()), 7, 24 * M + 4 * M + 3 * 4 * M + 4 * M + 24 * M + 4 * M + 8 * M)})
 
-trees = [("this", HERE, a.loss)] + ([("parent", os.path.abspath(a.parent), ["cce"])] if a.parent else [])
-runs = {}
+
+print(f"the top-k loss's launches at M = {M}, C = {C_}, fraction 0.1 (HIP-graph replay, {a.rounds} rounds, the calls of a scope alternating):")
+for scope in ("batch", "image"):
+    scope_rows(scope)
+
+trees = [("this", HERE, ["--loss", *a.loss])] + ([("parent", os.path.abspath(a.parent), ["--loss", "cce"])] if a.parent else [])
 print(f"Arch B {B} x {H} x {W} x 1 training step, HIP-graph replay, {a.rounds} rounds of {a.replays} replays, the trees alternating:")
-for r in range(a.rounds):
-    for tag, root, losses in trees:
-        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", root, "--loss", *losses, "--replays", str(a.replays), str(B), str(H), str(W)],
-                           capture_output=True, text=True, timeout=600)
-        if p.returncode != 0:
-            sys.exit(f"{tag} tree, round {r}: exit {p.returncode}\n{p.stdout[-2000:]}\n{p.stderr[-2000:]}")        # nothing more is started after a failure
-        line = [ln for ln in p.stdout.splitlines() if ln.startswith("TIME_TOPK ")][-1]
-        for name, ms in json.loads(line[len("TIME_TOPK "):]).items():
-            runs.setdefault(f"{tag}:{name}", []).append(ms)
+runs = timing.alternate_trees(os.path.abspath(__file__), trees, a.rounds, "TIME_TOPK", ["--replays", str(a.replays), str(B), str(H), str(W)], timeout=600)
 for key, ts in runs.items():
-    out["step_ms"][key] = dict(min=round(min(ts), 4), median=round(median(ts), 4), max=round(max(ts), 4), rounds=[round(v, 4) for v in ts])
-    print(f"  step, {key:18s} {min(ts):8.4f} ms min, {median(ts):8.4f} median, {max(ts):8.4f} max", flush=True)
+    sp = timing.spread(ts)
+    out["step_ms"][key] = dict(sp, rounds=[round(v, 4) for v in ts])
+    print(f"  step, {key:18s} {sp['min']:8.4f} ms min, {sp['median']:8.4f} median, {sp['max']:8.4f} max", flush=True)
 base = out["step_ms"].get("parent:cce", out["step_ms"].get("this:cce"))
 if base:
     for key, v in out["step_ms"].items():
         v["vs_cce_us"] = round((v["median"] - base["median"]) * 1e3, 1)
 if a.json:
-    os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
-    with open(a.json, "w") as f:
-        json.dump(out, f, indent=1)
+    timing.write_json(a.json, out)

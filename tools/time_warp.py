@@ -8,13 +8,13 @@ numbers to --out.  DESIGN.md section 4h-2.
 usage: python tools/time_warp.py [--reps 20] [--iters 15] [--out profiles/warp_time.json]"""
 import argparse
 import ctypes as C
-import json
 import os
 import random
-import statistics
 import sys
 
 import torch
+
+import timing
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from ultrasound_modeling_amd import DataAugs, _lib as L, ops, warp as Wp  # noqa: E402
@@ -23,36 +23,13 @@ SHAPE = (16, 256, 80, 10)
 STEP_MS = (2.77, 2.91)          # the Arch B training step (README)
 
 
-def _time(fn, reps, iters):
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(s):
-        fn()
-    torch.cuda.current_stream().wait_stream(s)
-    torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        for _ in range(reps):
-            fn()
-    graph.replay()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(iters):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        graph.replay()
-        e1.record()
-        torch.cuda.synchronize()
-        ts.append(e0.elapsed_time(e1) * 1e3 / reps)
-    return statistics.median(ts), min(ts)
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--iters", type=int, default=15)
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "warp_time.json"))
     a = ap.parse_args()
+    timing.require_gpu("time_warp")
     B, H, W, Cc = SHAPE
     g = torch.Generator(device="cuda").manual_seed(1)
     x = torch.randn(SHAPE, generator=g, device="cuda", dtype=torch.float64)
@@ -75,8 +52,8 @@ def main():
     def warp_augment():
         Wp.elastic_warp(x, y, warp_table, weights, out=(xw, yw))
         augment(xw, yw)
-    aug, aug_min = _time(lambda: augment(x, y), a.reps, a.iters)
-    both, both_min = _time(warp_augment, a.reps, a.iters)
+    ts = timing.time_calls({"augment": lambda: augment(x, y), "both": warp_augment}, a.iters, a.reps, replays=1)      # the two alternate
+    (aug, aug_min), (both, both_min) = ((sp["median"], sp["min"]) for sp in (timing.spread(ts["augment"]), timing.spread(ts["both"])))
     added = both - aug
     pixels = B * H * W
     nbytes = 2 * pixels * Cc * 8 + 2 * pixels * 4 + 2 * int(lib.usseg_warp_ws_bytes(B, H, W))
@@ -90,10 +67,7 @@ def main():
     print(f"warp, then augment       median {both:7.1f} us  min {both_min:7.1f} us", flush=True)
     print(f"added by the warp        {added:7.1f} us = {100 * added * 1e-3 / STEP_MS[0]:.1f} % of a {STEP_MS[0]} ms step; {nbytes / 1e6:.1f} MB at "
           f"{result['warp_achieved_TB_per_s']} TB/s", flush=True)
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump(result, f, indent=1)
-        f.write("\n")
+    timing.write_json(a.out, result)
 
 
 if __name__ == "__main__":
