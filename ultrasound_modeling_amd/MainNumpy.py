@@ -77,6 +77,7 @@ class Process(object):
                     print()
                 if terminator:
                     break
+            flush(neuralnet)        # accumulate=N: a short last group still takes its optimiser step, before validation and saving
             print()
             loss = float(loss)      # the epoch's last step (:47,70: reduce_sum of a scalar); after a graph replay the static buffer
             m = self.tr_metrics.result()
@@ -157,7 +158,7 @@ class Process(object):
 
 
 def main(train_path, val_path, save_path=None, epochs=50, batch_size=32, num_classes=3, *, loss="cce", overlap=None, boundary=None, lovasz=None,
-         average=None, warp=None, warp_seed=0, topk=None, teacher=None, distill=None):
+         average=None, warp=None, warp_seed=0, topk=None, teacher=None, distill=None, accumulate=None):
     """MainNumpy.py:150-177 with the paths as arguments: ``VisionTransformer(32, img_size=(256, 80))`` over a ``Dataset_2.Dataset``,
     50 epochs, then a save if ``save_path`` is given.  ``loss``: the model's ``loss=`` ("cce", "my_loss_cat", "focal", "dice", "tversky",
     "dice_ce"); ``overlap``: the settings of the last three (``VisionTransformer(overlap=...)``), which also add a per-class Dice line to the test report;
@@ -169,7 +170,9 @@ def main(train_path, val_path, save_path=None, epochs=50, batch_size=32, num_cla
     "topk" / "dice_topk" with their settings in ``topk`` (``VisionTransformer(topk=...)``: the top-k cross-entropy; the Dice line too).
     "distill" with ``teacher`` (a model, an ``Ensemble``, or checkpoint paths - a list or a comma-separated string; several make an ensemble) and
     its settings in ``distill`` (``VisionTransformer(distill=...)``): knowledge distillation; the test report adds the hard and soft terms of
-    the last validation batch."""
+    the last validation batch.  ``accumulate`` (an integer N >= 1; None: 1): ``VisionTransformer(accumulate=N)`` - every ``batch_size`` batch is a
+    micro-batch and N of them make one optimiser step; a short last group of an epoch is flushed before validation and saving, and the epoch
+    loss stays the last micro-batch's."""
     from .Dataset_2 import Dataset
     from .VisionTransformer import VisionTransformer, overlap_settings
     dataset = Dataset(train_path, val_path, num_classes, warp=warp, warp_seed=warp_seed)
@@ -180,7 +183,7 @@ def main(train_path, val_path, save_path=None, epochs=50, batch_size=32, num_cla
             teacher = load_teacher(teacher, input_size, 10, "cuda", num_classes=num_classes)
         kw.update(teacher=teacher, distill=distill)
     neuralnet = VisionTransformer(batch_size, img_size=input_size, num_classes=num_classes, loss=loss, overlap=overlap_settings(loss, overlap),
-                                  boundary=boundary, lovasz=lovasz, average=average_setting(average), **kw)
+                                  boundary=boundary, lovasz=lovasz, average=average_setting(average), accumulate=accumulate, **kw)
     print(len(neuralnet.visionModel.layers))
     process = Process(batch_size=batch_size, num_classes=num_classes)
     process.training(neuralnet=neuralnet, dataset=dataset, epochs=epochs)
@@ -189,6 +192,13 @@ def main(train_path, val_path, save_path=None, epochs=50, batch_size=32, num_cla
         if average is not None:
             neuralnet.save_averaged(save_path + ".avg")
     return neuralnet, process
+
+
+def flush(neuralnet):
+    """``flush_step()`` of a model that has it (``step.TrainStepDriver``; nothing pending: nothing happens): the end of an epoch's training loop."""
+    fn = getattr(neuralnet, "flush_step", None)
+    if fn is not None:
+        fn()
 
 
 def averaging(neuralnet) -> bool:

@@ -50,7 +50,7 @@ from typing import Optional, Tuple
 import torch
 import torch.distributed as dist
 from . import knobs
-from .MainNumpy import averaging
+from .MainNumpy import averaging, flush
 from .distill import distill_line
 from .metrics import dice_line
 
@@ -280,6 +280,7 @@ class Process(object):
             self._print('.', end='')
             if (self.train_iter + 1) % 100 == 0:
                 self._print()
+        flush(neuralnet)     # accumulate=N: a short last group still takes its optimiser step (every rank holds the same count: one more exchange)
         loss = last.detach().reshape(()).clone()         # after a replay ``last`` is the step's static buffer, still this last step's
         if tr.world > 1:
             dist.all_reduce(loss, op=dist.ReduceOp.SUM, group=self.group)                        # :131
@@ -305,7 +306,7 @@ class Process(object):
 
 def main(train_path, val_path, save_path=None, epochs=51, batch_size=64, use_vit=True, *, seed=0, schedule=False, capture_graph=True,
          loss="cce", overlap=None, boundary=None, lovasz=None, average=None, warp=None, topk=None, teacher=None, distill=None,
-         teacher_use_vit=None, teacher_flip=False):
+         teacher_use_vit=None, teacher_flip=False, accumulate=None):
     """MainParallel.py:201-216 with the paths as arguments: ``VisionTransformer(batch_size=64)`` with the ViT bottleneck, 51 epochs,
     then rank 0 saves if ``save_path`` is given.  Every rank seeds ``random`` with ``seed``, so all draw the same augmentations.
     ``loss``: the model's ``loss=`` ("cce", "my_loss_cat", "focal"); every replica divides it by the global batch all the same.  The
@@ -325,6 +326,8 @@ def main(train_path, val_path, save_path=None, epochs=51, batch_size=64, use_vit
     every rank keeps the same average (no exchange is added), the tests report the averaged model and rank 0 also saves ``<save_path>.avg``.
     ``warp`` (a ``warp.warp_config`` dict or the ``--warp`` string; default off): elastic / affine warp of every training batch ahead of ``dataAug``;
     its draws come from ``random.Random(seed)`` on every rank, each rank draws the whole global batch and keeps its slice.
+    ``accumulate`` (``--accumulate N``; None: 1): every global batch is a micro-batch and N of them make one optimiser step - ONE gradient exchange
+    and one update per N batches; a short last group of an epoch is flushed before the test and the save.
     Under ``nccl`` the model lives on ``cuda:LOCAL_RANK``; the ``USSEG_DIST_BACKEND=gloo`` rehearsal keeps every rank on device 0."""
     from .Dataset import Dataset
     from .MainNumpy import average_setting
@@ -344,7 +347,7 @@ def main(train_path, val_path, save_path=None, epochs=51, batch_size=64, use_vit
         kw.update(teacher=teacher, distill=distill)
     neuralnet = VisionTransformer(batch_size, img_size=(dataset.height, dataset.width), in_channels=dataset.channel, use_vit=use_vit,
                                   device=str(device), loss=loss, overlap=overlap_settings(loss, overlap), boundary=boundary, lovasz=lovasz,
-                                  average=average_setting(average), **kw)
+                                  average=average_setting(average), accumulate=accumulate, **kw)
     if rank == 0:
         print(len(neuralnet.visionModel.layers))
     process = Process(batch_size, schedule=schedule, capture_graph=capture_graph)
@@ -387,6 +390,8 @@ def _cli(argv=None):
     ap.add_argument("--average", default=None, metavar="ema:DECAY[:dynamic] | swa:START:PERIOD",
                     help="keep an EMA or SWA average of the weights inside the optimiser step; the tests report the averaged model and "
                          "--save also writes SAVE.avg with the averaged weights")
+    ap.add_argument("--accumulate", type=int, default=None, metavar="N",
+                    help="gradient accumulation: N global batches (micro-batches) per optimiser step - one gradient exchange and one update per N")
     ap.add_argument("--warp", default=None, metavar="SPEC",
                     help="warp every training batch elastically and affinely on the device before dataAug, e.g. "
                          "sigma=8,magnitude=2:1,p=0.5,rotate=5,scale=0.05,shift=0:0 (any subset; these are the defaults)")
@@ -395,6 +400,12 @@ def _cli(argv=None):
         from .warp import parse_warp
         try:
             parse_warp(a.warp)
+        except ValueError as e:
+            raise SystemExit(str(e))
+    if a.accumulate is not None:
+        from .flat import accumulate_config
+        try:
+            accumulate_config(a.accumulate)
         except ValueError as e:
             raise SystemExit(str(e))
     if a.average is not None:
@@ -430,7 +441,7 @@ def _cli(argv=None):
         dkw = dict(teacher=a.teacher, distill=dst, teacher_use_vit=True if a.teacher_use_vit else None, teacher_flip=a.teacher_flip)
     main(a.train, a.val, a.save, epochs=a.epochs, batch_size=a.batch_size, use_vit=not a.no_vit, seed=a.seed, schedule=a.schedule,
          capture_graph=not a.no_graph, loss=a.loss, boundary=None if a.boundary_weight is None else {"weight": a.boundary_weight},
-         average=a.average, warp=a.warp, **({"topk": topk} if topk else {}), **dkw)
+         average=a.average, warp=a.warp, accumulate=a.accumulate, **({"topk": topk} if topk else {}), **dkw)
     if dist.is_initialized():
         dist.barrier()
         dist.destroy_process_group()

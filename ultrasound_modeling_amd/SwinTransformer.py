@@ -35,7 +35,7 @@ import torch.nn as nn
 from .step import TrainStepDriver
 from . import knobs
 from . import ops
-from .flat import AdamClip, FlatParams
+from .flat import AdamClip, FlatParams, accumulate_config
 from .layers import _FUSE_LN_RES, Conv2D
 from .ops import ACT_GELU, ACT_NONE, BF16, roundup
 
@@ -289,8 +289,9 @@ class SwinTransformerModel(TrainStepDriver, nn.Module):
     def __init__(self, model_name="swin_large_384", include_top=False, img_size=(224, 224), patch_size=(4, 4), in_chans=3, num_classes=1000,
                  embed_dim=96, depths=(2, 2, 6, 2), num_heads=(3, 6, 12, 24), window_size=4, mlp_ratio=4.0, qkv_bias=True, qk_scale=None,
                  drop_rate=0.0, attn_drop_rate=0.0, drop_path_rate=0.1, norm_layer=None, ape=False, patch_norm=True, use_checkpoint=False, *,
-                 device: Optional[str] = None, seed: Optional[int] = 0, learning_rate=1e-3, weight_decay=None, average=None, **kwargs):
+                 device: Optional[str] = None, seed: Optional[int] = 0, learning_rate=1e-3, weight_decay=None, average=None, accumulate=None, **kwargs):
         super().__init__()
+        accumulate_config(accumulate)           # (a refusal comes before any device is touched)
         if seed is not None:
             torch.manual_seed(seed)
         self.include_top, self.num_classes, self.num_layers, self.embed_dim = include_top, num_classes, len(depths), embed_dim
@@ -313,7 +314,7 @@ class SwinTransformerModel(TrainStepDriver, nn.Module):
             raise RuntimeError("SwinTransformerModel needs a HIP device: the product path has no CPU fallback")
         self.device = torch.device(dev)
         self.flat = FlatParams(self, self.device)
-        self.optimizer = AdamClip(self.flat, lr=learning_rate, clip_norm=None, weight_decay=weight_decay, average=average)   # a float or a schedule each; average: EMA / SWA
+        self.optimizer = AdamClip(self.flat, lr=learning_rate, clip_norm=None, weight_decay=weight_decay, average=average, accumulate=accumulate)   # a float or a schedule each; average: EMA / SWA; accumulate: micro-batches per step
         self.features: List[torch.Tensor] = []
 
     def repack(self):

@@ -24,7 +24,7 @@ import torch.nn as nn
 
 from . import knobs
 from . import ops
-from .flat import AdamClip, FlatParams
+from .flat import AdamClip, FlatParams, accumulate_config
 from .layers import (KERAS_BN_EPS, KERAS_ELU_ALPHA, AveragePooling2D, BatchNormalization, Conv2D, Conv2DTranspose, QuadHead, QuadTConv,
                      _Workspace)
 from .ops import ACT_ELU, ACT_NONE, ACT_RELU, BF16, roundup
@@ -491,10 +491,13 @@ class ResNest(TrainStepDriver, PredictDriver):
     """TBI_ResNest.py:15-55.  ``step(x, y, train)`` -> (loss map [H,W], accuracy, probabilities)."""
 
     def __init__(self, height, width, channel, num_class, ksize, radix=4, kpaths=4, learning_rate=1e-3, ckpt_dir="./Checkpoint", *,
-                 device: Optional[str] = None, seed: Optional[int] = 0, weight_decay=None, average=None):
+                 device: Optional[str] = None, seed: Optional[int] = 0, weight_decay=None, average=None, accumulate=None):
         """``learning_rate`` may be a ``schedules.PiecewiseConstantDecay``; ``weight_decay`` (a float or a schedule) turns on the
         decoupled weight decay of tfa AdamW (None: plain Adam, as the reference).  ``average`` (None: off) is ``flat.AdamClip(average=...)``: an EMA or SWA average of the weights kept by the update
-        kernel; ``averaged_weights()`` computes with it, ``save_averaged(path)`` writes it as a plain checkpoint."""
+        kernel; ``averaged_weights()`` computes with it, ``save_averaged(path)`` writes it as a plain checkpoint.  ``accumulate`` (None or 1: off) is
+        ``flat.AdamClip(accumulate=N)``: every training step is a micro-step and the N-th takes one optimiser step on the mean of the N gradients
+        (this model's loss scale and dropout draws are per micro-batch); ``pending_micro_steps`` / ``flush_step()``."""
+        accumulate_config(accumulate)           # (a refusal comes before any device is touched)
         if seed is not None:
             torch.manual_seed(seed)
         assert height % 64 == 0 and width % 64 == 0, "six 2x2 poolings: H and W must be multiples of 64"
@@ -507,7 +510,7 @@ class ResNest(TrainStepDriver, PredictDriver):
         self.resModel = _ResModel(height, width, channel, num_class, ksize, radix, kpaths)       # :26
         self.flat = FlatParams(self.resModel, self.device)
         self.resModel.repack()
-        self.optimizer = AdamClip(self.flat, lr=learning_rate, clip_norm=None, weight_decay=weight_decay, average=average)   # :28 (no clipping, :46)
+        self.optimizer = AdamClip(self.flat, lr=learning_rate, clip_norm=None, weight_decay=weight_decay, average=average, accumulate=accumulate)   # :28 (no clipping, :46)
         self.class_factor = [0.06329, 0.027567, 0.90914]                                        # :30 (unused by my_loss_cat)
         self._loss_map = torch.zeros(height * width, dtype=torch.float32, device=self.device)
         self._scale = torch.zeros(height * width * num_class, dtype=torch.float32, device=self.device)
@@ -515,10 +518,15 @@ class ResNest(TrainStepDriver, PredictDriver):
         self._graph = None
         self._predict_dev = torch.zeros(1, dtype=torch.int32, device=self.device)     # predict calls so far (dropout masks of predict)
         self.resModel.step_dev = self.optimizer.step_dev      # dropout masks follow the device step counter (graph replays)
+        self._micro_dev = None
+        if self.optimizer.accumulate_steps > 1:     # ... which stands still inside a group: the masks follow a count of the micro-steps instead
+            self._micro_dev = torch.zeros(1, dtype=torch.int32, device=self.device)
+            self.resModel.step_dev = self._micro_dev
         object.__setattr__(self.resModel, "save", self.save_params)     # the driver calls neuralnet.resModel.save(path) (TBI_ResNest.py:472)
 
     # parameters in / out under the Keras layer names ------------------------------------------------------------------
     def load_params(self, params: dict):
+        self._no_pending("load_params")        # (the accumulator holds gradients of the weights about to be replaced)
         own = dict(self.resModel.named_parameters())
         bufs = {}
         for name, mod in self.resModel.named_modules():
@@ -551,6 +559,7 @@ class ResNest(TrainStepDriver, PredictDriver):
     def save_params(self, path=None):
         """TBI_ResNest.py:57-66 (a tf.train.CheckpointManager there, broken as committed): variables, BN statistics and the
         optimiser state in one file."""
+        self._no_pending("save_params")
         path = path or os.path.join(self.ckpt_dir, "usseg_arch_a.pt")
         os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
         d = self.export_params()
@@ -560,8 +569,11 @@ class ResNest(TrainStepDriver, PredictDriver):
 
     def load_params_file(self, path=None):
         """TBI_ResNest.py:68-78 ``load_params``: restore what ``save_params`` wrote."""
+        self._no_pending("load_params_file")
         d = torch.load(path or os.path.join(self.ckpt_dir, "usseg_arch_a.pt"), map_location="cpu", weights_only=True)
         self.optimizer.load_state_dict({k: d.pop(k) for k in list(d) if k.startswith("__adam_")})
+        if self._micro_dev is not None:         # a checkpoint is written between groups: step * N micro-steps drew masks before it
+            self._micro_dev.copy_(self.optimizer.step_dev * self.optimizer.accumulate_steps)
         self.load_params(d)
 
     def my_loss_cat(self, y_true, y_pred):
@@ -607,6 +619,8 @@ class ResNest(TrainStepDriver, PredictDriver):
         probs, dlogits = self._forward_loss(x, y, with_grad=True)
         with ops.overlap_region():              # deferred / batched finishing reductions of the norm backward and bias sums
             self.resModel.backward(dlogits)                                                    # :43 (gradient of the SUM of the map)
+        if self._micro_dev is not None:
+            ops.counter_add(self._micro_dev)    # one launch, eager and replayed alike: the next micro-step draws fresh masks
         return probs
 
     def _repack(self):
@@ -614,7 +628,7 @@ class ResNest(TrainStepDriver, PredictDriver):
 
     def _graph_state(self):
         bn = [b for m in self.resModel.modules() if isinstance(m, BatchNormalization) for b in (m.moving_mean_p, m.moving_variance_p)]
-        return [self.flat.flat] + self.optimizer.state_tensors() + bn
+        return [self.flat.flat] + self.optimizer.state_tensors() + bn + ([] if self._micro_dev is None else [self._micro_dev])
 
     def step(self, x, y, train=False):
         """TBI_ResNest.py:35-55 -> (loss map [H,W], accuracy, probabilities)."""

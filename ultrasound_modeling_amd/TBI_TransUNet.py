@@ -38,7 +38,7 @@ import torch
 
 from . import DataAugs
 from . import Dataset_2
-from .MainNumpy import _labels, _raw_test_loss, average_setting, averaging, install_schedule
+from .MainNumpy import _labels, _raw_test_loss, average_setting, averaging, flush, install_schedule
 from .distill import distill_line
 from .metrics import SegMetrics, dice_line
 from .schedules import PiecewiseConstantDecay
@@ -54,14 +54,14 @@ class VisionTransformer(_VisionTransformer):
                  in_channels: int = 10, device: Optional[str] = None, seed: Optional[int] = 0, adamw: bool = False,
                  loss: str = "cce", class_factor=None, focal_gamma=None, overlap=None,
                  alpha=None, beta=None, smooth=None, power=None, class_weight=None, ce_weight=None, ov_weight=None, boundary=None,
-                 lovasz=None, average=None, topk=None, distill=None, teacher=None):
+                 lovasz=None, average=None, topk=None, distill=None, teacher=None, accumulate=None):
         """``loss`` / ``class_factor`` / ``focal_gamma`` / ``overlap`` / ``boundary`` / ``lovasz`` / ``topk`` / ``distill`` + ``teacher``: as in the newer model (``VisionTransformer.VisionTransformer``), with this file's
         reduction - the mean over the B*H*W pixels of the batch (the overlap term of "dice" / "tversky" / "dice_ce" is a ratio of sums and has weight 1, and so
         has the Lovasz term of "lovasz" / "lovasz_ce"; "topk" is the mean over the selected pixels).  ``average``: the newer model's (EMA / SWA weight averaging)."""
         super().__init__(batch_size, img_size, num_classes, learning_rate, weight_decay, in_channels=in_channels, use_vit=True,
                          device=device, seed=seed, transunet=True, adamw=adamw, loss=loss, class_factor=class_factor, focal_gamma=focal_gamma,
                          overlap=overlap, alpha=alpha, beta=beta, smooth=smooth, power=power, class_weight=class_weight, ce_weight=ce_weight,
-                         ov_weight=ov_weight, boundary=boundary, lovasz=lovasz, average=average, topk=topk, distill=distill, teacher=teacher)
+                         ov_weight=ov_weight, boundary=boundary, lovasz=lovasz, average=average, topk=topk, distill=distill, teacher=teacher, accumulate=accumulate)
 
     def step(self, x, y, train=False):
         """TBI_TransUNet.py:571-588 -> (loss, probabilities); ``train=True`` also clips and applies the gradients."""
@@ -143,6 +143,7 @@ def training(neuralnet, dataset, epochs, batch_size, *, schedule=False):
                 print()
             if terminator:
                 break
+        flush(neuralnet)            # accumulate=N: a short last group still takes its optimiser step, before validation and saving
         print()
         loss = float(loss)          # the epoch's last step (:892 reduce_sum of a scalar); after a graph replay the static buffer
         m = tr_metrics.result()
@@ -196,7 +197,7 @@ def test(neuralnet, dataset, epoch):
 
 
 def main(train_path, val_path, save_path=None, epochs=51, batch_size=16, *, loss="cce", overlap=None, boundary=None, lovasz=None, average=None,
-         warp=None, warp_seed=0, topk=None, teacher=None, distill=None):
+         warp=None, warp_seed=0, topk=None, teacher=None, distill=None, accumulate=None):
     """:997-1010 with the paths as arguments: 256x80x10 input, batch 16, 51 epochs, then a save if ``save_path`` is given.
     ``loss``: the model's ``loss=`` ("cce", "my_loss_cat", "focal", "dice", "tversky", "dice_ce"); ``overlap``: the settings of the last three,
     which also add a per-class Dice line to the test report; ``boundary``: the boundary term on top of one of those three; "lovasz" / "lovasz_ce" with their
@@ -205,7 +206,9 @@ def main(train_path, val_path, save_path=None, epochs=51, batch_size=16, *, loss
     ``warp`` (a ``warp.warp_config`` dict or ``parse_warp`` string; default off): elastic / affine warp of every training batch ahead of ``dataAug``.
     "topk" / "dice_topk" with their settings in ``topk`` (the top-k cross-entropy; the Dice line too).
     "distill" with ``teacher`` (a model, an ``Ensemble``, or checkpoint paths of this file's model - a list or a comma-separated string; several
-    make an ensemble) and its settings in ``distill``: knowledge distillation; the test report adds the two terms of the last validation batch."""
+    make an ensemble) and its settings in ``distill``: knowledge distillation; the test report adds the two terms of the last validation batch.
+    ``accumulate`` (an integer N >= 1; None: 1): every ``batch_size`` batch is a micro-batch and N of them make one optimiser step (DESIGN.md section
+    4g-3); ``training`` flushes a short last group at the end of every epoch, before ``test`` and the save."""
     dataset = Dataset(train_path, val_path, warp=warp, warp_seed=warp_seed)
     kw = {} if topk is None else {"topk": topk}
     if teacher is not None or distill is not None:
@@ -214,7 +217,7 @@ def main(train_path, val_path, save_path=None, epochs=51, batch_size=16, *, loss
             teacher = load_teacher(teacher, input_size, 10, "cuda", transunet=True)
         kw.update(teacher=teacher, distill=distill)
     neuralnet = VisionTransformer(img_size=input_size, num_classes=3, learning_rate=1e-3, batch_size=batch_size, loss=loss, overlap=overlap_settings(loss, overlap),
-                                  boundary=boundary, lovasz=lovasz, average=average_setting(average), **kw)
+                                  boundary=boundary, lovasz=lovasz, average=average_setting(average), accumulate=accumulate, **kw)
     print(len(neuralnet.visionModel.layers))
     training(neuralnet=neuralnet, dataset=dataset, epochs=epochs, batch_size=batch_size)
     if save_path is not None:

@@ -25,7 +25,7 @@ from . import seg_loss
 from . import Decoder as _DEC
 from . import ResNest as _ENC
 from .Decoder import DecoderBlock, DecoderCup
-from .flat import AdamClip, FlatParams
+from .flat import AdamClip, FlatParams, accumulate_config
 from .layers import BatchNormalization, Conv2D, LayerNormalization, _Workspace
 from .ResNest import ResNest, cardinal, residual_S
 from .seg_loss import LOSSES, OVERLAP_LOSSES, LOVASZ_LOSSES, TOPK_LOSSES, DISTILL_LOSSES, overlap_settings, overlap_config, lovasz_config, topk_config, boundary_config, _boundary_weight  # noqa: F401  (imported from here by the drivers and the tests)
@@ -312,7 +312,7 @@ class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
                  in_channels: int = 10, use_vit: bool = False, device: Optional[str] = None, seed: Optional[int] = 0,
                  transunet: bool = False, adamw: bool = False, loss: str = "cce", class_factor=None, focal_gamma=None,
                  overlap=None, alpha=None, beta=None, smooth=None, power=None, class_weight=None, ce_weight=None, ov_weight=None,
-                 boundary=None, lovasz=None, average=None, topk=None, distill=None, teacher=None):
+                 boundary=None, lovasz=None, average=None, topk=None, distill=None, teacher=None, accumulate=None):
         """``transunet=True`` builds the older self-contained copy of this model in TBI_TransUNet.py (BASELINE configs[3]):
         BatchNormalization where ResNest.py / Decoder.py use LayerNormalization (:304,426,465,472,503), conv_4 = 256 channels
         (:368), and the loss is CategoricalCrossentropy(label_smoothing=0.1) with the DEFAULT reduction - the mean over all
@@ -373,8 +373,14 @@ class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
         ``lovasz`` and ``topk`` do not combine with it.
 
         ``average`` (None: off) is ``flat.AdamClip(average=...)``: an EMA or SWA average of the weights kept by the update
-        kernel; ``averaged_weights()`` computes with it, ``save_averaged(path)`` writes it as a plain checkpoint."""
+        kernel; ``averaged_weights()`` computes with it, ``save_averaged(path)`` writes it as a plain checkpoint.
+
+        ``accumulate`` (None or 1: off) is ``flat.AdamClip(accumulate=N)``: every ``train_step`` is a micro-step on its batch and the N-th takes ONE
+        optimiser step on the mean of the N gradients - with ``batch_size=b`` and the per-pixel losses that is the
+        gradient of the N*b images in a model built with ``batch_size=N*b``.  ``pending_micro_steps`` counts, ``flush_step()`` finishes a short
+        group, ``save`` refuses while micro-steps are pending."""
         super().__init__()
+        accumulate_config(accumulate)           # (every refusal comes first, before any device is touched)
         own = seg_loss.resolve(loss, num_classes, class_factor=class_factor, focal_gamma=focal_gamma, overlap=overlap, alpha=alpha, beta=beta, smooth=smooth, power=power,
                                class_weight=class_weight, ce_weight=ce_weight, ov_weight=ov_weight, boundary=boundary, lovasz=lovasz, topk=topk, distill=distill, teacher=teacher)
         self._seg_loss, self.loss_name, self.alpha, self.class_factor = own, loss, own.alpha, own.class_factor      # (every refusal comes first; seg_loss.py has the families)
@@ -396,7 +402,7 @@ class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
         self.device = torch.device(dev)
         self.flat = FlatParams(self, self.device)
         self.optimizer = AdamClip(self.flat, lr=learning_rate, clip_norm=1.0,          # :204,:244
-                                  weight_decay=weight_decay if adamw else None, average=average)
+                                  weight_decay=weight_decay if adamw else None, average=average, accumulate=accumulate)
         own.place(self)                         # the device settings, the accumulator and, for "distill", the checks of the teacher
         self._loss = own.acc                    # [0] = the scalar loss; this tensor for the model's life (a captured graph holds it)
         self.grad_sync = None                   # set by the data-parallel wrapper: callable(flat_grad)
@@ -434,12 +440,14 @@ class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
 
     def save(self, path):
         """model.save of a compiled Keras model (MainNumpy.py:177): variables, BN statistics AND the optimiser state."""
+        self._no_pending("save")
         d = self.export_params()
         d.update(self.optimizer.state_dict())
         d.update(self._seg_loss.state())        # the loss's device settings (the boundary weight, the top-k fraction, the distillation table)
         torch.save(d, path)
 
     def load(self, path):
+        self._no_pending("load")               # (the accumulator holds gradients of the weights about to be replaced)
         d = torch.load(path, map_location="cpu", weights_only=True)
         self.optimizer.load_state_dict({k: d.pop(k) for k in list(d) if k.startswith("__adam_")})
         self._seg_loss.load_state(d)            # (a checkpoint without an entry leaves the constructor's value; another family's entry is ignored)
@@ -451,6 +459,7 @@ class VisionTransformer(TrainStepDriver, PredictDriver, nn.Module):
 
     def load_params(self, params: dict):
         """Load a {reference-attribute-path: tensor} dict (the oracle's naming).  BN moving statistics included."""
+        self._no_pending("load_params")
         own = dict(self.named_parameters())
         bufs = {}
         for name, mod in self.named_modules():

@@ -1,6 +1,6 @@
 """ctypes binding of libusseg_hip.so, generated at import from the C ABI declared in include/usseg.h and, for the evaluator's score kernels,
-include/usseg_scores.h and, for the distillation loss, include/usseg_distill.h (_abi.py reads all three; ``ABI`` is the first header's,
-``SCORES_ABI`` the second's, ``DISTILL_ABI`` the third's).
+include/usseg_scores.h, for the distillation loss, include/usseg_distill.h and, for gradient accumulation, include/usseg_accumulate.h (_abi.py
+reads all four; ``ABI`` is the first header's, ``SCORES_ABI`` the second's, ``DISTILL_ABI`` the third's, ``GRAD_ACC_ABI`` the fourth's).
 
 There is NO fallback: if the header or the shared library is missing or a call fails, an exception is raised.
 Nothing here imports the oracle.
@@ -18,6 +18,7 @@ LIB_PATH = knobs.get("USSEG_LIB") or os.path.join(_HERE, "libusseg_hip.so")   # 
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "usseg.h")
 SCORES_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "usseg_scores.h")
 DISTILL_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "usseg_distill.h")
+GRAD_ACC_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "usseg_accumulate.h")
 
 c_i32, c_i64, c_f32, c_vp = C.c_int32, C.c_int64, C.c_float, C.c_void_p
 
@@ -56,6 +57,10 @@ DISTILL_SYMBOLS = tuple(DISTILL_ABI.protos)
 DistillDesc = DISTILL_ABI.structs["UssegDistillDesc"]
 DISTILL_ACC_FLOATS, DISTILL_SETTINGS = DISTILL_ABI.consts["USSEG_DISTILL_ACC_FLOATS"], DISTILL_ABI.consts["USSEG_DISTILL_SETTINGS"]
 
+# the fourth header (csrc/accumulate.hip): one entry point, no struct, no constant
+GRAD_ACC_ABI = read_header(GRAD_ACC_HEADER_PATH)
+GRAD_ACC_SYMBOLS = tuple(GRAD_ACC_ABI.protos)
+
 _lib = None
 
 
@@ -77,6 +82,7 @@ def load() -> C.CDLL:
         raise UssegError(f"{LIB_PATH} not found: build the HIP extension first (python -c 'import __graft_entry__ as g; "
                          f"g.build()'). There is no CPU fallback.")
     _lib = bind(bind(bind(C.CDLL(LIB_PATH)), SCORES_SYMBOLS, SCORES_ABI.protos), DISTILL_SYMBOLS, DISTILL_ABI.protos)
+    bind(_lib, GRAD_ACC_SYMBOLS, GRAD_ACC_ABI.protos)
     return _lib
 
 

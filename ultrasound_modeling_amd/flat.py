@@ -107,11 +107,18 @@ class AdamClip:
     write per parameter, no further launch), on the table path and on the fixed-rate path alike; ``flat``, ``m`` and ``v`` get the bits they
     get without averaging.  The settings live in a device descriptor (``UssegAverage``), so ``set_average_decay`` reaches a captured
     graph's next replay.  BatchNorm moving statistics are not variables and are not averaged.
+
+    ``accumulate`` (None or 1: off - nothing is allocated, nothing new is launched) is the number N of micro-batches whose gradients make one
+    optimiser step: one more flat fp32 buffer ``acc`` holds their sum, and ``accumulate(finish)`` - a hook of
+    ``step.TrainStepDriver``, like ``clip_local`` / ``apply`` - adds ``flat.grad`` to it or, on the N-th, leaves their mean in ``flat.grad`` and
+    ``acc`` at zero.  Everything else here runs once per optimiser step, on that mean.
     """
 
     def __init__(self, flat: FlatParams, lr=1e-3, clip_norm: Optional[float] = 1.0, beta1=0.9, beta2=0.999, eps=1e-7, weight_decay=None,
-                 decay_exclude: Optional[Sequence[str]] = None, average: Optional[dict] = None):
+                 decay_exclude: Optional[Sequence[str]] = None, average: Optional[dict] = None, accumulate: Optional[int] = None):
         self.flat, self.clip_norm = flat, clip_norm
+        self.accumulate_steps = accumulate_config(accumulate)
+        self.acc = torch.zeros_like(flat.grad) if self.accumulate_steps > 1 else None
         self.average = None if average is None else average_config(average)
         self.lr = _rate(lr, "lr")
         self.weight_decay = None if weight_decay is None else _rate(weight_decay, "weight_decay")
@@ -218,6 +225,13 @@ class AdamClip:
         ops.sumsq(self.flat.grad, self.sumsq)        # sumsq[0] is overwritten: no zero-fill launch
         return self.sumsq
 
+    def accumulate(self, finish: bool):
+        """One micro-batch gradient (``flat.grad``) into ``acc``; ``finish``: the group's mean into ``flat.grad`` and ``acc`` back to zero
+        (``ops.grad_accumulate``: it divides by N however many micro-steps the group really had)."""
+        if self.acc is None:
+            raise RuntimeError("AdamClip.accumulate: the optimiser was built without accumulate=N, N > 1")
+        ops.grad_accumulate(self.acc, self.flat.grad, finish, float(self.accumulate_steps))
+
     def clip_local(self):
         """Per-replica clip, BEFORE the data-parallel all-reduce (VisionTransformer.py:244 precedes :245)."""
         if self.clip_norm is not None:
@@ -263,7 +277,8 @@ class AdamClip:
     def state_tensors(self):
         t = [self.m, self.v, self.step_dev, self.lr_t_dev]
         t = t if self.sched_dev is None else t + [self.sched_dev, self.wd_t_dev]
-        return t if self.avg is None else t + [self.avg, self.avg_desc]
+        t = t if self.avg is None else t + [self.avg, self.avg_desc]
+        return t if self.acc is None else t + [self.acc]
 
     def state_dict(self):
         """Adam moments in the flat layout + the step counter (what Keras saves with a compiled model); + the rate table if one is used."""
@@ -352,6 +367,18 @@ def _decay_mask(flat: FlatParams, exclude) -> Optional[torch.Tensor]:
     for o, n in hit:
         mask[o:o + n] = 0
     return mask.to(flat.device)
+
+
+# ---------------------------------------------------------------------------------------------------- gradient accumulation
+def accumulate_config(accumulate) -> int:
+    """``accumulate=`` of ``AdamClip`` and the models -> the number of micro-steps per optimiser step (None: 1); ValueError unless it is an
+    integer >= 1 (a bool is not one) and at most 2^24, up to where the kernel's divisor ``(float)N`` is N itself."""
+    if accumulate is None:
+        return 1
+    if isinstance(accumulate, bool) or not isinstance(accumulate, (int, np.integer)) or not 1 <= accumulate <= 2 ** 24:
+        raise ValueError(f"accumulate must be an integer >= 1 (micro-batches per optimiser step) and <= 2^24 (the kernel divides by (float)N, "
+                         f"exact up to there), got {accumulate!r}")
+    return int(accumulate)
 
 
 # ---------------------------------------------------------------------------------------------------- weight averaging

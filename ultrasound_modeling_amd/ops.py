@@ -1021,6 +1021,15 @@ def swap_f32(a: torch.Tensor, b: torch.Tensor):
     L.check(L.load().usseg_swap_f32(a.data_ptr(), b.data_ptr(), a.numel(), _stream()), "swap_f32")
 
 
+def grad_accumulate(acc: torch.Tensor, grad: torch.Tensor, finish: bool, divisor: float):
+    """One micro-batch gradient into the accumulator.  ``finish`` False: ``acc += grad``.  True: ``grad = (acc + grad) / divisor`` and
+    ``acc = 0`` - every operation one rounded fp32 operation (usseg_accumulate.h), ``divisor`` the number of micro-steps of a group."""
+    assert acc.dtype == torch.float32 and grad.dtype == torch.float32 and acc.is_contiguous() and grad.is_contiguous()
+    assert acc.numel() == grad.numel()
+    L.check(L.load().usseg_grad_accumulate(acc.data_ptr(), grad.data_ptr(), acc.numel(), 1 if finish else 0, float(divisor), _stream()),
+            "grad_accumulate")
+
+
 # ------------------------------------------------------------------------------------------------ fused stem
 def stem_fwd(x, w1, b1, w2, b2, w3, b3, gamma, beta, mean, var, eps, alpha):
     """ResNest.py:39-47 in one launch -> (y1 [B,H,W,16], t1 [B,H,W,32], c2 [B,H,W,32] pre-norm, pooled [B,H/2,W/2,32])."""

@@ -7,8 +7,13 @@ and by the data-parallel path (MainParallel.py:117-146).
     clip (single replica only) + Adam                        (:244-245)
     rebuild the bf16 GEMM operands from the fp32 masters
 
+With gradient accumulation (``optimizer.accumulate_steps`` = N > 1; not in the reference) the first line is a
+MICRO-STEP, followed by ``optimizer.accumulate(finish)``: N - 1 micro-steps add their gradient to the accumulator and stop there; the N-th
+leaves the mean of the N gradients in ``flat.grad`` and the rest of the order runs on it unchanged, once per N micro-batches.
+
 This file is host logic only (no kernel is launched from here directly): a wrapper supplies three hooks
-(``_zero_grad``, ``_forward_backward``, ``_repack``) and an ``optimizer`` with ``clip_local / advance / apply / apply_range``.
+(``_zero_grad``, ``_forward_backward``, ``_repack``) and an ``optimizer`` with ``clip_local / advance / apply / apply_range``
+(and ``accumulate`` when it accumulates).
 That makes the ordering testable on CPU with gloo (tests/test_cpu_host.py drives THIS class with oracle arithmetic in the
 hooks) and on one GPU with an in-process RCCL group (tests/test_gpu_step.py).
 
@@ -42,10 +47,70 @@ class TrainStepDriver:
         """Tensors that the capture warm-up steps modify and ``capture_graph`` must put back (weights, Adam state, BN statistics)."""
         return []
 
+    # ------------------------------------------------------------------ gradient accumulation (flat.AdamClip(accumulate=N))
+    _pending = 0             # host counter: micro-steps of the current group that are in the accumulator
+    _graph_micro = None      # the captured micro-step (``capture_graph`` with accumulate > 1), beside ``_graph``
+
+    @property
+    def accumulate(self) -> int:
+        """Micro-batches per optimiser step (1: every ``train_step`` is an optimiser step)."""
+        return getattr(self.optimizer, "accumulate_steps", 1)
+
+    @property
+    def pending_micro_steps(self) -> int:
+        """Micro-steps taken since the last optimiser step; ``flush_step()`` (or N - k more micro-steps) puts it back to 0."""
+        return self._pending
+
+    def _finishes(self) -> bool:
+        """Whether the micro-step about to run is the last of its group."""
+        return self._pending + 1 >= self.accumulate
+
+    def _micro_body(self, x, y):
+        """A micro-step that does not finish its group: no clip, no exchange, no Adam, no repack, no step-counter advance."""
+        self._zero_grad()
+        probs = self._forward_backward(x, y)
+        self.optimizer.accumulate(False)
+        return probs
+
+    def _finish_empty(self):
+        """The finishing micro-step of a replica that holds no image (``empty_step``) or of a short group (``flush_step``): a zero gradient
+        into the accumulator, then the tail of the step - through the captured update graph where there is one."""
+        self._zero_grad()
+        if self.accumulate > 1:
+            self.optimizer.accumulate(True)
+        self._pending = 0
+        if self.grad_sync is None:
+            self._update_body()
+            return
+        self.optimizer.clip_local()
+        g2 = None if self._graph is None else self._graph[1]
+        if g2 is not None:
+            self.grad_sync(self.flat.grad)
+            g2.replay()
+        else:
+            self._sync_and_update()
+
+    def flush_step(self):
+        """Finishes a group of k < N pending micro-steps with one optimiser step on (their sum) / N - the reference divides a short last
+        batch by the constant global batch size in the same way.  Nothing pending: nothing happens.  Under a ``grad_sync`` every replica
+        calls it (they hold the same count)."""
+        if self._pending == 0:
+            return
+        self._not_averaged()
+        self._finish_empty()
+
+    def _no_pending(self, what: str):
+        if self._pending:
+            raise RuntimeError(f"{what}: {self._pending} of {self.accumulate} micro-steps are pending in the gradient accumulator, which a "
+                               f"checkpoint does not hold; call flush_step() first")
+
     # ------------------------------------------------------------------ the step
     def _grad_body(self, x, y):
+        """The micro-step that ends in an optimiser step (with ``accumulate`` 1: every step)."""
         self._zero_grad()
         probs = self._forward_backward(x, y)                       # :240-243
+        if self.accumulate > 1:
+            self.optimizer.accumulate(True)                        # flat.grad = the mean of the group's gradients
         if self.grad_sync is not None:
             self.optimizer.clip_local()                            # per-replica clip (:244) BEFORE the exchange
         return probs
@@ -70,8 +135,7 @@ class TrainStepDriver:
             self.optimizer.apply_range(lo, hi)
         self._repack()
 
-    def _train_body(self, x, y):
-        self._not_averaged()
+    def _step_body(self, x, y):
         probs = self._grad_body(x, y)
         if self.grad_sync is not None:
             self._sync_and_update()
@@ -79,24 +143,30 @@ class TrainStepDriver:
             self._update_body()
         return probs
 
+    def _train_body(self, x, y):
+        self._not_averaged()
+        if not self._finishes():
+            probs = self._micro_body(x, y)
+            self._pending += 1
+            return probs
+        probs = self._step_body(x, y)
+        self._pending = 0
+        return probs
+
     def empty_step(self):
         """This replica's part of a step in which it holds no image (a short last batch split over the replicas): no forward pass and
         so no BatchNorm-statistics update, a zero gradient, and the same exchange and update as every other replica - the collective is
         joined, so no rank waits on it, and the weights stay identical.  The per-replica clip of a zero gradient is a no-op
         (scale = clip / max(0, clip) = 1), so the replica adds exactly nothing to the sum.  With a captured step the update replays
-        the captured update graph; a single replica (no ``grad_sync``) takes one Adam step on the zero gradient."""
+        the captured update graph; a single replica (no ``grad_sync``) takes one Adam step on the zero gradient.
+        With gradient accumulation it counts as a micro-step: a zero gradient into the accumulator, and the update only as the N-th."""
         self._not_averaged()
-        self._zero_grad()
-        if self.grad_sync is None:
-            self._update_body()
+        if not self._finishes():
+            self._zero_grad()
+            self.optimizer.accumulate(False)
+            self._pending += 1
             return
-        self.optimizer.clip_local()
-        g2 = None if self._graph is None else self._graph[1]
-        if g2 is not None:
-            self.grad_sync(self.flat.grad)
-            g2.replay()
-        else:
-            self._sync_and_update()
+        self._finish_empty()
 
     # ------------------------------------------------------------------ the averaged weights (flat.AdamClip(average=...))
     _averaged = False
@@ -140,7 +210,11 @@ class TrainStepDriver:
     def capture_graph(self, x, y, warmup: int = 2):
         """Capture the training step for inputs of this shape.  The ``warmup`` eager steps it needs (workspaces grow, lazy
         tables are built) run on a throw-away copy of the training state: weights, Adam moments / step counter and BatchNorm
-        statistics are restored afterwards, so enabling the graph does not consume optimisation steps."""
+        statistics are restored afterwards, so enabling the graph does not consume optimisation steps.
+        With gradient accumulation two steps are captured, each warmed up: the micro-step (one graph) and the step that finishes a group (the
+        graphs below); the accumulator is part of the restored state and the host counter of pending micro-steps is not touched, so a
+        capture in the middle of a group leaves the group as it was.  ``train_step`` replays whichever the counter calls for."""
+        self._not_averaged()
         x, y = self._prep_x(x), self._prep_y(y)
         self._gx, self._gy = x.clone(), y.clone()
         state = self._graph_state()
@@ -151,7 +225,9 @@ class TrainStepDriver:
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
             for _ in range(warmup):
-                self._train_body(self._gx, self._gy)
+                if self.accumulate > 1:
+                    self._micro_body(self._gx, self._gy)
+                self._step_body(self._gx, self._gy)
         torch.cuda.current_stream().wait_stream(s)
         torch.cuda.synchronize()
         self.grad_sync = sync_saved
@@ -162,13 +238,19 @@ class TrainStepDriver:
         mark = getattr(self.optimizer, "mark_captured", None)
         if mark is not None:
             mark()                    # the optimiser's kernel path is now part of the graph (flat.AdamClip)
-        g1 = torch.cuda.CUDAGraph()
+        g1, pool = torch.cuda.CUDAGraph(), {}
+        self._graph_micro = None
+        if self.accumulate > 1:       # the micro-step: its own graph and probability buffer, the memory pool shared with the graphs below
+            self._graph_micro = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self._graph_micro):
+                self._gprobs_micro = self._micro_body(self._gx, self._gy)
+            pool = {"pool": self._graph_micro.pool()}
         if self.grad_sync is None:
-            with torch.cuda.graph(g1):
-                self._gprobs = self._train_body(self._gx, self._gy)
+            with torch.cuda.graph(g1, **pool):
+                self._gprobs = self._step_body(self._gx, self._gy)
             self._graph = (g1, None)
             return
-        with torch.cuda.graph(g1):
+        with torch.cuda.graph(g1, **pool):
             self._gprobs = self._grad_body(self._gx, self._gy)
         g2 = None
         if getattr(self.grad_sync, "chunks", None) is None:          # one collective -> the update is a second graph
@@ -198,6 +280,11 @@ class TrainStepDriver:
             self._gx.copy_(x)
         if y.data_ptr() != self._gy.data_ptr():
             self._gy.copy_(y)
+        if not self._finishes():      # a micro-step inside a group: the probabilities are those of the micro-batch just run
+            self._graph_micro.replay()
+            self._pending += 1
+            return self._gprobs_micro
+        self._pending = 0
         g1, g2 = self._graph
         g1.replay()
         if self.grad_sync is not None:
