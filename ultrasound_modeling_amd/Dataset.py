@@ -15,7 +15,8 @@ pipeline ``from_tensor_slices(...).map(...).batch(batch_size)`` of MainParallel.
 Every replica draws the augmentation parameters of the WHOLE global batch (one ``DataAugs.draw`` per sample, in sample order, from its
 own seeded ``random``) and keeps its slice: each sample gets the draw it gets in a single-process run, and the replicas' generators
 never drift apart.  With ``warp=`` (``Dataset_2.Dataset``; off by default) the same holds for the warp's draws, which come from a generator of
-their own, and the replica's slice is warped before it is augmented.  The draws are host work; the noise is seeded from them, so the device
+their own, and the replica's slice is warped before it is augmented; and for the draws of ``paste=`` (lesion copy-paste, off by default), whose
+lesions go into the slice before the warp.  The draws are host work; the noise is seeded from them, so the device
 output is a function of the draw (and, for the noise alone, of the sample's position in the launch: ``usseg_augment`` counts pixels over the
 launched batch).
 
@@ -55,12 +56,13 @@ class Dataset(Dataset_2.Dataset):
     """Dataset.py:5-52.  ``batch_size`` is the GLOBAL batch (``BATCH_SIZE``); the replicas' share of it is ``replica_block``."""
     draw = staticmethod(draw)
 
-    def __init__(self, train_path=None, val_path=None, batch_size=16, *, device="cuda", train_data=None, val_data=None, warp=None, warp_seed=0):
+    def __init__(self, train_path=None, val_path=None, batch_size=16, *, device="cuda", train_data=None, val_data=None, warp=None, warp_seed=0,
+                 paste=None, paste_seed=0):
         print("\nInitializing Dataset...")
         self.OUTPUT_CHANNELS = 3                                                                   # :11
         self.BATCH_SIZE = batch_size                                                               # :13
         super().__init__(train_path, val_path, num_classes=self.OUTPUT_CHANNELS, device=device, train_data=train_data, val_data=val_data,
-                         warp=warp, warp_seed=warp_seed)
+                         warp=warp, warp_seed=warp_seed, paste=paste, paste_seed=paste_seed)
         self.shape = [self.height, self.width, self.channel]                                       # :12 ([256, 80, 10] in the reference)
 
     def preProcess(self, input_data):
@@ -79,17 +81,21 @@ class Dataset(Dataset_2.Dataset):
     def train_batches(self, rank: int = 0, world: int = 1, rng=random) -> Iterator[Tuple[Optional[torch.Tensor], Optional[torch.Tensor], int]]:
         """Yields ``(x bf16 [b_r,H,W,roundup(C,8)], y fp32 [b_r,H,W,3], b)`` per global batch of ``b`` images: the augmented slice of replica
         ``rank``, or ``(None, None, b)`` when it holds none.  The draws of all ``b`` samples are taken from ``rng`` in sample order; with ``warp``
-        (``Dataset_2.Dataset``) so are the warp's, from its own generator, and the slice is warped before it is augmented."""
+        (``Dataset_2.Dataset``) so are the warp's, from its own generator, and the slice is warped before it is augmented; with ``paste`` the paste's,
+        from a third generator, and its lesions go into the slice first."""
         B = self.BATCH_SIZE
         for start in range(0, self.num_tr, B):
             b = min(B, self.num_tr - start)
             params = [self.draw(rng) for _ in range(b)]
-            warps = self.draw_warps(b)                      # None without warp; every replica draws all b, as for params
+            pastes = self.draw_pastes(b)                    # None without paste; every replica draws all b, as for params
+            warps = self.draw_warps(b)                      # None without warp; likewise
             lo, hi = replica_block(b, B, rank, world)
             if lo == hi:
                 yield None, None, b
                 continue
             x, y = self.x_tr[start + lo:start + hi], self.y_tr[start + lo:start + hi]
+            if pastes is not None:
+                x, y = self.pasted(x, y, pastes[lo:hi])
             if warps is not None:
                 x, y = self.warped(x, y, warps[lo:hi])
             x, y = self._augment(x, y, params[lo:hi])

@@ -34,11 +34,14 @@ def label2vec(label: torch.Tensor, num_classes: int) -> torch.Tensor:
 class Dataset(object):
     draw = staticmethod(draw)       # one sample's augmentation draws (DataAugs.draw); TBI_TransUNet.Dataset draws its script's
 
-    def __init__(self, train_path=None, val_path=None, num_classes=3, device="cuda", train_data=None, val_data=None, warp=None, warp_seed=0):
+    def __init__(self, train_path=None, val_path=None, num_classes=3, device="cuda", train_data=None, val_data=None, warp=None, warp_seed=0,
+                 paste=None, paste_seed=0):
         """``train_data`` / ``val_data``: arrays of the on-disk layout [N,1,H,W,12] (label, 10 displacement channels, bMode;
         Dataset_2.py:33-43) may be passed instead of paths.  ``warp`` (default None: off; a ``warp.warp_config`` dict or ``parse_warp``
         string): every TRAINING batch is warped elastically and affinely on the device before ``dataAug_batch`` sees it; the warp's draws come
-        from ``random.Random(warp_seed)``, never from the generator of ``draw``."""
+        from ``random.Random(warp_seed)``, never from the generator of ``draw``.  ``paste`` (default None: off - nothing is imported, allocated
+        or launched; a ``paste.paste_config`` dict or ``parse_paste`` string): lesions of the training set are pasted into every TRAINING batch
+        on the device, BEFORE the warp; the bank is built here, once, and the draws come from ``random.Random(paste_seed)``."""
         train_data = np.load(train_path, allow_pickle=False) if train_data is None else np.asarray(train_data)
         val_data = np.load(val_path, allow_pickle=False) if val_data is None else np.asarray(val_data)
         self.device = torch.device(device)
@@ -58,6 +61,44 @@ class Dataset(object):
             import random
             from .warp import warp_config
             self.warp, self.warp_rng = warp_config(warp), random.Random(warp_seed)
+        self.paste = None
+        if paste is not None:
+            import random
+            from .paste import paste_config
+            self.paste, self.paste_rng = paste_config(paste), random.Random(paste_seed)
+            self.paste_bank = self._lesion_bank(self.paste)
+            self.paste_counts = torch.zeros(2, dtype=torch.int64, device=self.device)      # items accepted, pixels pasted: read once an epoch
+            self.paste_drawn = 0                                                            # lesions drawn for active samples since the last report
+
+    def _lesion_bank(self, cfg):
+        from .paste import LesionBank
+        return LesionBank(self.y_tr, cfg["connectivity"], cfg["min_area"])
+
+    def draw_pastes(self, n):
+        """The paste draws of ``n`` samples, in sample order, from the paste's own generator (None without ``paste``)."""
+        if self.paste is None:
+            return None
+        from .paste import draw_paste
+        draws = [draw_paste(self.paste_rng, self.paste, self.paste_bank, self.height, self.width) for _ in range(n)]
+        self.paste_drawn += sum(d["n"] for d in draws if d["active"])
+        return draws
+
+    def pasted(self, x, y, params):
+        """(x, y) of a training batch with the lesions of ``params`` pasted in (as they are without ``paste``)."""
+        if self.paste is None:
+            return x, y
+        from .paste import paste_batch
+        return paste_batch(x, y, params, self.paste, self.paste_bank, self.x_tr, self.y_tr, counts=self.paste_counts)
+
+    def paste_report(self):
+        """(lesions placed, lesions drawn, pixels pasted) since the last call - ONE read-back of the device counters - or None without
+        ``paste``.  The counters start again at zero."""
+        if self.paste is None:
+            return None
+        placed, pixels = (int(v) for v in self.paste_counts.cpu())
+        drawn, self.paste_drawn = self.paste_drawn, 0
+        self.paste_counts.zero_()
+        return placed, drawn, pixels
 
     def draw_warps(self, n):
         """The warp draws of ``n`` samples, in sample order, from the warp's own generator (None without ``warp``)."""
@@ -78,7 +119,8 @@ class Dataset(object):
 
     def next_train(self, batch_size=1, fix=False, params=None):
         """Dataset_2.py:88-114 -> (x bf16 [B,H,W,roundup(C,8)], y fp32 [B,H,W,num_classes], terminator), all on the device.  With ``warp`` the
-        batch is warped first (its draws: ``draw_warps``), so ``imageReduc`` zeroes the image where the WARPED label is 0."""
+        batch is warped first (its draws: ``draw_warps``), so ``imageReduc`` zeroes the image where the WARPED label is 0.  With ``paste`` lesions
+        are pasted in before that (``draw_pastes``): a pasted lesion is warped too, and ``imageReduc`` sees the pasted label."""
         start, end = self.idx_tr, self.idx_tr + batch_size
         x_tr, y_tr = self.x_tr[start:end], self.y_tr[start:end]
         terminator = False
@@ -93,6 +135,8 @@ class Dataset(object):
             x_tr, y_tr = self.x_tr[-1 - batch_size:-1], self.y_tr[-1 - batch_size:-1]
         if params is None:
             params = [self.draw() for _ in range(x_tr.shape[0])]
+        if self.paste is not None:
+            x_tr, y_tr = self.pasted(x_tr, y_tr, self.draw_pastes(x_tr.shape[0]))
         if self.warp is not None:
             x_tr, y_tr = self.warped(x_tr, y_tr, self.draw_warps(x_tr.shape[0]))
         x, y = dataAug_batch(x_tr, y_tr, params=params, num_classes=self.num_classes)      # :106-112

@@ -85,6 +85,7 @@ class Process(object):
                   % (epoch, epochs, iteration, loss, m["recall"], m["precision"], m["mean_iou"]))
             self.history.append(dict(m, phase="train", epoch=epoch, iteration=iteration, loss=loss))
             self.tr_metrics.reset_states()                                                       # :73-75
+            paste_report(dataset)
             if prev_loss == loss:
                 print("Model is throwing a fit")
                 print(class_score)
@@ -158,7 +159,7 @@ class Process(object):
 
 
 def main(train_path, val_path, save_path=None, epochs=50, batch_size=32, num_classes=3, *, loss="cce", overlap=None, boundary=None, lovasz=None,
-         average=None, warp=None, warp_seed=0, topk=None, teacher=None, distill=None, accumulate=None):
+         average=None, warp=None, warp_seed=0, topk=None, teacher=None, distill=None, accumulate=None, paste=None, paste_seed=0):
     """MainNumpy.py:150-177 with the paths as arguments: ``VisionTransformer(32, img_size=(256, 80))`` over a ``Dataset_2.Dataset``,
     50 epochs, then a save if ``save_path`` is given.  ``loss``: the model's ``loss=`` ("cce", "my_loss_cat", "focal", "dice", "tversky",
     "dice_ce"); ``overlap``: the settings of the last three (``VisionTransformer(overlap=...)``), which also add a per-class Dice line to the test report;
@@ -172,10 +173,12 @@ def main(train_path, val_path, save_path=None, epochs=50, batch_size=32, num_cla
     its settings in ``distill`` (``VisionTransformer(distill=...)``): knowledge distillation; the test report adds the hard and soft terms of
     the last validation batch.  ``accumulate`` (an integer N >= 1; None: 1): ``VisionTransformer(accumulate=N)`` - every ``batch_size`` batch is a
     micro-batch and N of them make one optimiser step; a short last group of an epoch is flushed before validation and saving, and the epoch
-    loss stays the last micro-batch's."""
+    loss stays the last micro-batch's.  ``paste`` (a ``paste.paste_config`` dict or ``parse_paste`` string; default off): lesions of the training set
+    are pasted into every training batch ahead of the warp, its draws from ``random.Random(paste_seed)``; ``training`` then
+    prints one line per epoch: lesions placed of lesions drawn, and the pixels pasted."""
     from .Dataset_2 import Dataset
     from .VisionTransformer import VisionTransformer, overlap_settings
-    dataset = Dataset(train_path, val_path, num_classes, warp=warp, warp_seed=warp_seed)
+    dataset = Dataset(train_path, val_path, num_classes, warp=warp, warp_seed=warp_seed, paste=paste, paste_seed=paste_seed)
     kw = {} if topk is None else {"topk": topk}
     if teacher is not None or distill is not None:
         if isinstance(teacher, (str, list, tuple)):
@@ -192,6 +195,17 @@ def main(train_path, val_path, save_path=None, epochs=50, batch_size=32, num_cla
         if average is not None:
             neuralnet.save_averaged(save_path + ".avg")
     return neuralnet, process
+
+
+def paste_report(dataset, show=print):
+    """With ``paste=``: the epoch's line - lesions placed out of lesions drawn, pixels pasted - from ONE read-back of the dataset's device counters
+    -> (placed, drawn, pixels); None, and nothing printed or read, without."""
+    fn = getattr(dataset, "paste_report", None)
+    rep = fn() if fn is not None else None
+    if rep is not None:
+        from .paste import paste_line
+        show(paste_line(*rep))
+    return rep
 
 
 def flush(neuralnet):

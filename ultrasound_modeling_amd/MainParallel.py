@@ -213,12 +213,23 @@ class Process(object):
                         % (epoch, epochs, self.train_iter, loss, m["recall"], m["precision"], m["mean_iou"]))
             self.history.append(dict(m, phase="train", epoch=epoch, iteration=self.train_iter, loss=loss))
             self.tr_metrics.reset_states()                                                       # :66-68
+            self._paste_report(dataset)
             if prev_loss == loss:
                 self._print("Model is throwing a fit")
             prev_loss = loss
             if boundary_ramp is not None:
                 neuralnet.set_boundary_weight(neuralnet.boundary_weight + float(boundary_ramp))
             self.test(neuralnet, dataset, epoch)                                                 # :72
+
+    def _paste_report(self, dataset):
+        """With ``paste=``: the epoch's line on rank 0.  Every rank drew the lesions of the whole global batches, so ``drawn`` is the same
+        everywhere; the device counters hold the rank's own slices and are SUM-reduced before the one read-back."""
+        if getattr(dataset, "paste", None) is None:
+            return None
+        if self.trainer is not None and self.trainer.world > 1:
+            dist.all_reduce(dataset.paste_counts, op=dist.ReduceOp.SUM, group=self.group)
+        from .MainNumpy import paste_report
+        return paste_report(dataset, show=self._print)
 
     def test(self, neuralnet, dataset, epoch):
         """MainParallel.py:81-115 -> F1 of the test set; its dict (``phase`` "test") is appended to ``history``.  A model built with
@@ -306,7 +317,7 @@ class Process(object):
 
 def main(train_path, val_path, save_path=None, epochs=51, batch_size=64, use_vit=True, *, seed=0, schedule=False, capture_graph=True,
          loss="cce", overlap=None, boundary=None, lovasz=None, average=None, warp=None, topk=None, teacher=None, distill=None,
-         teacher_use_vit=None, teacher_flip=False, accumulate=None):
+         teacher_use_vit=None, teacher_flip=False, accumulate=None, paste=None):
     """MainParallel.py:201-216 with the paths as arguments: ``VisionTransformer(batch_size=64)`` with the ViT bottleneck, 51 epochs,
     then rank 0 saves if ``save_path`` is given.  Every rank seeds ``random`` with ``seed``, so all draw the same augmentations.
     ``loss``: the model's ``loss=`` ("cce", "my_loss_cat", "focal"); every replica divides it by the global batch all the same.  The
@@ -328,6 +339,9 @@ def main(train_path, val_path, save_path=None, epochs=51, batch_size=64, use_vit
     its draws come from ``random.Random(seed)`` on every rank, each rank draws the whole global batch and keeps its slice.
     ``accumulate`` (``--accumulate N``; None: 1): every global batch is a micro-batch and N of them make one optimiser step - ONE gradient exchange
     and one update per N batches; a short last group of an epoch is flushed before the test and the save.
+    ``paste`` (a ``paste.paste_config`` dict or the ``--paste`` string; default off): lesions of the training set are pasted into every training
+    batch ahead of the warp; its draws come from ``random.Random(seed)`` on every rank, each rank draws the whole global
+    batch and keeps its slice, and rank 0 prints one line per epoch: lesions placed of lesions drawn, summed over the ranks.
     Under ``nccl`` the model lives on ``cuda:LOCAL_RANK``; the ``USSEG_DIST_BACKEND=gloo`` rehearsal keeps every rank on device 0."""
     from .Dataset import Dataset
     from .MainNumpy import average_setting
@@ -337,7 +351,7 @@ def main(train_path, val_path, save_path=None, epochs=51, batch_size=64, use_vit
     device = torch.device("cuda", local if nccl else 0)
     torch.cuda.set_device(device)
     random.seed(seed)
-    dataset = Dataset(train_path, val_path, batch_size, device=device, warp=warp, warp_seed=seed)
+    dataset = Dataset(train_path, val_path, batch_size, device=device, warp=warp, warp_seed=seed, paste=paste, paste_seed=seed)
     kw = {} if topk is None else {"topk": topk}
     if teacher is not None or distill is not None:
         if isinstance(teacher, (str, list, tuple)):
@@ -395,7 +409,17 @@ def _cli(argv=None):
     ap.add_argument("--warp", default=None, metavar="SPEC",
                     help="warp every training batch elastically and affinely on the device before dataAug, e.g. "
                          "sigma=8,magnitude=2:1,p=0.5,rotate=5,scale=0.05,shift=0:0 (any subset; these are the defaults)")
+    ap.add_argument("--paste", default=None, metavar="SPEC",
+                    help="paste lesions of the training set into every training batch on the device, before the warp and dataAug, e.g. "
+                         "p=0.5,max_lesions=2,min_area=4,min_landed=0.5,flip=1,shift=none,protect=1,connectivity=8 (any subset; these are "
+                         "the defaults, whose effect on this data nobody has measured)")
     a = ap.parse_args(argv)
+    if a.paste is not None:
+        from .paste import parse_paste
+        try:
+            parse_paste(a.paste)
+        except ValueError as e:
+            raise SystemExit(str(e))
     if a.warp is not None:
         from .warp import parse_warp
         try:
@@ -441,7 +465,7 @@ def _cli(argv=None):
         dkw = dict(teacher=a.teacher, distill=dst, teacher_use_vit=True if a.teacher_use_vit else None, teacher_flip=a.teacher_flip)
     main(a.train, a.val, a.save, epochs=a.epochs, batch_size=a.batch_size, use_vit=not a.no_vit, seed=a.seed, schedule=a.schedule,
          capture_graph=not a.no_graph, loss=a.loss, boundary=None if a.boundary_weight is None else {"weight": a.boundary_weight},
-         average=a.average, warp=a.warp, accumulate=a.accumulate, **({"topk": topk} if topk else {}), **dkw)
+         average=a.average, warp=a.warp, accumulate=a.accumulate, paste=a.paste, **({"topk": topk} if topk else {}), **dkw)
     if dist.is_initialized():
         dist.barrier()
         dist.destroy_process_group()

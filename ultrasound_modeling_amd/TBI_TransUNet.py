@@ -38,7 +38,7 @@ import torch
 
 from . import DataAugs
 from . import Dataset_2
-from .MainNumpy import _labels, _raw_test_loss, average_setting, averaging, flush, install_schedule
+from .MainNumpy import _labels, _raw_test_loss, average_setting, averaging, flush, install_schedule, paste_report
 from .distill import distill_line
 from .metrics import SegMetrics, dice_line
 from .schedules import PiecewiseConstantDecay
@@ -109,8 +109,10 @@ class Dataset(Dataset_2.Dataset):
     ``dataAug`` in ``next_train``; ``next_test`` does not augment."""
     draw = staticmethod(draw)
 
-    def __init__(self, train_path=None, val_path=None, device="cuda", train_data=None, val_data=None, warp=None, warp_seed=0):
-        super().__init__(train_path, val_path, num_classes=3, device=device, train_data=train_data, val_data=val_data, warp=warp, warp_seed=warp_seed)
+    def __init__(self, train_path=None, val_path=None, device="cuda", train_data=None, val_data=None, warp=None, warp_seed=0,
+                 paste=None, paste_seed=0):
+        super().__init__(train_path, val_path, num_classes=3, device=device, train_data=train_data, val_data=val_data, warp=warp, warp_seed=warp_seed,
+                         paste=paste, paste_seed=paste_seed)
         self.num_class = 3                                                                         # :682
 
 
@@ -150,6 +152,7 @@ def training(neuralnet, dataset, epochs, batch_size, *, schedule=False):
         print("Epoch [%d / %d] (%d iteration)  Loss:%.5f, Recall:%.5f, Precision:%.5f, IoU:%.5f"
               % (epoch, epochs, iteration, loss, m["recall"], m["precision"], m["mean_iou"]))
         history.append(dict(m, phase="train", epoch=epoch, iteration=iteration, loss=loss))
+        paste_report(dataset)
         tr_metrics.reset_states()                                                                    # :917-919
         if prev_loss == loss:
             print("Model is throwing a fit")
@@ -197,7 +200,7 @@ def test(neuralnet, dataset, epoch):
 
 
 def main(train_path, val_path, save_path=None, epochs=51, batch_size=16, *, loss="cce", overlap=None, boundary=None, lovasz=None, average=None,
-         warp=None, warp_seed=0, topk=None, teacher=None, distill=None, accumulate=None):
+         warp=None, warp_seed=0, topk=None, teacher=None, distill=None, accumulate=None, paste=None, paste_seed=0):
     """:997-1010 with the paths as arguments: 256x80x10 input, batch 16, 51 epochs, then a save if ``save_path`` is given.
     ``loss``: the model's ``loss=`` ("cce", "my_loss_cat", "focal", "dice", "tversky", "dice_ce"); ``overlap``: the settings of the last three,
     which also add a per-class Dice line to the test report; ``boundary``: the boundary term on top of one of those three; "lovasz" / "lovasz_ce" with their
@@ -208,8 +211,10 @@ def main(train_path, val_path, save_path=None, epochs=51, batch_size=16, *, loss
     "distill" with ``teacher`` (a model, an ``Ensemble``, or checkpoint paths of this file's model - a list or a comma-separated string; several
     make an ensemble) and its settings in ``distill``: knowledge distillation; the test report adds the two terms of the last validation batch.
     ``accumulate`` (an integer N >= 1; None: 1): every ``batch_size`` batch is a micro-batch and N of them make one optimiser step (DESIGN.md section
-    4g-3); ``training`` flushes a short last group at the end of every epoch, before ``test`` and the save."""
-    dataset = Dataset(train_path, val_path, warp=warp, warp_seed=warp_seed)
+    4g-3); ``training`` flushes a short last group at the end of every epoch, before ``test`` and the save.
+    ``paste`` (a ``paste.paste_config`` dict or ``parse_paste`` string; default off): lesions of the training set are pasted into every training batch
+    ahead of the warp, its draws from ``random.Random(paste_seed)``; ``training`` prints one line per epoch: lesions placed of drawn."""
+    dataset = Dataset(train_path, val_path, warp=warp, warp_seed=warp_seed, paste=paste, paste_seed=paste_seed)
     kw = {} if topk is None else {"topk": topk}
     if teacher is not None or distill is not None:
         if isinstance(teacher, (str, list, tuple)):

@@ -1,6 +1,7 @@
 """ctypes binding of libusseg_hip.so, generated at import from the C ABI declared in include/usseg.h and, for the evaluator's score kernels,
-include/usseg_scores.h, for the distillation loss, include/usseg_distill.h and, for gradient accumulation, include/usseg_accumulate.h (_abi.py
-reads all four; ``ABI`` is the first header's, ``SCORES_ABI`` the second's, ``DISTILL_ABI`` the third's, ``GRAD_ACC_ABI`` the fourth's).
+include/usseg_scores.h, for the distillation loss, include/usseg_distill.h, for gradient accumulation, include/usseg_accumulate.h and, for the
+lesion copy-paste augmentation, include/usseg_paste.h (_abi.py reads all five; ``ABI`` is the first header's, ``SCORES_ABI`` the second's,
+``DISTILL_ABI`` the third's, ``GRAD_ACC_ABI`` the fourth's, ``PASTE_ABI`` the fifth's).
 
 There is NO fallback: if the header or the shared library is missing or a call fails, an exception is raised.
 Nothing here imports the oracle.
@@ -19,6 +20,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "usseg.h")
 SCORES_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "usseg_scores.h")
 DISTILL_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "usseg_distill.h")
 GRAD_ACC_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "usseg_accumulate.h")
+PASTE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "usseg_paste.h")
 
 c_i32, c_i64, c_f32, c_vp = C.c_int32, C.c_int64, C.c_float, C.c_void_p
 
@@ -61,6 +63,12 @@ DISTILL_ACC_FLOATS, DISTILL_SETTINGS = DISTILL_ABI.consts["USSEG_DISTILL_ACC_FLO
 GRAD_ACC_ABI = read_header(GRAD_ACC_HEADER_PATH)
 GRAD_ACC_SYMBOLS = tuple(GRAD_ACC_ABI.protos)
 
+# the fifth header (csrc/paste.hip): one entry point, the sample table's structs and the item limit
+PASTE_ABI = read_header(PASTE_HEADER_PATH)
+PASTE_SYMBOLS = tuple(PASTE_ABI.protos)
+PasteItem, PasteSample, PasteDesc = (PASTE_ABI.structs[n] for n in ("UssegPasteItem", "UssegPasteSample", "UssegPasteDesc"))
+PASTE_MAX_ITEMS = PASTE_ABI.consts["USSEG_PASTE_MAX_ITEMS"]
+
 _lib = None
 
 
@@ -83,6 +91,7 @@ def load() -> C.CDLL:
                          f"g.build()'). There is no CPU fallback.")
     _lib = bind(bind(bind(C.CDLL(LIB_PATH)), SCORES_SYMBOLS, SCORES_ABI.protos), DISTILL_SYMBOLS, DISTILL_ABI.protos)
     bind(_lib, GRAD_ACC_SYMBOLS, GRAD_ACC_ABI.protos)
+    bind(_lib, PASTE_SYMBOLS, PASTE_ABI.protos)
     return _lib
 
 
